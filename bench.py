@@ -14,12 +14,19 @@ sharded (weak scaling: each rank decodes its own batch, no data-path
 collective); the only exchange is the final max-of-times / counter
 all-reduce over RCCL.  Rank 0 prints ONE JSON line.
 
-Beside the headline the default line carries the other BASELINE configs,
-each timed on every rank with its own roofline: `fp64_leg` (configs[1] in
-binary64), `batched_legs` (configs[2] C3 B = 256 in binary32 / binary64,
-configs[3] C4 B = 256), `mc_stream` (configs[3]'s 10 k-rep Monte-Carlo sweep,
-one refilled stream, with its own CPU baseline) and `joint_leg` (configs[4],
-the joint AMP<->BP step).
+A plain run does only what the headline needs: set-up, warmup, the K timed
+steps, the outputs of the last timed step when ``--dump-outputs DIR`` is given
+(DIR/<name>.npy, the same inputs and so the same arrays from run to run), and
+the result line.
+
+With ``--full`` the line also carries everything else the bench measures: the
+decode-only timing, the roofline of the dominant kernel, the dense GEMV probe,
+the CPU baseline, and the other BASELINE configs, each timed on every rank
+with its own roofline: `fp64_leg` (configs[1] in binary64), `batched_legs`
+(configs[2] C3 B = 256 in binary32 / binary64, configs[3] C4 B = 256),
+`mc_stream` (configs[3]'s 10 k-rep Monte-Carlo sweep, one refilled stream,
+with its own CPU baseline) and `joint_leg` (configs[4], the joint AMP<->BP
+step).  The --no-* options below trim a ``--full`` run.
 """
 from __future__ import annotations
 
@@ -648,6 +655,33 @@ def joint_leg(args, device, rank, world):
     return {k: res[k] for k in keep if k in res}
 
 
+DUMP_BETA_BYTES = 48 << 20  # --dump-outputs keeps at most this much of beta (the other arrays are small)
+
+
+def dump_outputs(path, op, B, decisions, rank):
+    """--dump-outputs: what the last timed step left for its caller, written as
+    <name>.npy under `path` (<name>_rank<r>.npy on the ranks above 0):
+    `decisions`, the (B, L) section indices the step returned, in float32;
+    `beta`, the decode's estimate (sa_fetch), (B, L*M) in float64, or, where
+    that exceeds DUMP_BETA_BYTES, its codewords `beta_rows` (a fixed sample:
+    RandomState(0), ascending; float32 indices); `iters`, the (B,) iteration
+    counts, in float32.  Returns {name: shape}."""
+    beta, iters = op.fetch(B)
+    out = {"decisions": np.asarray(decisions, dtype=np.float32), "iters": np.asarray(iters, dtype=np.float32)}
+    keep = DUMP_BETA_BYTES // (beta.shape[1] * 8)
+    if keep < 1:
+        raise ValueError(f"--dump-outputs: one codeword's beta ({beta.shape[1] * 8} bytes) exceeds the dump's budget")
+    if B > keep:
+        rows = np.sort(np.random.RandomState(0).choice(B, keep, replace=False))
+        out["beta_rows"] = rows.astype(np.float32)
+        beta = beta[rows]
+    out["beta"] = np.ascontiguousarray(beta, dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -659,6 +693,12 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp64"])
     ap.add_argument("--batch", type=int, default=0, help="override codewords per step")
     ap.add_argument("--plan", default="", help="comma-separated plan options (sa_create_ex), e.g. ONE_PASS")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the decode-only timing, the roofline, the binary64 and batched "
+                         "legs, the Monte-Carlo stream, the joint leg, the dense GEMV probe and the CPU baseline "
+                         "(the --no-* options trim these)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=0)
@@ -667,7 +707,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-fp64", action="store_true", help="skip the binary64 leg of an fp32 run")
     ap.add_argument("--no-legs", action="store_true",
                     help="skip the batched legs (configs[2] fp32 / fp64, configs[3], the configs[3] Monte-Carlo "
-                         "stream) of the default configs[1] line")
+                         "stream) of the --full configs[1] line")
     ap.add_argument("--leg-steps", type=int, default=10)
     ap.add_argument("--leg-warmup", type=int, default=2)
     ap.add_argument("--joint-steps", type=int, default=3, help="timed steps of the configs[4] joint leg (0: skip it)")
@@ -730,9 +770,8 @@ def main(argv=None, make_op=None):
     times = dist.allreduce_sum(np.eye(world)[rank] * mine) if world > 1 else np.array([mine])
     errs = dist.allreduce_sum(np.array([ts["section_errors"], ts["decided_steps"]], dtype=np.float64))
     ms_per_step = round(elapsed / args.steps * 1e3, 4)
-    # the decodes alone (no decision), same protocol: the round-4 definition of a step
-    ts0 = timed_steps(op, B, T, args.steps, min(args.warmup, 1), decide=False)
-    roofline = measure_roofline(op, args.workload, L, M, n, B, T, args.precision, ms_per_step)
+    # the last timed step's outputs, before anything else runs on the operator
+    dumped = dump_outputs(args.dump_outputs, op, B, ts["last_decisions"], rank) if args.dump_outputs else None
     result = {
         "metric": f"decoded codewords/sec (T AMP iters) at L={L},M={M}; achieved HBM GB/s vs roofline",
         "value": round(B * args.steps * world / elapsed, 3),
@@ -760,11 +799,16 @@ def main(argv=None, make_op=None):
                               "AMP leaves many sections wrong (the reference studies initialisations there); "
                               "cpu_baseline.decisions_vs_gpu_codeword0 holds the oracle's decisions of codeword 0 "
                               "against these"},
-        "decode_only": {"value": round(B * args.steps * world / ts0["elapsed"], 3),
-                        "ms_per_step": round(ts0["elapsed"] / args.steps * 1e3, 4),
-                        "note": "sa_run alone, beta left on the device (no decision)"},
-        "roofline": roofline,
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if args.full:
+        # the decodes alone (no decision), same protocol: the round-4 definition of a step
+        ts0 = timed_steps(op, B, T, args.steps, min(args.warmup, 1), decide=False)
+        result["decode_only"] = {"value": round(B * args.steps * world / ts0["elapsed"], 3),
+                                 "ms_per_step": round(ts0["elapsed"] / args.steps * 1e3, 4),
+                                 "note": "sa_run alone, beta left on the device (no decision)"}
+        result["roofline"] = measure_roofline(op, args.workload, L, M, n, B, T, args.precision, ms_per_step)
     # the headline's context (and its HIP stream) goes before the legs: a
     # process has GPU_MAX_HW_QUEUES (4) hardware queues, and the joint leg's
     # four streams (two AMP slices, two BP contexts) overlap only on queues of
@@ -775,7 +819,7 @@ def main(argv=None, make_op=None):
         rates = B * args.steps / np.asarray(times)
         result["per_rank"] = {"value_min": round(float(rates.min()), 3), "value_max": round(float(rates.max()), 3),
                               "ms_per_step": [round(float(t) / args.steps * 1e3, 4) for t in times]}
-    if args.precision == "fp32" and args.backend == "hadamard" and not args.no_fp64:
+    if args.full and args.precision == "fp32" and args.backend == "hadamard" and not args.no_fp64:
         # the same workload in binary64 (the reference's precision; the joint
         # decoder's): same seeds, same timing protocol, every rank, with its
         # own live roofline
@@ -792,8 +836,8 @@ def main(argv=None, make_op=None):
                               "section_kernel": op64.plan(B)["section_kernel"],
                               "roofline": measure_roofline(op64, args.workload, L, M, n, B, T, "fp64", ms64)}
         del op64
-    if args.workload == "c2" and args.backend == "hadamard" and args.precision == "fp32" and not args.no_legs \
-            and not args.batch:
+    if args.full and args.workload == "c2" and args.backend == "hadamard" and args.precision == "fp32" \
+            and not args.no_legs and not args.batch:
         # the batched configurations, every rank, each with its own roofline
         legs = {}
         for tag, wl, prec in LEGS:
@@ -803,14 +847,14 @@ def main(argv=None, make_op=None):
             result["mc_stream"] = mc_stream_leg(sp, args, device, rank, world)
             if args.joint_steps > 0:
                 result["joint_leg"] = joint_leg(args, device, rank, world)
-    if rank == 0 and not args.no_dense:
+    if args.full and rank == 0 and not args.no_dense:
         # after the timed region, on rank 0's GPU: the N-rank line carries the
         # dense GEMV probe as well
         try:
             result["dense_gemv"] = dense_gemv_probe(device)
         except Exception as e:  # report, never hide
             result["dense_gemv"] = {"error": str(e)}
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         # after the timed region (every rank), on rank 0's host cores: the
         # N-rank line carries its own CPU baseline
         result["cpu_baseline"] = cpu_baseline(w, args.cpu_procs or None, args.cpu_iters or None,

@@ -11,7 +11,7 @@ for var in "$@"; do
   [ "$lib" != "$var" ] && envs=${var%@*}
   for wl in ${WORKLOADS:-c2}; do
     i=$((i+1)); log=gpurun_out/ab_${i}_$wl.log
-    env ${envs//,/ } SPARC_AMP_LIB=$lib timeout -k 10 120 python bench.py --no-cpu --no-dense --workload $wl $ARGS > $log 2>&1
+    env ${envs//,/ } SPARC_AMP_LIB=$lib timeout -k 10 120 python bench.py --full --no-cpu --no-dense --workload $wl $ARGS > $log 2>&1
     rc=$?
     python - "$var" "$wl" $log <<'PY'
 import json, sys

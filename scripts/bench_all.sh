@@ -16,23 +16,23 @@ b() {  # tag, args...
 }
 GROUP=${1:-all}  # a: the factorised-operator lines; b: dense / matrix / joint / rehearsal / sweep
 if [ "$GROUP" != b ]; then
-b c2
-b c3 --workload c3 --no-cpu --no-dense
-b c4 --workload c4 --no-cpu --no-dense
-b c4b1 --workload c4 --batch 1 --no-cpu --no-dense
-b c3f64 --workload c3 --precision fp64 --no-fp64 --no-cpu --no-dense
-b c4f64 --workload c4 --precision fp64 --no-fp64 --no-cpu --no-dense --steps 10 --warmup 2
+b c2 --full
+b c3 --full --workload c3 --no-cpu --no-dense
+b c4 --full --workload c4 --no-cpu --no-dense
+b c4b1 --full --workload c4 --batch 1 --no-cpu --no-dense
+b c3f64 --full --workload c3 --precision fp64 --no-fp64 --no-cpu --no-dense
+b c4f64 --full --workload c4 --precision fp64 --no-fp64 --no-cpu --no-dense --steps 10 --warmup 2
 fi
 [ "$GROUP" = a ] && exit 0
-b c3dense --workload c3 --backend dense --no-cpu --no-dense --steps 5 --warmup 1
-b c4b1dense --workload c4 --batch 1 --backend dense --no-cpu --no-dense --steps 3 --warmup 1
-b c2matrix --backend matrix --no-cpu --no-dense --no-fp64 --steps 5 --warmup 1
-b c3matrix --workload c3 --backend matrix --no-cpu --no-dense --no-fp64 --steps 2 --warmup 1
+b c3dense --full --workload c3 --backend dense --no-cpu --no-dense --steps 5 --warmup 1
+b c4b1dense --full --workload c4 --batch 1 --backend dense --no-cpu --no-dense --steps 3 --warmup 1
+b c2matrix --full --backend matrix --no-cpu --no-dense --no-fp64 --steps 5 --warmup 1
+b c3matrix --full --workload c3 --backend matrix --no-cpu --no-dense --no-fp64 --steps 2 --warmup 1
 timeout -k 10 600 python scripts/bench_joint.py > gpurun_out/bench_joint.log 2>&1 || { echo "joint failed"; tail -5 gpurun_out/bench_joint.log; exit 1; }
 grep '^{' gpurun_out/bench_joint.log | tail -1 > gpurun_out/bench_joint.json
 python3 -c "import json; d=json.load(open('gpurun_out/bench_joint.json')); print('joint', d['value'], d['ms_per_step'], d['step_share_ms'], d['cpu_baseline']['value'])"
 SPARC_DIST_BACKEND=socket timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --no-fp64 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 --no-fp64 \
   > gpurun_out/bench_c2_rehearse_socket2.log 2>&1 || { echo "rehearsal failed"; tail -20 gpurun_out/bench_c2_rehearse_socket2.log; exit 1; }
 grep '^{' gpurun_out/bench_c2_rehearse_socket2.log | tail -1 > gpurun_out/bench_c2_rehearse_socket2.json
 python3 -c "import json; d=json.load(open('gpurun_out/bench_c2_rehearse_socket2.json')); print('rehearsal', d['n_gpus'], d['value'], d['config']['parallelism'])"

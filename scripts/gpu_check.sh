@@ -16,5 +16,5 @@ step() {  # name timeout cmd...
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 900 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS}
-step bench 600 python bench.py --steps 10 --warmup 2 ${BENCH_ARGS}
+step bench 600 python bench.py --full --steps 10 --warmup 2 ${BENCH_ARGS}
 if [ -n "$EXTRA_BENCH" ]; then step bench_extra 600 python bench.py $EXTRA_BENCH; fi

@@ -26,7 +26,7 @@ done
 step bp_empty_tail 200 python scripts/bp_empty_tail.py
 cat gpurun_out/bp_empty_tail.log
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  step bench 500 python bench.py
+  step bench 500 python bench.py --full
   tail -1 gpurun_out/bench.log > gpurun_out/bench.json
   python3 - <<'PY'
 import json

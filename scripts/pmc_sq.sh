@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${1:-sq}; shift
 # SCRIPT=scripts/bp_time.py runs another program with its own arguments
-if [ -n "$SCRIPT" ]; then PROG=("$SCRIPT" "$@"); else PROG=(bench.py --no-cpu --no-dense "$@"); fi
+if [ -n "$SCRIPT" ]; then PROG=("$SCRIPT" "$@"); else PROG=(bench.py --full --no-cpu --no-dense "$@"); fi
 OUT=gpurun_out/sq_$TAG; mkdir -p $OUT
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM" \

@@ -59,6 +59,10 @@ class FakeOp:
     def wait(self):
         pass
 
+    def fetch(self, B):
+        beta = np.arange(B * self.L * self.M, dtype=np.float64).reshape(B, self.L * self.M) + self.runs
+        return beta, np.full(B, self.T, dtype=np.int32)
+
     def plan(self, B):
         return dict(section_kernel="k_sec4", partials=256, row_splits=1, codewords_per_wg=1, zz_partials=288,
                     w=self.w, row_kernel="k_row2_16", cus=256)
@@ -91,7 +95,8 @@ def test_n_rank_bench_line_carries_cpu_baseline_and_spread(world):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    argv = ["--gpus", str(world), "--steps", "4", "--warmup", "1", "--no-dense", "--cpu-procs", "1", "--cpu-iters", "1"]
+    argv = ["--gpus", str(world), "--steps", "4", "--warmup", "1", "--full", "--no-dense", "--cpu-procs", "1",
+            "--cpu-iters", "1"]
     ps = [ctx.Process(target=_rank, args=(r, world, port, q, argv)) for r in range(world)]
     for p in ps:
         p.start()
@@ -146,6 +151,63 @@ def test_n_rank_bench_line_carries_cpu_baseline_and_spread(world):
         assert it["minimal_bytes"] > 0 and it["partials_bytes"] > 0 and 0 < it["frac_minimal"] < r["frac"] + 1, tag
         assert de["flops_per_iteration"] == 4.0 * n * L * M * 256, tag
         assert abs(de["tflops"] - de["flops_per_iteration"] / (it["ms"] * 1e-3) / 1e12) <= 0.1 + 1e-3 * de["tflops"], tag
+
+
+def test_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path, monkeypatch, capsys):
+    """A run without --full sets up, warms up, times --steps steps and prints
+    the headline line: none of the other measurements run (no profiling decode,
+    no further operator, no CPU baseline).  --dump-outputs writes the last
+    timed step's arrays, the same from run to run; a batch whose beta exceeds
+    the dump's budget is sampled by a fixed choice of codewords."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SPARC_DIST_BACKEND"):
+        monkeypatch.delenv(k, raising=False)
+    made = []
+
+    class PlainOp(FakeOp):
+        def __init__(self, *a):
+            super().__init__(*a)
+            made.append(self)
+
+        def profile(self, *a, **k):
+            raise AssertionError("a plain run profiles nothing")
+
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("a plain run has no CPU baseline"))
+    steps, warmup = 3, 2
+    lines = []
+    for d in ("a", "b"):
+        res = bench.main(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path / d)], make_op=PlainOp)
+        lines.append(json.loads(capsys.readouterr().out.strip().splitlines()[-1]))
+        assert lines[-1] == json.loads(json.dumps(res))
+    assert len(made) == 2 and all(op.runs == steps + warmup for op in made)  # one operator per run, no other decode
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["steps"] == steps and line["dtype"] == "f32" and line["unit"] == "codewords/s"
+    assert abs(line["value"] - steps / (line["ms_per_step"] * steps / 1e3)) <= 1e-3 * line["value"]
+    assert line["decisions"]["decided_steps"] == steps
+    for k in ("decode_only", "roofline", "fp64_leg", "batched_legs", "mc_stream", "joint_leg", "dense_gemv",
+              "cpu_baseline"):
+        assert k not in line, k
+    # the dump: c2 is one codeword of L = M = 512
+    assert line["dumped_outputs"] == {"decisions": [1, 512], "iters": [1], "beta": [1, 512 * 512]}
+    got = {d: {f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))} for d in ("a", "b")}
+    assert sorted(got["a"]) == ["beta.npy", "decisions.npy", "iters.npy"]
+    for f, a in got["a"].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, got["b"][f]), f
+    assert got["a"]["beta.npy"][0, 0] == steps + warmup  # fetched after the last timed step, before anything else ran
+    # a batch above the budget: a fixed, ascending sample of whole codewords, within 64 MB in all
+    op = FakeOp(512, 512, 4608, "hadamard", "fp32", 0, None)
+    op.reserve(64, 1)
+    shapes = [bench.dump_outputs(str(tmp_path / d), op, 64, np.zeros((64, 512), dtype=np.int32), 0) for d in ("c", "d")]
+    rows = np.load(tmp_path / "c" / "beta_rows.npy")
+    keep = bench.DUMP_BETA_BYTES // (512 * 512 * 8)
+    assert shapes[0] == shapes[1] and shapes[0]["beta"] == [keep, 512 * 512] and keep < 64
+    assert np.array_equal(rows, np.load(tmp_path / "d" / "beta_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "c" / "beta.npy")[:, 0], rows * 512 * 512)
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 64e6
 
 
 def test_timed_step_includes_the_decision():
