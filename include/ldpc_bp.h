@@ -99,6 +99,37 @@ int lb_info(lb_ctx* ctx, long long* out);
  * default chosen at lb_create (8, or the environment's LDPC_BP_TAIL); 0: off.
  * Needs variable degrees <= 12 (LB_ERR_UNSUPPORTED otherwise). */
 int lb_set_tail(lb_ctx* ctx, int tail_at);
+
+/* ---- LDPC-only Monte-Carlo (sim_ldpc sparc_ldpc.py:1064-1124, ldpc_awgn.py, ldpc_bsc.py) ---- */
+/* Block s is its seed: RandomState(seeds[i]) draws randint(0, 2, K) into
+ * u[i][K] (bits as bytes; skipped when K == 0, u may then be NULL) and then
+ * randn(N) (kind 0) or random_sample(N) (kind 1) into w[i][N], bit for bit
+ * NumPy's legacy generator, over at most `threads` host threads (<= 0: the
+ * host's, at most 16).  Host arrays; needs no device. */
+int lb_draw_blocks(const unsigned int* seeds, int nblk, int K, int N, int kind, unsigned char* u, double* w,
+                   int threads);
+
+/* The quasi-cyclic encoder of the context's code: proto[Mp][Np] base matrix of
+ * shifts (-1: no block, as ldpc.py:26-663), lifting size z, Np z = Nv and
+ * Mp z = Nc.  Mp == 0: no encoder (the all-zero word).  LB_ERR_ARG when the
+ * shifts of column Np - Mp do not reduce to a single offset (ldpc.py:815-822;
+ * checked on the host before anything else). */
+int lb_mc_set_code(lb_ctx* ctx, const int* proto, int Mp, int Np, int z);
+
+/* x[B][Nv] = the systematic codewords of u[B][Nv - Nc] (bits as bytes), encoded
+ * on the device.  Host pointers; blocking. */
+int lb_encode(lb_ctx* ctx, int B, const unsigned char* u, unsigned char* x);
+
+/* nblk blocks, `batch` at a time: encode u[nblk][Nv - Nc] (NULL: the all-zero
+ * word), channel LLRs from w[nblk][Nv] on the device, decode, count.
+ *   kind 0 (AWGN, a = sigma): ch = (2 / sigma^2) ((1 - 2 x) + sigma w)
+ *   kind 1 (BSC, a = p, u NULL): ch = -log((1 - p) / p) where w < p, + elsewhere
+ * errs[nblk] = sum((app < 0) != x) over the Nv bits, iters[nblk] = the
+ * decoder's iteration counts.  Host pointers; blocking; lb_run_event_ms gives
+ * the device time of the whole run. */
+int lb_mc_run(lb_ctx* ctx, int nblk, const unsigned char* u, const double* w, double a, int kind, int batch,
+              int algo, double corr_factor, int max_iter, int* errs, int* iters);
+
 int lb_device_count(void);
 const char* lb_last_error(void);
 const char* lb_version(void);

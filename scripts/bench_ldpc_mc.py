@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""sim_ldpc (host draws / encode / count, GPU decode) against ldpc_mc.sim_ldpc_mc
+(native draws, everything else on the device) at 802.16 5/6 z=192,
+sigma = sqrt(1 / (2 * 10**(5.33/20))): exactly 8192 blocks each (MIN_ERRORS out
+of reach, MAX_BLOCKS = 8192), batch 1024.  One warm-up of each, then the two
+alternate three times in one process; every wall time is taken around a device
+synchronise.  Prints one JSON line and writes it to results/ldpc_mc.json
+(or --out): medians, spread, blocks/s, and the new path's split."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BLOCKS, BATCH, REPS = 8192, 1024, 3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "results", "ldpc_mc.json"))
+    args = ap.parse_args()
+    import sparc_ldpc_amd as sp
+    from sparc_ldpc_amd import ldpc
+    lib = ldpc.load_bp_library()
+    assert lib.lb_device_count() > 0, "no HIP device visible"
+    lp = sp.LDPCParams("802.16", "5/6", 192)
+    sigma = float(np.sqrt(1 / (2 * 10 ** (5.33 / 20))))
+    never = 10 ** 9
+
+    def sync():
+        assert lib.hipDeviceSynchronize() == 0
+
+    def old(seed):
+        sync()
+        t0 = time.perf_counter()
+        ber = sp.sim_ldpc(lp, sigma, MIN_ERRORS=never, MAX_BLOCKS=BLOCKS, batch=BATCH, seed=seed)
+        sync()
+        return time.perf_counter() - t0, ber
+
+    def new(seed0):
+        tm = {}
+        sync()
+        t0 = time.perf_counter()
+        r = sp.sim_ldpc_mc(lp, sigma, MIN_ERRORS=never, MAX_BLOCKS=BLOCKS, seed0=seed0, batch=BATCH, timings=tm)
+        sync()
+        wall = time.perf_counter() - t0
+        assert r["blocks"] == BLOCKS
+        return wall, r, tm
+
+    old(1)
+    new(1)
+    t_old, t_new, bers_old, res_new, splits = [], [], [], [], []
+    for k in range(REPS):
+        w, ber = old(100 + k)
+        t_old.append(w)
+        bers_old.append(ber)
+        w, r, tm = new(100_000 * (k + 1))
+        t_new.append(w)
+        res_new.append(r)
+        splits.append(dict(wall_s=w, draw_s=tm["draw_s"], device_ms=tm["device_ms"],
+                           rest_s=w - tm["device_ms"] / 1e3))
+    med_old, med_new = statistics.median(t_old), statistics.median(t_new)
+    spread = max(max(t_old) - min(t_old), max(t_new) - min(t_new))
+    out = dict(
+        workload="802.16 5/6 z=192, sigma=%.6f, %d blocks, batch %d" % (sigma, BLOCKS, BATCH),
+        sim_ldpc=dict(wall_s=t_old, median_s=med_old, blocks_per_s=BLOCKS / med_old, ber=bers_old),
+        sim_ldpc_mc=dict(wall_s=t_new, median_s=med_new, blocks_per_s=BLOCKS / med_new,
+                         ber=[r["ber"] for r in res_new], block_errors=[r["block_errors"] for r in res_new],
+                         nit_total=[r["nit_total"] for r in res_new], split=splits,
+                         split_note="draw_s: native draws, in a worker thread beside the device work after the "
+                                    "first round; device_ms: events around encode + BP + count; rest_s: wall "
+                                    "minus device time (exposed draw, staging copies, Python)"),
+        spread_s=spread, speedup=med_old / med_new,
+        within_bar=bool(med_new <= med_old + spread),
+    )
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

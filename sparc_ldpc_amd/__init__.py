@@ -18,6 +18,8 @@ from . import ldpc
 from .ldpc import code, LdpcBpError
 from .joint import (JointDecoder, joint_decoder, soft_amp_ldpc_sim, hardinitbeta_amp_ldpc_sim, sim_ldpc, soft_hard_plot,
                     waterfall, sp2bp, bp2sp, mc_joint)
+from . import ldpc_mc, ldpc_awgn, ldpc_bsc
+from .ldpc_mc import draw_blocks, mc_ldpc, sim_ldpc_mc
 from . import threshold
 from .threshold import (hard_initialisation, prep_y, calc_E, hist_E, calc_I_e, J, J_inverse,
                         soft_amp_ldpc_hardinit, ber_from_LLRs, soft_hardinit_plot, calc_E_batch, amp_exit_curve)

@@ -32,7 +32,7 @@
 #include <tuple>
 #include <vector>
 
-#include "ldpc_bp.h"
+#include "ldpc_bp_int.h"
 
 #pragma clang fp contract(off)
 
@@ -42,17 +42,20 @@ namespace {
 
 thread_local std::string g_err;
 
+}  // namespace
+
+namespace lb {
+
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIP_TRY(expr)                                                            \
-  do {                                                                           \
-    hipError_t _e = (expr);                                                      \
-    if (_e != hipSuccess)                                                        \
-      return fail(LB_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
-  } while (0)
+}  // namespace lb
+
+using namespace lb;
+
+namespace {
 
 constexpr int kMaxThreads = 1024;
 constexpr size_t kLdsBytes = 160 * 1024;
@@ -535,37 +538,11 @@ int default_device() {
 
 }  // namespace
 
-struct lb_ctx {
-  int dev = 0, Nv = 0, Nc = 0, Nmsg = 0, maxdv = 0, maxdc = 0, mindc = 0, nt = 0;
-  bool fixed = false;  // check-regular with a straight-line check kernel (lxfb_fixed)
-  bool lds = false;
-  // tail launches (k_bp_tail): edge tables, per-word state, first tail iteration
-  int tail_at = 0, nq = 0, ncu = 256;
-  int* d_evar = nullptr;
-  int *d_active = nullptr, *d_nact = nullptr, *d_done = nullptr, *d_lastbad = nullptr;
-  int* h_nact = nullptr;  // pinned: [0] words entering the tail, [1..2] done counts of the last chunks,
-                        // [3] the last device-sized tail's words
-  hipEvent_t evc[2] = {nullptr, nullptr};
-  hipEvent_t evn = nullptr;   // device-sized tails: its word count has landed in h_nact[0]
-  bool est_pending = false;   // a device-sized tail's word count is in flight
-  int est_n = 0, est_B = 0, est_Bq = 0;  // the last landed count and its batch; the batch in flight
-  int capTailB = 0;
-  int tail_default = 0;       // tail_at chosen at lb_create (kTailAt or LDPC_BP_TAIL)
-  int* d_vedge = nullptr;
-  uint8_t* d_vdeg = nullptr;
-  int* d_cstart = nullptr;
-  double *d_ch = nullptr, *d_app = nullptr, *d_msg = nullptr;
-  int* d_it = nullptr;
-  int capB = 0, capMsgB = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool attrs_set = false;
-};
-
-namespace {
+namespace lb {
 
 void release(lb_ctx* c) {
   if (!c) return;
+  mc_release(c);
   (void)hipSetDevice(c->dev);
   (void)hipFree(c->d_vedge);
   (void)hipFree(c->d_vdeg);
@@ -662,6 +639,7 @@ int set_attrs(lb_ctx* c) {
   return LB_OK;
 }
 
+// (lb::launch, declared in ldpc_bp_int.h)
 // sized_on_host: the tail's shape from the number of words still running
 // (one read-back; the caller blocks anyway), else sized on the device and
 // queued without waiting (see TailArgs)
@@ -800,6 +778,10 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
   HIP_TRY(hipGetLastError());
   return LB_OK;
 }
+
+}  // namespace lb
+
+namespace {
 
 // Graph cache for the reference-signature entry points (one decode per call,
 // the graph identical across calls in the reference's harness).

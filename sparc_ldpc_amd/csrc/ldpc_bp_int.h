@@ -1,0 +1,67 @@
+// ldpc_bp_int.h — what the translation units of libldpc_bp.so share: the
+// decoder context and the helpers defined in ldpc_bp.hip that the Monte-Carlo
+// unit (ldpc_mc.hip) builds on.  Not part of the C ABI (include/ldpc_bp.h).
+#ifndef LDPC_BP_INT_H
+#define LDPC_BP_INT_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "ldpc_bp.h"
+
+struct lb_mc;  // the Monte-Carlo pipeline's state (ldpc_mc.hip)
+
+struct lb_ctx {
+  int dev = 0, Nv = 0, Nc = 0, Nmsg = 0, maxdv = 0, maxdc = 0, mindc = 0, nt = 0;
+  bool fixed = false;  // check-regular with a straight-line check kernel (lxfb_fixed)
+  bool lds = false;
+  // tail launches (k_bp_tail): edge tables, per-word state, first tail iteration
+  int tail_at = 0, nq = 0, ncu = 256;
+  int* d_evar = nullptr;
+  int *d_active = nullptr, *d_nact = nullptr, *d_done = nullptr, *d_lastbad = nullptr;
+  int* h_nact = nullptr;  // pinned: [0] words entering the tail, [1..2] done counts of the last chunks,
+                        // [3] the last device-sized tail's words
+  hipEvent_t evc[2] = {nullptr, nullptr};
+  hipEvent_t evn = nullptr;   // device-sized tails: its word count has landed in h_nact[0]
+  bool est_pending = false;   // a device-sized tail's word count is in flight
+  int est_n = 0, est_B = 0, est_Bq = 0;  // the last landed count and its batch; the batch in flight
+  int capTailB = 0;
+  int tail_default = 0;       // tail_at chosen at lb_create (kTailAt or LDPC_BP_TAIL)
+  int* d_vedge = nullptr;
+  uint8_t* d_vdeg = nullptr;
+  int* d_cstart = nullptr;
+  double *d_ch = nullptr, *d_app = nullptr, *d_msg = nullptr;
+  int* d_it = nullptr;
+  int capB = 0, capMsgB = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool attrs_set = false;
+  lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
+};
+
+namespace lb {
+
+// record the message lb_last_error returns (per thread) and hand `code` back
+int fail(int code, const std::string& msg);
+
+int dev_alloc(void** p, size_t bytes);
+// the context's ch / app / iters buffers sized for B words
+int ensure_io(lb_ctx* c, int B);
+// queue a decode of B words on the context's stream; sized_on_host = false never waits
+int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
+           int max_iter, bool sized_on_host);
+// free the Monte-Carlo state of a context (ldpc_mc.hip)
+void mc_release(lb_ctx* c);
+
+}  // namespace lb
+
+#define HIP_TRY(expr)                                                                \
+  do {                                                                               \
+    hipError_t _e = (expr);                                                          \
+    if (_e != hipSuccess)                                                            \
+      return lb::fail(LB_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+#endif  // LDPC_BP_INT_H

@@ -1,0 +1,433 @@
+// ldpc_mc.hip — the LDPC-only Monte-Carlo simulators (sim_ldpc,
+// sparc_ldpc.py:1064-1124; ldpc/py/ldpc_awgn.py:60-123; ldpc/ldpc_bsc.py:63-113)
+// around the belief-propagation decoder of ldpc_bp.hip:
+//
+//  * lb_draw_blocks: block s draws RandomState(s).randint(0, 2, K) and then
+//    .randn(N) (or .random_sample(N)), restated natively on the host cores
+//    (legacy_mt.h), bit for bit the same values, over several threads.  Needs
+//    no device.
+//  * k_mc_prep: one workgroup per word.  The quasi-cyclic systematic encoder
+//    of ldpc.py:790-850 on the word's bits in LDS (systematic syndromes, first
+//    parity block, dual-diagonal recursion), then the channel LLRs
+//    ch = (2 / sigma^2) ((1 - 2 x) + sigma w) (AWGN) or +-log((1 - p) / p)
+//    (BSC) in the host's operation order, no contraction: the same bits as
+//    the NumPy expression.
+//  * lb::launch (ldpc_bp.hip), unchanged, queued without waiting.
+//  * k_mc_count: one workgroup per word, sum((app < 0) != x) over the N bits
+//    and the word's iteration count: two ints per word return to the host.
+//  * lb_mc_run: the blocks in batches; the next batch's bits and noise go up
+//    on a second stream through a second pinned staging buffer while the
+//    current batch is encoded, decoded and counted.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "ldpc_bp_int.h"
+#include "legacy_mt.h"
+
+#pragma clang fp contract(off)
+
+struct lb_mc {
+  int Mp = 0, Np = 0, z = 0;  // base matrix shape and lifting size; Mp == 0: no encoder
+  int off = 0;                // the single offset column Kp's shifts reduce to
+  int* d_proto = nullptr;     // [Mp][Np] shifts mod z, -1: no block
+  int cap = 0;                // words the staging buffers hold
+  uint8_t* h_u[2] = {nullptr, nullptr};  // pinned staging, two batches
+  double* h_w[2] = {nullptr, nullptr};
+  uint8_t* d_u[2] = {nullptr, nullptr};
+  double* d_w[2] = {nullptr, nullptr};
+  uint8_t* d_x = nullptr;     // [cap][Nv] codeword bits
+  int* d_res = nullptr;       // [2][capRes] bit errors, iterations
+  int* h_res = nullptr;       // pinned
+  int capRes = 0;
+  hipStream_t copy = nullptr;
+  hipEvent_t ev_up[2] = {nullptr, nullptr};    // staging buffer i has landed on the device
+  hipEvent_t ev_prep[2] = {nullptr, nullptr};  // k_mc_prep has read device buffer i
+};
+
+namespace {
+
+using lb::fail;
+
+constexpr int kPrepThreads = 256, kCountThreads = 256;
+constexpr size_t kPrepLdsBytes = 64 * 1024;
+
+struct PrepArgs {
+  const uint8_t* u;  // [B][K] information bits (encoder only)
+  const double* w;   // [B][N] randn (kind 0) or random_sample (kind 1) values
+  double* ch;        // [B][N]
+  uint8_t* x;        // [B][N] codeword bits
+  const int* proto;  // [Mp][Np]
+  int Mp, Np, z, off, N, K;
+  int kind;          // 0: AWGN, 1: BSC, -1: encode only
+  double c0, a;      // AWGN: 2 / sigma^2, sigma; BSC: log((1 - p) / p), p
+};
+
+// ldpc.py:790-850 (ldpc.encode_batch) per word; np.roll(v, -s)[i] = v[(i + s) mod z]
+__global__ void __launch_bounds__(kPrepThreads) k_mc_prep(PrepArgs a) {
+  extern __shared__ uint8_t lds_bits[];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int z = a.z, Np = a.Np, Mp = a.Mp, Kp = Np - Mp, N = a.N;
+  uint8_t* xs = lds_bits;      // [N] the word
+  uint8_t* ps = lds_bits + N;  // [Mp][z] systematic syndromes
+  if (Mp > 0) {
+    const uint8_t* u = a.u + (size_t)b * a.K;
+    for (int i = tid; i < a.K; i += nt) xs[i] = u[i];
+    __syncthreads();
+    for (int e = tid; e < Mp * z; e += nt) {
+      const int j = e / z, i = e % z;
+      uint8_t acc = 0;
+      for (int k = 0; k < Kp; ++k) {
+        const int s = a.proto[j * Np + k];
+        if (s >= 0) acc ^= xs[k * z + (i + s) % z];
+      }
+      ps[e] = acc;
+    }
+    __syncthreads();
+    // first parity block: the XOR of all p_j rolled by the surviving offset
+    for (int i = tid; i < z; i += nt) {
+      const int src = (i + z - a.off) % z;
+      uint8_t acc = 0;
+      for (int j = 0; j < Mp; ++j) acc ^= ps[j * z + src];
+      xs[Kp * z + i] = acc;
+    }
+    __syncthreads();
+    // dual-diagonal recursion: parity block j + 1 from row j
+    for (int j = 0; j < Mp - 1; ++j) {
+      for (int i = tid; i < z; i += nt) {
+        uint8_t acc = ps[j * z + i];
+        for (int k = 0; k <= j; ++k) {
+          const int s = a.proto[j * Np + Kp + k];
+          if (s >= 0) acc ^= xs[(Kp + k) * z + (i + s) % z];
+        }
+        xs[(Kp + j + 1) * z + i] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  uint8_t* xo = a.x + (size_t)b * N;
+  if (a.kind < 0) {
+    for (int n = tid; n < N; n += nt) xo[n] = xs[n];
+    return;
+  }
+  const double* w = a.w + (size_t)b * N;
+  double* ch = a.ch + (size_t)b * N;
+  for (int n = tid; n < N; n += nt) {
+    const uint8_t bit = Mp > 0 ? xs[n] : (uint8_t)0;
+    xo[n] = bit;
+    if (a.kind == 0)
+      ch[n] = a.c0 * ((1.0 - 2.0 * (double)bit) + a.a * w[n]);
+    else
+      ch[n] = w[n] < a.a ? -a.c0 : a.c0;
+  }
+}
+
+__global__ void __launch_bounds__(kCountThreads) k_mc_count(const double* app, const uint8_t* x, const int* it,
+                                                             int N, int* errs, int* iters) {
+  __shared__ int part[kCountThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const double* ap = app + (size_t)b * N;
+  const uint8_t* xb = x + (size_t)b * N;
+  int cnt = 0;
+  for (int n = tid; n < N; n += kCountThreads) cnt += ((ap[n] < 0.0) != (xb[n] != 0)) ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+  if ((tid & 63) == 0) part[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+    for (int k = 0; k < kCountThreads / 64; ++k) s += part[k];
+    errs[b] = s;
+    iters[b] = it[b];
+  }
+}
+
+// the C library's pow / log, as the Python expressions 2.0 / sigma**2 and
+// log((1 - p) / p) call them (not folded at compile time)
+double (*volatile libm_pow)(double, double) = static_cast<double (*)(double, double)>(::pow);
+double (*volatile libm_log)(double) = static_cast<double (*)(double)>(::log);
+
+void free_staging(lb_mc* m) {
+  for (int i = 0; i < 2; ++i) {
+    if (m->h_u[i]) (void)hipHostFree(m->h_u[i]);
+    if (m->h_w[i]) (void)hipHostFree(m->h_w[i]);
+    (void)hipFree(m->d_u[i]);
+    (void)hipFree(m->d_w[i]);
+    m->h_u[i] = m->d_u[i] = nullptr;
+    m->h_w[i] = m->d_w[i] = nullptr;
+  }
+  (void)hipFree(m->d_x);
+  m->d_x = nullptr;
+  m->cap = 0;
+}
+
+int ensure_state(lb_ctx* c) {
+  if (c->mc) return LB_OK;
+  lb_mc* m = new lb_mc;
+  c->mc = m;  // released with the context whatever fails below
+  if (hipStreamCreateWithFlags(&m->copy, hipStreamNonBlocking) != hipSuccess) {
+    m->copy = nullptr;
+    return fail(LB_ERR_HIP, "stream creation failed");
+  }
+  for (hipEvent_t* e : {&m->ev_up[0], &m->ev_up[1], &m->ev_prep[0], &m->ev_prep[1]})
+    if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) {
+      *e = nullptr;
+      return fail(LB_ERR_HIP, "hipEventCreate failed");
+    }
+  return LB_OK;
+}
+
+// staging for `B` words: two pinned and two device buffers of bits and noise, the codeword bits
+int ensure_staging(lb_ctx* c, int B) {
+  lb_mc* m = c->mc;
+  if (B <= m->cap) return LB_OK;
+  free_staging(m);
+  const size_t K = (size_t)(c->Nv - c->Nc), N = (size_t)c->Nv;
+  int rc;
+  for (int i = 0; i < 2; ++i) {
+    if (K > 0) {
+      if (hipHostMalloc((void**)&m->h_u[i], B * K, hipHostMallocDefault) != hipSuccess) {
+        m->h_u[i] = nullptr;
+        return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
+      }
+      if ((rc = lb::dev_alloc((void**)&m->d_u[i], B * K))) return rc;
+    }
+    if (hipHostMalloc((void**)&m->h_w[i], B * N * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      m->h_w[i] = nullptr;
+      return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
+    }
+    if ((rc = lb::dev_alloc((void**)&m->d_w[i], B * N * sizeof(double)))) return rc;
+  }
+  if ((rc = lb::dev_alloc((void**)&m->d_x, B * N))) return rc;
+  m->cap = B;
+  return LB_OK;
+}
+
+int ensure_results(lb_mc* m, int nblk) {
+  if (nblk <= m->capRes) return LB_OK;
+  (void)hipFree(m->d_res);
+  if (m->h_res) (void)hipHostFree(m->h_res);
+  m->d_res = m->h_res = nullptr;
+  m->capRes = 0;
+  int rc;
+  if ((rc = lb::dev_alloc((void**)&m->d_res, (size_t)2 * nblk * sizeof(int)))) return rc;
+  if (hipHostMalloc((void**)&m->h_res, (size_t)2 * nblk * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+    m->h_res = nullptr;
+    return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
+  }
+  m->capRes = nblk;
+  return LB_OK;
+}
+
+// what ldpc.encode_batch checks (ldpc.py:815-822): the shifts of column Kp,
+// counted mod 2 by their value mod z, leave exactly one offset
+int surviving_offset(const int* proto, int Mp, int Np, int z, int* off) {
+  const int Kp = Np - Mp;
+  std::vector<int> par(z, 0);
+  for (int j = 0; j < Mp; ++j) {
+    const int s = proto[j * Np + Kp];
+    if (s >= 0) par[s % z] ^= 1;
+  }
+  int n = 0;
+  for (int i = 0; i < z; ++i)
+    if (par[i]) {
+      *off = i;
+      ++n;
+    }
+  return n == 1 ? LB_OK : LB_ERR_ARG;
+}
+
+void fill_prep(PrepArgs& p, const lb_ctx* c, bool enc) {
+  const lb_mc* m = c->mc;
+  p.proto = m->d_proto;
+  p.Mp = enc ? m->Mp : 0;
+  p.Np = enc ? m->Np : 0;
+  p.z = enc ? m->z : 1;
+  p.off = m->off;
+  p.N = c->Nv;
+  p.K = c->Nv - c->Nc;
+}
+
+size_t prep_lds(const PrepArgs& p) { return p.Mp > 0 ? (size_t)(p.Np + p.Mp) * p.z : 0; }
+
+}  // namespace
+
+namespace lb {
+
+void mc_release(lb_ctx* c) {
+  lb_mc* m = c->mc;
+  if (!m) return;
+  (void)hipSetDevice(c->dev);
+  free_staging(m);
+  (void)hipFree(m->d_proto);
+  (void)hipFree(m->d_res);
+  if (m->h_res) (void)hipHostFree(m->h_res);
+  for (hipEvent_t e : {m->ev_up[0], m->ev_up[1], m->ev_prep[0], m->ev_prep[1]})
+    if (e) (void)hipEventDestroy(e);
+  if (m->copy) (void)hipStreamDestroy(m->copy);
+  delete m;
+  c->mc = nullptr;
+}
+
+}  // namespace lb
+
+extern "C" {
+
+int lb_draw_blocks(const uint32_t* seeds, int nblk, int K, int N, int kind, uint8_t* u, double* w, int threads) {
+  if (nblk < 0 || K < 0 || N < 0 || (kind != 0 && kind != 1) ||
+      (nblk > 0 && (!seeds || (K > 0 && !u) || (N > 0 && !w))))
+    return fail(LB_ERR_ARG, "lb_draw_blocks: bad arguments");
+  int nt = threads > 0 ? threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  nt = std::max(1, std::min(nt, std::max(1, nblk)));
+  auto work = [&](int t0) {
+    for (int i = t0; i < nblk; i += nt) {
+      legacy_rng::LegacyMT mt(seeds[i]);
+      uint8_t* ub = u + (size_t)i * K;
+      for (int k = 0; k < K; ++k) ub[k] = (uint8_t)mt.bounded(1u);  // randint(0, 2, K)
+      double* wb = w + (size_t)i * N;
+      if (kind == 0)
+        for (int n = 0; n < N; ++n) wb[n] = mt.gaussian();  // randn(N)
+      else
+        for (int n = 0; n < N; ++n) wb[n] = mt.next_double();  // random_sample(N)
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nt; ++t) pool.emplace_back(work, t);
+  work(0);
+  for (auto& th : pool) th.join();
+  return LB_OK;
+}
+
+int lb_mc_set_code(lb_ctx* c, const int* proto, int Mp, int Np, int z) {
+  int off = 0;
+  if (Mp < 0) return fail(LB_ERR_ARG, "lb_mc_set_code: Mp < 0");
+  if (Mp > 0) {
+    if (!proto || Np <= Mp || z < 1) return fail(LB_ERR_ARG, "lb_mc_set_code: bad base matrix shape");
+    for (int i = 0; i < Mp * Np; ++i)
+      if (proto[i] < -1) return fail(LB_ERR_ARG, "lb_mc_set_code: shift below -1");
+    if (surviving_offset(proto, Mp, Np, z, &off))
+      return fail(LB_ERR_ARG, "lb_mc_set_code: the offsets in column Kp do not add to a single offset");
+  }
+  if (!c) return fail(LB_ERR_ARG, "lb_mc_set_code: null context");
+  if (Mp > 0) {
+    if ((long long)Np * z != c->Nv || (long long)Mp * z != c->Nc)
+      return fail(LB_ERR_ARG, "lb_mc_set_code: base matrix does not match the context's graph");
+    if ((size_t)(Np + Mp) * z > kPrepLdsBytes)
+      return fail(LB_ERR_UNSUPPORTED, "lb_mc_set_code: the word does not fit in LDS");
+  }
+  HIP_TRY(hipSetDevice(c->dev));
+  int rc;
+  if ((rc = ensure_state(c))) return rc;
+  lb_mc* m = c->mc;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // no encode in flight reads the old table
+  (void)hipFree(m->d_proto);
+  m->d_proto = nullptr;
+  m->Mp = 0;
+  if (Mp == 0) return LB_OK;
+  std::vector<int> red((size_t)Mp * Np);
+  for (int i = 0; i < Mp * Np; ++i) red[i] = proto[i] < 0 ? -1 : proto[i] % z;
+  if ((rc = lb::dev_alloc((void**)&m->d_proto, red.size() * sizeof(int)))) return rc;
+  HIP_TRY(hipMemcpyAsync(m->d_proto, red.data(), red.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  m->Mp = Mp;
+  m->Np = Np;
+  m->z = z;
+  m->off = off;
+  return LB_OK;
+}
+
+int lb_encode(lb_ctx* c, int B, const uint8_t* u, uint8_t* x) {
+  if (!c) return fail(LB_ERR_ARG, "lb_encode: null context");
+  if (B < 0 || (B > 0 && (!u || !x))) return fail(LB_ERR_ARG, "lb_encode: bad arguments");
+  if (!c->mc || c->mc->Mp == 0) return fail(LB_ERR_ARG, "lb_encode: no encoder set (lb_mc_set_code)");
+  if (B == 0) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  int rc;
+  if ((rc = ensure_staging(c, B))) return rc;
+  lb_mc* m = c->mc;
+  const size_t K = (size_t)(c->Nv - c->Nc), N = (size_t)c->Nv;
+  std::memcpy(m->h_u[0], u, B * K);
+  HIP_TRY(hipMemcpyAsync(m->d_u[0], m->h_u[0], B * K, hipMemcpyHostToDevice, c->stream));
+  PrepArgs p{};
+  fill_prep(p, c, true);
+  p.u = m->d_u[0];
+  p.x = m->d_x;
+  p.kind = -1;
+  hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), c->stream, p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(x, m->d_x, B * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LB_OK;
+}
+
+int lb_mc_run(lb_ctx* c, int nblk, const uint8_t* u, const double* w, double a, int kind, int batch, int algo,
+              double corr, int max_iter, int* errs, int* iters) {
+  if (!c) return fail(LB_ERR_ARG, "lb_mc_run: null context");
+  if (nblk < 0 || batch <= 0 || (kind != 0 && kind != 1) || (nblk > 0 && (!w || !errs || !iters)))
+    return fail(LB_ERR_ARG, "lb_mc_run: bad arguments");
+  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0))
+    return fail(LB_ERR_ARG, "lb_mc_run: sigma must be > 0, p in (0, 1)");
+  const bool enc = u != nullptr;
+  if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_run: the BSC sends the all-zero word (u must be null)");
+  if (enc && (!c->mc || c->mc->Mp == 0)) return fail(LB_ERR_ARG, "lb_mc_run: no encoder set (lb_mc_set_code)");
+  if (nblk == 0) return LB_OK;
+  batch = std::min(batch, nblk);
+  HIP_TRY(hipSetDevice(c->dev));
+  int rc;
+  if ((rc = ensure_state(c))) return rc;
+  if ((rc = lb::ensure_io(c, batch))) return rc;
+  if ((rc = ensure_staging(c, batch))) return rc;
+  lb_mc* m = c->mc;
+  if ((rc = ensure_results(m, nblk))) return rc;
+  const size_t K = (size_t)(c->Nv - c->Nc), N = (size_t)c->Nv;
+  PrepArgs p{};
+  fill_prep(p, c, enc);
+  p.ch = c->d_ch;
+  p.x = m->d_x;
+  p.kind = kind;
+  p.a = a;
+  p.c0 = kind == 0 ? 2.0 / libm_pow(a, 2.0) : libm_log((1.0 - a) / a);
+  const int nb = (nblk + batch - 1) / batch;
+  // batch j into staging buffer j & 1: the host waits only for that buffer's
+  // previous upload (batch j - 2); the upload itself waits for the prep
+  // kernel that read the device buffer
+  auto stage = [&](int j) -> int {
+    const int i = j & 1;
+    const size_t b0 = (size_t)j * batch, B = std::min<size_t>(batch, nblk - b0);
+    if (j >= 2) HIP_TRY(hipEventSynchronize(m->ev_up[i]));
+    if (enc) std::memcpy(m->h_u[i], u + b0 * K, B * K);
+    std::memcpy(m->h_w[i], w + b0 * N, B * N * sizeof(double));
+    if (j >= 2) HIP_TRY(hipStreamWaitEvent(m->copy, m->ev_prep[i], 0));
+    if (enc) HIP_TRY(hipMemcpyAsync(m->d_u[i], m->h_u[i], B * K, hipMemcpyHostToDevice, m->copy));
+    HIP_TRY(hipMemcpyAsync(m->d_w[i], m->h_w[i], B * N * sizeof(double), hipMemcpyHostToDevice, m->copy));
+    HIP_TRY(hipEventRecord(m->ev_up[i], m->copy));
+    return LB_OK;
+  };
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  if ((rc = stage(0))) return rc;
+  for (int k = 0; k < nb; ++k) {
+    const int i = k & 1;
+    const int b0 = k * batch, B = std::min(batch, nblk - b0);
+    HIP_TRY(hipStreamWaitEvent(c->stream, m->ev_up[i], 0));
+    p.u = m->d_u[i];
+    p.w = m->d_w[i];
+    hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), c->stream, p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(m->ev_prep[i], c->stream));
+    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr, max_iter, false))) return rc;
+    hipLaunchKernelGGL(k_mc_count, dim3(B), dim3(kCountThreads), 0, c->stream, c->d_app, m->d_x, c->d_it, (int)N,
+                       m->d_res + b0, m->d_res + nblk + b0);
+    HIP_TRY(hipGetLastError());
+    if (k + 1 < nb && (rc = stage(k + 1))) return rc;
+  }
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  HIP_TRY(hipMemcpyAsync(m->h_res, m->d_res, (size_t)2 * nblk * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::memcpy(errs, m->h_res, (size_t)nblk * sizeof(int));
+  std::memcpy(iters, m->h_res + nblk, (size_t)nblk * sizeof(int));
+  return LB_OK;
+}
+
+}  // extern "C"

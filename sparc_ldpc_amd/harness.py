@@ -288,7 +288,7 @@ def ber_point(decode_round, total_bits, min_errors, max_blocks, batch, rank=0, w
             break
         rnd += 1
     return dict(BER=ber_cum / nblocks, blocks=nblocks, block_errors=nerr, bit_errors=errbits,
-                mean_iters=iters / nblocks)
+                mean_iters=iters / nblocks, iters_total=iters)
 
 
 def waterfall_plain(L, M, P, R, T, ebno_dbs, min_errors=200, max_blocks=250, csv_filename=None,

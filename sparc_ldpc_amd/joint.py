@@ -517,12 +517,14 @@ def sim_ldpc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, b
 def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None, png_filename=None,
               init="soft", pa_param=False, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, bpsk=True,
               sections=512, batch=64, seed0=0, backend=None, precision=None, rank=0, world=1, allreduce=None,
-              ebno_dbs=None):
+              ebno_dbs=None, bpsk_mc=False):
     """The reference's waterfall sweep on the GPU.  Per Eb/N0 point (20 log10
     convention): blocks of the joint scheme ``init`` and of plain SPARC at the
     same overall rate, consumed in seed order until MIN_ERRORS plain block
     errors or MAX_BLOCKS blocks (:1217-1245 counts the PLAIN block errors);
-    BER_bpsk from sim_ldpc.  Reps are sharded over ranks like ber_point.
+    BER_bpsk from sim_ldpc, or with ``bpsk_mc`` from the device-side
+    ldpc_mc.sim_ldpc_mc (its own seeded blocks, sharded over ranks).  Reps are
+    sharded over ranks like ber_point.
     Returns the rows; writes the reference CSV schema (:1257-1264) on rank 0."""
     from .harness import mc_decode
     precision = precision or "fp64"  # see joint_decoder
@@ -569,7 +571,12 @@ def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=Non
         bpsk_ber = 0.0
         if bpsk:
             sigma_bpsk = np.sqrt((1 / ebno) / 2)
-            bpsk_ber = sim_ldpc(ldp, sigma_bpsk, MIN_ERRORS, MAX_BLOCKS, seed=base + 7_000_000)
+            if bpsk_mc:
+                from .ldpc_mc import sim_ldpc_mc
+                bpsk_ber = sim_ldpc_mc(ldp, float(sigma_bpsk), MIN_ERRORS, MAX_BLOCKS, seed0=base + 7_000_000,
+                                       rank=rank, world=world, allreduce=allreduce)["ber"]
+            else:
+                bpsk_ber = sim_ldpc(ldp, sigma_bpsk, MIN_ERRORS, MAX_BLOCKS, seed=base + 7_000_000)
         rows.append(dict(EbN0_dB=float(ebno_db), BER_amp_1=res["cols"][0], BER_ldpc=res["cols"][1],
                          BER_amp_2=res["cols"][2], BER_ldpc_2=res["cols"][3], BER_plain=res["BER"],
                          BER_bpsk=bpsk_ber, blocks=res["blocks"], block_errors=res["block_errors"]))

@@ -26,6 +26,7 @@ LIB_PATH = os.environ.get("LDPC_BP_LIB") or os.path.join(_HERE, "libldpc_bp.so")
 
 LB_SUMPROD2, LB_SUMPROD, LB_MINSUM = 0, 1, 2
 _ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM}
+_CHANNELS = {"awgn": 0, "bsc": 1}  # lb_mc_run / lb_draw_blocks kinds
 
 # Every symbol include/ldpc_bp.h declares (tests check the export table).
 EXPORTS = (
@@ -33,10 +34,12 @@ EXPORTS = (
     "lb_create", "lb_destroy", "lb_decode", "lb_decode_device", "lb_stage", "lb_run", "lb_wait",
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
     "lb_buffers", "lb_set_tail",
+    "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run",
 )
 
 _P, _I, _D = ct.c_void_p, ct.c_int, ct.POINTER(ct.c_double)
 _LP = ct.POINTER(ct.c_long)
+_U8, _IP = ct.POINTER(ct.c_uint8), ct.POINTER(ct.c_int)
 _SIG = {
     "sumprod": (_I, [_D, _LP, _LP, _LP, _I, _I, _I, _D]),
     "sumprod2": (_I, [_D, _LP, _LP, _LP, _I, _I, _I, _D]),
@@ -58,6 +61,10 @@ _SIG = {
     "lb_device_count": (_I, []),
     "lb_last_error": (ct.c_char_p, []),
     "lb_version": (ct.c_char_p, []),
+    "lb_draw_blocks": (_I, [ct.POINTER(ct.c_uint32), _I, _I, _I, _I, _U8, _D, _I]),
+    "lb_mc_set_code": (_I, [_P, _IP, _I, _I, _I]),
+    "lb_encode": (_I, [_P, _I, _U8, _U8]),
+    "lb_mc_run": (_I, [_P, _I, _U8, _D, ct.c_double, _I, _I, _I, ct.c_double, _I, _IP, _IP]),
 }
 
 _lib = None
@@ -189,7 +196,9 @@ class code:
     """Drop-in for ``ldpc.code`` (ldpc/py/ldpc.py:6-24): same attributes
     (standard, rate, z, ptype, proto, vdeg, cdeg, intrlv, Nv, Nc, Nmsg, N, K)
     and methods (assign_proto, pcmat, prepare_decoder, encode, decode, Lxor,
-    Lxfb), plus ``encode_batch`` / ``decode_batch`` for Monte-Carlo."""
+    Lxfb), plus ``encode_batch`` / ``decode_batch`` for Monte-Carlo and the
+    device-side ``encode_device`` / ``mc_blocks`` (encode, channel, decode and
+    error count without a host round trip)."""
 
     def __init__(self, standard="802.11n", rate="1/2", z=27, ptype="A", device=None):
         self.standard = standard
@@ -208,6 +217,7 @@ class code:
         self.K = self.Nv - self.Nc
         self._device = device
         self._ctx = None
+        self._encoder_set = False
 
     # -- construction ---------------------------------------------------------
     def assign_proto(self):
@@ -266,6 +276,70 @@ class code:
                              it.ctypes.data_as(ct.POINTER(ct.c_int)), _ALGOS[dectype],
                              float(corr_factor), int(max_iter)))
         return app, it.astype(np.int64)
+
+    # -- device-side Monte-Carlo (csrc/ldpc_mc.hip) ------------------------------
+    def _set_encoder(self):
+        """Upload the base matrix to the context once (lb_mc_set_code); like
+        encode_batch, NameError when column Kp does not reduce to one offset."""
+        if self._encoder_set:
+            return
+        proto = np.ascontiguousarray(self.proto, dtype=np.intc)
+        Mp, Np = proto.shape
+        lib = load_bp_library()
+        rc = lib.lb_mc_set_code(self._context(), proto.ctypes.data_as(_IP), Mp, Np, int(self.z))
+        if rc == -1 and b"single offset" in lib.lb_last_error():
+            raise NameError("The offsets in colum Kp+1 of proto do not add to a single offset")
+        _check(rc)
+        self._encoder_set = True
+
+    def encode_device(self, U):
+        """encode_batch on the GPU (k_mc_prep's encoder): rows of 0/1 bits -> (B, N) uint8."""
+        U = np.atleast_2d(np.asarray(U))
+        if U.shape[1] != self.K:
+            raise NameError("information word length not compatible with proto and z")
+        if U.size and (U.min() < 0 or U.max() > 1):
+            raise ValueError("information bits must be 0 or 1")
+        U = np.ascontiguousarray(U, dtype=np.uint8)
+        self._set_encoder()
+        X = np.empty((U.shape[0], self.N), dtype=np.uint8)
+        _check(load_bp_library().lb_encode(self._context(), U.shape[0], U.ctypes.data_as(_U8), X.ctypes.data_as(_U8)))
+        return X
+
+    def mc_blocks(self, u, w, a, channel="awgn", batch=1024, dectype="sumprod2", corr_factor=0.7,
+                  max_iter=MAX_ITCOUNT):
+        """Blocks through the device pipeline (lb_mc_run): u (B, K) 0/1 uint8
+        information bits (None: the all-zero word), w (B, N) float64 draws
+        (randn for "awgn", random_sample for "bsc"), a = sigma or p.  Per block:
+        encode, ch = (2/sigma**2) * ((1 - 2x) + sigma*w) or -/+ log((1-p)/p)
+        where w < p / elsewhere, decode, count.  Returns int64 (bit_errors,
+        iters); only those come back from the device."""
+        if dectype not in _ALGOS:
+            raise NameError("Decoder type unknonwn")
+        if channel not in _CHANNELS:
+            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
+        w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
+        if w.shape[1] != self.N:
+            raise NameError("Channel inputs not consistent with variable degrees")
+        B = w.shape[0]
+        up = None
+        if u is not None:
+            if channel == "bsc":
+                raise ValueError("the BSC simulation sends the all-zero word (u must be None)")
+            u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.uint8)
+            if u.shape != (B, self.K):
+                raise NameError("information word length not compatible with proto and z")
+            self._set_encoder()
+            up = u.ctypes.data_as(_U8)
+        errs = np.empty(B, dtype=np.intc)
+        it = np.empty(B, dtype=np.intc)
+        _check(load_bp_library().lb_mc_run(self._context(), B, up, w.ctypes.data_as(_D), float(a),
+                                            _CHANNELS[channel], int(batch), _ALGOS[dectype], float(corr_factor),
+                                            int(max_iter), errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP)))
+        return errs.astype(np.int64), it.astype(np.int64)
+
+    def mc_event_ms(self):
+        """Device milliseconds of the last mc_blocks / run_buffers (events on the context's stream)."""
+        return float(load_bp_library().lb_run_event_ms(self._context()))
 
     def device_buffers(self, B):
         """Device pointers (ch, app, iters) of the decoder's buffers for B words."""
