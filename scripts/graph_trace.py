@@ -35,19 +35,21 @@ def main():
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     seq = [(short(r["Kernel_Name"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"])
            for r in rows]
-    # one decode = k_fill32 (iteration counters) ... k_iters_final; the graph
-    # replays are the decodes whose dispatches follow each other with no host
-    # gap (median gap < 1 us), the eager profiling decodes have launch gaps
-    runs, cur = [], None
+    # one decode = a maximal run of loop kernels: whatever else the stream
+    # carries (the fills and k_iters_final / k_beta_final of the paths that
+    # launch them, k_decide behind every step, conversions, copies) ends a run.
+    # The graph replays are the decodes whose dispatches follow each other with
+    # no host gap (median gap < 1 us), the eager profiling decodes have launch gaps
+    runs, cur = [], []
     for k in seq:
-        if "k_fill32" in k[3]:
-            cur = []
-        elif "k_iters_final" in k[3]:
+        if k[0] in LOOP:
+            cur.append(k[:3])
+        else:
             if cur:
                 runs.append(cur)
-            cur = None
-        elif cur is not None and k[0] in LOOP:
-            cur.append(k[:3])
+            cur = []
+    if cur:
+        runs.append(cur)
     def med_gap(r):
         return st.median([r[i + 1][1] - r[i][2] for i in range(len(r) - 1)]) if len(r) > 1 else 1e9
     timed = [r for r in runs if len(r) > 2 and med_gap(r) < 1000]

@@ -69,6 +69,17 @@ __device__ __forceinline__ T ld_off(const T* base, unsigned byte_off) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
+// Kernel arguments wanted in scalar registers HERE: each value is the SGPR
+// input of an empty asm, so its kernarg load cannot be sunk to its first use
+// along the control flow; the loads of one call (and of adjacent calls) go
+// out as one batch.  Input only: the values stay what the optimiser knows
+// them to be (a pointer through an asm output would lose its global address
+// space and load through FLAT).
+template <typename... T>
+__device__ __forceinline__ void sgpr_now(const T&... v) {
+  (..., [](const auto& x) { asm volatile("" ::"s"(x)); }(v));
+}
+
 // Store of a partial another kernel reads after the boundary (Ab partials):
 // non-temporal, so no dirty L2 line is left for the kernel-end writeback to
 // drain (c2: k_sec4 7.85 -> 7.65 us, +1.5 % codewords/s; c3 neutral).
@@ -910,27 +921,40 @@ struct SecArgs {
   // -1 for an empty slot; null: every codeword is at iteration t
   const int* tb;
   int dead;  // leading dead columns of a padded section (sa_ctx::dead; k_sec only)
+  // k_sec4 / k_sec43: the previous estimate is zero whatever `beta` holds (the
+  // first iteration of a decode without beta0: no zero fill of the buffer)
+  int bzero;
 };
 
 template <typename real>
 struct RowArgs {
-  const real* __restrict__ y;    // [B][n]
-  real* __restrict__ z;          // [B][n] the residual (k_row2: the new one is written here)
-  const real* __restrict__ z_in; // [B][n] the previous residual (= z)
-  const real* __restrict__ abp;  // [B][G][n]
-  const real* __restrict__ bbp;  // [B][G]
-  real* __restrict__ zzp;        // [B][NZ]
+  // Field order: what a launch's first loads need (addresses, counts, mode)
+  // lies in the leading 96 bytes of the kernel-argument segment, what only
+  // the tail of the kernel needs behind it.
   const real* __restrict__ tau;  // [B][T1]
-  real* __restrict__ out;        // [B][n] (ROW_ABOUT)
-  int n, G, Gb, NZ, T1, t, mode, early_stop;  // G Ab partials, Gb beta^2 partials
-  real sqrt_n;
+  const real* __restrict__ y;    // [B][n]
+  const real* __restrict__ z_in; // [B][n] the previous residual (= z)
+  const real* __restrict__ bbp;  // [B][G]
   // total power P = sum(Pl) read from device memory (never a captured
   // argument: a graph replayed after set_power must see the new P):
   // [B] per codeword (sa_stage_power_batch, Pbst = 1) or one shared value (Pbst = 0)
   const real* __restrict__ Pb;
+  const real* __restrict__ abp;  // [B][G][n]
+  // G Ab partials, Gb beta^2 partials; NZ z^2 partials per codeword = the row
+  // blocks of the launch (gridDim.x, asserted in launch_row: the kernels never
+  // read the hidden grid-size argument)
+  int n, G, Gb, NZ, T1, t, mode, early_stop;
   int Pbst;
   int pt;  // Ab partial layout (SecArgs::pt); k_row2 only
   int Bc;  // k_rowc: codewords of the decode (the last chunk may be partial)
+  // k_row2: value its block 0 writes into iters[b] (-1 with the residual's
+  // initialisation, T with the decode's last iteration), 0 for none
+  int itset;
+  real sqrt_n;
+  real* __restrict__ z;          // [B][n] the residual (k_row2: the new one is written here)
+  real* __restrict__ zzp;        // [B][NZ]
+  real* __restrict__ out;        // [B][n] (ROW_ABOUT)
+  int* __restrict__ iters;       // [B] (itset)
   const int* tb;  // k_rowc: per-codeword iteration index (SecArgs::tb), or null
 };
 

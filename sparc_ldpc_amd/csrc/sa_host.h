@@ -139,6 +139,7 @@ struct sa_ctx {
   int last_B = 0, last_T = 0;
   // pinned ring of sa_decide_async: SA_DECIDE_SLOTS slots of dec_cap indices
   int32_t* h_dec = nullptr;
+  int32_t* d_dec = nullptr;  // the ring's device address (k_decide writes the slots itself)
   size_t dec_cap = 0;
   hipEvent_t dec_ev[SA_DECIDE_SLOTS] = {};
   int dec_B[SA_DECIDE_SLOTS] = {};
@@ -271,6 +272,7 @@ SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
   a.sqrt_n = (real)std::sqrt((double)c->n);
   a.tb = c->mc_tb;
   a.dead = c->dead;
+  a.bzero = 0;
   return a;
 }
 
@@ -290,6 +292,8 @@ RowArgs<real> row_args(sa_ctx* c, int mode, int t, int early_stop, int G, int Gb
   a.pt = 0;
   a.Bc = 0;
   a.tb = c->mc_tb;
+  a.iters = c->d_iters;
+  a.itset = 0;
   return a;
 }
 
@@ -331,7 +335,7 @@ extern __global__ void k_fill32(uint32_t* p, uint32_t v, size_t nw);
 template <typename real>
 int launch_sec(sa_ctx* c, int B, int mode, int t, int es, void* bin = nullptr, void* bout = nullptr);
 template <typename real>
-int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt = 0);
+int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt = 0, int bzero = 0);
 hipError_t sec_lds_attrs();
 
 // ---- sa_secb.hip: the batched section kernel ------------------------------------
@@ -343,8 +347,10 @@ bool secb_no_static_lds();
 // ---- sa_row.hip: row kernels, decisions ----------------------------------------
 template <typename real>
 int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt = 0, void* zin = nullptr,
-               void* zout = nullptr);
-int launch_decide(sa_ctx* c, int B);
+               void* zout = nullptr, int itset = 0);
+// k_row2 is the row kernel of the current decode: its launches can carry the iters writes (RowArgs::itset)
+inline bool row_sets_iters(const sa_ctx* c) { return c->row_kind == 1 || c->row_kind == 4; }
+int launch_decide(sa_ctx* c, int B, int32_t* idx);  // idx: device-visible [B][L]
 
 // ---- sa_dense.hip: the materialised-matrix backends ----------------------------
 int dense_parts(const sa_ctx* c, int B);  // Ab partials of the dense A beta (GEMM K splits or GEMV splits)

@@ -28,11 +28,12 @@ __global__ void __launch_bounds__(kRowWaves * 64) k_row(RowArgs<real> a) {
   // partials (y, z, the beta^2 partials) are loaded up front, in the same
   // round trip as the partials
   const size_t o = (size_t)b * n + (r < n ? r : 0);
-  real yv = 0, zv = 0, bbv[2] = {0, 0};
+  real yv = 0, zv = 0, Pv = 0, bbv[2] = {0, 0};
   if (wv == 0) {
     yv = a.y[o];
     if (a.mode == ROW_AMP) {
       zv = a.z[o];
+      Pv = ld_vmem(a.Pb + (size_t)b * a.Pbst);  // with the first loads, not behind the barrier
       const real* bp = a.bbp + (size_t)b * a.Gb;
       bbv[0] = lane < a.Gb ? bp[lane] : (real)0;
       bbv[1] = lane + 64 < a.Gb ? bp[lane + 64] : (real)0;
@@ -61,7 +62,7 @@ __global__ void __launch_bounds__(kRowWaves * 64) k_row(RowArgs<real> a) {
   real ons = 0;
   if (a.mode == ROW_AMP) {
     const real bb = a.Gb <= 128 ? wave_sum_pair(bbv[0], bbv[1]) : wave_sum_parts(a.bbp + (size_t)b * a.Gb, a.Gb);
-    ons = a.Pb[(size_t)b * a.Pbst] - bb / (real)n;
+    ons = Pv - bb / (real)n;
   }
   real zn = 0;
   if (r < n) {
@@ -106,11 +107,12 @@ __global__ void __launch_bounds__(256) k_rowv(RowArgs<real> a) {
   }
   const size_t o = (size_t)b * n + (in ? r : 0);
   fv yv = {}, zv = {};
-  real bbv[2] = {0, 0};
+  real Pv = 0, bbv[2] = {0, 0};
   if (wv == 0) {
     yv = *reinterpret_cast<const fv*>(a.y + o);
     if (a.mode == ROW_AMP) {
       zv = *reinterpret_cast<const fv*>(a.z + o);
+      Pv = ld_vmem(a.Pb + (size_t)b * a.Pbst);  // with the first loads, not behind the barrier
       const real* bp = a.bbp + (size_t)b * a.Gb;
       bbv[0] = lane < a.Gb ? bp[lane] : (real)0;
       bbv[1] = lane + 64 < a.Gb ? bp[lane + 64] : (real)0;
@@ -140,7 +142,7 @@ __global__ void __launch_bounds__(256) k_rowv(RowArgs<real> a) {
   real ons = 0;
   if (a.mode == ROW_AMP) {
     const real bb = a.Gb <= 128 ? wave_sum_pair(bbv[0], bbv[1]) : wave_sum_parts(a.bbp + (size_t)b * a.Gb, a.Gb);
-    ons = a.Pb[(size_t)b * a.Pbst] - bb / (real)n;
+    ons = Pv - bb / (real)n;
   }
   fv zn = {};
   if (in) {
@@ -212,7 +214,7 @@ __global__ void __launch_bounds__(256) k_rowc(RowArgs<real> a, int pil) {
   }
   if (!anyv) return;  // uniform: a chunk of empty slots (Monte-Carlo stream tail)
   // wave 0's operands that do not depend on the partials, loaded with them
-  real tau[CB], last[CB], yv[RPL][CB], bbv[CB][2];
+  real tau[CB], last[CB], yv[RPL][CB], bbv[CB][2], Pv[CB];
   V zo[RPL] = {};
   if (wv == 0) {
 #pragma unroll
@@ -225,6 +227,7 @@ __global__ void __launch_bounds__(256) k_rowc(RowArgs<real> a, int pil) {
         const real* bp = a.bbp + (size_t)bc[c] * a.Gb;
         bbv[c][0] = lane < a.Gb ? bp[lane] : (real)0;
         bbv[c][1] = lane + 64 < a.Gb ? bp[lane + 64] : (real)0;
+        Pv[c] = ld_vmem(a.Pb + (size_t)bc[c] * a.Pbst);  // with the first loads, not behind the barrier
       }
 #pragma unroll
       for (int k = 0; k < RPL; ++k) yv[k][c] = a.y[(size_t)bc[c] * n + ro[k]];
@@ -275,7 +278,7 @@ __global__ void __launch_bounds__(256) k_rowc(RowArgs<real> a, int pil) {
       sacc += bbv[c][0];
       sacc += bbv[c][1];
       const real bb = a.Gb <= 128 ? wave_sum(sacc) : wave_sum_parts(a.bbp + (size_t)bc[c] * a.Gb, a.Gb);
-      ons = a.Pb[(size_t)bc[c] * a.Pbst] - bb / (real)n;
+      ons = Pv[c] - bb / (real)n;
     }
 #pragma unroll
     for (int k = 0; k < RPL; ++k) {
@@ -310,43 +313,67 @@ __global__ void __launch_bounds__(256) k_rowc(RowArgs<real> a, int pil) {
 // (all loads of a thread in flight together); the 16 group sums are added in
 // group order; wave 0 finishes the rows (Onsager residual, z^2 partial).
 // R = 16 (row-block-major partials only, where the line holds two partials of
-// the same block): twice the workgroups, NG = 32 partial groups of G / 32
+// the same block): twice the workgroups, NG = 32 partial groups of G / 32.
+//
+// One scalar and one vector memory trip per launch: every argument the kernel
+// uses is read into registers at the top (sgpr_now: one batch of scalar
+// loads, none left to trickle in along the control flow), the row-block count
+// is RowArgs::NZ (no hidden grid-size argument), and everything wave 0 needs
+// behind the barrier (y, z, the beta^2 partials, the codeword's power) is
+// loaded with the Ab partials in front of it.
 template <typename real, int R = kRow2Rows, int NT = 512>
 __global__ void __launch_bounds__(NT) k_row2(RowArgs<real> a) {
   constexpr int NG = NT / R;  // partial groups
   __shared__ real red[NG][R + 1];
+  const real* tau_p = a.tau;
+  const real* y_p = a.y;
+  const real* zin_p = a.z_in;
+  const real* bbp_p = a.bbp;
+  const real* Pb_p = a.Pb;
+  const real* abp_p = a.abp;
+  int n = a.n, G = a.G, Gb = a.Gb, NZ = a.NZ, T1 = a.T1, t = a.t, mode = a.mode, es = a.early_stop;
+  int Pbst = a.Pbst, pt = a.pt, itset = a.itset;
+  real* z_p = a.z;
+  real* zzp_p = a.zzp;
+  real* out_p = a.out;
+  int* iters_p = a.iters;
+  real sqrt_n = a.sqrt_n;
+  sgpr_now(tau_p, y_p, zin_p, bbp_p, Pb_p, abp_p);
+  sgpr_now(n, G, Gb, NZ, T1, t, mode, es, Pbst, pt, itset);
+  sgpr_now(z_p, zzp_p, out_p, iters_p, sqrt_n);
   const int b = blockIdx.y, tid = threadIdx.x;
   const int rl = tid & (R - 1), pg = tid / R;
   const int r = blockIdx.x * R + rl;
-  const int n = a.n;
   // tau_t and tau_{t-1} are loaded with everything else; the early-stop
   // test waits for them only after the Ab-partial loads are in flight
   // (testing first cost a whole memory round trip per launch)
   real tau = 1, last = 0;
-  if (a.mode == ROW_AMP) {
-    tau = ld_vmem(a.tau + (size_t)b * a.T1 + a.t);
-    last = a.t > 0 ? ld_vmem(a.tau + (size_t)b * a.T1 + a.t - 1) : (real)0;
+  if (mode == ROW_AMP) {
+    tau = ld_vmem(tau_p + (size_t)b * T1 + t);
+    last = t > 0 ? ld_vmem(tau_p + (size_t)b * T1 + t - 1) : (real)0;
   }
   const size_t o = (size_t)b * n + (r < n ? r : 0);
-  real yv = 0, zv = 0, bbv[4] = {0, 0, 0, 0};
+  real yv = 0, zv = 0, Pv = 0, bbv[4] = {0, 0, 0, 0};
   if (tid < 64) {
-    yv = a.y[o];
-    if (a.mode == ROW_AMP) {
-      zv = a.z_in[o];
-      const real* bp = a.bbp + (size_t)b * a.Gb;
+    yv = y_p[o];
+    if (mode == ROW_AMP) {
+      zv = zin_p[o];
+      // the codeword's power: constant over the decode, but behind the barrier
+      // its load was a second memory round trip of every launch
+      Pv = ld_vmem(Pb_p + (size_t)b * Pbst);
+      const real* bp = bbp_p + (size_t)b * Gb;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) bbv[q] = tid + 64 * q < a.Gb ? bp[tid + 64 * q] : (real)0;
+      for (int q = 0; q < 4; ++q) bbv[q] = tid + 64 * q < Gb ? bp[tid + 64 * q] : (real)0;
     }
   }
-  if (a.mode != ROW_INIT0) {
+  if (mode != ROW_INIT0) {
     // pt: partial g of row r at [b][r / R][g][r % R] (n padded to R rows)
-    const size_t gs = a.pt ? (size_t)R : (size_t)n;
-    const real* p = a.pt ? a.abp + (size_t)b * a.G * ((size_t)gridDim.x * R) +
-                               (size_t)blockIdx.x * a.G * R + rl
-                         : a.abp + (size_t)b * a.G * n + (r < n ? r : 0);
+    const size_t gs = pt ? (size_t)R : (size_t)n;
+    const real* p = pt ? abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R + rl
+                       : abp_p + (size_t)b * G * n + (r < n ? r : 0);
     real acc = 0;
     constexpr int U = 256 / NG;  // G = 256 (C2, C4): every load of a thread in one pass
-    if (a.pt && (R == 16 || sizeof(real) == 4) && a.G == NG * U) {
+    if (pt && (R == 16 || sizeof(real) == 4) && G == NG * U) {
       // row-block-major partials with exactly NG x U partials (32-row blocks:
       // binary32 only, C4 single codeword +1 %; the binary64 32-row blocks
       // measured 1.4 % slower in this form).  The [G][n] partials of k_sec
@@ -354,65 +381,69 @@ __global__ void __launch_bounds__(NT) k_row2(RowArgs<real> a) {
       // constant strides from the block base, no bounds, 32-bit offsets (the
       // general form spent ~40 VALU ops of 64-bit address math before the
       // first load); the same loads and sums in the same order
-      const real* pb = a.abp + (size_t)b * a.G * ((size_t)gridDim.x * R) + (size_t)blockIdx.x * a.G * R;
-      real t[U];
+      const real* pb = abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R;
+      real tt[U];
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        t[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
+        tt[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
 #pragma unroll
-      for (int u = 0; u < U; ++u) acc += t[u];
+      for (int u = 0; u < U; ++u) acc += tt[u];
     } else
-    for (int g0 = pg; g0 < a.G; g0 += NG * U) {
-      real t[U];
+    for (int g0 = pg; g0 < G; g0 += NG * U) {
+      real tt[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int g = g0 + NG * u;
-        t[u] = p[(size_t)(g < a.G ? g : pg) * gs];
+        tt[u] = p[(size_t)(g < G ? g : pg) * gs];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        if (g0 + NG * u < a.G) acc += t[u];
+        if (g0 + NG * u < G) acc += tt[u];
     }
     red[pg][rl] = acc;
   }
-  if (a.mode == ROW_AMP && a.early_stop && tau == last) return;  // uniform over the workgroup
+  if (mode == ROW_AMP && es && tau == last) return;  // uniform over the workgroup
   const real tau2 = tau * tau;
   __syncthreads();
   if (tid >= 64) return;
+  // the decode's iters[b]: -1 with the residual's initialisation; T with the
+  // last iteration, which runs to here only when no stop has fired (a stopped
+  // codeword stops every later launch too, and keeps the index it stopped at)
+  if (itset != 0 && blockIdx.x == 0 && tid == 0) iters_p[b] = itset;
   real ons = 0;
-  if (a.mode == ROW_AMP) {
+  if (mode == ROW_AMP) {
     real bb;
-    if (a.Gb <= 256) {
+    if (Gb <= 256) {
       real sacc = 0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) sacc += bbv[q];
       bb = wave_sum(sacc);
     } else {
-      bb = wave_sum_parts(a.bbp + (size_t)b * a.Gb, a.Gb);
+      bb = wave_sum_parts(bbp_p + (size_t)b * Gb, Gb);
     }
-    ons = a.Pb[(size_t)b * a.Pbst] - bb / (real)n;
+    ons = Pv - bb / (real)n;
   }
   real zn = 0;
   if (tid < R && r < n) {
-    if (a.mode == ROW_INIT0) {
+    if (mode == ROW_INIT0) {
       zn = yv;
     } else {
       real acc = 0;
 #pragma unroll
       for (int q = 0; q < NG; ++q) acc += red[q][rl];
-      const real ab = acc / a.sqrt_n;
-      if (a.mode == ROW_ABOUT) {
-        a.out[o] = ab;
+      const real ab = acc / sqrt_n;
+      if (mode == ROW_ABOUT) {
+        out_p[o] = ab;
         return;
       }
       zn = yv - ab;
-      if (a.mode == ROW_AMP) zn += (zv / tau2) * ons;
+      if (mode == ROW_AMP) zn += (zv / tau2) * ons;
     }
-    a.z[o] = zn;
+    z_p[o] = zn;
   }
-  if (a.mode == ROW_ABOUT) return;
+  if (mode == ROW_ABOUT) return;
   const real sz = wave_sum(zn * zn);
-  if (tid == 0) a.zzp[(size_t)b * a.NZ + blockIdx.x] = sz;
+  if (tid == 0) zzp_p[(size_t)b * NZ + blockIdx.x] = sz;
 }
 
 // Per-section decision (sparc_ldpc.py:452-455): argmax, first index on ties.
@@ -427,9 +458,14 @@ __global__ void __launch_bounds__(256) k_decide(const real* beta, int32_t* idx, 
 
 // ---- launchers ------------------------------------------------------------
 template <typename real>
-int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt, void* zin, void* zout) {
+int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt, void* zin, void* zout, int itset) {
   RowArgs<real> a = row_args<real>(c, mode, t, es, G, Gb);
   a.pt = pt;
+  if (itset && !row_sets_iters(c)) return fail(SA_ERR_UNSUPPORTED, "launch_row: only k_row2 writes iters");
+  a.itset = itset;
+  // k_row2 takes its row-block count from RowArgs::NZ (no hidden grid argument)
+  if (row_sets_iters(c) && a.NZ != (c->row_kind == 4 ? c->NZh : c->NZ16))
+    return fail(SA_ERR_ARG, "launch_row: the z^2 partial count is not k_row2's row-block count");
   if (zout) a.z = (real*)zout;
   if (zin) a.z_in = (const real*)zin;
   if (c->prof) c->prof->begin(c->stream, K_ROW);
@@ -466,14 +502,14 @@ int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt,
   return SA_OK;
 }
 
-int launch_decide(sa_ctx* c, int B) {
+int launch_decide(sa_ctx* c, int B, int32_t* idx) {
   dim3 grid((c->L + 3) / 4, B);
 #define SA_DEC(EE)                                                                                             \
   case EE:                                                                                                     \
     if (c->prec == SA_PREC_F64)                                                                                \
-      k_decide<double, EE><<<grid, 256, 0, c->stream>>>((const double*)c->d_beta, c->d_idx, c->L, c->M, c->dead);      \
+      k_decide<double, EE><<<grid, 256, 0, c->stream>>>((const double*)c->d_beta, idx, c->L, c->M, c->dead);      \
     else                                                                                                       \
-      k_decide<float, EE><<<grid, 256, 0, c->stream>>>((const float*)c->d_beta, c->d_idx, c->L, c->M, c->dead);        \
+      k_decide<float, EE><<<grid, 256, 0, c->stream>>>((const float*)c->d_beta, idx, c->L, c->M, c->dead);        \
     break;
   switch (c->E) { SA_DEC(1) SA_DEC(2) SA_DEC(4) SA_DEC(8) SA_DEC(16) SA_DEC(32) SA_DEC(64) }
 #undef SA_DEC
@@ -481,7 +517,7 @@ int launch_decide(sa_ctx* c, int B) {
   return SA_OK;
 }
 
-template int launch_row<float>(sa_ctx*, int, int, int, int, int, int, int, void*, void*);
-template int launch_row<double>(sa_ctx*, int, int, int, int, int, int, int, void*, void*);
+template int launch_row<float>(sa_ctx*, int, int, int, int, int, int, int, void*, void*, int);
+template int launch_row<double>(sa_ctx*, int, int, int, int, int, int, int, void*, void*, int);
 
 }  // namespace sa

@@ -634,6 +634,13 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   load_section<real, EQ>(bl, bprev, lane, Mq);
   const real cl = ld_vmem(a.c + (size_t)b * a.cst + lc);
   const real tau = zz.tau(zzb, a.NZ, n);
+  // a decode without beta0: its first launch takes the previous estimate as
+  // zero, selected after the (unconditional) load: the buffer is not filled
+  // and may hold anything, NaN included
+  if (a.bzero) {
+#pragma unroll
+    for (int i = 0; i < EQ; ++i) bprev[i] = 0;
+  }
   const bool stop = a.early_stop && (tau == last);
   if (g == 0 && tid == 0) {
     a.tau[(size_t)b * a.T1 + a.t] = tau;
@@ -641,6 +648,9 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   }
   if (stop) {  // uniform over the grid row
     if (dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA write may outlive the workgroup
+    if (a.bzero && have) {  // stopped at once (tau_0 = 0, y = 0): the estimate is the zero nobody filled in
+      store_section<real, EQ>(a.beta + (size_t)b * LM + (size_t)lc * M + eoff, bprev, lane, Mq);
+    }
     return;
   }
   const real tau2 = tau * tau;
@@ -825,9 +835,11 @@ void launch_sec_e(sa_ctx* c, int B, SecArgs<real> a) {
 }
 
 template <typename real>
-int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt) {
+int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt, int bzero) {
   SecArgs<real> a = sec_args<real>(c, SEC_AMP, t, es);
   a.pt = pt;
+  if (bzero && !(c->sec3 || c->sec4)) return fail(SA_ERR_UNSUPPORTED, "k_sec2 reads its previous estimate");
+  a.bzero = bzero;
   a.beta = (real*)bin;
   a.beta_out = (real*)bout;
   a.G = sec2_parts(c);
@@ -891,8 +903,8 @@ int launch_sec(sa_ctx* c, int B, int mode, int t, int es, void* bin, void* bout)
 
 template int launch_sec<float>(sa_ctx*, int, int, int, int, void*, void*);
 template int launch_sec<double>(sa_ctx*, int, int, int, int, void*, void*);
-template int launch_sec2<float>(sa_ctx*, int, int, int, void*, void*, int);
-template int launch_sec2<double>(sa_ctx*, int, int, int, void*, void*, int);
+template int launch_sec2<float>(sa_ctx*, int, int, int, void*, void*, int, int);
+template int launch_sec2<double>(sa_ctx*, int, int, int, void*, void*, int, int);
 
 // Every single-codeword section-kernel instantiation may use the full 160 KB LDS.
 template <typename real>

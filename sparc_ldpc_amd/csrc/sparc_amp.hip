@@ -234,18 +234,31 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const int G = dense ? dense_parts(c, B) : (batched ? c->Gb : (sec2 ? sec2_parts(c) : c->G));
   const int Gb = dense ? c->Gd : (batched ? c->Gb : (sec2 ? sec2_parts(c) : c->G));
   int rc;
-  k_fill32<<<(B + 255) / 256, 256, 0, c->stream>>>((uint32_t*)c->d_iters, 0xffffffffu, (size_t)B);
+  // The fixed launches around the T iterations.  Behind k_row2 (the small-batch
+  // path) the iters writes ride on row launches the decode makes anyway: -1
+  // with the residual's initialisation, T with the last iteration.  Behind
+  // k_sec4 / k_sec43 a decode without beta0 fills no zero estimate: its first
+  // section launch takes the previous estimate as zero.  With the early stop
+  // off the final estimate's buffer is known here: without beta0 the ping-pong
+  // starts on the side that ends in d_beta, and k_beta_final is launched only
+  // where the estimate ends in d_beta2.
+  const bool it_row = !dense && !batched && row_sets_iters(c) && T > 0;
+  const bool bzero = !has_b0 && !dense && !batched && sec2 && (c->sec3 || c->sec4) && T > 0;
+  const int flip = (bzero && !es) ? (T & 1) : 0;  // beta0 lies in d_beta: no choice of side
+  if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, c->stream>>>((uint32_t*)c->d_iters, 0xffffffffu, (size_t)B);
   if (has_b0) {
     if (dense) {
       if ((rc = dense_start<real>(c, B, G))) return rc;
     } else {
       if ((rc = launch_sec<real>(c, B, SEC_AB, 0, 0))) return rc;
-      if ((rc = launch_row<real>(c, B, ROW_INIT, 0, 0, c->G, c->G))) return rc;
+      if ((rc = launch_row<real>(c, B, ROW_INIT, 0, 0, c->G, c->G, 0, nullptr, nullptr, it_row ? -1 : 0))) return rc;
     }
   } else {
-    const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
-    k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, c->stream>>>((uint32_t*)c->d_beta, 0u, nw);
-    if ((rc = launch_row<real>(c, B, ROW_INIT0, 0, 0, G, Gb))) return rc;
+    if (!bzero) {
+      const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
+      k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, c->stream>>>((uint32_t*)c->d_beta, 0u, nw);
+    }
+    if ((rc = launch_row<real>(c, B, ROW_INIT0, 0, 0, G, Gb, 0, nullptr, nullptr, it_row ? -1 : 0))) return rc;
   }
   for (int t = 0; t < T; ++t) {
     if (dense) {
@@ -253,19 +266,22 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
     } else if (batched) {
       if ((rc = launch_secb<real>(c, B, t, es))) return rc;
     } else {
-      void* pin = (t & 1) ? c->d_beta2 : c->d_beta;
-      void* pout = (t & 1) ? c->d_beta : c->d_beta2;
+      void* pin = ((t ^ flip) & 1) ? c->d_beta2 : c->d_beta;
+      void* pout = ((t ^ flip) & 1) ? c->d_beta : c->d_beta2;
       if (sec2) {
-        if ((rc = launch_sec2<real>(c, B, t, es, pin, pout, pt))) return rc;
+        if ((rc = launch_sec2<real>(c, B, t, es, pin, pout, pt, bzero && t == 0))) return rc;
       } else if ((rc = launch_sec<real>(c, B, SEC_AMP, t, es, pin, pout))) {
         return rc;
       }
     }
-    if ((rc = launch_row<real>(c, B, ROW_AMP, t, es, G, Gb, pt))) return rc;
+    if ((rc = launch_row<real>(c, B, ROW_AMP, t, es, G, Gb, pt, nullptr, nullptr, it_row && t == T - 1 ? T : 0)))
+      return rc;
   }
-  k_iters_final<<<(B + 255) / 256, 256, 0, c->stream>>>(c->d_iters, B, T);
+  if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, c->stream>>>(c->d_iters, B, T);
   HIP_TRY(hipGetLastError());
-  if (!dense && !batched && T > 0) {
+  // early stop off: every codeword runs T iterations, the last one into pout(T - 1)
+  const bool home = !es && (((T - 1) ^ flip) & 1);
+  if (!dense && !batched && T > 0 && !home) {
     // the estimate of codeword b is in the buffer of parity iters[b]
     const size_t LM = (size_t)c->L * c->M;
     k_beta_final<real><<<dim3((unsigned)std::min<size_t>((LM + 255) / 256, 4096), B), 256, 0, c->stream>>>(
@@ -1394,7 +1410,7 @@ int sa_decide(sa_ctx* c, int B, int32_t* idx_out) {
   if (check_ctx(c)) return SA_ERR_ARG;
   if (B <= 0 || B > c->Bcap || !idx_out) return fail(SA_ERR_ARG, "sa_decide: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
-  if (int rc = launch_decide(c, B)) return rc;
+  if (int rc = launch_decide(c, B, c->d_idx)) return rc;
   HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return SA_OK;
@@ -1416,19 +1432,20 @@ int sa_decide_async(sa_ctx* c, int B, int slot) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->h_dec) (void)hipHostFree(c->h_dec);
     c->h_dec = nullptr;
+    c->d_dec = nullptr;
     c->dec_cap = 0;
     HIP_TRY(hipHostMalloc((void**)&c->h_dec, per * SA_DECIDE_SLOTS * sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(hipHostGetDevicePointer((void**)&c->d_dec, c->h_dec, 0));
     c->dec_cap = per;
     for (int k = 0; k < SA_DECIDE_SLOTS; ++k) {
       if (!c->dec_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->dec_ev[k], hipEventDisableTiming));
       c->dec_B[k] = 0;
     }
   }
-  // the slot's previous indices must have left the ring before they are overwritten
-  // (the stream is in order: the copy below cannot overtake it anyway)
-  if (int rc = launch_decide(c, B)) return rc;
-  int32_t* dst = c->h_dec + (size_t)slot * c->dec_cap;
-  HIP_TRY(hipMemcpyAsync(dst, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  // k_decide writes the indices straight into the slot (the pinned ring is
+  // mapped into the device's address space: no copy behind the kernel); the
+  // host reads them after the event recorded behind it
+  if (int rc = launch_decide(c, B, c->d_dec + (size_t)slot * c->dec_cap)) return rc;
   HIP_TRY(hipEventRecord(c->dec_ev[slot], c->stream));
   c->dec_B[slot] = B;
   return SA_OK;

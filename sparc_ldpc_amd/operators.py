@@ -231,8 +231,8 @@ class SparcOperator:
     DECIDE_SLOTS = 4  # SA_DECIDE_SLOTS
 
     def decide_async(self, B: int, slot: int) -> None:
-        """Queue the section argmax of the decode on the stream and the copy of
-        its (B, L) indices into pinned ring slot `slot`; returns at once."""
+        """Queue the section argmax of the decode on the stream, its (B, L)
+        indices written into pinned ring slot `slot`; returns at once."""
         check(self._lib.sa_decide_async(self._ctx, int(B), int(slot)))
 
     def decide_collect(self, B: int, slot: int) -> np.ndarray:
