@@ -72,8 +72,8 @@ int sa_create(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
  * normally chosen by built-in rules from (L, M, n, precision, batch, CUs)
  * (sa_plan reports the choice); these bits override a rule, e.g. to test a
  * kernel on shapes where the rule would not pick it.  Every option keeps the
- * results within the same parity bounds; SA_PLAN_NO_PT, SA_PLAN_EAGER and
- * SA_PLAN_ONE_PASS are bit-identical to the default plan.  `sa_subset` contexts
+ * results within the same parity bounds; SA_PLAN_NO_PT, SA_PLAN_EAGER,
+ * SA_PLAN_ONE_PASS and SA_PLAN_NO_LANES are bit-identical to the default plan.  `sa_subset` contexts
  * inherit their parent's options. */
 enum {
   SA_PLAN_DEFAULT = 0,
@@ -89,7 +89,8 @@ enum {
   SA_PLAN_NO_BANKS = 1 << 9,  /* batched: bucket slots summed in h order (no bank-aware slot order) */
   SA_PLAN_EAGER = 1 << 10,    /* sa_run launches eagerly instead of replaying a captured hipGraph */
   SA_PLAN_ONE_PASS = 1 << 11, /* batched: every section group of an XCD in one pass of the work order */
-  SA_PLAN_ALL = (1 << 12) - 1
+  SA_PLAN_NO_LANES = 1 << 12, /* every sa_run on one stream and one set of state buffers (no decode lanes) */
+  SA_PLAN_ALL = (1 << 13) - 1
 };
 int sa_create_ex(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
                  int backend, int precision, int device, int plan);
@@ -153,7 +154,37 @@ int sa_amp(sa_ctx* ctx, int B, const double* y, const double* Pl, int T,
  * buffers; sa_run decodes the staged batch asynchronously on the context's
  * stream (replayed hipGraph); sa_wait blocks until it is done; sa_fetch
  * copies the results back.  sa_run_event_ms returns the device time of the
- * last sa_run measured with HIP events on the context's stream. */
+ * last sa_run measured with HIP events on the context's stream.
+ *
+ * Decode lanes.  A context holds two lanes, each a stream plus everything one
+ * decode mutates (y, z, both beta buffers, the partials, tau, iters, the
+ * captured graphs); the tables, the power arrays and the sa_decide_async ring
+ * are shared.  A small-batch decode (Hadamard backend, fewer than 4 codewords
+ * or no batched kernel, graph mode, no SA_FLAG_BETA0, no SA_PLAN_NO_LANES)
+ * issued while the previous step is still outstanding (its decode in flight,
+ * or decisions queued by sa_decide_async and not yet collected) takes the lane
+ * the previous sa_run did not take, so sa_run(k + 1) overlaps sa_run(k) on the
+ * chip when the caller collects one step behind (sa_decide_async /
+ * sa_decide_collect); every other run, a lone decode (sa_run, sa_wait)
+ * among them, stays on the lane of the previous one and is the single-lane
+ * decode.  The second lane is created at the first run that takes it; at
+ * L = M = 512, n = 4608, one codeword, binary32 it costs about 4.7 MB of
+ * partials, 2 x 1 MB of beta and the small buffers (sa_info's byte count
+ * includes it).  Batched, dense, matrix, host-operator, eager and NO_LANES
+ * contexts never get a second stream or workspace.  What holds:
+ *  - each sa_run decodes the inputs staged most recently before it; without an
+ *    sa_stage since the previous run it decodes the same y again.  sa_stage
+ *    does not wait for a decode in flight: y goes into the lane the next
+ *    run is expected to take, on that lane's stream (a run that finds its lane's y
+ *    older than the latest staged one copies it over on the device first).
+ *    beta0 and the SA_FLAG_BETA0 run stay on the lane of the previous run;
+ *  - sa_decide_async, sa_decide, sa_fetch, sa_fetch_z, sa_run_event_ms and the
+ *    glue calls (sa_llr, ...) refer to the most recent sa_run and are ordered
+ *    behind it on its lane's stream;
+ *  - sa_wait, sa_destroy, sa_reserve when it grows the workspace and a changed
+ *    Pl wait for every lane; an sa_stage whose Pl equals the staged one writes
+ *    nothing to the device;
+ *  - results are bit-identical to a single-lane context's. */
 int sa_reserve(sa_ctx* ctx, int B, int T);
 int sa_stage(sa_ctx* ctx, int B, const double* y, const double* Pl, const double* beta0);
 /* Per-codeword power allocations Pl [B][L] (Hadamard backend) for the next

@@ -17,6 +17,13 @@ Two durations per kernel:
     front of it; these add up to the decode's wall time exactly, and are what
     bench.py's back-to-back HIP-event timing measures.
 
+Kernels are attributed to decodes per (queue, stream) of the trace: with decode
+lanes two consecutive decodes run on two streams and interleave in one
+timeline.  When the timed decodes sit on more than one stream the summary adds
+how many of them overlap a decode of another stream, the overlapped share of
+their wall time and the decode period (the in-graph durations then measure a
+shared chip).
+
 Usage: graph_trace.py <kernel_trace.csv> [out.txt] [source-hash]
 """
 import csv
@@ -33,30 +40,36 @@ LOOP = ("k_sec4", "k_sec43", "k_sec2", "k_sec", "k_secb", "k_row2", "k_rowv", "k
 def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    seq = [(short(r["Kernel_Name"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"])
-           for r in rows]
+    streams = {}
+    for r in rows:
+        key = (r.get("Queue_Id", ""), r.get("Stream_Id", ""))
+        streams.setdefault(key, []).append(
+            (short(r["Kernel_Name"]), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     # one decode = a maximal run of loop kernels: whatever else the stream
     # carries (the fills and k_iters_final / k_beta_final of the paths that
     # launch them, k_decide behind every step, conversions, copies) ends a run.
     # The graph replays are the decodes whose dispatches follow each other with
     # no host gap (median gap < 1 us), the eager profiling decodes have launch gaps
-    runs, cur = [], []
-    for k in seq:
-        if k[0] in LOOP:
-            cur.append(k[:3])
-        else:
-            if cur:
-                runs.append(cur)
-            cur = []
-    if cur:
-        runs.append(cur)
+    runs, where = [], []
+    for key, seq in streams.items():
+        cur = []
+        for k in seq + [("", 0, 0, "")]:
+            if k[0] in LOOP:
+                cur.append(k[:3])
+            else:
+                if cur:
+                    runs.append(cur)
+                    where.append(key)
+                cur = []
     def med_gap(r):
         return st.median([r[i + 1][1] - r[i][2] for i in range(len(r) - 1)]) if len(r) > 1 else 1e9
-    timed = [r for r in runs if len(r) > 2 and med_gap(r) < 1000]
+    timed = [(r, w) for r, w in zip(runs, where) if len(r) > 2 and med_gap(r) < 1000]
     if not timed:
         sys.exit("no graph-replayed decode found")
-    n0 = st.mode([len(r) for r in timed])
-    timed = [r for r in timed if len(r) == n0]
+    n0 = st.mode([len(r) for r, _ in timed])
+    timed = sorted([(r, w) for r, w in timed if len(r) == n0], key=lambda x: x[0][0][1])
+    lanes = sorted({w for _, w in timed})
+    timed, where = [r for r, _ in timed], [w for _, w in timed]
     out = []
     if len(sys.argv) > 3:
         out.append(f"sources sha256 {sys.argv[3]}")
@@ -78,6 +91,24 @@ def main():
     sums = [sum(e - s for _, s, e in r) for r in timed]
     out.append(f"replay wall (first start -> last end): median {st.median(walls) / 1e3:.1f} us; "
                f"sum of durations median {st.median(sums) / 1e3:.1f} us")
+    if len(lanes) > 1:
+        # two decodes of different streams in flight at once: the share of a
+        # decode's wall time during which a decode of another stream runs, and
+        # the period between the starts of consecutive decodes (any stream)
+        share, hit = [], 0
+        for i, r in enumerate(timed):
+            a, b = r[0][1], r[-1][2]
+            ov = 0
+            for j in range(max(0, i - 3), min(len(timed), i + 4)):
+                if j != i and where[j] != where[i]:
+                    ov += max(0, min(b, timed[j][-1][2]) - max(a, timed[j][0][1]))
+            hit += ov > 0
+            share.append(min(1.0, ov / (b - a)))
+        period = [timed[i + 1][0][1] - timed[i][0][1] for i in range(len(timed) - 1)]
+        per_lane = ", ".join(f"queue {q} stream {s}: {where.count((q, s))}" for q, s in lanes)
+        out.append(f"decodes on {len(lanes)} streams ({per_lane}); {hit} of {len(timed)} overlap a decode of another "
+                   f"stream, overlapped share of a decode's wall time median {st.median(share):.2f}; "
+                   f"decode period (start to next start, any stream) median {st.median(period) / 1e3:.1f} us")
     txt = "\n".join(out)
     print(txt)
     if len(sys.argv) > 2:

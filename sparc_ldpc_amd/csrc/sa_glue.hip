@@ -250,12 +250,13 @@ int sa_encode(sa_ctx* c, int B, const int32_t* idx, const double* noise) {
   HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   const double* d_noise = nullptr;
   if (noise && (rc = dev_in(c, noise, (size_t)B * c->n, 0, &d_noise))) return rc;
+  if ((rc = y_begin_write(c, c->stream, B))) return rc;  // the current lane's y becomes the staged one
   rc = c->prec == SA_PREC_F64
            ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (double*)c->d_y, B)
            : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (float*)c->d_y, B);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return SA_OK;
+  return y_mark(c);
 }
 
 namespace {
@@ -351,6 +352,8 @@ int sa_hard_cancel(sa_ctx* c, int B, int l0, int ns, const double* app, int flag
   k_app_idx<<<(B * ns + 255) / 256, 256, 0, c->stream>>>(d_app, lgM, ns, B, c->d_idx);
   HIP_TRY(hipGetLastError());
   if (dst) {
+    // reads the staged y (wherever it was staged), writes dst's
+    if ((rc = y_sync(c)) || (rc = y_begin_write(dst, c->stream, B))) return rc;
     rc = c->prec == SA_PREC_F64
              ? launch_colsum<double>(c, c->d_idx, ns, l0, ns, (const double*)c->d_y, nullptr, (double*)dst->d_y, B)
              : launch_colsum<float>(c, c->d_idx, ns, l0, ns, (const float*)c->d_y, nullptr, (float*)dst->d_y, B);
@@ -359,7 +362,7 @@ int sa_hard_cancel(sa_ctx* c, int B, int l0, int ns, const double* app, int flag
   if (idx_out)
     HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return SA_OK;
+  return dst ? y_mark(dst) : SA_OK;
 }
 
 int sa_threshold(sa_ctx* c, int B, int l0, int ns, const double* app, int flags, double threshold,
@@ -393,12 +396,13 @@ int sa_cancel_scaled(sa_ctx* c, int B, const int32_t* idx, double scale, sa_ctx*
   int rc;
   if ((rc = ensure_workspace(dst, B, dst->Tcap > 0 ? dst->Tcap : 1))) return rc;
   HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if ((rc = y_sync(c)) || (rc = y_begin_write(dst, c->stream, B))) return rc;  // as sa_hard_cancel
   rc = c->prec == SA_PREC_F64
            ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, (const double*)c->d_y, nullptr, (double*)dst->d_y, B, scale)
            : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, (const float*)c->d_y, nullptr, (float*)dst->d_y, B, scale);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return SA_OK;
+  return y_mark(dst);
 }
 
 int sa_cancel(sa_ctx* c, int B, const int32_t* idx, sa_ctx* dst) { return sa_cancel_scaled(c, B, idx, 1.0, dst); }

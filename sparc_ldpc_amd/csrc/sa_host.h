@@ -48,8 +48,41 @@ enum { K_SEC = 0, K_ROW = 1, K_DAZ = 2, K_DDEN = 3, K_DAB = 4, K_QNT = 5, K_NKIN
 
 }  // namespace sa
 
+// A decode lane: everything one small-batch decode mutates, so that two
+// consecutive decodes of a context can share the chip (step k + 1 reads
+// nothing step k writes; the tables, the power arrays and the decision ring
+// are read-only during a decode and stay shared).  The context's own stream /
+// d_* / graphs fields ARE the current lane (the lane of the last sa_run):
+// lane_switch parks them here and loads the other lane's, so every entry point
+// written against c->d_* addresses the last run's lane.  lane[cur]'s parked
+// fields are stale while it is current; y_ev / y_ver / y_read are never
+// swapped and always authoritative.
+struct sa_lane {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_beta2 = nullptr, *d_abp = nullptr;
+  void *d_bbp = nullptr, *d_zzp = nullptr, *d_tau = nullptr;
+  int* d_iters = nullptr;
+  double* d_stage = nullptr;  // a lane's uploads go through its own staging buffer
+  size_t stage_cap = 0;
+  int beta2_cap = 0;
+  std::map<std::tuple<int, int, int, int>, hipGraphExec_t> graphs;  // their kernel arguments hold the lane's pointers
+  hipEvent_t y_ev = nullptr;      // behind the last write of this lane's d_y (staging, or the copy from the other lane)
+  unsigned long long y_ver = 0;   // version of the y this lane holds (sa_ctx::y_ver: the latest staged)
+  bool y_read = false;            // this lane's last y copy read the other lane's d_y (that lane's next y write waits for y_ev)
+};
+
 struct sa_ctx {
   sa::Prof* prof = nullptr;
+  // decode lanes (compile-time 2: the ring and bench protocols keep at most two steps in flight)
+  enum { kLanes = 2 };
+  sa_lane lane[kLanes];
+  int cur = 0;            // the current lane (its fields live in this struct)
+  bool lanes_on = false;  // lane 1's buffers exist (created at the first eligible sa_run)
+  unsigned long long y_ver = 0;  // version of the y staged last
+  int y_lane = 0;                // the lane that holds it
+  std::vector<double> h_Pl;      // the Pl behind d_c / d_cd / d_P1 (set_power skips an unchanged one)
+  std::vector<double> h_Plb;     // the Pl behind d_cb / d_Pb (set_power_batch)
   int L = 0, M = 0, n = 0, w = 0, nhi = 0, backend = 0, prec = 0, device = 0;
   int plan = 0;       // SA_PLAN_* options of sa_create_ex (0: every choice by the built-in rules)
   bool pow2 = true;  // M a power of two (the Hadamard kernels, bit-level glue)
@@ -320,7 +353,20 @@ int check_ctx(const sa_ctx* c);
 int check_tables(const sa_ctx* c, const char* what);
 int dev_alloc(sa_ctx* c, void** p, size_t bytes);
 void dev_free(void* p);
-void drop_graphs(sa_ctx* c);
+void drop_graphs(sa_ctx* c);  // every lane's
+// decode lanes: wait for every lane; make lane k current; drop lane 1's buffers
+// (after waiting for every lane; lane 0 becomes current and keeps the staged y)
+int sync_all(sa_ctx* c);
+void lane_switch(sa_ctx* c, int k);
+int lanes_release(sa_ctx* c);
+// the staged y across lanes: y_sync brings the current lane's d_y up to the
+// latest staged version (a device-to-device copy on its stream, behind the
+// event recorded after the staging); a writer of B codewords of the current
+// lane's d_y on stream s calls y_begin_write before it launches and y_mark
+// after (when s is not the lane's own stream: after waiting for s)
+int y_sync(sa_ctx* c);
+int y_begin_write(sa_ctx* c, hipStream_t s, int B);
+int y_mark(sa_ctx* c);
 int ensure_workspace(sa_ctx* c, int B, int T);
 int ensure_stage(sa_ctx* c, size_t count);
 int upload(sa_ctx* c, void* dst, const double* src, size_t count);

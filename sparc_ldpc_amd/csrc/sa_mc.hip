@@ -445,6 +445,7 @@ int sa_mc_stage(sa_ctx* c, int nreps, const int32_t* idx, const double* noise) {
   for (size_t i = 0; i < (size_t)nreps * c->L; ++i)
     if (idx[i] < 0 || idx[i] >= c->M) return fail(SA_ERR_ARG, "sa_mc_stage: index outside [0, M)");
   HIP_TRY(hipSetDevice(c->device));
+  lane_switch(c, 0);  // the stream and its graphs live with lane 0 (the batched decode's lane)
   if (nreps > c->mc_cap) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
@@ -484,6 +485,7 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
     return fail(SA_ERR_UNSUPPORTED, "sa_mc_run: needs the batched codeword-interleaved Hadamard decode "
                                     "(k_secb + k_rowc)");
   HIP_TRY(hipSetDevice(c->device));
+  lane_switch(c, 0);  // lane 1's buffers hold no batched layout
   int rc;
   if ((rc = ensure_workspace(c, B, T))) return rc;
   if ((rc = ensure_invb(c))) return rc;

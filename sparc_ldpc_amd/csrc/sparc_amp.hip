@@ -83,9 +83,165 @@ void dev_free(void* p) {
   if (p) (void)hipFree(p);
 }
 
+// ---- decode lanes (sa_host.h: sa_lane) ---------------------------------------
+
+int sync_all(sa_ctx* c) {
+  if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < sa_ctx::kLanes; ++k)
+    if (k != c->cur && c->lane[k].stream) HIP_TRY(hipStreamSynchronize(c->lane[k].stream));
+  return SA_OK;
+}
+
+// The current lane's fields of the context <-> lane l (a swap: parks one set, loads the other).
+static void lane_swap_fields(sa_ctx* c, sa_lane& l) {
+  std::swap(c->stream, l.stream);
+  std::swap(c->ev0, l.ev0);
+  std::swap(c->ev1, l.ev1);
+  std::swap(c->d_y, l.d_y);
+  std::swap(c->d_z, l.d_z);
+  std::swap(c->d_beta, l.d_beta);
+  std::swap(c->d_beta2, l.d_beta2);
+  std::swap(c->d_abp, l.d_abp);
+  std::swap(c->d_bbp, l.d_bbp);
+  std::swap(c->d_zzp, l.d_zzp);
+  std::swap(c->d_tau, l.d_tau);
+  std::swap(c->d_iters, l.d_iters);
+  std::swap(c->d_stage, l.d_stage);
+  std::swap(c->stage_cap, l.stage_cap);
+  std::swap(c->beta2_cap, l.beta2_cap);
+  c->graphs.swap(l.graphs);
+}
+
+void lane_switch(sa_ctx* c, int k) {
+  if (k == c->cur) return;
+  lane_swap_fields(c, c->lane[c->cur]);  // park
+  lane_swap_fields(c, c->lane[k]);       // load
+  c->cur = k;
+}
+
+static int y_wait_reader(sa_ctx* c, hipStream_t s) {
+  sa_lane& o = c->lane[1 - c->cur];
+  if (c->lanes_on && o.y_read) {  // the other lane's copy of this lane's y must have read it
+    HIP_TRY(hipStreamWaitEvent(s, o.y_ev, 0));
+    o.y_read = false;
+  }
+  return SA_OK;
+}
+
+int y_begin_write(sa_ctx* c, hipStream_t s, int B) {
+  if (!c->lanes_on) return SA_OK;
+  if (B < c->Bcap) {  // the rows past B keep the latest staged values
+    if (int rc = y_sync(c)) return rc;
+    if (s != c->stream) HIP_TRY(hipStreamWaitEvent(s, c->lane[c->cur].y_ev, 0));
+  }
+  return y_wait_reader(c, s);
+}
+
+int y_mark(sa_ctx* c) {
+  sa_lane& l = c->lane[c->cur];
+  l.y_ver = ++c->y_ver;
+  c->y_lane = c->cur;  // (y_read stays: the event recorded here lies behind the lane's earlier copy too)
+  if (l.y_ev) HIP_TRY(hipEventRecord(l.y_ev, c->stream));
+  return SA_OK;
+}
+
+int y_sync(sa_ctx* c) {
+  sa_lane& l = c->lane[c->cur];
+  if (!c->lanes_on || l.y_ver == c->y_ver) return SA_OK;
+  sa_lane& src = c->lane[c->y_lane];  // parked: the holder is not the current lane
+  HIP_TRY(hipStreamWaitEvent(c->stream, src.y_ev, 0));
+  if (int rc = y_wait_reader(c, c->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_y, src.d_y, (size_t)c->Bcap * c->n * rsz(c), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipEventRecord(l.y_ev, c->stream));
+  l.y_ver = c->y_ver;
+  l.y_read = true;
+  return SA_OK;
+}
+
+// Lane 1's stream, events and buffers, sized like lane 0's for the small-batch
+// path (no batched-layout padding: a lane never runs the batched kernels).
+static int lane_create(sa_ctx* c) {
+  sa_lane& l = c->lane[1 - c->cur];
+  if (!l.stream) HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+  if (!l.ev0) HIP_TRY(hipEventCreate(&l.ev0));
+  if (!l.ev1) HIP_TRY(hipEventCreate(&l.ev1));
+  if (!l.y_ev) HIP_TRY(hipEventCreateWithFlags(&l.y_ev, hipEventDisableTiming));
+  const size_t s = rsz(c), LM = (size_t)c->L * c->M, nB = (size_t)c->Bcap;
+  int Gmax = c->G;
+  if (c->G2 > Gmax) Gmax = c->G2;
+  if (c->G3 > Gmax) Gmax = c->G3;
+  int rc;
+  if ((rc = dev_alloc(c, &l.d_y, nB * c->n * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_z, nB * c->n * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_beta, nB * LM * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_beta2, nB * LM * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_abp, nB * Gmax * ((size_t)c->NZ16 * kRow2Rows) * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_bbp, nB * Gmax * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_zzp, nB * c->NZh * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_tau, nB * (c->Tcap + 1) * s))) return rc;
+  if ((rc = dev_alloc(c, (void**)&l.d_iters, nB * sizeof(int)))) return rc;
+  // the staging buffer the caller's uploads / fetches have needed so far: the
+  // lane's first stage allocates nothing
+  if (c->stage_cap > 0 && !l.d_stage) {
+    if ((rc = dev_alloc(c, (void**)&l.d_stage, c->stage_cap * sizeof(double)))) return rc;
+    l.stage_cap = c->stage_cap;
+  }
+  l.beta2_cap = c->Bcap;
+  l.y_ver = 0;  // older than any staged y: copied before the lane's first run
+  l.y_read = false;
+  c->lanes_on = true;
+  return SA_OK;
+}
+
+// The caller is pipelining: something of the previous step is still
+// outstanding when the next one is issued (its decode in flight, or decisions
+// queued by sa_decide_async and not collected yet).  Only then does a run take
+// the other lane: a lone decode (run, wait) stays where its buffers and its
+// graph are, exactly the single-lane path.
+static bool pipelining(const sa_ctx* c) {
+  for (int k = 0; k < SA_DECIDE_SLOTS; ++k)
+    if (c->dec_B[k] != 0) return true;
+  return c->ev1 && hipEventQuery(c->ev1) == hipErrorNotReady;
+}
+
+// Whether a run of B codewords may rotate lanes at all (the plan, the backend, the batch).
+static bool lane_shape(const sa_ctx* c, int B) {
+  return c->backend == SA_BACKEND_HADAMARD && !use_batched(c, B) && !(c->plan & (SA_PLAN_EAGER | SA_PLAN_NO_LANES));
+}
+
+int lanes_release(sa_ctx* c) {
+  int rc = sync_all(c);
+  if (!c->lanes_on) return rc;
+  lane_switch(c, 0);
+  if (!rc) rc = y_sync(c);  // the staged y stays with lane 0
+  if (!rc && c->stream && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(SA_ERR_HIP, "lanes_release: sync failed");
+  sa_lane& l = c->lane[1];
+  for (auto& kv : l.graphs) (void)hipGraphExecDestroy(kv.second);
+  l.graphs.clear();
+  void** bufs[] = {&l.d_y, &l.d_z, &l.d_beta, &l.d_beta2, &l.d_abp, &l.d_bbp, &l.d_zzp, &l.d_tau};
+  for (void** p : bufs) {
+    dev_free(*p);
+    *p = nullptr;
+  }
+  dev_free(l.d_iters); l.d_iters = nullptr;
+  dev_free(l.d_stage); l.d_stage = nullptr;
+  l.stage_cap = 0;
+  l.beta2_cap = 0;
+  l.y_read = false;
+  c->lane[0].y_read = false;
+  c->lane[0].y_ver = c->y_ver;
+  c->y_lane = 0;
+  c->lanes_on = false;
+  return rc;
+}
+
 void drop_graphs(sa_ctx* c) {
   for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
   c->graphs.clear();
+  for (auto& l : c->lane) {  // the parked lane's (the current lane's parked map is empty)
+    for (auto& kv : l.graphs) (void)hipGraphExecDestroy(kv.second);
+    l.graphs.clear();
+  }
   for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);  // sa_mc_run's
   c->mc_graphs.clear();
 }
@@ -103,6 +259,7 @@ void free_workspace(sa_ctx* c) {
   dev_free(c->d_beta2); c->d_beta2 = nullptr;
   c->beta2_cap = 0;
   c->Bcap = c->Tcap = 0;
+  c->h_Plb.clear();  // d_cb / d_Pb went
   if (c->pb_on) {  // the per-codeword powers went with the workspace
     c->pb_on = false;
     c->power_set = c->shared_power;
@@ -122,7 +279,7 @@ int ensure_workspace(sa_ctx* c, int B, int T) {
     if (rcf) return rcf;
   }
   if (B <= c->Bcap && T <= c->Tcap) return SA_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int rcl = lanes_release(c)) return rcl;  // waits for every lane; lane 1 returns at the next eligible run
   drop_graphs(c);
   const int nB = B > c->Bcap ? B : c->Bcap;
   const int nT = T > c->Tcap ? T : c->Tcap;
@@ -293,7 +450,7 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
 
 int ensure_beta2(sa_ctx* c, int B) {
   if (is_dense(c) || use_batched(c, B) || c->beta2_cap >= c->Bcap) return SA_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int rcl = lanes_release(c)) return rcl;
   dev_free(c->d_beta2);
   c->d_beta2 = nullptr;
   c->beta2_cap = 0;
@@ -311,6 +468,18 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   int rc0 = ensure_beta2(c, B);
   if (!rc0 && use_batched(c, B)) rc0 = ensure_invb(c);  // before any capture: it uploads
   if (rc0) return rc0;
+  // Decode lanes: a small-batch graph decode without beta0, issued while the
+  // previous step is outstanding, takes the lane the previous run did not, so
+  // consecutive decodes overlap on the chip; every other run stays on the
+  // current lane.  Lane 1 appears at the first such run.
+  if (lane_shape(c, B) && !c->prof && !has_b0 && pipelining(c)) {
+    if (!c->lanes_on)
+      if (int rcl = lane_create(c)) return rcl;
+    lane_switch(c, 1 - c->cur);
+  } else if (use_batched(c, B)) {
+    lane_switch(c, 0);  // lane 1's buffers hold no batched layout (no chunk padding, no k_secb partials)
+  }
+  if (int rcy = y_sync(c)) return rcy;  // a lane whose y is older than the latest staged one
   if (c->plan & SA_PLAN_EAGER) {  // eager launches instead of the captured graph
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     int rc = seq_amp<real>(c, B, T, flags, has_b0);
@@ -411,6 +580,18 @@ int set_power(sa_ctx* c, const double* Pl) {
     cl[l] = std::sqrt((double)c->n * Pl[l]);  // np.sqrt(n*Pl), sparc_ldpc.py:214
     P += Pl[l];                                // np.sum(Pl), sparc_ldpc.py:190
   }
+  // A decode in flight on either lane reads d_c / d_P1: an unchanged Pl (a
+  // caller passing it with every stage) writes nothing, a new one waits for
+  // every lane first.
+  const bool same = c->h_Pl.size() == (size_t)c->L && std::memcmp(c->h_Pl.data(), Pl, (size_t)c->L * 8) == 0;
+  if (same) {
+    c->pb_on = false;
+    c->shared_power = true;
+    c->power_set = true;
+    return SA_OK;
+  }
+  if (int rcs = sync_all(c)) return rcs;
+  c->h_Pl.clear();
   c->P = P;
   c->cmax = 0;
   for (int l = 0; l < c->L; ++l) c->cmax = cl[l] > c->cmax ? cl[l] : c->cmax;
@@ -423,6 +604,7 @@ int set_power(sa_ctx* c, const double* Pl) {
   c->shared_power = true;
   c->power_set = true;
   if (c->d_bfix && (rc = i8_set_bfix(c))) return rc;
+  c->h_Pl.assign(Pl, Pl + c->L);
   return SA_OK;
 }
 
@@ -436,6 +618,14 @@ int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   if (!Pl) return fail(SA_ERR_ARG, "Pl is NULL");
   if (is_dense(c)) return fail(SA_ERR_UNSUPPORTED, "per-codeword power: Hadamard backend only");
   const size_t L = (size_t)c->L;
+  // as set_power: unchanged allocations write nothing, new ones wait for every lane
+  if (c->h_Plb.size() == (size_t)B * L && std::memcmp(c->h_Plb.data(), Pl, (size_t)B * L * 8) == 0) {
+    c->pb_on = true;
+    c->power_set = true;
+    return SA_OK;
+  }
+  if (int rcs = sync_all(c)) return rcs;
+  c->h_Plb.clear();
   std::vector<double> cb((size_t)B * L), Pb(B);
   for (int b = 0; b < B; ++b) {
     double P = 0;
@@ -453,6 +643,7 @@ int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->pb_on = true;
   c->power_set = true;
+  c->h_Plb.assign(Pl, Pl + (size_t)B * L);
   return SA_OK;
 }
 
@@ -1080,7 +1271,8 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
     }
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+      hipEventCreateWithFlags(&c->lane[0].y_ev, hipEventDisableTiming) != hipSuccess) {
     delete c;
     return fail(SA_ERR_HIP, "stream/event creation failed");
   }
@@ -1169,7 +1361,13 @@ int sa_create_twin(sa_ctx* src, sa_ctx** out) {
 void sa_destroy(sa_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)lanes_release(c);  // waits for every lane; lane 0 is current from here
+  for (auto& l : c->lane) {
+    if (l.y_ev) (void)hipEventDestroy(l.y_ev);
+    if (l.ev0) (void)hipEventDestroy(l.ev0);
+    if (l.ev1) (void)hipEventDestroy(l.ev1);
+    if (l.stream) (void)hipStreamDestroy(l.stream);
+  }
   drop_graphs(c);
   free_workspace(c);
   mc_release(c);
@@ -1251,7 +1449,20 @@ int sa_stage(sa_ctx* c, int B, const double* y, const double* Pl, const double* 
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
   if (Pl && (rc = set_power(c, Pl))) return rc;
-  if (y && (rc = upload(c, c->d_y, y, (size_t)B * c->n))) return rc;  // NULL: keep the staged y
+  if (y) {  // NULL: keep the staged y
+    // Into the lane the next run will take, on that lane's stream: a decode in
+    // flight on the current lane is not waited for.  (A run that takes another
+    // lane after all copies y over first: y_sync.)  With beta0 the next run is
+    // a beta0 run, which stays on the current lane.
+    const int prev = c->cur;
+    const bool rotate = c->lanes_on && !beta0 && lane_shape(c, B) && pipelining(c);
+    lane_switch(c, rotate ? 1 - prev : prev);
+    rc = y_begin_write(c, c->stream, B);
+    if (!rc) rc = upload(c, c->d_y, y, (size_t)B * c->n);
+    if (!rc) rc = y_mark(c);
+    lane_switch(c, prev);
+    if (rc) return rc;
+  }
   if (beta0 && (rc = upload_sections(c, c->d_beta, beta0, B))) return rc;
   return SA_OK;
 }
@@ -1283,8 +1494,7 @@ int sa_run(sa_ctx* c, int B, int T, int flags) {
 int sa_wait(sa_ctx* c) {
   if (check_ctx(c)) return SA_ERR_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return SA_OK;
+  return sync_all(c);  // every lane
 }
 
 double sa_run_event_ms(sa_ctx* c) {
@@ -1354,8 +1564,10 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   if (B <= 0 || T <= 0 || !out || B > c->Bcap || T > c->Tcap || !c->power_set || rep < 1 || rep > 1024)
     return fail(SA_ERR_ARG, "sa_profile: bad arguments (reserve and stage first)");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int rcs = sync_all(c)) return rcs;  // the profiled decode has the chip to itself (it stays on the current lane)
   if (int rcb = ensure_beta2(c, B)) return rcb;
+  if (use_batched(c, B)) lane_switch(c, 0);  // as sa_run
+  if (int rcy = y_sync(c)) return rcy;
   if (use_batched(c, B))
     if (int rci = ensure_invb(c)) return rci;
   Prof prof;
@@ -1429,7 +1641,7 @@ int sa_decide_async(sa_ctx* c, int B, int slot) {
       if (c->h_dec && c->dec_B[k] != 0)
         return fail(SA_ERR_ARG, "sa_decide_async: the staged batch grew while slot " + std::to_string(k) +
                                     " holds decisions not yet collected (sa_decide_collect them first)");
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rcs = sync_all(c)) return rcs;  // either lane's k_decide may still write the old ring
     if (c->h_dec) (void)hipHostFree(c->h_dec);
     c->h_dec = nullptr;
     c->d_dec = nullptr;
