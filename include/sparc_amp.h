@@ -200,6 +200,12 @@ int sa_wait(sa_ctx* ctx);
 int sa_fetch(sa_ctx* ctx, int B, double* beta_out, int* iters_out);
 /* The residual z of the last decode's final iteration, B x n (diagnostics). */
 int sa_fetch_z(sa_ctx* ctx, int B, double* z_out);
+/* The staged y, B x n, widened to binary64: what the next sa_run would read
+ * (sa_stage's, or what sa_encode, sa_hard_cancel with dst or sa_cancel left
+ * as this context's input).  With two lanes live, the current lane's y is
+ * first brought up to the latest staged one, as a run does; no kernel other
+ * than the binary32 widening is launched and no layout changes. */
+int sa_fetch_y(sa_ctx* ctx, int B, double* y_out);
 double sa_run_event_ms(sa_ctx* ctx);
 
 /* Per-kernel device time of one EAGER decode of the staged batch (every
@@ -264,7 +270,8 @@ int sa_stage_onehot_scaled(sa_ctx* ctx, int B, const int32_t* idx, double scale)
 
 /* sp2bp + LLR (sparc_ldpc.py:470-479, :257-281) of sections [l0, l0+ns) of
  * the current beta: llr = nan_to_num(log(1-p) - log(p)), p the bitwise
- * posterior of beta_l / c_l. */
+ * posterior of beta_l / c_l (binary64 c_l; an entry equal to c_l in the
+ * context's precision counts as posterior 1, a decided section). */
 int sa_llr(sa_ctx* ctx, int B, int l0, int ns, double* llr, int flags);
 
 /* Soft exchange (sparc_ldpc.py:683-698): beta0 := beta with sections

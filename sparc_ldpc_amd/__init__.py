@@ -6,7 +6,7 @@ with the design operator and the whole iteration loop running as HIP kernels
 in ``libsparc_amp.so`` (C ABI: include/sparc_amp.h).  There is no CPU
 fallback: without the library or a HIP device every call raises.
 """
-from ._lib import SparcAmpError, load as load_library
+from ._lib import SparcAmpArgumentError, SparcAmpError, load as load_library
 from .operators import (SparcOperator, AbOp, AzOp, make_ordering, sub_fht, block_sub_fht, dense_transforms,
                         gaussian_transforms,
                         sparc_transforms, sparc_transforms_shorter, default_device)

@@ -62,7 +62,7 @@ def plan_bits(plan) -> int:
 # Every symbol include/sparc_amp.h declares (tests check the export table).
 EXPORTS = (
     "sa_create", "sa_create_ex", "sa_create_matrix", "sa_create_matrix_random", "sa_subset", "sa_create_twin", "sa_destroy", "sa_Ab", "sa_Az", "sa_amp",
-    "sa_reserve", "sa_stage", "sa_stage_power_batch", "sa_run", "sa_wait", "sa_fetch", "sa_fetch_z", "sa_run_event_ms",
+    "sa_reserve", "sa_stage", "sa_stage_power_batch", "sa_run", "sa_wait", "sa_fetch", "sa_fetch_z", "sa_fetch_y", "sa_run_event_ms",
     "sa_profile", "sa_profile_rep", "sa_profile_dispatch", "sa_profile_kinds", "sa_decide",
     "sa_decide_async", "sa_decide_collect", "sa_info", "sa_device_count", "sa_last_error", "sa_version",
     "sa_encode", "sa_stage_onehot", "sa_llr", "sa_soft_beta0", "sa_hard_cancel",
@@ -92,6 +92,7 @@ _SIG = {
     "sa_wait": (_I, [_P]),
     "sa_fetch": (_I, [_P, _I, _D, ct.POINTER(ct.c_int)]),
     "sa_fetch_z": (_I, [_P, _I, _D]),
+    "sa_fetch_y": (_I, [_P, _I, _D]),
     "sa_run_event_ms": (ct.c_double, [_P]),
     "sa_profile": (_I, [_P, _I, _I, _I, _D]),
     "sa_profile_rep": (_I, [_P, _I, _I, _I, _I, _D]),
@@ -180,11 +181,16 @@ def load(path: str = LIB_PATH) -> ct.CDLL:
     return lib
 
 
+class SparcAmpArgumentError(SparcAmpError, AssertionError):
+    """SA_ERR_ARG: the reference's ``assert`` cases.  An AssertionError, as the
+    reference raises, and a SparcAmpError like every other refusal of the library."""
+
+
 def check(rc: int) -> None:
     if rc != SA_OK:
         msg = load().sa_last_error().decode(errors="replace")
         if rc == SA_ERR_ARG:
-            raise AssertionError(msg)
+            raise SparcAmpArgumentError(rc, msg)
         raise SparcAmpError(rc, msg)
 
 

@@ -76,7 +76,12 @@ __global__ void __launch_bounds__(64) k_llr(const real* __restrict__ beta, const
   const int l = l0 + (int)(bl % ns);
   const real* bs = beta + ((bl / ns) * L + l) * M;
   const double c = cd[l];
-  for (int j = threadIdx.x; j < M; j += 64) post[j] = (double)bs[j] / c;
+  // An entry holding the whole section amplitude in the working type is a
+  // decided section: posterior 1, as c_l / c_l in binary64.  (In binary32
+  // (float)c_l / c_l is 1 -+ 6e-8: the bits of a decided section would get
+  // |LLR| near 16.6 or, with p above 1, NaN -> 0 instead of the saturated -+max.)
+  const real cr = (real)c;
+  for (int j = threadIdx.x; j < M; j += 64) post[j] = bs[j] == cr ? 1.0 : (double)bs[j] / c;
   __syncthreads();
   const int t = threadIdx.x;
   if (t >= lgM) return;

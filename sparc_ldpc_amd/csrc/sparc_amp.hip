@@ -1523,6 +1523,16 @@ int sa_fetch_z(sa_ctx* c, int B, double* z_out) {
   return SA_OK;
 }
 
+int sa_fetch_y(sa_ctx* c, int B, double* y_out) {
+  if (check_ctx(c) || !y_out) return fail(SA_ERR_ARG, "sa_fetch_y: bad arguments");
+  if (B <= 0 || B > c->Bcap) return fail(SA_ERR_ARG, "sa_fetch_y: bad batch");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = y_sync(c))) return rc;  // the y the next run would read, wherever it was staged
+  if ((rc = download(c, y_out, c->d_y, (size_t)B * c->n))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return SA_OK;
+}
 
 int sa_fetch(sa_ctx* c, int B, double* beta_out, int* iters_out) {
   if (check_ctx(c)) return SA_ERR_ARG;

@@ -309,6 +309,13 @@ class SparcOperator:
         check(self._lib.sa_fetch_z(self._ctx, int(B), z.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_double))))
         return z
 
+    def fetch_y(self, B):
+        """The staged y, (B, n): what the next run would read (stage's, or what
+        encode / cancel / hard_cancel with dst left as this operator's input)."""
+        y = np.empty((B, self.n))
+        check(self._lib.sa_fetch_y(self._ctx, int(B), dptr(y)))
+        return y
+
     def plan(self, B):
         """Which kernels a decode of B codewords runs (sa_plan)."""
         o = np.zeros(8, dtype=np.int64)
