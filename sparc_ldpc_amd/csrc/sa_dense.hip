@@ -332,8 +332,8 @@ int i8_set_bfix(sa_ctx* c) {
   if (c->cmax > 0) (void)std::frexp(c->cmax * (1.0 + 1.0 / 1024), &E);
   const double sfix = std::ldexp(1.0, i8_bits<kI8NPB>() - E);
   const double h[2] = {sfix, 1.0 / (sfix * std::sqrt((double)c->n))};
-  HIP_TRY(hipMemcpyAsync(c->d_bfix, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_bfix, h, sizeof(h), hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -350,18 +350,18 @@ int ensure_i8(sa_ctx* c, int B) {
     if ((rc = dev_alloc(c, (void**)&c->d_bfix, 2 * sizeof(double)))) return rc;
     uint32_t* d_ord = nullptr;
     HIP_TRY(hipMalloc(&d_ord, c->ordering.size() * 4));
-    HIP_TRY(hipMemcpyAsync(d_ord, c->ordering.data(), c->ordering.size() * 4, hipMemcpyHostToDevice, c->stream));
-    k_i8_build<<<8192, 256, 0, c->stream>>>(d_ord, c->d_A8, c->L, c->M, c->n, c->w, c->np8, c->LMp8, 0);
-    k_i8_build<<<8192, 256, 0, c->stream>>>(d_ord, c->d_AT8, c->L, c->M, c->n, c->w, c->LMp8, c->np8, 1);
+    HIP_TRY(hipMemcpyAsync(d_ord, c->ordering.data(), c->ordering.size() * 4, hipMemcpyHostToDevice, c->at().stream));
+    k_i8_build<<<8192, 256, 0, c->at().stream>>>(d_ord, c->d_A8, c->L, c->M, c->n, c->w, c->np8, c->LMp8, 0);
+    k_i8_build<<<8192, 256, 0, c->at().stream>>>(d_ord, c->d_AT8, c->L, c->M, c->n, c->w, c->LMp8, c->np8, 1);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->at().stream);
     (void)hipFree(d_ord);
     if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("k_i8_build: ") + hipGetErrorString(e));
     if (c->power_set && (rc = i8_set_bfix(c))) return rc;
   }
   const int Bp = i8_bp(B);
   if (Bp > c->Bp8) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
     drop_graphs(c);
     dev_free(c->d_zq); dev_free(c->d_bq); dev_free(c->d_zsc); dev_free(c->d_bsc0);
     c->d_zq = c->d_bq = nullptr;
@@ -372,9 +372,9 @@ int ensure_i8(sa_ctx* c, int B) {
     if ((rc = dev_alloc(c, (void**)&c->d_bq, bb))) return rc;
     if ((rc = dev_alloc(c, (void**)&c->d_zsc, (size_t)Bp * sizeof(double)))) return rc;
     if ((rc = dev_alloc(c, (void**)&c->d_bsc0, (size_t)Bp * sizeof(double)))) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_zq, 0, zb, c->stream));  // K and codeword padding stays zero
-    HIP_TRY(hipMemsetAsync(c->d_bq, 0, bb, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_zq, 0, zb, c->at().stream));  // K and codeword padding stays zero
+    HIP_TRY(hipMemsetAsync(c->d_bq, 0, bb, c->at().stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
     c->Bp8 = Bp;
   }
   return SA_OK;
@@ -383,9 +383,10 @@ int ensure_i8(sa_ctx* c, int B) {
 template <typename real>
 DenseArgs<real> dense_args(sa_ctx* c, int t, int es, int mode) {
   DenseArgs<real> a;
-  a.A = (const real*)c->d_A; a.z = (const real*)c->d_z; a.azp = (real*)c->d_azp;
-  a.beta = (const real*)c->d_beta; a.abp = (real*)c->d_abp; a.zzp = (const real*)c->d_zzp;
-  a.tau = (const real*)c->d_tau;
+  const sa_lane& ln = c->at();
+  a.A = (const real*)c->d_A; a.z = (const real*)ln.d_z; a.azp = (real*)c->d_azp;
+  a.beta = (const real*)ln.d_beta; a.abp = (real*)ln.d_abp; a.zzp = (const real*)ln.d_zzp;
+  a.tau = (const real*)ln.d_tau;
   a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = c->nz_cur; a.T1 = c->Tcap + 1; a.t = t;
   a.early_stop = es; a.RS = c->RS; a.KS = c->KS; a.mode = mode; a.lda = c->lda;
   return a;
@@ -395,9 +396,9 @@ template <typename real>
 int launch_dense_az(sa_ctx* c, int B, int t, int es, int mode) {
   DenseArgs<real> a = dense_args<real>(c, t, es, mode);
   dim3 grid((unsigned)((c->lda / V16<real>::N + 255) / 256), c->RS, B);
-  if (c->prof) c->prof->begin(c->stream, K_DAZ);
+  if (c->prof) c->prof->begin(c->at().stream, K_DAZ);
   plaunch(c, k_dense_az<real>, grid, 256, 0, a);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -406,9 +407,9 @@ template <typename real>
 int launch_dense_ab(sa_ctx* c, int B, int t, int es, int mode) {
   DenseArgs<real> a = dense_args<real>(c, t, es, mode);
   dim3 grid((unsigned)((c->n + kDenseRows - 1) / kDenseRows), c->KS, B);
-  if (c->prof) c->prof->begin(c->stream, K_DAB);
-  plaunch(c, k_dense_ab<real>, grid, 256, 0, a, (const real*)c->d_tau);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->begin(c->at().stream, K_DAB);
+  plaunch(c, k_dense_ab<real>, grid, 256, 0, a, (const real*)c->at().d_tau);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -416,12 +417,13 @@ int launch_dense_ab(sa_ctx* c, int B, int t, int es, int mode) {
 template <typename real, int E>
 void launch_dense_den_e(sa_ctx* c, int B, const DenArgs<real>& a, bool i8) {
   dim3 grid(c->Gd, B);
-  if (c->prof) c->prof->begin(c->stream, K_DDEN);
-  plaunch(c, k_dense_den<real, E>, grid, 256, 0, a, (const real*)c->d_c, (real*)c->d_beta,
-                                               (real*)c->d_bbp, (real*)c->d_tau, c->d_iters, c->Gd,
+  const sa_lane& ln = c->at();
+  if (c->prof) c->prof->begin(ln.stream, K_DDEN);
+  plaunch(c, k_dense_den<real, E>, grid, 256, 0, a, (const real*)c->d_c, (real*)ln.d_beta,
+                                               (real*)ln.d_bbp, (real*)ln.d_tau, ln.d_iters, c->Gd,
                                                i8 ? c->d_bq : nullptr, (long long)c->Bp8 * c->LMp8,
                                                c->LMp8, c->d_bfix);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(ln.stream);
 }
 
 // i8 = true: the Az of the matrix-core GEMM (one partial, d_azp[b][0][:]) and
@@ -430,7 +432,7 @@ void launch_dense_den_e(sa_ctx* c, int B, const DenArgs<real>& a, bool i8) {
 template <typename real>
 int launch_dense_den(sa_ctx* c, int B, int t, int es, bool i8 = false, bool one_partial = false) {
   DenArgs<real> a;
-  a.azp = (const real*)c->d_azp; a.zzp = (const real*)c->d_zzp; a.tau = (const real*)c->d_tau;
+  a.azp = (const real*)c->d_azp; a.zzp = (const real*)c->at().d_zzp; a.tau = (const real*)c->at().d_tau;
   a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = c->nz_cur; a.T1 = c->Tcap + 1; a.t = t; a.early_stop = es;
   a.RS = (i8 || one_partial || c->backend == SA_BACKEND_HOST) ? 1 : c->RS;
   a.lda = c->lda;
@@ -452,10 +454,10 @@ int launch_dense_den(sa_ctx* c, int B, int t, int es, bool i8 = false, bool one_
 // bytes per row (K = np8 for z, LMp8 for beta), scales sc[b] = 1/(s_b sqrt(n)).
 template <int NP>
 int launch_i8_quant(sa_ctx* c, int B, const void* src, long long ld, int len, int8_t* q, long long K, double* sc) {
-  if (c->prof) c->prof->begin(c->stream, K_QNT);
+  if (c->prof) c->prof->begin(c->at().stream, K_QNT);
   plaunch(c, k_i8_quant<NP>, B, 256, 0, (const float*)src, ld, len, q, (long long)c->Bp8 * K, K,
                                                          sc, 1.0 / std::sqrt((double)c->n));
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -475,9 +477,9 @@ int launch_gemm_i8(sa_ctx* c, int B, const int8_t* X, long long K, const int8_t*
   if (i8_bp(B) > c->Bp8 || K % kI8KS || Yrows % kI8TY) return fail(SA_ERR_ARG, "k_gemm_i8: operand shapes");
   const long long grid = (long long)a.XT * a.YT * S;
   if (grid > 0x7fffffff) return fail(SA_ERR_UNSUPPORTED, "k_gemm_i8: grid too large");
-  if (c->prof) c->prof->begin(c->stream, kind);
+  if (c->prof) c->prof->begin(c->at().stream, kind);
   plaunch(c, k_gemm_i8<NP>, (unsigned)grid, 512, I8Tile<NP>::Lds, a);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -486,15 +488,15 @@ int launch_gemm_i8(sa_ctx* c, int B, const int8_t* X, long long K, const int8_t*
 // (quantised at a per-codeword scale: an arbitrary beta, e.g. beta0)
 int i8_ab_any(sa_ctx* c, int B, int S) {
   const long long LM = (long long)c->L * c->M;
-  int rc = launch_i8_quant<kI8NPB>(c, B, c->d_beta, LM, (int)LM, c->d_bq, c->LMp8, c->d_bsc0);
+  int rc = launch_i8_quant<kI8NPB>(c, B, c->at().d_beta, LM, (int)LM, c->d_bq, c->LMp8, c->d_bsc0);
   if (rc) return rc;
-  return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->d_abp, (long long)S * c->n,
+  return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->at().d_abp, (long long)S * c->n,
                         c->n, S, c->d_bsc0, 1, K_DAB);
 }
 
 // Az of the z in d_z on the GEMM path into out[b][0 .. L*M) (rows ldb apart)
 int i8_az(sa_ctx* c, int B, float* out, long long ldb) {
-  int rc = launch_i8_quant<kI8NPZ>(c, B, c->d_z, c->n, c->n, c->d_zq, c->np8, c->d_zsc);
+  int rc = launch_i8_quant<kI8NPZ>(c, B, c->at().d_z, c->n, c->n, c->d_zq, c->np8, c->d_zsc);
   if (rc) return rc;
   return launch_gemm_i8<kI8NPZ>(c, B, c->d_zq, c->np8, c->d_AT8, c->LMp8, c->L * c->M, out, ldb, 0, 1, c->d_zsc, 1,
                         K_DAZ);
@@ -527,16 +529,16 @@ int ensure_fgemm(sa_ctx* c, int B) {
     if ((rc = dev_alloc(c, &c->d_AT, (size_t)c->LMy * (size_t)c->nk * s))) return rc;
     const dim3 grid((unsigned)((c->LMy + 63) / 64), (unsigned)((c->nk + 63) / 64));
     if (s == 8)
-      k_transpose<double><<<grid, 256, 0, c->stream>>>((const double*)c->d_A, (long long)c->lda, c->n,
+      k_transpose<double><<<grid, 256, 0, c->at().stream>>>((const double*)c->d_A, (long long)c->lda, c->n,
                                                        (long long)c->L * c->M, (double*)c->d_AT, c->LMy, c->nk);
     else
-      k_transpose<float><<<grid, 256, 0, c->stream>>>((const float*)c->d_A, (long long)c->lda, c->n,
+      k_transpose<float><<<grid, 256, 0, c->at().stream>>>((const float*)c->d_A, (long long)c->lda, c->n,
                                                       (long long)c->L * c->M, (float*)c->d_AT, c->LMy, c->nk);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
   }
   if (B > c->fg_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
     drop_graphs(c);
     dev_free(c->d_xz); dev_free(c->d_xb);
     c->d_xz = c->d_xb = nullptr;
@@ -560,12 +562,12 @@ int launch_gemm_f(sa_ctx* c, int B, const real* X, long long ldx, const real* Y,
     return fail(SA_ERR_ARG, "k_gemm_f: operand shapes");
   const long long grid = (long long)a.XT * a.YT * S;
   if (grid > 0x7fffffff) return fail(SA_ERR_UNSUPPORTED, "k_gemm_f: grid too large");
-  if (c->prof) c->prof->begin(c->stream, kind);
+  if (c->prof) c->prof->begin(c->at().stream, kind);
   if (kind == K_DAB)
     plaunch(c, k_gemm_f<real, 1>, (unsigned)grid, 512, kFLds, a);
   else
     plaunch(c, k_gemm_f<real, 0>, (unsigned)grid, 512, kFLds, a);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -574,22 +576,21 @@ int launch_gemm_f(sa_ctx* c, int B, const real* X, long long ldx, const real* Y,
 template <typename real>
 int fgemm_ab(sa_ctx* c, int B, int S) {
   const long long LM = (long long)c->L * c->M;
-  const real* X = (const real*)c->d_beta;
+  const real* X = (const real*)c->at().d_beta;
   if (LM != (long long)c->lda) {  // L*M not a whole number of K stages: a zero-padded copy
-    k_pad_rows<real><<<4096, 256, 0, c->stream>>>((const real*)c->d_beta, LM, LM, (real*)c->d_xb, (long long)c->lda,
-                                                  B);
+    k_pad_rows<real><<<4096, 256, 0, c->at().stream>>>(X, LM, LM, (real*)c->d_xb, (long long)c->lda, B);
     HIP_TRY(hipGetLastError());
     X = (const real*)c->d_xb;
   }
   return launch_gemm_f<real>(c, B, X, (long long)c->lda, (const real*)c->d_A, (long long)c->lda, (long long)c->lda,
-                             c->np, c->n, (real*)c->d_abp, (long long)S * c->n, c->n, S, K_DAB);
+                             c->np, c->n, (real*)c->at().d_abp, (long long)S * c->n, c->n, S, K_DAB);
 }
 
 // A^T z of the z in d_z on the GEMM path into out[b][0 .. L*M) (rows ldb apart)
 template <typename real>
 int fgemm_az(sa_ctx* c, int B, real* out, long long ldb) {
-  k_pad_rows<real><<<4096, 256, 0, c->stream>>>((const real*)c->d_z, (long long)c->n, (long long)c->n,
-                                                (real*)c->d_xz, c->nk, B);
+  k_pad_rows<real><<<4096, 256, 0, c->at().stream>>>((const real*)c->at().d_z, (long long)c->n, (long long)c->n,
+                                                     (real*)c->d_xz, c->nk, B);
   HIP_TRY(hipGetLastError());
   return launch_gemm_f<real>(c, B, (const real*)c->d_xz, c->nk, (const real*)c->d_AT, c->nk, c->nk, c->LMy,
                              c->L * c->M, out, ldb, 0, 1, K_DAZ);
@@ -602,11 +603,11 @@ int build_dense(sa_ctx* c) {
   if ((rc = dev_alloc(c, (void**)&c->d_A, (size_t)n * c->lda * sizeof(float)))) return rc;
   uint32_t* d_ord = nullptr;
   HIP_TRY(hipMalloc(&d_ord, c->ordering.size() * 4));
-  HIP_TRY(hipMemcpyAsync(d_ord, c->ordering.data(), c->ordering.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_ord, c->ordering.data(), c->ordering.size() * 4, hipMemcpyHostToDevice, c->at().stream));
   const float s = (float)(1.0 / std::sqrt((double)n));
-  k_dense_build<<<8192, 256, 0, c->stream>>>(d_ord, (float*)c->d_A, L, M, n, w, c->lda, s);
+  k_dense_build<<<8192, 256, 0, c->at().stream>>>(d_ord, (float*)c->d_A, L, M, n, w, c->lda, s);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->at().stream);
   (void)hipFree(d_ord);
   if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("k_dense_build: ") + hipGetErrorString(e));
   return SA_OK;
@@ -643,7 +644,7 @@ int dense_iter(sa_ctx* c, int B, int t, int es, int S) {
     // -> denoiser (+ beta digit planes) -> A beta GEMM (S partials)
     if ((rc = i8_az(c, B, (float*)c->d_azp, (long long)c->lda))) return rc;
     if ((rc = launch_dense_den<float>(c, B, t, es, true))) return rc;
-    return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->d_abp,
+    return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->at().d_abp,
                                   (long long)S * c->n, c->n, S, c->d_bfix + 1, 0, K_DAB);
   }
   if (use_fgemm(c, B)) {
@@ -686,7 +687,7 @@ int dense_az(sa_ctx* c, int B) {
   int rc = launch_dense_az<real>(c, B, 0, 0, 1);
   if (rc) return rc;
   // the RS row-split partials into d_out
-  k_dense_az_reduce<real><<<4096, 256, 0, c->stream>>>((const real*)c->d_azp, (real*)c->d_out, c->RS, c->lda,
+  k_dense_az_reduce<real><<<4096, 256, 0, c->at().stream>>>((const real*)c->d_azp, (real*)c->d_out, c->RS, c->lda,
                                                        (size_t)c->L * c->M, B);
   HIP_TRY(hipGetLastError());
   return SA_OK;
@@ -712,7 +713,7 @@ int matrix_init(sa_ctx* c) {
   c->LMy = ((long long)c->L * c->M + kFTY - 1) / kFTY * kFTY;
   int rc = dev_alloc(c, &c->d_A, (size_t)c->np * c->lda * s);
   if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_A, 0, (size_t)c->np * c->lda * s, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_A, 0, (size_t)c->np * c->lda * s, c->at().stream));
   return SA_OK;
 }
 
@@ -748,17 +749,18 @@ int sa_create_matrix(sa_ctx** out, int L, int M, int n, const double* A, int pre
   const long long LM = (long long)L * M;
   const long long chunk = std::max(1LL, std::min<long long>(n, (32LL << 20) / LM));
   rc = ensure_stage(c, (size_t)(chunk * LM));
+  const sa_lane& ln = c->at();
   for (long long r0 = 0; !rc && r0 < n; r0 += chunk) {
     const long long rows = std::min<long long>(chunk, n - r0);
-    hipError_t e = hipMemcpyAsync(c->d_stage, A + r0 * LM, (size_t)(rows * LM) * 8, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(ln.d_stage, A + r0 * LM, (size_t)(rows * LM) * 8, hipMemcpyHostToDevice, ln.stream);
     if (e == hipSuccess) {
       if (c->prec == SA_PREC_F64)
-        k_matrix_rows<double><<<4096, 256, 0, c->stream>>>(c->d_stage, (double*)c->d_A, rows, LM, c->lda, r0);
+        k_matrix_rows<double><<<4096, 256, 0, ln.stream>>>(ln.d_stage, (double*)c->d_A, rows, LM, c->lda, r0);
       else
-        k_matrix_rows<float><<<4096, 256, 0, c->stream>>>(c->d_stage, (float*)c->d_A, rows, LM, c->lda, r0);
+        k_matrix_rows<float><<<4096, 256, 0, ln.stream>>>(ln.d_stage, (float*)c->d_A, rows, LM, c->lda, r0);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the staging buffer is reused
+    if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);  // the staging buffer is reused
     if (e != hipSuccess) rc = fail(SA_ERR_HIP, std::string("sa_create_matrix upload: ") + hipGetErrorString(e));
   }
   if (rc) {
@@ -779,13 +781,13 @@ int sa_create_matrix_random(sa_ctx** out, int L, int M, int n, uint64_t seed, do
   if (rc) return rc;
   const long long LM = (long long)L * M;
   if (c->prec == SA_PREC_F64)
-    k_matrix_gauss<double><<<8192, 256, 0, c->stream>>>((double*)c->d_A, n, LM, c->lda, (unsigned long long)seed,
+    k_matrix_gauss<double><<<8192, 256, 0, c->at().stream>>>((double*)c->d_A, n, LM, c->lda, (unsigned long long)seed,
                                                          scale);
   else
-    k_matrix_gauss<float><<<8192, 256, 0, c->stream>>>((float*)c->d_A, n, LM, c->lda, (unsigned long long)seed,
+    k_matrix_gauss<float><<<8192, 256, 0, c->at().stream>>>((float*)c->d_A, n, LM, c->lda, (unsigned long long)seed,
                                                         scale);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->at().stream);
   if (e != hipSuccess) {
     sa_destroy(c);
     return fail(SA_ERR_HIP, std::string("k_matrix_gauss: ") + hipGetErrorString(e));
@@ -809,14 +811,15 @@ template <typename real>
 int host_init_impl(sa_ctx* c, int B, const double* beta0, const double* ab0) {
   int rc;
   pick_row(c, B);
-  k_fill32<<<(B + 255) / 256, 256, 0, c->stream>>>((uint32_t*)c->d_iters, 0xffffffffu, (size_t)B);
+  const sa_lane& ln = c->at();
+  k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
   if (beta0) {  // z = y - Ab(beta0) with the caller's Ab(beta0) (sparc_ldpc.py:196-200)
-    if ((rc = upload(c, c->d_beta, beta0, (size_t)B * c->L * c->M))) return rc;
-    if ((rc = upload(c, c->d_abp, ab0, (size_t)B * c->n))) return rc;
+    if ((rc = upload(c, ln.d_beta, beta0, (size_t)B * c->L * c->M))) return rc;
+    if ((rc = upload(c, ln.d_abp, ab0, (size_t)B * c->n))) return rc;
     return launch_row<real>(c, B, ROW_INIT, 0, 0, 1, c->Gd);
   }
   const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
-  k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, c->stream>>>((uint32_t*)c->d_beta, 0u, nw);
+  k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, ln.stream>>>((uint32_t*)ln.d_beta, 0u, nw);
   return launch_row<real>(c, B, ROW_INIT0, 0, 0, 1, c->Gd);
 }
 }  // namespace
@@ -830,7 +833,7 @@ int sa_host_init(sa_ctx* c, int B, int T, const double* y, const double* Pl, con
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, T > 0 ? T : 1);
   if (!rc) rc = set_power(c, Pl);
-  if (!rc) rc = upload(c, c->d_y, y, (size_t)B * c->n);
+  if (!rc) rc = upload(c, c->at().d_y, y, (size_t)B * c->n);
   if (rc) return rc;
   rc = c->prec == SA_PREC_F64 ? host_init_impl<double>(c, B, beta0, ab0) : host_init_impl<float>(c, B, beta0, ab0);
   if (rc) return rc;
@@ -843,15 +846,16 @@ int sa_host_tau(sa_ctx* c, int B, int t, int flags, int* stopped) {
   if (t < 0 || t >= c->Tcap || !stopped) return fail(SA_ERR_ARG, "sa_host_tau: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
+  const sa_lane& ln = c->at();
   if (c->prec == SA_PREC_F64)
-    k_tau<double><<<B, 64, 0, c->stream>>>((const double*)c->d_zzp, c->nz_cur, c->n, (double*)c->d_tau, c->Tcap + 1,
-                                            t, es, c->d_iters, c->d_stop);
+    k_tau<double><<<B, 64, 0, ln.stream>>>((const double*)ln.d_zzp, c->nz_cur, c->n, (double*)ln.d_tau, c->Tcap + 1,
+                                           t, es, ln.d_iters, c->d_stop);
   else
-    k_tau<float><<<B, 64, 0, c->stream>>>((const float*)c->d_zzp, c->nz_cur, c->n, (float*)c->d_tau, c->Tcap + 1,
-                                           t, es, c->d_iters, c->d_stop);
+    k_tau<float><<<B, 64, 0, ln.stream>>>((const float*)ln.d_zzp, c->nz_cur, c->n, (float*)ln.d_tau, c->Tcap + 1,
+                                          t, es, ln.d_iters, c->d_stop);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(stopped, c->d_stop, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(stopped, c->d_stop, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 
@@ -870,7 +874,7 @@ int sa_host_residual(sa_ctx* c, int B, int t, int flags, const double* ab) {
   if (t < 0 || t >= c->Tcap || !ab) return fail(SA_ERR_ARG, "sa_host_residual: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
-  int rc = upload(c, c->d_abp, ab, (size_t)B * c->n);
+  int rc = upload(c, c->at().d_abp, ab, (size_t)B * c->n);
   if (!rc)
     rc = c->prec == SA_PREC_F64 ? launch_row<double>(c, B, ROW_AMP, t, es, 1, c->Gd)
                                 : launch_row<float>(c, B, ROW_AMP, t, es, 1, c->Gd);

@@ -220,8 +220,8 @@ int dev_in(sa_ctx* c, const double* p, size_t count, int flags, const double** o
   }
   int rc = ensure_stage(c, count);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_stage, p, count * 8, hipMemcpyHostToDevice, c->stream));
-  *out = c->d_stage;
+  HIP_TRY(hipMemcpyAsync(c->at().d_stage, p, count * 8, hipMemcpyHostToDevice, c->at().stream));
+  *out = c->at().d_stage;
   return SA_OK;
 }
 
@@ -229,7 +229,7 @@ template <typename real>
 int launch_colsum(sa_ctx* c, const int32_t* d_idx, int ldi, int l0, int ns, const real* base, const double* add,
                   real* out, int B, double amp = 1.0) {
   dim3 grid((c->n + 255) / 256, B);
-  k_colsum<real><<<grid, 256, (size_t)ns * sizeof(int32_t), c->stream>>>(
+  k_colsum<real><<<grid, 256, (size_t)ns * sizeof(int32_t), c->at().stream>>>(
       (const ushort4*)c->d_fwd, c->d_cd, d_idx, ldi, l0, ns, base, add, out, c->n, std::sqrt((double)c->n), amp);
   HIP_TRY(hipGetLastError());
   return SA_OK;
@@ -250,17 +250,18 @@ int sa_encode(sa_ctx* c, int B, const int32_t* idx, const double* noise) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
+  sa_lane& ln = c->at();
   for (size_t i = 0; i < (size_t)B * c->L; ++i)
     if (idx[i] < 0 || idx[i] >= c->M) return fail(SA_ERR_ARG, "sa_encode: index outside [0, M)");
-  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
   const double* d_noise = nullptr;
   if (noise && (rc = dev_in(c, noise, (size_t)B * c->n, 0, &d_noise))) return rc;
-  if ((rc = y_begin_write(c, c->stream, B))) return rc;  // the current lane's y becomes the staged one
+  if ((rc = y_begin_write(c, ln.stream, B))) return rc;  // the current lane's y becomes the staged one
   rc = c->prec == SA_PREC_F64
-           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (double*)c->d_y, B)
-           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (float*)c->d_y, B);
+           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (double*)ln.d_y, B)
+           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (float*)ln.d_y, B);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return y_mark(c);
 }
 
@@ -275,14 +276,15 @@ int stage_onehot_impl(sa_ctx* c, int B, const int32_t* idx, double scale, bool a
     if (idx[i] >= c->M || (idx[i] < 0 && !(allow_empty && idx[i] == -1)))
       return fail(SA_ERR_ARG, "sa_stage_onehot: index outside [0, M)");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  sa_lane& ln = c->at();
+  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
   const size_t tot = (size_t)B * c->L * c->M;
   if (c->prec == SA_PREC_F64)
-    k_onehot<double><<<grid_of(tot), 256, 0, c->stream>>>(c->d_idx, c->d_cd, c->L, c->M, B, scale, (double*)c->d_beta);
+    k_onehot<double><<<grid_of(tot), 256, 0, ln.stream>>>(c->d_idx, c->d_cd, c->L, c->M, B, scale, (double*)ln.d_beta);
   else
-    k_onehot<float><<<grid_of(tot), 256, 0, c->stream>>>(c->d_idx, c->d_cd, c->L, c->M, B, scale, (float*)c->d_beta);
+    k_onehot<float><<<grid_of(tot), 256, 0, ln.stream>>>(c->d_idx, c->d_cd, c->L, c->M, B, scale, (float*)ln.d_beta);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 }  // namespace
@@ -298,21 +300,22 @@ int sa_llr(sa_ctx* c, int B, int l0, int ns, double* llr, int flags) {
   if (rc) return rc;
   if (!llr) return fail(SA_ERR_ARG, "sa_llr: llr is NULL");
   HIP_TRY(hipSetDevice(c->device));
+  sa_lane& ln = c->at();
   const int lgM = ilog2(c->M);
   const size_t cnt = (size_t)B * ns * lgM;
   double* d_out = llr;
   if (!(flags & SA_PTR_DEVICE)) {
     if ((rc = ensure_stage(c, cnt))) return rc;
-    d_out = c->d_stage;
+    d_out = ln.d_stage;
   }
   const size_t lds = (size_t)c->M * sizeof(double);
   if (c->prec == SA_PREC_F64)
-    k_llr<double><<<B * ns, 64, lds, c->stream>>>((const double*)c->d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
+    k_llr<double><<<B * ns, 64, lds, ln.stream>>>((const double*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
   else
-    k_llr<float><<<B * ns, 64, lds, c->stream>>>((const float*)c->d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
+    k_llr<float><<<B * ns, 64, lds, ln.stream>>>((const float*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
   HIP_TRY(hipGetLastError());
-  if (!(flags & SA_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(llr, d_out, cnt * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!(flags & SA_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(llr, d_out, cnt * 8, hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 
@@ -321,24 +324,25 @@ int sa_soft_beta0(sa_ctx* c, int B, int l0, int ns, const double* app, int flags
   if (rc) return rc;
   if (!app) return fail(SA_ERR_ARG, "sa_soft_beta0: app is NULL");
   HIP_TRY(hipSetDevice(c->device));
+  sa_lane& ln = c->at();
   const int lgM = ilog2(c->M);
   const size_t na = (size_t)B * ns * lgM;
   const double* d_app = app;
   if (!(flags & SA_PTR_DEVICE)) {
     if ((rc = ensure_stage(c, na))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_stage, app, na * 8, hipMemcpyHostToDevice, c->stream));
-    d_app = c->d_stage;
+    HIP_TRY(hipMemcpyAsync(ln.d_stage, app, na * 8, hipMemcpyHostToDevice, ln.stream));
+    d_app = ln.d_stage;
   }
   const size_t tot = (size_t)B * c->L * c->M, lds = (size_t)c->M * sizeof(double);
   if (c->prec == SA_PREC_F64) {
-    if (ns < c->L) k_rescale<double><<<grid_of(tot), 256, 0, c->stream>>>((double*)c->d_beta, c->d_cd, c->L, c->M, l0, ns, B);
-    k_soft_sec<double><<<B * ns, 64, lds, c->stream>>>(d_app, c->d_cd, c->L, c->M, lgM, l0, ns, (double*)c->d_beta);
+    if (ns < c->L) k_rescale<double><<<grid_of(tot), 256, 0, ln.stream>>>((double*)ln.d_beta, c->d_cd, c->L, c->M, l0, ns, B);
+    k_soft_sec<double><<<B * ns, 64, lds, ln.stream>>>(d_app, c->d_cd, c->L, c->M, lgM, l0, ns, (double*)ln.d_beta);
   } else {
-    if (ns < c->L) k_rescale<float><<<grid_of(tot), 256, 0, c->stream>>>((float*)c->d_beta, c->d_cd, c->L, c->M, l0, ns, B);
-    k_soft_sec<float><<<B * ns, 64, lds, c->stream>>>(d_app, c->d_cd, c->L, c->M, lgM, l0, ns, (float*)c->d_beta);
+    if (ns < c->L) k_rescale<float><<<grid_of(tot), 256, 0, ln.stream>>>((float*)ln.d_beta, c->d_cd, c->L, c->M, l0, ns, B);
+    k_soft_sec<float><<<B * ns, 64, lds, ln.stream>>>(d_app, c->d_cd, c->L, c->M, lgM, l0, ns, (float*)ln.d_beta);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 
@@ -351,22 +355,23 @@ int sa_hard_cancel(sa_ctx* c, int B, int l0, int ns, const double* app, int flag
     return fail(SA_ERR_ARG, "sa_hard_cancel: dst must share n, precision and device");
   HIP_TRY(hipSetDevice(c->device));
   if (dst && (rc = ensure_workspace(dst, B, dst->Tcap > 0 ? dst->Tcap : 1))) return rc;
+  sa_lane& ln = c->at();  // (dst may be c: after its workspace)
   const int lgM = ilog2(c->M);
   const double* d_app = nullptr;
   if ((rc = dev_in(c, app, (size_t)B * ns * lgM, flags, &d_app))) return rc;
-  k_app_idx<<<(B * ns + 255) / 256, 256, 0, c->stream>>>(d_app, lgM, ns, B, c->d_idx);
+  k_app_idx<<<(B * ns + 255) / 256, 256, 0, ln.stream>>>(d_app, lgM, ns, B, c->d_idx);
   HIP_TRY(hipGetLastError());
   if (dst) {
     // reads the staged y (wherever it was staged), writes dst's
-    if ((rc = y_sync(c)) || (rc = y_begin_write(dst, c->stream, B))) return rc;
+    if ((rc = y_sync(c)) || (rc = y_begin_write(dst, ln.stream, B))) return rc;
     rc = c->prec == SA_PREC_F64
-             ? launch_colsum<double>(c, c->d_idx, ns, l0, ns, (const double*)c->d_y, nullptr, (double*)dst->d_y, B)
-             : launch_colsum<float>(c, c->d_idx, ns, l0, ns, (const float*)c->d_y, nullptr, (float*)dst->d_y, B);
+             ? launch_colsum<double>(c, c->d_idx, ns, l0, ns, (const double*)ln.d_y, nullptr, (double*)dst->at().d_y, B)
+             : launch_colsum<float>(c, c->d_idx, ns, l0, ns, (const float*)ln.d_y, nullptr, (float*)dst->at().d_y, B);
     if (rc) return rc;
   }
   if (idx_out)
-    HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return dst ? y_mark(dst) : SA_OK;
 }
 
@@ -376,13 +381,14 @@ int sa_threshold(sa_ctx* c, int B, int l0, int ns, const double* app, int flags,
   if (rc) return rc;
   if (!app || !idx_out) return fail(SA_ERR_ARG, "sa_threshold: null argument");
   HIP_TRY(hipSetDevice(c->device));
+  sa_lane& ln = c->at();
   const int lgM = ilog2(c->M);
   const double* d_app = nullptr;
   if ((rc = dev_in(c, app, (size_t)B * ns * lgM, flags, &d_app))) return rc;
-  k_threshold<<<B * ns, 256, (size_t)c->M * sizeof(double), c->stream>>>(d_app, c->M, lgM, ns, threshold, c->d_idx);
+  k_threshold<<<B * ns, 256, (size_t)c->M * sizeof(double), ln.stream>>>(d_app, c->M, lgM, ns, threshold, c->d_idx);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 
@@ -400,13 +406,14 @@ int sa_cancel_scaled(sa_ctx* c, int B, const int32_t* idx, double scale, sa_ctx*
   HIP_TRY(hipSetDevice(c->device));
   int rc;
   if ((rc = ensure_workspace(dst, B, dst->Tcap > 0 ? dst->Tcap : 1))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  if ((rc = y_sync(c)) || (rc = y_begin_write(dst, c->stream, B))) return rc;  // as sa_hard_cancel
+  sa_lane& ln = c->at();  // (dst may be c: after its workspace)
+  HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+  if ((rc = y_sync(c)) || (rc = y_begin_write(dst, ln.stream, B))) return rc;  // as sa_hard_cancel
   rc = c->prec == SA_PREC_F64
-           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, (const double*)c->d_y, nullptr, (double*)dst->d_y, B, scale)
-           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, (const float*)c->d_y, nullptr, (float*)dst->d_y, B, scale);
+           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, (const double*)ln.d_y, nullptr, (double*)dst->at().d_y, B, scale)
+           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, (const float*)ln.d_y, nullptr, (float*)dst->at().d_y, B, scale);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return y_mark(dst);
 }
 

@@ -51,17 +51,19 @@ enum { K_SEC = 0, K_ROW = 1, K_DAZ = 2, K_DDEN = 3, K_DAB = 4, K_QNT = 5, K_NKIN
 // A decode lane: everything one small-batch decode mutates, so that two
 // consecutive decodes of a context can share the chip (step k + 1 reads
 // nothing step k writes; the tables, the power arrays and the decision ring
-// are read-only during a decode and stay shared).  The context's own stream /
-// d_* / graphs fields ARE the current lane (the lane of the last sa_run):
-// lane_switch parks them here and loads the other lane's, so every entry point
-// written against c->d_* addresses the last run's lane.  lane[cur]'s parked
-// fields are stale while it is current; y_ev / y_ver / y_read are never
-// swapped and always authoritative.
+// are read-only during a decode and stay shared).  A lane's state lives here
+// and nowhere else: the context holds lane[kLanes] and the index cur of the
+// current lane (the lane of the last sa_run), and every entry point reaches
+// the stream / d_* / graphs of that lane through sa_ctx::at().  A field added
+// to a lane is declared here once.  A reference taken from at() names a lane
+// object, not "the current lane": take it after the last call that can change
+// cur (lane_switch, lanes_release, ensure_workspace, ensure_beta2, run_graph).
 struct sa_lane {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_beta2 = nullptr, *d_abp = nullptr;
+  void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_abp = nullptr;
   void *d_bbp = nullptr, *d_zzp = nullptr, *d_tau = nullptr;
+  void* d_beta2 = nullptr;  // ping-pong partner of d_beta for k_sec (B x L*M), sized beta2_cap
   int* d_iters = nullptr;
   double* d_stage = nullptr;  // a lane's uploads go through its own staging buffer
   size_t stage_cap = 0;
@@ -77,7 +79,9 @@ struct sa_ctx {
   // decode lanes (compile-time 2: the ring and bench protocols keep at most two steps in flight)
   enum { kLanes = 2 };
   sa_lane lane[kLanes];
-  int cur = 0;            // the current lane (its fields live in this struct)
+  int cur = 0;            // the current lane
+  sa_lane& at() { return lane[cur]; }
+  const sa_lane& at() const { return lane[cur]; }
   bool lanes_on = false;  // lane 1's buffers exist (created at the first eligible sa_run)
   unsigned long long y_ver = 0;  // version of the y staged last
   int y_lane = 0;                // the lane that holds it
@@ -112,12 +116,11 @@ struct sa_ctx {
   bool row16 = false;  // k_row2<16> after k_sec4 (row-block-major partials, NZh <= 320)
   int NZ4 = 0, NZ2 = 0;  // k_rowv<4> 256-row / k_rowv<2> 128-row blocks
   int row_kind = 0;    // row kernel of the current decode: 0 k_row, 1 k_row2, 2 k_rowv<4>, 3 k_rowv<2>, 4 k_row2<16>, 5 k_rowc
+  // (describes one lane's d_z, yet stays here: in the lane, sa_fetch_z after sa_mc_stage would answer differently)
   bool zil_last = false;  // the last decode left z codeword-interleaved ([NC][n][CB], zil_for)
   int nz_cur = 0;
   size_t sec2_lds = 0;
   std::vector<uint32_t> ordering;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint16_t* d_inv = nullptr;
   // operators whose z does not fit the section kernels' LDS (n >= 65535, or
   // the z image past 160 KB): k_secg with 32-bit bucket entries, no batched /
@@ -147,18 +150,12 @@ struct sa_ctx {
   void *d_AT = nullptr, *d_xz = nullptr, *d_xb = nullptr;
   int fg_cap = 0;
   double cmax = 0;  // max_l sqrt(n Pl_l) of the shared power allocation
-  // workspace
+  // workspace shared by the lanes (lane 0's decode buffers are sized with it)
   int Bcap = 0, Tcap = 0;
-  void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_out = nullptr, *d_abp = nullptr;
-  void *d_bbp = nullptr, *d_zzp = nullptr, *d_tau = nullptr, *d_c = nullptr, *d_azp = nullptr;
-  int* d_iters = nullptr;
+  void *d_out = nullptr, *d_c = nullptr, *d_azp = nullptr;
   int* d_stop = nullptr;  // host-operator loop: codewords whose exact-tau stop fired
   int32_t* d_idx = nullptr;
-  double* d_stage = nullptr;
-  size_t stage_cap = 0;
   double* d_cd = nullptr;  // c_l = sqrt(n Pl_l) in binary64 (joint-decoding glue)
-  void* d_beta2 = nullptr;  // ping-pong partner of d_beta for k_sec (B x L*M), sized beta2_cap
-  int beta2_cap = 0;
   double P = 0;
   bool power_set = false;
   // per-codeword power allocation (sa_stage_power_batch): c [Bcap][L], P [Bcap]
@@ -168,7 +165,6 @@ struct sa_ctx {
   bool pb_on = false;
   bool shared_power = false;  // sa_stage's Pl staged (c_l of the binary64 glue kernels)
   size_t bytes = 0;
-  std::map<std::tuple<int, int, int, int>, hipGraphExec_t> graphs;
   int last_B = 0, last_T = 0;
   // pinned ring of sa_decide_async: SA_DECIDE_SLOTS slots of dec_cap indices
   int32_t* h_dec = nullptr;
@@ -203,12 +199,12 @@ void plaunch(sa_ctx* c, F kernel, dim3 grid, dim3 block, size_t lds, Args... arg
   if (c->prof && c->prof->dispatch) {
     hipEvent_t a = nullptr, b = nullptr;
     if (c->prof->add(&a, &b) == 0) {
-      hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)lds, c->stream, a, b, 0u, args...);
+      hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)lds, c->at().stream, a, b, 0u, args...);
       return;
     }
   }
   const int nrep = c->prof ? c->prof->rep : 1;
-  for (int r = 0; r < nrep; ++r) kernel<<<grid, block, lds, c->stream>>>(args...);
+  for (int r = 0; r < nrep; ++r) kernel<<<grid, block, lds, c->at().stream>>>(args...);
 }
 
 
@@ -289,12 +285,13 @@ inline int pt_for(const sa_ctx* c, int B, bool sec2) {
 template <typename real>
 SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
   SecArgs<real> a;
+  const sa_lane& ln = c->at();
   a.inv = c->d_inv; a.inv32 = c->d_inv32; a.invb = c->d_invb; a.invl = c->d_invl; a.hs = c->d_hs;
   a.fwd = (const ushort4*)c->d_fwd;
   a.fwdb = (const ushort4*)c->d_fwdb; a.fwd2 = c->d_fwd2; a.fwd3 = c->d_fwd3; a.c = (const real*)c->d_c;
-  a.z = (const real*)c->d_z; a.beta = (real*)c->d_beta; a.beta_out = (real*)c->d_beta; a.out = (real*)c->d_out;
-  a.abp = (real*)c->d_abp; a.bbp = (real*)c->d_bbp; a.zzp = (const real*)c->d_zzp;
-  a.tau = (real*)c->d_tau; a.iters = c->d_iters;
+  a.z = (const real*)ln.d_z; a.beta = (real*)ln.d_beta; a.beta_out = (real*)ln.d_beta; a.out = (real*)c->d_out;
+  a.abp = (real*)ln.d_abp; a.bbp = (real*)ln.d_bbp; a.zzp = (const real*)ln.d_zzp;
+  a.tau = (real*)ln.d_tau; a.iters = ln.d_iters;
   a.L = c->L; a.M = c->M; a.n = c->n; a.w = c->w; a.nhi = c->nhi; a.G = c->G; a.NZ = c->nz_cur;
   a.T1 = c->Tcap + 1; a.t = t; a.mode = mode; a.early_stop = early_stop;
   a.RS = 1;
@@ -312,8 +309,9 @@ SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
 template <typename real>
 RowArgs<real> row_args(sa_ctx* c, int mode, int t, int early_stop, int G, int Gb) {
   RowArgs<real> a;
-  a.y = (const real*)c->d_y; a.z = (real*)c->d_z; a.z_in = a.z; a.abp = (const real*)c->d_abp;
-  a.bbp = (const real*)c->d_bbp; a.zzp = (real*)c->d_zzp; a.tau = (const real*)c->d_tau;
+  const sa_lane& ln = c->at();
+  a.y = (const real*)ln.d_y; a.z = (real*)ln.d_z; a.z_in = a.z; a.abp = (const real*)ln.d_abp;
+  a.bbp = (const real*)ln.d_bbp; a.zzp = (real*)ln.d_zzp; a.tau = (const real*)ln.d_tau;
   a.out = (real*)c->d_out;
   a.n = c->n; a.G = G; a.NZ = c->nz_cur;
   a.Gb = Gb; a.T1 = c->Tcap + 1; a.t = t; a.mode = mode;
@@ -325,7 +323,7 @@ RowArgs<real> row_args(sa_ctx* c, int mode, int t, int early_stop, int G, int Gb
   a.pt = 0;
   a.Bc = 0;
   a.tb = c->mc_tb;
-  a.iters = c->d_iters;
+  a.iters = ln.d_iters;
   a.itset = 0;
   return a;
 }
@@ -357,20 +355,28 @@ void drop_graphs(sa_ctx* c);  // every lane's
 // decode lanes: wait for every lane; make lane k current; drop lane 1's buffers
 // (after waiting for every lane; lane 0 becomes current and keeps the staged y)
 int sync_all(sa_ctx* c);
-void lane_switch(sa_ctx* c, int k);
+inline void lane_switch(sa_ctx* c, int k) { c->cur = k; }
 int lanes_release(sa_ctx* c);
-// the staged y across lanes: y_sync brings the current lane's d_y up to the
-// latest staged version (a device-to-device copy on its stream, behind the
-// event recorded after the staging); a writer of B codewords of the current
-// lane's d_y on stream s calls y_begin_write before it launches and y_mark
-// after (when s is not the lane's own stream: after waiting for s)
-int y_sync(sa_ctx* c);
-int y_begin_write(sa_ctx* c, hipStream_t s, int B);
-int y_mark(sa_ctx* c);
+// the staged y across lanes: y_sync brings lane k's d_y up to the latest
+// staged version (a device-to-device copy on its stream, behind the event
+// recorded after the staging); a writer of B codewords of lane k's d_y on
+// stream s calls y_begin_write before it launches and y_mark after (when s is
+// not the lane's own stream: after waiting for s).  Without k: the current lane.
+int y_sync(sa_ctx* c, int k);
+int y_begin_write(sa_ctx* c, int k, hipStream_t s, int B);
+int y_mark(sa_ctx* c, int k);
+inline int y_sync(sa_ctx* c) { return y_sync(c, c->cur); }
+inline int y_begin_write(sa_ctx* c, hipStream_t s, int B) { return y_begin_write(c, c->cur, s, B); }
+inline int y_mark(sa_ctx* c) { return y_mark(c, c->cur); }
 int ensure_workspace(sa_ctx* c, int B, int T);
-int ensure_stage(sa_ctx* c, size_t count);
-int upload(sa_ctx* c, void* dst, const double* src, size_t count);
-int download(sa_ctx* c, double* dst, const void* src, size_t count);
+// host fp64 <-> a device `real` buffer through lane l's staging buffer, on its
+// stream.  Without l: the current lane.
+int ensure_stage(sa_ctx* c, sa_lane& l, size_t count);
+int upload(sa_ctx* c, sa_lane& l, void* dst, const double* src, size_t count);
+int download(sa_ctx* c, sa_lane& l, double* dst, const void* src, size_t count);
+inline int ensure_stage(sa_ctx* c, size_t count) { return ensure_stage(c, c->at(), count); }
+inline int upload(sa_ctx* c, void* dst, const double* src, size_t count) { return upload(c, c->at(), dst, src, count); }
+inline int download(sa_ctx* c, double* dst, const void* src, size_t count) { return download(c, c->at(), dst, src, count); }
 int set_power(sa_ctx* c, const double* Pl);
 int ensure_invb(sa_ctx* c);
 int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int backend, int prec, int device,

@@ -294,7 +294,7 @@ McArgs mc_args(sa_ctx* c, int B, int T) {
   a.rep = c->d_slots; a.tb = c->d_slots + S; a.done = c->d_slots + 2 * S; a.fresh = c->d_slots + 3 * S;
   a.fin_list = c->d_slots + 4 * S; a.fresh_list = c->d_slots + 5 * S;
   a.ctl = c->d_slots + 6 * S;
-  a.iters = c->d_iters;
+  a.iters = c->at().d_iters;
   a.dec = c->d_mc_dec; a.its = c->d_mc_its; a.errs = c->d_mc_its + c->mc_cap; a.idx = c->d_mc_idx;
   a.noise = c->d_mc_noise;
   a.B = B; a.T = T; a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = c->NZ2;
@@ -310,12 +310,13 @@ int mc_turnover(sa_ctx* c, const McArgs& a) {
   constexpr int CBz = 16 / (int)sizeof(real);
   const real* ya = (const real*)c->d_mc_y;
   const real* za = (const real*)c->d_mc_zzp;
+  const sa_lane& ln = c->at();
   switch (c->E) {
 #define SA_TO(EE)                                                                                             \
   case EE:                                                                                                    \
-    k_mc_turnover<real, EE, CBz><<<gto + gfill, 256, 0, c->stream>>>(a, (real*)c->d_beta, gto, ya, za,        \
-                                                                     (real*)c->d_y, (real*)c->d_z,            \
-                                                                     (real*)c->d_zzp);                        \
+    k_mc_turnover<real, EE, CBz><<<gto + gfill, 256, 0, ln.stream>>>(a, (real*)ln.d_beta, gto, ya, za,        \
+                                                                     (real*)ln.d_y, (real*)ln.d_z,            \
+                                                                     (real*)ln.d_zzp);                        \
     break;
     SA_TO(1) SA_TO(2) SA_TO(4) SA_TO(8) SA_TO(16)
 #undef SA_TO
@@ -328,8 +329,8 @@ int mc_turnover(sa_ctx* c, const McArgs& a) {
 // every staged rep's y and z^2 partials (k_mc_encode)
 template <typename real>
 int mc_encode_all(sa_ctx* c, const McArgs& a, int nreps) {
-  k_mc_encode<real><<<dim3(c->NZ2, (nreps + kFillSlots - 1) / kFillSlots), 128, 0, c->stream>>>(a, nreps, (const ushort4*)c->d_fwd, c->d_cd, std::sqrt((double)c->n),
-                                   (real*)c->d_mc_y, (real*)c->d_mc_zzp);
+  k_mc_encode<real><<<dim3(c->NZ2, (nreps + kFillSlots - 1) / kFillSlots), 128, 0, c->at().stream>>>(
+      a, nreps, (const ushort4*)c->d_fwd, c->d_cd, std::sqrt((double)c->n), (real*)c->d_mc_y, (real*)c->d_mc_zzp);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -344,7 +345,7 @@ int mc_iterations(sa_ctx* c, int B, int T, int K, int es) {
   for (int k = 0; k < K && !rc; ++k) {
     if ((rc = launch_secb<real>(c, B, 0, es))) break;
     if ((rc = launch_row<real>(c, B, ROW_AMP, 0, es, c->Gb, c->Gb))) break;
-    k_mc_step<<<1, kMcStepThreads, 0, c->stream>>>(a);
+    k_mc_step<<<1, kMcStepThreads, 0, c->at().stream>>>(a);
     if ((rc = mc_turnover<real>(c, a))) break;
   }
   c->mc_tb = nullptr;
@@ -355,7 +356,7 @@ int mc_iterations(sa_ctx* c, int B, int T, int K, int es) {
 
 int mc_ensure_slots(sa_ctx* c, int B) {
   if (c->slot_cap >= B) return SA_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);
   c->mc_graphs.clear();
   dev_free(c->d_slots);
@@ -447,7 +448,7 @@ int sa_mc_stage(sa_ctx* c, int nreps, const int32_t* idx, const double* noise) {
   HIP_TRY(hipSetDevice(c->device));
   lane_switch(c, 0);  // the stream and its graphs live with lane 0 (the batched decode's lane)
   if (nreps > c->mc_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
     dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
     dev_free(c->d_mc_y); dev_free(c->d_mc_zzp);
     c->d_mc_idx = c->d_mc_dec = c->d_mc_its = nullptr;
@@ -467,10 +468,10 @@ int sa_mc_stage(sa_ctx* c, int nreps, const int32_t* idx, const double* noise) {
     if ((rc = dev_alloc(c, &c->d_mc_zzp, (size_t)nreps * c->NZ2 * rsz(c)))) return rc;
     c->mc_cap = nreps;
   }
-  HIP_TRY(hipMemcpyAsync(c->d_mc_idx, idx, (size_t)nreps * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_mc_idx, idx, (size_t)nreps * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->at().stream));
   HIP_TRY(hipMemcpyAsync(c->d_mc_noise, noise, (size_t)nreps * c->n * sizeof(double), hipMemcpyHostToDevice,
-                         c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+                         c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   c->mc_nreps = nreps;
   return SA_OK;
 }
@@ -490,6 +491,7 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   if ((rc = ensure_workspace(c, B, T))) return rc;
   if ((rc = ensure_invb(c))) return rc;
   if ((rc = mc_ensure_slots(c, B))) return rc;
+  sa_lane& ln = c->at();  // lane 0, for the rest of the run
   if (!c->h_mc_live) {
     HIP_TRY(hipHostMalloc((void**)&c->h_mc_live, 4 * sizeof(int), hipHostMallocDefault));
     for (auto& e : c->mc_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -519,14 +521,14 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
     ctl[2] = nreps;
     ctl[3] = 0;       // finished (none yet)
     ctl[4] = n0;      // refilled
-    HIP_TRY(hipMemcpyAsync(c->d_slots, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_beta, 0, (size_t)B * c->L * c->M * rsz(c), c->stream));
-    k_fill32<<<(B + 255) / 256, 256, 0, c->stream>>>((uint32_t*)c->d_iters, 0xffffffffu, (size_t)B);
-    k_fill32<<<(nreps + 255) / 256, 256, 0, c->stream>>>((uint32_t*)(c->d_mc_its + c->mc_cap), 0u, (size_t)nreps);
+    HIP_TRY(hipMemcpyAsync(c->d_slots, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, ln.stream));
+    HIP_TRY(hipMemsetAsync(ln.d_beta, 0, (size_t)B * c->L * c->M * rsz(c), ln.stream));
+    k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
+    k_fill32<<<(nreps + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)(c->d_mc_its + c->mc_cap), 0u, (size_t)nreps);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));  // h is a host temporary
+    HIP_TRY(hipStreamSynchronize(ln.stream));  // h is a host temporary
   }
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
   const McArgs a = mc_args(c, B, T);
   if ((rc = f64 ? mc_encode_all<double>(c, a, nreps) : mc_encode_all<float>(c, a, nreps))) return rc;
   if ((rc = f64 ? mc_turnover<double>(c, a) : mc_turnover<float>(c, a))) return rc;
@@ -536,10 +538,10 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   const auto key = std::make_tuple(B, T, K, flags & 0xff);
   auto it = c->mc_graphs.find(key);
   if (it == c->mc_graphs.end()) {
-    HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
     rc = f64 ? mc_iterations<double>(c, B, T, K, es) : mc_iterations<float>(c, B, T, K, es);
     hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(c->stream, &g);
+    hipError_t e = hipStreamEndCapture(ln.stream, &g);
     if (rc) {
       if (g) (void)hipGraphDestroy(g);
       return rc;
@@ -558,33 +560,33 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   int* live_dev = c->d_slots + 6 * c->slot_cap + 1;
   long long r = 0;
   for (; r < max_replays; ++r) {
-    HIP_TRY(hipGraphLaunch(it->second, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_mc_live + (r & 3), live_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->mc_ev[r & 3], c->stream));
+    HIP_TRY(hipGraphLaunch(it->second, ln.stream));
+    HIP_TRY(hipMemcpyAsync(c->h_mc_live + (r & 3), live_dev, sizeof(int), hipMemcpyDeviceToHost, ln.stream));
+    HIP_TRY(hipEventRecord(c->mc_ev[r & 3], ln.stream));
     if (r >= 2) {
       HIP_TRY(hipEventSynchronize(c->mc_ev[(r - 2) & 3]));
       if (c->h_mc_live[(r - 2) & 3] == 0) break;
     }
   }
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   int ctl[2] = {0, 0};
   HIP_TRY(hipMemcpy(ctl, c->d_slots + 6 * c->slot_cap, sizeof(ctl), hipMemcpyDeviceToHost));
   if (ctl[1] != 0 || ctl[0] != nreps) return fail(SA_ERR_HIP, "sa_mc_run: the stream did not drain");
   if (ms_out) {
     float ms = -1.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, ln.ev0, ln.ev1));
     *ms_out = ms;
   }
   if (dec_out)
     HIP_TRY(hipMemcpyAsync(dec_out, c->d_mc_dec, (size_t)nreps * c->L * sizeof(int32_t), hipMemcpyDeviceToHost,
-                           c->stream));
+                           ln.stream));
   if (iters_out)
-    HIP_TRY(hipMemcpyAsync(iters_out, c->d_mc_its, (size_t)nreps * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iters_out, c->d_mc_its, (size_t)nreps * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
   if (errs_out)
     HIP_TRY(hipMemcpyAsync(errs_out, c->d_mc_its + c->mc_cap, (size_t)nreps * sizeof(int32_t), hipMemcpyDeviceToHost,
-                           c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+                           ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   c->last_B = B;
   c->last_T = T;
   return SA_OK;

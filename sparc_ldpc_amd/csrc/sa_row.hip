@@ -468,7 +468,7 @@ int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt,
     return fail(SA_ERR_ARG, "launch_row: the z^2 partial count is not k_row2's row-block count");
   if (zout) a.z = (real*)zout;
   if (zin) a.z_in = (const real*)zin;
-  if (c->prof) c->prof->begin(c->stream, K_ROW);
+  if (c->prof) c->prof->begin(c->at().stream, K_ROW);
   // small batch: 16-row workgroups cover the chip; many codewords: 64-row
   // workgroups, 4 waves with deeper per-lane load streams
   if (c->row_kind == 5 && mode != ROW_ABOUT) {
@@ -497,19 +497,20 @@ int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt,
   } else {
     plaunch(c, k_row<real, 4>, dim3(c->NZ, B), 4 * 64, 0, a);
   }
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
 
 int launch_decide(sa_ctx* c, int B, int32_t* idx) {
   dim3 grid((c->L + 3) / 4, B);
+  const sa_lane& ln = c->at();
 #define SA_DEC(EE)                                                                                             \
   case EE:                                                                                                     \
     if (c->prec == SA_PREC_F64)                                                                                \
-      k_decide<double, EE><<<grid, 256, 0, c->stream>>>((const double*)c->d_beta, idx, c->L, c->M, c->dead);      \
+      k_decide<double, EE><<<grid, 256, 0, ln.stream>>>((const double*)ln.d_beta, idx, c->L, c->M, c->dead);   \
     else                                                                                                       \
-      k_decide<float, EE><<<grid, 256, 0, c->stream>>>((const float*)c->d_beta, idx, c->L, c->M, c->dead);        \
+      k_decide<float, EE><<<grid, 256, 0, ln.stream>>>((const float*)ln.d_beta, idx, c->L, c->M, c->dead);     \
     break;
   switch (c->E) { SA_DEC(1) SA_DEC(2) SA_DEC(4) SA_DEC(8) SA_DEC(16) SA_DEC(32) SA_DEC(64) }
 #undef SA_DEC

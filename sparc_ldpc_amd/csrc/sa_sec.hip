@@ -826,12 +826,12 @@ template <typename real, int E>
 void launch_sec_e(sa_ctx* c, int B, SecArgs<real> a) {
   a.RS = row_splits(c, B);
   dim3 grid(c->G * a.RS, B);
-  if (c->prof) c->prof->begin(c->stream, K_SEC);
+  if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   if (c->big)
     plaunch(c, k_secg<real, E>, grid, 256, c->sec_lds, a);
   else
     plaunch(c, k_sec<real, E>, grid, 256, c->sec_lds, a);
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
 }
 
 template <typename real>
@@ -844,14 +844,14 @@ int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt, 
   a.beta_out = (real*)bout;
   a.G = sec2_parts(c);
   dim3 grid(a.G, B);
-  if (c->prof) c->prof->begin(c->stream, K_SEC);
+  if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   if (c->sec3) {
     switch (c->M / 256) {
       case 1: plaunch(c, k_sec43<real, 1>, grid, 768, c->sec3_lds, a); break;
       case 2: plaunch(c, k_sec43<real, 2>, grid, 768, c->sec3_lds, a); break;
       default: return fail(SA_ERR_UNSUPPORTED, "k_sec43: M");
     }
-    if (c->prof) c->prof->end(c->stream);
+    if (c->prof) c->prof->end(c->at().stream);
     HIP_TRY(hipGetLastError());
     return SA_OK;
   }
@@ -864,7 +864,7 @@ int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt, 
       case 16: plaunch(c, k_sec4<real, 16>, grid, 512, c->sec4_lds, a); break;
       default: return fail(SA_ERR_UNSUPPORTED, "k_sec4: M");
     }
-    if (c->prof) c->prof->end(c->stream);
+    if (c->prof) c->prof->end(c->at().stream);
     HIP_TRY(hipGetLastError());
     return SA_OK;
   }
@@ -877,7 +877,7 @@ int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt, 
     case 32: plaunch(c, k_sec2<real, 32>, grid, 256, c->sec2_lds, a); break;
     default: return fail(SA_ERR_UNSUPPORTED, "k_sec2: M");
   }
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }

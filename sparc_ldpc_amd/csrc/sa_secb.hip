@@ -630,7 +630,7 @@ void launch_secb_e(sa_ctx* c, int B, SecArgs<real> a) {
   a.NC = (B + CB - 1) / CB;
   a.zil = zil_for(c, B) ? 1 : 0;
   a.gpx = c->gpx;
-  if (c->prof) c->prof->begin(c->stream, K_SEC);
+  if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   const dim3 grid(c->Gb * a.NC);
   bool done = false;
   if constexpr (CB * sizeof(real) == 16) {
@@ -648,7 +648,7 @@ void launch_secb_e(sa_ctx* c, int B, SecArgs<real> a) {
     else
       plaunch(c, k_secb<real, E, CB, kWB>, grid, kWB * 64, c->secb_lds, a);
   }
-  if (c->prof) c->prof->end(c->stream);
+  if (c->prof) c->prof->end(c->at().stream);
 }
 
 template <typename real, int CB>

@@ -86,107 +86,111 @@ void dev_free(void* p) {
 // ---- decode lanes (sa_host.h: sa_lane) ---------------------------------------
 
 int sync_all(sa_ctx* c) {
-  if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < sa_ctx::kLanes; ++k)
-    if (k != c->cur && c->lane[k].stream) HIP_TRY(hipStreamSynchronize(c->lane[k].stream));
+  for (auto& l : c->lane)
+    if (l.stream) HIP_TRY(hipStreamSynchronize(l.stream));
   return SA_OK;
 }
 
-// The current lane's fields of the context <-> lane l (a swap: parks one set, loads the other).
-static void lane_swap_fields(sa_ctx* c, sa_lane& l) {
-  std::swap(c->stream, l.stream);
-  std::swap(c->ev0, l.ev0);
-  std::swap(c->ev1, l.ev1);
-  std::swap(c->d_y, l.d_y);
-  std::swap(c->d_z, l.d_z);
-  std::swap(c->d_beta, l.d_beta);
-  std::swap(c->d_beta2, l.d_beta2);
-  std::swap(c->d_abp, l.d_abp);
-  std::swap(c->d_bbp, l.d_bbp);
-  std::swap(c->d_zzp, l.d_zzp);
-  std::swap(c->d_tau, l.d_tau);
-  std::swap(c->d_iters, l.d_iters);
-  std::swap(c->d_stage, l.d_stage);
-  std::swap(c->stage_cap, l.stage_cap);
-  std::swap(c->beta2_cap, l.beta2_cap);
-  c->graphs.swap(l.graphs);
-}
-
-void lane_switch(sa_ctx* c, int k) {
-  if (k == c->cur) return;
-  lane_swap_fields(c, c->lane[c->cur]);  // park
-  lane_swap_fields(c, c->lane[k]);       // load
-  c->cur = k;
-}
-
-static int y_wait_reader(sa_ctx* c, hipStream_t s) {
-  sa_lane& o = c->lane[1 - c->cur];
-  if (c->lanes_on && o.y_read) {  // the other lane's copy of this lane's y must have read it
+// Before stream s writes lane k's d_y: the other lane's copy of it must have read it.
+static int y_wait_reader(sa_ctx* c, int k, hipStream_t s) {
+  sa_lane& o = c->lane[1 - k];
+  if (c->lanes_on && o.y_read) {
     HIP_TRY(hipStreamWaitEvent(s, o.y_ev, 0));
     o.y_read = false;
   }
   return SA_OK;
 }
 
-int y_begin_write(sa_ctx* c, hipStream_t s, int B) {
+int y_begin_write(sa_ctx* c, int k, hipStream_t s, int B) {
   if (!c->lanes_on) return SA_OK;
   if (B < c->Bcap) {  // the rows past B keep the latest staged values
-    if (int rc = y_sync(c)) return rc;
-    if (s != c->stream) HIP_TRY(hipStreamWaitEvent(s, c->lane[c->cur].y_ev, 0));
+    if (int rc = y_sync(c, k)) return rc;
+    if (s != c->lane[k].stream) HIP_TRY(hipStreamWaitEvent(s, c->lane[k].y_ev, 0));
   }
-  return y_wait_reader(c, s);
+  return y_wait_reader(c, k, s);
 }
 
-int y_mark(sa_ctx* c) {
-  sa_lane& l = c->lane[c->cur];
+int y_mark(sa_ctx* c, int k) {
+  sa_lane& l = c->lane[k];
   l.y_ver = ++c->y_ver;
-  c->y_lane = c->cur;  // (y_read stays: the event recorded here lies behind the lane's earlier copy too)
-  if (l.y_ev) HIP_TRY(hipEventRecord(l.y_ev, c->stream));
+  c->y_lane = k;  // (y_read stays: the event recorded here lies behind the lane's earlier copy too)
+  if (l.y_ev) HIP_TRY(hipEventRecord(l.y_ev, l.stream));
   return SA_OK;
 }
 
-int y_sync(sa_ctx* c) {
-  sa_lane& l = c->lane[c->cur];
+int y_sync(sa_ctx* c, int k) {
+  sa_lane& l = c->lane[k];
   if (!c->lanes_on || l.y_ver == c->y_ver) return SA_OK;
-  sa_lane& src = c->lane[c->y_lane];  // parked: the holder is not the current lane
-  HIP_TRY(hipStreamWaitEvent(c->stream, src.y_ev, 0));
-  if (int rc = y_wait_reader(c, c->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_y, src.d_y, (size_t)c->Bcap * c->n * rsz(c), hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(hipEventRecord(l.y_ev, c->stream));
+  sa_lane& src = c->lane[c->y_lane];
+  HIP_TRY(hipStreamWaitEvent(l.stream, src.y_ev, 0));
+  if (int rc = y_wait_reader(c, k, l.stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(l.d_y, src.d_y, (size_t)c->Bcap * c->n * rsz(c), hipMemcpyDeviceToDevice, l.stream));
+  HIP_TRY(hipEventRecord(l.y_ev, l.stream));
   l.y_ver = c->y_ver;
   l.y_read = true;
   return SA_OK;
 }
 
-// Lane 1's stream, events and buffers, sized like lane 0's for the small-batch
-// path (no batched-layout padding: a lane never runs the batched kernels).
-static int lane_create(sa_ctx* c) {
-  sa_lane& l = c->lane[1 - c->cur];
+// A lane's stream and events (lane 0: with the context; lane 1: at its first use).
+static int lane_open(sa_lane& l) {
   if (!l.stream) HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
   if (!l.ev0) HIP_TRY(hipEventCreate(&l.ev0));
   if (!l.ev1) HIP_TRY(hipEventCreate(&l.ev1));
   if (!l.y_ev) HIP_TRY(hipEventCreateWithFlags(&l.y_ev, hipEventDisableTiming));
-  const size_t s = rsz(c), LM = (size_t)c->L * c->M, nB = (size_t)c->Bcap;
-  int Gmax = c->G;
-  if (c->G2 > Gmax) Gmax = c->G2;
-  if (c->G3 > Gmax) Gmax = c->G3;
+  return SA_OK;
+}
+
+static int beta2_alloc(sa_ctx* c, sa_lane& l, size_t nB) {
+  int rc = dev_alloc(c, &l.d_beta2, nB * c->L * c->M * rsz(c));
+  if (!rc) l.beta2_cap = (int)nB;
+  return rc;
+}
+
+// A lane's decode buffers for nB codewords and T iterations.  What differs
+// between the lanes: nBp, the codewords d_z and d_abp are padded to (lane 0:
+// whole chunks of the interleaved batched layout); Gmax, the most Ab / beta^2
+// partials per codeword of any kernel the lane runs; and whether d_beta2 comes
+// now or with the first run that needs it (ensure_beta2).
+static int lane_alloc(sa_ctx* c, sa_lane& l, size_t nB, size_t nBp, int T, int Gmax, bool beta2) {
+  const size_t s = rsz(c), LM = (size_t)c->L * c->M;
   int rc;
   if ((rc = dev_alloc(c, &l.d_y, nB * c->n * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_z, nB * c->n * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_z, nBp * c->n * s))) return rc;
   if ((rc = dev_alloc(c, &l.d_beta, nB * LM * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_beta2, nB * LM * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_abp, nB * Gmax * ((size_t)c->NZ16 * kRow2Rows) * s))) return rc;
+  // rows padded to 32: the row-block-major layout of the pair / triple kernels (SecArgs::pt)
+  if ((rc = dev_alloc(c, &l.d_abp, nBp * Gmax * ((size_t)c->NZ16 * kRow2Rows) * s))) return rc;
   if ((rc = dev_alloc(c, &l.d_bbp, nB * Gmax * s))) return rc;
   if ((rc = dev_alloc(c, &l.d_zzp, nB * c->NZh * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_tau, nB * (c->Tcap + 1) * s))) return rc;
+  if ((rc = dev_alloc(c, &l.d_tau, nB * (T + 1) * s))) return rc;
   if ((rc = dev_alloc(c, (void**)&l.d_iters, nB * sizeof(int)))) return rc;
+  return beta2 ? beta2_alloc(c, l, nB) : SA_OK;
+}
+
+static void lane_free(sa_lane& l) {
+  void** bufs[] = {&l.d_y, &l.d_z, &l.d_beta, &l.d_beta2, &l.d_abp, &l.d_bbp, &l.d_zzp, &l.d_tau, (void**)&l.d_iters};
+  for (void** p : bufs) {
+    dev_free(*p);
+    *p = nullptr;
+  }
+  l.beta2_cap = 0;
+}
+
+static void stage_free(sa_lane& l) {
+  dev_free(l.d_stage);
+  l.d_stage = nullptr;
+  l.stage_cap = 0;
+}
+
+// Lane 1's stream, events and buffers for the small-batch path (no batched-
+// layout padding or partials: a lane never runs the batched kernels).
+static int lane_create(sa_ctx* c) {
+  sa_lane& l = c->lane[1];  // (lane 0 is current while lane 1 is off)
+  if (int rco = lane_open(l)) return rco;
+  const int Gmax = std::max(c->G, std::max(c->G2, c->G3));
+  if (int rc = lane_alloc(c, l, c->Bcap, c->Bcap, c->Tcap, Gmax, true)) return rc;
   // the staging buffer the caller's uploads / fetches have needed so far: the
   // lane's first stage allocates nothing
-  if (c->stage_cap > 0 && !l.d_stage) {
-    if ((rc = dev_alloc(c, (void**)&l.d_stage, c->stage_cap * sizeof(double)))) return rc;
-    l.stage_cap = c->stage_cap;
-  }
-  l.beta2_cap = c->Bcap;
+  if (int rc = ensure_stage(c, l, c->lane[0].stage_cap)) return rc;
   l.y_ver = 0;  // older than any staged y: copied before the lane's first run
   l.y_read = false;
   c->lanes_on = true;
@@ -201,7 +205,7 @@ static int lane_create(sa_ctx* c) {
 static bool pipelining(const sa_ctx* c) {
   for (int k = 0; k < SA_DECIDE_SLOTS; ++k)
     if (c->dec_B[k] != 0) return true;
-  return c->ev1 && hipEventQuery(c->ev1) == hipErrorNotReady;
+  return c->at().ev1 && hipEventQuery(c->at().ev1) == hipErrorNotReady;
 }
 
 // Whether a run of B codewords may rotate lanes at all (the plan, the backend, the batch).
@@ -209,55 +213,43 @@ static bool lane_shape(const sa_ctx* c, int B) {
   return c->backend == SA_BACKEND_HADAMARD && !use_batched(c, B) && !(c->plan & (SA_PLAN_EAGER | SA_PLAN_NO_LANES));
 }
 
+static void graphs_clear(std::map<std::tuple<int, int, int, int>, hipGraphExec_t>& m) {
+  for (auto& kv : m) (void)hipGraphExecDestroy(kv.second);
+  m.clear();
+}
+
 int lanes_release(sa_ctx* c) {
   int rc = sync_all(c);
   if (!c->lanes_on) return rc;
   lane_switch(c, 0);
-  if (!rc) rc = y_sync(c);  // the staged y stays with lane 0
-  if (!rc && c->stream && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(SA_ERR_HIP, "lanes_release: sync failed");
-  sa_lane& l = c->lane[1];
-  for (auto& kv : l.graphs) (void)hipGraphExecDestroy(kv.second);
-  l.graphs.clear();
-  void** bufs[] = {&l.d_y, &l.d_z, &l.d_beta, &l.d_beta2, &l.d_abp, &l.d_bbp, &l.d_zzp, &l.d_tau};
-  for (void** p : bufs) {
-    dev_free(*p);
-    *p = nullptr;
-  }
-  dev_free(l.d_iters); l.d_iters = nullptr;
-  dev_free(l.d_stage); l.d_stage = nullptr;
-  l.stage_cap = 0;
-  l.beta2_cap = 0;
+  sa_lane &l0 = c->lane[0], &l = c->lane[1];
+  if (!rc) rc = y_sync(c, 0);  // the staged y stays with lane 0
+  if (!rc && l0.stream && hipStreamSynchronize(l0.stream) != hipSuccess)
+    rc = fail(SA_ERR_HIP, "lanes_release: sync failed");
+  graphs_clear(l.graphs);
+  lane_free(l);
+  stage_free(l);
   l.y_read = false;
-  c->lane[0].y_read = false;
-  c->lane[0].y_ver = c->y_ver;
+  l0.y_read = false;
+  l0.y_ver = c->y_ver;
   c->y_lane = 0;
   c->lanes_on = false;
   return rc;
 }
 
 void drop_graphs(sa_ctx* c) {
-  for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
-  c->graphs.clear();
-  for (auto& l : c->lane) {  // the parked lane's (the current lane's parked map is empty)
-    for (auto& kv : l.graphs) (void)hipGraphExecDestroy(kv.second);
-    l.graphs.clear();
-  }
-  for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);  // sa_mc_run's
-  c->mc_graphs.clear();
+  for (auto& l : c->lane) graphs_clear(l.graphs);
+  graphs_clear(c->mc_graphs);  // sa_mc_run's
 }
 
+// Lane 0's decode buffers and the buffers every lane shares.
 void free_workspace(sa_ctx* c) {
-  void** bufs[] = {&c->d_y, &c->d_z, &c->d_beta, &c->d_out, &c->d_abp, &c->d_bbp,
-                   &c->d_zzp, &c->d_tau, &c->d_azp, &c->d_cb, &c->d_Pb};
+  lane_free(c->lane[0]);
+  void** bufs[] = {&c->d_out, &c->d_azp, &c->d_cb, &c->d_Pb, (void**)&c->d_stop, (void**)&c->d_idx};
   for (void** p : bufs) {
     dev_free(*p);
     *p = nullptr;
   }
-  dev_free(c->d_iters); c->d_iters = nullptr;
-  dev_free(c->d_stop); c->d_stop = nullptr;
-  dev_free(c->d_idx); c->d_idx = nullptr;
-  dev_free(c->d_beta2); c->d_beta2 = nullptr;
-  c->beta2_cap = 0;
   c->Bcap = c->Tcap = 0;
   c->h_Plb.clear();  // d_cb / d_Pb went
   if (c->pb_on) {  // the per-codeword powers went with the workspace
@@ -281,7 +273,7 @@ int ensure_workspace(sa_ctx* c, int B, int T) {
   if (B <= c->Bcap && T <= c->Tcap) return SA_OK;
   if (int rcl = lanes_release(c)) return rcl;  // waits for every lane; lane 1 returns at the next eligible run
   drop_graphs(c);
-  const int nB = B > c->Bcap ? B : c->Bcap;
+  const size_t nB = B > c->Bcap ? B : c->Bcap;
   const int nT = T > c->Tcap ? T : c->Tcap;
   free_workspace(c);
   const size_t s = rsz(c), LM = (size_t)c->L * c->M;
@@ -292,73 +284,64 @@ int ensure_workspace(sa_ctx* c, int B, int T) {
   if (c->G2 > Gmax) Gmax = c->G2;
   if (c->G3 > Gmax) Gmax = c->G3;
   int rc;
-  if ((rc = dev_alloc(c, &c->d_y, nB * c->n * s))) return rc;
-  const size_t nBp = (size_t)(nB + 3) / 4 * 4;  // whole chunks of the interleaved batched layout
-  if ((rc = dev_alloc(c, &c->d_z, nBp * c->n * s))) return rc;
-  if ((rc = dev_alloc(c, &c->d_beta, nB * LM * s))) return rc;
+  const size_t nBp = (nB + 3) / 4 * 4;  // whole chunks of the interleaved batched layout
+  if ((rc = lane_alloc(c, c->lane[0], nB, nBp, nT, Gmax, false))) return rc;
   if ((rc = dev_alloc(c, &c->d_out, nB * (LM > (size_t)c->n ? LM : (size_t)c->n) * s))) return rc;
-  // rows padded to 32: the row-block-major layout of the pair / triple kernels (SecArgs::pt)
-  if ((rc = dev_alloc(c, &c->d_abp, nBp * Gmax * ((size_t)c->NZ16 * kRow2Rows) * s))) return rc;
-  if ((rc = dev_alloc(c, &c->d_bbp, (size_t)nB * Gmax * s))) return rc;
-  if ((rc = dev_alloc(c, &c->d_zzp, (size_t)nB * c->NZh * s))) return rc;
-  if ((rc = dev_alloc(c, &c->d_tau, (size_t)nB * (nT + 1) * s))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_iters, (size_t)nB * sizeof(int)))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_stop, (size_t)nB * sizeof(int)))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_idx, (size_t)nB * c->L * sizeof(int32_t)))) return rc;
-  if ((rc = dev_alloc(c, &c->d_cb, (size_t)nB * c->L * s))) return rc;
-  if ((rc = dev_alloc(c, &c->d_Pb, (size_t)nB * s))) return rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_stop, nB * sizeof(int)))) return rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_idx, nB * c->L * sizeof(int32_t)))) return rc;
+  if ((rc = dev_alloc(c, &c->d_cb, nB * c->L * s))) return rc;
+  if ((rc = dev_alloc(c, &c->d_Pb, nB * s))) return rc;
   if (is_dense(c))
-    if ((rc = dev_alloc(c, &c->d_azp, (size_t)nB * c->RS * c->lda * s))) return rc;
+    if ((rc = dev_alloc(c, &c->d_azp, nB * c->RS * c->lda * s))) return rc;
   if (c->backend == SA_BACKEND_HOST)  // the caller's A^T z, one partial per codeword
-    if ((rc = dev_alloc(c, &c->d_azp, (size_t)nB * c->lda * s))) return rc;
-  c->Bcap = nB;
+    if ((rc = dev_alloc(c, &c->d_azp, nB * c->lda * s))) return rc;
+  c->Bcap = (int)nB;
   c->Tcap = nT;
   return SA_OK;
 }
 
-int ensure_stage(sa_ctx* c, size_t count) {
-  if (count <= c->stage_cap) return SA_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  dev_free(c->d_stage);
-  c->d_stage = nullptr;
-  int rc = dev_alloc(c, (void**)&c->d_stage, count * sizeof(double));
+int ensure_stage(sa_ctx* c, sa_lane& l, size_t count) {
+  if (count <= l.stage_cap) return SA_OK;
+  HIP_TRY(hipStreamSynchronize(l.stream));
+  stage_free(l);
+  int rc = dev_alloc(c, (void**)&l.d_stage, count * sizeof(double));
   if (rc) return rc;
-  c->stage_cap = count;
+  l.stage_cap = count;
   return SA_OK;
 }
 
 // Host fp64 -> device `real` buffer (through the fp64 staging buffer).
-int upload(sa_ctx* c, void* dst, const double* src, size_t count) {
+int upload(sa_ctx* c, sa_lane& l, void* dst, const double* src, size_t count) {
   if (c->prec == SA_PREC_F64) {
-    HIP_TRY(hipMemcpyAsync(dst, src, count * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, src, count * 8, hipMemcpyHostToDevice, l.stream));
     return SA_OK;
   }
-  int rc = ensure_stage(c, count);
+  int rc = ensure_stage(c, l, count);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_stage, src, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(l.d_stage, src, count * 8, hipMemcpyHostToDevice, l.stream));
   const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-  k_convert<double, float><<<blocks > 0 ? blocks : 1, 256, 0, c->stream>>>(c->d_stage, (float*)dst, count);
+  k_convert<double, float><<<blocks > 0 ? blocks : 1, 256, 0, l.stream>>>(l.d_stage, (float*)dst, count);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
 
-int download(sa_ctx* c, double* dst, const void* src, size_t count) {
+int download(sa_ctx* c, sa_lane& l, double* dst, const void* src, size_t count) {
   if (c->prec == SA_PREC_F64) {
-    HIP_TRY(hipMemcpyAsync(dst, src, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, src, count * 8, hipMemcpyDeviceToHost, l.stream));
     return SA_OK;
   }
-  int rc = ensure_stage(c, count);
+  int rc = ensure_stage(c, l, count);
   if (rc) return rc;
   const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-  k_convert<float, double><<<blocks > 0 ? blocks : 1, 256, 0, c->stream>>>((const float*)src, c->d_stage, count);
+  k_convert<float, double><<<blocks > 0 ? blocks : 1, 256, 0, l.stream>>>((const float*)src, l.d_stage, count);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dst, c->d_stage, count * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(dst, l.d_stage, count * 8, hipMemcpyDeviceToHost, l.stream));
   return SA_OK;
 }
 
 
 
-// ---- composite sequences (all asynchronous on c->stream) ----------------
+// ---- composite sequences (all asynchronous on the current lane's stream) ----
 
 // Ab of the batch staged in d_beta -> d_out  (B x n)
 template <typename real>
@@ -380,6 +363,7 @@ int seq_az(sa_ctx* c, int B) {
 template <typename real>
 int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
+  sa_lane& ln = c->at();  // (nothing below changes lanes)
   const bool dense = is_dense(c);
   const bool batched = !dense && use_batched(c, B);
   const bool sec2 = use_sec2(c, B);
@@ -402,7 +386,7 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const bool it_row = !dense && !batched && row_sets_iters(c) && T > 0;
   const bool bzero = !has_b0 && !dense && !batched && sec2 && (c->sec3 || c->sec4) && T > 0;
   const int flip = (bzero && !es) ? (T & 1) : 0;  // beta0 lies in d_beta: no choice of side
-  if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, c->stream>>>((uint32_t*)c->d_iters, 0xffffffffu, (size_t)B);
+  if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
   if (has_b0) {
     if (dense) {
       if ((rc = dense_start<real>(c, B, G))) return rc;
@@ -413,7 +397,7 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   } else {
     if (!bzero) {
       const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
-      k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, c->stream>>>((uint32_t*)c->d_beta, 0u, nw);
+      k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, ln.stream>>>((uint32_t*)ln.d_beta, 0u, nw);
     }
     if ((rc = launch_row<real>(c, B, ROW_INIT0, 0, 0, G, Gb, 0, nullptr, nullptr, it_row ? -1 : 0))) return rc;
   }
@@ -423,8 +407,8 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
     } else if (batched) {
       if ((rc = launch_secb<real>(c, B, t, es))) return rc;
     } else {
-      void* pin = ((t ^ flip) & 1) ? c->d_beta2 : c->d_beta;
-      void* pout = ((t ^ flip) & 1) ? c->d_beta : c->d_beta2;
+      void* pin = ((t ^ flip) & 1) ? ln.d_beta2 : ln.d_beta;
+      void* pout = ((t ^ flip) & 1) ? ln.d_beta : ln.d_beta2;
       if (sec2) {
         if ((rc = launch_sec2<real>(c, B, t, es, pin, pout, pt, bzero && t == 0))) return rc;
       } else if ((rc = launch_sec<real>(c, B, SEC_AMP, t, es, pin, pout))) {
@@ -434,29 +418,25 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
     if ((rc = launch_row<real>(c, B, ROW_AMP, t, es, G, Gb, pt, nullptr, nullptr, it_row && t == T - 1 ? T : 0)))
       return rc;
   }
-  if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, c->stream>>>(c->d_iters, B, T);
+  if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, ln.stream>>>(ln.d_iters, B, T);
   HIP_TRY(hipGetLastError());
   // early stop off: every codeword runs T iterations, the last one into pout(T - 1)
   const bool home = !es && (((T - 1) ^ flip) & 1);
   if (!dense && !batched && T > 0 && !home) {
     // the estimate of codeword b is in the buffer of parity iters[b]
     const size_t LM = (size_t)c->L * c->M;
-    k_beta_final<real><<<dim3((unsigned)std::min<size_t>((LM + 255) / 256, 4096), B), 256, 0, c->stream>>>(
-        (real*)c->d_beta, (const real*)c->d_beta2, c->d_iters, LM);
+    k_beta_final<real><<<dim3((unsigned)std::min<size_t>((LM + 255) / 256, 4096), B), 256, 0, ln.stream>>>(
+        (real*)ln.d_beta, (const real*)ln.d_beta2, ln.d_iters, LM);
     HIP_TRY(hipGetLastError());
   }
   return SA_OK;
 }
 
 int ensure_beta2(sa_ctx* c, int B) {
-  if (is_dense(c) || use_batched(c, B) || c->beta2_cap >= c->Bcap) return SA_OK;
+  if (is_dense(c) || use_batched(c, B) || c->at().beta2_cap >= c->Bcap) return SA_OK;
   if (int rcl = lanes_release(c)) return rcl;
-  dev_free(c->d_beta2);
-  c->d_beta2 = nullptr;
-  c->beta2_cap = 0;
-  int rc = dev_alloc(c, &c->d_beta2, (size_t)c->Bcap * c->L * c->M * rsz(c));
-  if (rc) return rc;
-  c->beta2_cap = c->Bcap;
+  // lane 0 has none yet (lane 1 is created with its own; a grown workspace drops lane 0's)
+  if (int rc = beta2_alloc(c, c->lane[0], c->Bcap)) return rc;
   drop_graphs(c);  // captured graphs hold the old pointer
   return SA_OK;
 }
@@ -480,11 +460,12 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
     lane_switch(c, 0);  // lane 1's buffers hold no batched layout (no chunk padding, no k_secb partials)
   }
   if (int rcy = y_sync(c)) return rcy;  // a lane whose y is older than the latest staged one
+  sa_lane& ln = c->at();  // the run's lane: cur is settled
   if (c->plan & SA_PLAN_EAGER) {  // eager launches instead of the captured graph
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
     int rc = seq_amp<real>(c, B, T, flags, has_b0);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
     c->last_B = B;
     c->last_T = T;
     c->zil_last = zil_for(c, B);
@@ -492,13 +473,13 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   }
   // the power-allocation mode selects the captured kernel arguments (c, P arrays)
   const auto key = std::make_tuple(B, T, flags | (c->pb_on ? 0x10000 : 0), has_b0);
-  auto it = c->graphs.find(key);
-  if (it == c->graphs.end()) {
+  auto it = ln.graphs.find(key);
+  if (it == ln.graphs.end()) {
     hipGraph_t g = nullptr;
-    HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
     int rc = seq_amp<real>(c, B, T, flags, has_b0);
     hipGraph_t cap = nullptr;
-    hipError_t e = hipStreamEndCapture(c->stream, &cap);
+    hipError_t e = hipStreamEndCapture(ln.stream, &cap);
     if (rc) {
       if (cap) (void)hipGraphDestroy(cap);
       return rc;
@@ -509,11 +490,11 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
     e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    it = c->graphs.emplace(key, ex).first;
+    it = ln.graphs.emplace(key, ex).first;
   }
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  HIP_TRY(hipGraphLaunch(it->second, c->stream));
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
+  HIP_TRY(hipGraphLaunch(it->second, ln.stream));
+  HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
   c->last_B = B;
   c->last_T = T;
   c->zil_last = zil_for(c, B);  // the layout d_z is left in by THIS run (a cached graph does not run seq_amp)
@@ -555,7 +536,7 @@ int upload_sections(sa_ctx* c, void* dst, const double* src, int B) {
     std::memcpy(pad.data() + bl * c->M + c->dead, src + bl * c->Mu, (size_t)c->Mu * sizeof(double));
   int rc = upload(c, dst, pad.data(), pad.size());
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));  // pad is a host temporary
+  HIP_TRY(hipStreamSynchronize(c->at().stream));  // pad is a host temporary
   return SA_OK;
 }
 
@@ -565,7 +546,7 @@ int download_sections(sa_ctx* c, double* dst, const void* src, int B) {
   std::vector<double> pad((size_t)B * LM);
   int rc = download(c, pad.data(), src, pad.size());
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   for (size_t bl = 0; bl < (size_t)B * c->L; ++bl)
     std::memcpy(dst + bl * c->Mu, pad.data() + bl * c->M + c->dead, (size_t)c->Mu * sizeof(double));
   return SA_OK;
@@ -598,8 +579,8 @@ int set_power(sa_ctx* c, const double* Pl) {
   int rc = upload(c, c->d_c, cl.data(), c->L);
   if (!rc) rc = upload(c, c->d_P1, &P, 1);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_cd, cl.data(), (size_t)c->L * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // cl is a host temporary
+  HIP_TRY(hipMemcpyAsync(c->d_cd, cl.data(), (size_t)c->L * 8, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));  // cl is a host temporary
   c->pb_on = false;  // back to one allocation (graphs are keyed on the mode)
   c->shared_power = true;
   c->power_set = true;
@@ -640,7 +621,7 @@ int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   int rc = upload(c, c->d_cb, cb.data(), (size_t)B * L);
   if (!rc) rc = upload(c, c->d_Pb, Pb.data(), (size_t)B);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   c->pb_on = true;
   c->power_set = true;
   c->h_Plb.assign(Pl, Pl + (size_t)B * L);
@@ -674,9 +655,9 @@ int build_tables_big(sa_ctx* c) {
   int rc;
   if ((rc = dev_alloc(c, (void**)&c->d_inv32, inv.size() * 4))) return rc;
   if ((rc = dev_alloc(c, (void**)&c->d_fwd, fwd.size() * 2))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_inv32, inv.data(), inv.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_inv32, inv.data(), inv.size() * 4, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -725,12 +706,12 @@ int build_tables(sa_ctx* c) {
   // On the context's (non-blocking) stream and waited for: a pageable
   // hipMemcpy may return once the data is staged, before the DMA lands, and
   // the null stream does not order the kernels of a non-blocking stream.
-  HIP_TRY(hipMemcpyAsync(c->d_inv, inv.data(), inv.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd2, fwd2.data(), fwd2.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_inv, inv.data(), inv.size() * 2, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipMemcpyAsync(c->d_fwd2, fwd2.data(), fwd2.size() * 4, hipMemcpyHostToDevice, c->at().stream));
   if (c->sec3)
-    HIP_TRY(hipMemcpyAsync(c->d_fwd3, fwd3.data(), fwd3.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_fwd3, fwd3.data(), fwd3.size() * 4, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   if (c->backend == SA_BACKEND_HADAMARD && c->CB > 0) {  // kept for the batched tables (ensure_invb)
     c->h_inv = std::move(inv);
     c->h_fwd = std::move(fwd);
@@ -882,9 +863,9 @@ int build_banked(sa_ctx* c, const std::vector<int>& sets, int gsize, int nbank, 
   int rc = dev_alloc(c, (void**)dst, out.size() * 2);
   if (!rc) rc = dev_alloc(c, (void**)&c->d_hs, hs.size() * 4);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(*dst, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_hs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(*dst, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipMemcpyAsync(c->d_hs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1042,8 +1023,8 @@ int build_fwdb(sa_ctx* c) {
   parallel_for(Gb, 1, [&](int g) { fwdb_group(c, g, fwd, npad, out.data()); });
   int rc = dev_alloc(c, (void**)&c->d_fwdb, out.size() * 2);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_fwdb, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_fwdb, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1077,10 +1058,10 @@ int ensure_invb(sa_ctx* c) {
   if (rows16 && c->E >= 4 && c->E % 4 == 0) {
     const size_t cnt = (size_t)c->L * c->nhi * 64 * c->E;
     if (int rc = dev_alloc(c, (void**)&c->d_invl, cnt * 2)) return rc;
-    k_lane_major<<<(int)std::min<size_t>((cnt + 255) / 256, 16384), 256, 0, c->stream>>>(
+    k_lane_major<<<(int)std::min<size_t>((cnt + 255) / 256, 16384), 256, 0, c->at().stream>>>(
         c->d_invb ? c->d_invb : c->d_inv, c->d_invl, c->L, c->nhi, c->M, c->w, c->E, sgn ? 1 : 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
   }
   std::vector<uint16_t>().swap(c->h_inv);  // the host copies have served
   std::vector<uint16_t>().swap(c->h_fwd);
@@ -1270,9 +1251,7 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
       c->sec3_lds = need3;
     }
   }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-      hipEventCreateWithFlags(&c->lane[0].y_ev, hipEventDisableTiming) != hipSuccess) {
+  if (lane_open(c->lane[0]) != SA_OK) {
     delete c;
     return fail(SA_ERR_HIP, "stream/event creation failed");
   }
@@ -1362,12 +1341,6 @@ void sa_destroy(sa_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)lanes_release(c);  // waits for every lane; lane 0 is current from here
-  for (auto& l : c->lane) {
-    if (l.y_ev) (void)hipEventDestroy(l.y_ev);
-    if (l.ev0) (void)hipEventDestroy(l.ev0);
-    if (l.ev1) (void)hipEventDestroy(l.ev1);
-    if (l.stream) (void)hipStreamDestroy(l.stream);
-  }
   drop_graphs(c);
   free_workspace(c);
   mc_release(c);
@@ -1389,13 +1362,16 @@ void sa_destroy(sa_ctx* c) {
   dev_free(c->d_c);
   dev_free(c->d_cd);
   dev_free(c->d_P1);
-  dev_free(c->d_stage);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
   for (auto& e : c->dec_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->h_dec) (void)hipHostFree(c->h_dec);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  for (auto& l : c->lane) {
+    stage_free(l);
+    if (l.y_ev) (void)hipEventDestroy(l.y_ev);
+    if (l.ev0) (void)hipEventDestroy(l.ev0);
+    if (l.ev1) (void)hipEventDestroy(l.ev1);
+    if (l.stream) (void)hipStreamDestroy(l.stream);
+  }
   delete c;
 }
 
@@ -1405,11 +1381,11 @@ int sa_Ab(sa_ctx* c, int B, const double* beta, double* out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
-  if ((rc = upload_sections(c, c->d_beta, beta, B))) return rc;
+  if ((rc = upload_sections(c, c->at().d_beta, beta, B))) return rc;
   rc = c->prec == SA_PREC_F64 ? seq_ab<double>(c, B) : seq_ab<float>(c, B);
   if (rc) return rc;
   if ((rc = download(c, out, c->d_out, (size_t)B * c->n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1419,7 +1395,7 @@ int sa_Az(sa_ctx* c, int B, const double* z, double* out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
-  if ((rc = upload(c, c->d_z, z, (size_t)B * c->n))) return rc;
+  if ((rc = upload(c, c->at().d_z, z, (size_t)B * c->n))) return rc;
   c->zil_last = false;  // d_z holds [B][n] now
   if (c->prec == SA_PREC_F64) {
     rc = seq_az<double>(c, B);
@@ -1428,7 +1404,7 @@ int sa_Az(sa_ctx* c, int B, const double* z, double* out) {
   }
   if (rc) return rc;
   if ((rc = download_sections(c, out, c->d_out, B))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1454,16 +1430,15 @@ int sa_stage(sa_ctx* c, int B, const double* y, const double* Pl, const double* 
     // flight on the current lane is not waited for.  (A run that takes another
     // lane after all copies y over first: y_sync.)  With beta0 the next run is
     // a beta0 run, which stays on the current lane.
-    const int prev = c->cur;
     const bool rotate = c->lanes_on && !beta0 && lane_shape(c, B) && pipelining(c);
-    lane_switch(c, rotate ? 1 - prev : prev);
-    rc = y_begin_write(c, c->stream, B);
-    if (!rc) rc = upload(c, c->d_y, y, (size_t)B * c->n);
-    if (!rc) rc = y_mark(c);
-    lane_switch(c, prev);
+    const int k = rotate ? 1 - c->cur : c->cur;
+    sa_lane& l = c->lane[k];
+    rc = y_begin_write(c, k, l.stream, B);
+    if (!rc) rc = upload(c, l, l.d_y, y, (size_t)B * c->n);
+    if (!rc) rc = y_mark(c, k);
     if (rc) return rc;
   }
-  if (beta0 && (rc = upload_sections(c, c->d_beta, beta0, B))) return rc;
+  if (beta0 && (rc = upload_sections(c, c->at().d_beta, beta0, B))) return rc;
   return SA_OK;
 }
 
@@ -1500,7 +1475,7 @@ int sa_wait(sa_ctx* c) {
 double sa_run_event_ms(sa_ctx* c) {
   if (!c) return -1.0;
   float ms = -1.f;
-  if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) return -1.0;
+  if (hipEventElapsedTime(&ms, c->at().ev0, c->at().ev1) != hipSuccess) return -1.0;
   return ms;
 }
 
@@ -1512,14 +1487,14 @@ int sa_fetch_z(sa_ctx* c, int B, double* z_out) {
   if (c->zil_last) {  // [NC][n][CB] -> [B][n]
     const int CB = 16 / (int)rsz(c), NC = (B + CB - 1) / CB;
     std::vector<double> il((size_t)NC * CB * c->n);
-    if ((rc = download(c, il.data(), c->d_z, il.size()))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, il.data(), c->at().d_z, il.size()))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
     for (int b = 0; b < B; ++b)
       for (int r = 0; r < c->n; ++r) z_out[(size_t)b * c->n + r] = il[((size_t)(b / CB) * c->n + r) * CB + b % CB];
     return SA_OK;
   }
-  if ((rc = download(c, z_out, c->d_z, (size_t)B * c->n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = download(c, z_out, c->at().d_z, (size_t)B * c->n))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1529,8 +1504,8 @@ int sa_fetch_y(sa_ctx* c, int B, double* y_out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc;
   if ((rc = y_sync(c))) return rc;  // the y the next run would read, wherever it was staged
-  if ((rc = download(c, y_out, c->d_y, (size_t)B * c->n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = download(c, y_out, c->at().d_y, (size_t)B * c->n))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1539,9 +1514,10 @@ int sa_fetch(sa_ctx* c, int B, double* beta_out, int* iters_out) {
   if (B <= 0 || B > c->Bcap) return fail(SA_ERR_ARG, "sa_fetch: bad batch");
   HIP_TRY(hipSetDevice(c->device));
   int rc;
-  if (beta_out && (rc = download_sections(c, beta_out, c->d_beta, B))) return rc;
-  if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out, c->d_iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (beta_out && (rc = download_sections(c, beta_out, c->at().d_beta, B))) return rc;
+  const sa_lane& ln = c->at();
+  if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out, ln.d_iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
   return SA_OK;
 }
 
@@ -1555,8 +1531,8 @@ int sa_amp(sa_ctx* c, int B, const double* y, const double* Pl, int T, const dou
   if ((rc = sa_stage(c, B, y, Pl, beta0))) return rc;
   if (T == 0) {
     // the loop body never runs: beta is beta0 (or zeros)
-    if (!beta0) HIP_TRY(hipMemsetAsync(c->d_beta, 0, (size_t)B * c->L * c->M * rsz(c), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_iters, 0, (size_t)B * sizeof(int), c->stream));
+    if (!beta0) HIP_TRY(hipMemsetAsync(c->at().d_beta, 0, (size_t)B * c->L * c->M * rsz(c), c->at().stream));
+    HIP_TRY(hipMemsetAsync(c->at().d_iters, 0, (size_t)B * sizeof(int), c->at().stream));
   } else {
     if ((rc = sa_run(c, B, T, (flags & 0xff) | (beta0 ? SA_FLAG_BETA0 : 0)))) return rc;
   }
@@ -1587,13 +1563,13 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipEventRecord(e0, c->stream));
+  HIP_TRY(hipEventRecord(e0, c->at().stream));
   const int has_b0 = (flags & SA_FLAG_BETA0) ? 1 : 0;
   int rc = c->prec == SA_PREC_F64 ? seq_amp<double>(c, B, T, flags & 0xff, has_b0)
                                   : seq_amp<float>(c, B, T, flags & 0xff, has_b0);
   c->prof = nullptr;
-  (void)hipEventRecord(e1, c->stream);
-  hipError_t e = hipStreamSynchronize(c->stream);
+  (void)hipEventRecord(e1, c->at().stream);
+  hipError_t e = hipStreamSynchronize(c->at().stream);
   if (rc == SA_OK && e != hipSuccess) rc = fail(SA_ERR_HIP, std::string("sa_profile: ") + hipGetErrorString(e));
   double sum[K_NKINDS] = {0}, cnt[K_NKINDS] = {0};
   if (rc == SA_OK) {
@@ -1633,8 +1609,8 @@ int sa_decide(sa_ctx* c, int B, int32_t* idx_out) {
   if (B <= 0 || B > c->Bcap || !idx_out) return fail(SA_ERR_ARG, "sa_decide: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   if (int rc = launch_decide(c, B, c->d_idx)) return rc;
-  HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, c->at().stream));
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
   return SA_OK;
 }
 
@@ -1668,7 +1644,7 @@ int sa_decide_async(sa_ctx* c, int B, int slot) {
   // mapped into the device's address space: no copy behind the kernel); the
   // host reads them after the event recorded behind it
   if (int rc = launch_decide(c, B, c->d_dec + (size_t)slot * c->dec_cap)) return rc;
-  HIP_TRY(hipEventRecord(c->dec_ev[slot], c->stream));
+  HIP_TRY(hipEventRecord(c->dec_ev[slot], c->at().stream));
   c->dec_B[slot] = B;
   return SA_OK;
 }

@@ -296,3 +296,49 @@ def test_three_codewords_pipelined(sp, prec):
     beta, it = op.fetch(B)
     assert np.array_equal(beta, refs[2]["beta"]) and np.array_equal(it, refs[2]["iters"])
     assert np.array_equal(op.fetch_z(B), refs[2]["z"])
+
+
+# ---- 7. a stage with no run behind it ------------------------------------------------------
+
+@pytest.mark.parametrize("outstanding", [False, True])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("shape", [(64, 512, 581), (256, 256, 2048)])
+def test_stage_then_fetch_y_then_run(sp, shape, prec, outstanding):
+    """Two pipelined steps (the second ran on lane 1, which stays current),
+    then a new y staged with no run behind it: fetch_y returns the staged word
+    (binary32: its float rounding), and run, wait, fetch give the serial
+    NO_LANES decode of that word bit for bit.  Again with beta0 given, which
+    keeps the next run on the current lane.  `outstanding`: step 1's decisions
+    are collected only after the run, so the stage without beta0 writes the
+    lane that is not current and fetch_y has to bring the word over."""
+    L, M, n = shape
+    T, Pl, ys = 4, power(L), inputs(*shape)
+    wt = np.float32 if prec == "fp32" else np.float64
+    b0 = np.zeros((1, L * M))
+    b0[0, np.arange(L) * M + np.random.RandomState(9).randint(0, M, L)] = np.sqrt(n * Pl)
+    for beta0, key in ((None, ("y", 2)), (b0, ("b0", 2))):
+        op = make(sp, shape, prec)
+        op.reserve(1, 6)
+        dec = [None, None]
+        for k in range(2):
+            op.stage(ys[k], Pl)
+            op.run(1, T, early_stop=False)
+            op.decide_async(1, k)
+            if k > 0:
+                dec[0] = op.decide_collect(1, 0)
+        if not outstanding:
+            dec[1] = op.decide_collect(1, 1)
+        op.stage(ys[2], Pl, beta0)
+        assert np.array_equal(op.fetch_y(1), ys[2].astype(wt).astype(np.float64)), key
+        op.run(1, T, early_stop=False, beta0=beta0 is not None)
+        op.wait()
+        beta, it = op.fetch(1)
+        if outstanding:
+            dec[1] = op.decide_collect(1, 1)
+        ref = serial(sp, shape, prec, ys[2], Pl, T, beta0=beta0, key=key)
+        assert np.array_equal(beta, ref["beta"]) and np.array_equal(it, ref["iters"]), key
+        assert np.array_equal(op.fetch_z(1), ref["z"]) and np.array_equal(op.decide(1), ref["dec"]), key
+        for k in range(2):  # the steps before the stage are unharmed
+            assert np.array_equal(dec[k], serial(sp, shape, prec, ys[k], Pl, T, key=("y", k))["dec"]), (key, k)
+    assert not np.array_equal(serial(sp, shape, prec, ys[2], Pl, T, key=("y", 2))["beta"],
+                              serial(sp, shape, prec, ys[2], Pl, T, beta0=b0, key=("b0", 2))["beta"])
