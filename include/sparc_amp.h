@@ -357,13 +357,28 @@ int sa_mc_run(sa_ctx* ctx, int B, int T, int flags, int32_t* dec_out, int32_t* i
 int sa_make_ordering(int L, int M, int n, uint32_t seed, uint32_t* out);
 
 /* Introspection. */
-/* The kernels a decode of B codewords runs: out8 = {section kernel (0 k_sec,
- * 1 k_sec2, 2 k_secb, 3 dense fp32 GEMVs, 4 k_sec4, 5 k_sec43, 6 dense int8
- * MFMA GEMMs, 7 caller-matrix f32 / f64 MFMA GEMMs, 8 k_secg: z from global
- * memory, 32-bit bucket entries, for n past the LDS image or >= 65535), Ab partials per codeword, row splits,
- * codewords per batched workgroup, z^2 partials, w, row kernel (1 k_row2,
- * 2 k_rowv 16-byte rows, 3 k_rowv 8-byte rows, 0 k_row, 4 k_row2 16-row
- * blocks, 5 k_rowc), number of CUs}. */
+/* The kernels a decode of B codewords runs: out8 = {section path (sa_sec_path),
+ * Ab partials per codeword, row splits, codewords per batched workgroup,
+ * z^2 partials, w, row kernel (sa_row_kernel), number of CUs}. */
+typedef enum sa_sec_path {
+  SA_SEC_K_SEC = 0,    /* k_sec: one wave per section, row splits */
+  SA_SEC_K_SEC2 = 1,   /* k_sec2: two waves per section */
+  SA_SEC_K_SECB = 2,   /* k_secb: the batched kernel */
+  SA_SEC_DENSE = 3,    /* dense fp32 GEMVs */
+  SA_SEC_K_SEC4 = 4,   /* k_sec4: four waves per section, pairs of sections */
+  SA_SEC_K_SEC43 = 5,  /* k_sec43: four waves per section, triples of sections */
+  SA_SEC_DENSE_I8 = 6, /* dense int8 MFMA GEMMs */
+  SA_SEC_MATRIX = 7,   /* caller-matrix f32 / f64 MFMA GEMMs */
+  SA_SEC_K_SECG = 8    /* k_secg: z from global memory, 32-bit bucket entries (n past the LDS image or >= 65535) */
+} sa_sec_path;
+typedef enum sa_row_kernel {
+  SA_ROW_K_ROW = 0,     /* k_row: 64-row blocks */
+  SA_ROW_K_ROW2 = 1,    /* k_row2: 32-row blocks */
+  SA_ROW_K_ROWV16 = 2,  /* k_rowv, 16-byte rows */
+  SA_ROW_K_ROWV8 = 3,   /* k_rowv, 8-byte rows */
+  SA_ROW_K_ROW2_16 = 4, /* k_row2: 16-row blocks */
+  SA_ROW_K_ROWC = 5     /* k_rowc: codeword-interleaved rows behind k_secb */
+} sa_row_kernel;
 int sa_plan(sa_ctx* ctx, int B, int64_t* out8);
 /* The batched section kernel's work order for B codewords (k_secb, B >= 4):
  * out4 = {section groups, sections per workgroup, section groups per XCD per

@@ -7,7 +7,10 @@
                                 (and the largest relative difference if not)
 
 Cases cover every batched-kernel element count (E = 1, 2, 4, 8), both
-precisions and the single-codeword kernels, at fixed T and with early stop.
+precisions and the single-codeword kernels, at fixed T and with early stop;
+the last four a padded section size, the dense backend, k_sec43 by plan
+option and k_secg.  Each case also stores sa_plan for B in PLAN_BS (and
+sa_plan_batched where it runs k_secb), so cmp covers the kernel choice too.
 """
 import os
 import sys
@@ -22,18 +25,21 @@ CASES = [  # L, M, R, B, precision
     (32, 64, 1.0, 8, "fp32"), (16, 16, 1.0, 8, "fp32"), (512, 512, 1.0, 8, "fp64"),
     (64, 128, 1.0, 8, "fp64"), (768, 512, 5 / 6, 1, "fp32"), (768, 512, 5 / 6, 2, "fp64"),
     (512, 512, 1.0, 1, "fp64"), (256, 256, 1.0, 2, "fp32"),
+    (64, 100, 1.0, 3, "fp32"), (32, 64, 1.0, 4, "fp32", dict(backend="dense")),
+    (96, 256, 1.0, 3, "fp32", dict(plan="SEC3")), (4, 256, 32 / 40000, 2, "fp64"),
 ]
+PLAN_BS = (1, 2, 3, 4, 8, 64)
 
 
 def run(out):
     import sparc_ldpc_amd as sp
     res = {}
     sel = os.environ.get("BITCMP_CASES")
-    for ci, (L, M, R, B, prec) in enumerate(CASES):
+    for ci, (L, M, R, B, prec, *opts) in enumerate(CASES):
         if sel and str(ci) not in sel.split(","):
             continue
         n = int(L * np.log2(M) / R)
-        op = sp.SparcOperator(L, M, n, sp.make_ordering(L, M, n), precision=prec)
+        op = sp.SparcOperator(L, M, n, sp.make_ordering(L, M, n), precision=prec, **(opts[0] if opts else {}))
         rs = np.random.RandomState(L + M + B)
         P = 4.0
         Pl = P / L * np.ones(L)
@@ -51,7 +57,11 @@ def run(out):
         bb, it = op.amp_batch(ys, Pl, 40)
         res[key + "_stop"] = bb
         res[key + "_it"] = it
-        print(key, op.plan(B)["section_kernel"], flush=True)
+        for b in PLAN_BS:
+            res[f"{key}_plan{b}"] = np.array(sorted(op.plan(b).items()), dtype=str)
+            if op.plan(b)["section_kernel"] == "k_secb":
+                res[f"{key}_planb{b}"] = np.array(sorted(op.plan_batched(b).items()), dtype=str)
+        print(key, op.plan(B)["section_kernel"], op.plan(B)["row_kernel"], flush=True)
     np.savez(out, **res)
 
 
@@ -62,6 +72,9 @@ def cmp(a, b):
         same = np.array_equal(A[k], Bz[k])
         if not same:
             bad += 1
+            if A[k].dtype.kind == "U":
+                print(f"{k:28s} DIFFERS ({A[k].tolist()} / {Bz[k].tolist()})")
+                continue
             d = np.abs(A[k] - Bz[k]).max() / max(np.abs(A[k]).max(), 1e-300)
             print(f"{k:28s} DIFFERS (max rel {d:.3g})")
         else:

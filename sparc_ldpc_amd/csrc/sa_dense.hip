@@ -381,20 +381,20 @@ int ensure_i8(sa_ctx* c, int B) {
 }
 
 template <typename real>
-DenseArgs<real> dense_args(sa_ctx* c, int t, int es, int mode) {
+DenseArgs<real> dense_args(sa_ctx* c, const Plan& p, int t, int es, int mode) {
   DenseArgs<real> a;
   const sa_lane& ln = c->at();
   a.A = (const real*)c->d_A; a.z = (const real*)ln.d_z; a.azp = (real*)c->d_azp;
   a.beta = (const real*)ln.d_beta; a.abp = (real*)ln.d_abp; a.zzp = (const real*)ln.d_zzp;
   a.tau = (const real*)ln.d_tau;
-  a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = c->nz_cur; a.T1 = c->Tcap + 1; a.t = t;
+  a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = p.nz; a.T1 = c->Tcap + 1; a.t = t;
   a.early_stop = es; a.RS = c->RS; a.KS = c->KS; a.mode = mode; a.lda = c->lda;
   return a;
 }
 
 template <typename real>
-int launch_dense_az(sa_ctx* c, int B, int t, int es, int mode) {
-  DenseArgs<real> a = dense_args<real>(c, t, es, mode);
+int launch_dense_az(sa_ctx* c, const Plan& p, int B, int t, int es, int mode) {
+  DenseArgs<real> a = dense_args<real>(c, p, t, es, mode);
   dim3 grid((unsigned)((c->lda / V16<real>::N + 255) / 256), c->RS, B);
   if (c->prof) c->prof->begin(c->at().stream, K_DAZ);
   plaunch(c, k_dense_az<real>, grid, 256, 0, a);
@@ -404,8 +404,8 @@ int launch_dense_az(sa_ctx* c, int B, int t, int es, int mode) {
 }
 
 template <typename real>
-int launch_dense_ab(sa_ctx* c, int B, int t, int es, int mode) {
-  DenseArgs<real> a = dense_args<real>(c, t, es, mode);
+int launch_dense_ab(sa_ctx* c, const Plan& p, int B, int t, int es, int mode) {
+  DenseArgs<real> a = dense_args<real>(c, p, t, es, mode);
   dim3 grid((unsigned)((c->n + kDenseRows - 1) / kDenseRows), c->KS, B);
   if (c->prof) c->prof->begin(c->at().stream, K_DAB);
   plaunch(c, k_dense_ab<real>, grid, 256, 0, a, (const real*)c->at().d_tau);
@@ -430,10 +430,10 @@ void launch_dense_den_e(sa_ctx* c, int B, const DenArgs<real>& a, bool i8) {
 // the beta digit planes written for the next A beta GEMM.  The host-operator
 // backend's A^T z is one uploaded partial as well.
 template <typename real>
-int launch_dense_den(sa_ctx* c, int B, int t, int es, bool i8 = false, bool one_partial = false) {
+int launch_dense_den(sa_ctx* c, const Plan& p, int B, int t, int es, bool i8 = false, bool one_partial = false) {
   DenArgs<real> a;
   a.azp = (const real*)c->d_azp; a.zzp = (const real*)c->at().d_zzp; a.tau = (const real*)c->at().d_tau;
-  a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = c->nz_cur; a.T1 = c->Tcap + 1; a.t = t; a.early_stop = es;
+  a.L = c->L; a.M = c->M; a.n = c->n; a.NZ = p.nz; a.T1 = c->Tcap + 1; a.t = t; a.early_stop = es;
   a.RS = (i8 || one_partial || c->backend == SA_BACKEND_HOST) ? 1 : c->RS;
   a.lda = c->lda;
   switch (c->E) {
@@ -620,71 +620,64 @@ int dense_parts(const sa_ctx* c, int B) {
   return use_i8(c, B) ? i8_splits(c, B) : (use_fgemm(c, B) ? fgemm_splits(c, B) : c->KS);
 }
 
-// the beta0 start: z = y - A beta0 from the S partials of A beta0
+// A beta of the beta in d_beta on the plan's path: p.G partials in d_abp
 template <typename real>
-int dense_start(sa_ctx* c, int B, int S) {
-  int rc;
-  if (use_i8(c, B)) {
-    if ((rc = i8_ab_any(c, B, S))) return rc;
-  } else if (use_fgemm(c, B)) {
-    if ((rc = fgemm_ab<real>(c, B, S))) return rc;
-  } else if ((rc = launch_dense_ab<real>(c, B, 0, 0, 1))) {
-    return rc;
+static int dense_ab_parts(sa_ctx* c, const Plan& p, int B) {
+  switch (p.sec) {
+    case SA_SEC_DENSE_I8: return i8_ab_any(c, B, p.G);
+    case SA_SEC_MATRIX: return fgemm_ab<real>(c, B, p.G);
+    default: return launch_dense_ab<real>(c, p, B, 0, 0, 1);
   }
-  return launch_row<real>(c, B, ROW_INIT, 0, 0, S, c->Gd);
 }
 
-// One iteration's operator steps: A^T z -> denoiser -> the S partials of A beta
+// the beta0 start: z = y - A beta0 from the partials of A beta0
+template <typename real>
+int dense_start(sa_ctx* c, const Plan& p, int B) {
+  if (int rc = dense_ab_parts<real>(c, p, B)) return rc;
+  return launch_row<real>(c, p, B, ROW_INIT, 0, 0, p.G, p.Gb);
+}
+
+// One iteration's operator steps: A^T z -> denoiser -> the p.G partials of A beta
 // (the row kernel that follows is seq_amp's)
 template <typename real>
-int dense_iter(sa_ctx* c, int B, int t, int es, int S) {
+int dense_iter(sa_ctx* c, const Plan& p, int B, int t, int es) {
   int rc;
-  if (use_i8(c, B)) {
-    // z -> digit planes -> Az GEMM (into the dense Az buffer, one partial)
-    // -> denoiser (+ beta digit planes) -> A beta GEMM (S partials)
-    if ((rc = i8_az(c, B, (float*)c->d_azp, (long long)c->lda))) return rc;
-    if ((rc = launch_dense_den<float>(c, B, t, es, true))) return rc;
-    return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->at().d_abp,
-                                  (long long)S * c->n, c->n, S, c->d_bfix + 1, 0, K_DAB);
+  switch (p.sec) {
+    case SA_SEC_DENSE_I8:
+      // z -> digit planes -> Az GEMM (into the dense Az buffer, one partial)
+      // -> denoiser (+ beta digit planes) -> A beta GEMM (S partials)
+      if ((rc = i8_az(c, B, (float*)c->d_azp, (long long)c->lda))) return rc;
+      if ((rc = launch_dense_den<float>(c, p, B, t, es, true))) return rc;
+      return launch_gemm_i8<kI8NPB>(c, B, c->d_bq, c->LMp8, c->d_A8, c->np8, c->n, (float*)c->at().d_abp,
+                                    (long long)p.G * c->n, c->n, p.G, c->d_bfix + 1, 0, K_DAB);
+    case SA_SEC_MATRIX:
+      // z -> Az GEMM (one partial) -> denoiser -> A beta GEMM (S partials);
+      // the GEMMs skip nothing for a stopped codeword: the row kernel keeps
+      // its residual and the denoiser its estimate
+      if ((rc = fgemm_az<real>(c, B, (real*)c->d_azp, (long long)c->lda))) return rc;
+      if ((rc = launch_dense_den<real>(c, p, B, t, es, false, true))) return rc;
+      return fgemm_ab<real>(c, B, p.G);
+    default:
+      if ((rc = launch_dense_az<real>(c, p, B, t, es, 0))) return rc;
+      if ((rc = launch_dense_den<real>(c, p, B, t, es))) return rc;
+      return launch_dense_ab<real>(c, p, B, t, es, 0);
   }
-  if (use_fgemm(c, B)) {
-    // z -> Az GEMM (one partial) -> denoiser -> A beta GEMM (S partials);
-    // the GEMMs skip nothing for a stopped codeword: the row kernel keeps
-    // its residual and the denoiser its estimate
-    if ((rc = fgemm_az<real>(c, B, (real*)c->d_azp, (long long)c->lda))) return rc;
-    if ((rc = launch_dense_den<real>(c, B, t, es, false, true))) return rc;
-    return fgemm_ab<real>(c, B, S);
-  }
-  if ((rc = launch_dense_az<real>(c, B, t, es, 0))) return rc;
-  if ((rc = launch_dense_den<real>(c, B, t, es))) return rc;
-  return launch_dense_ab<real>(c, B, t, es, 0);
 }
 
 // A beta of the batch staged in d_beta -> d_out (B x n)
 template <typename real>
-int dense_ab(sa_ctx* c, int B) {
-  int rc;
-  if (use_i8(c, B)) {
-    const int S = i8_splits(c, B);
-    if ((rc = i8_ab_any(c, B, S))) return rc;
-    return launch_row<real>(c, B, ROW_ABOUT, 0, 0, S, c->Gd);
-  }
-  if (use_fgemm(c, B)) {
-    const int S = fgemm_splits(c, B);
-    if ((rc = fgemm_ab<real>(c, B, S))) return rc;
-    return launch_row<real>(c, B, ROW_ABOUT, 0, 0, S, c->Gd);
-  }
-  if ((rc = launch_dense_ab<real>(c, B, 0, 0, 1))) return rc;
-  return launch_row<real>(c, B, ROW_ABOUT, 0, 0, c->KS, c->Gd);
+int dense_ab(sa_ctx* c, const Plan& p, int B) {
+  if (int rc = dense_ab_parts<real>(c, p, B)) return rc;
+  return launch_row<real>(c, p, B, ROW_ABOUT, 0, 0, p.G, p.Gb);
 }
 
 // A^T z of the batch staged in d_z -> d_out (B x L*M)
 template <typename real>
-int dense_az(sa_ctx* c, int B) {
+int dense_az(sa_ctx* c, const Plan& p, int B) {
   if constexpr (sizeof(real) == 4)
-    if (use_i8(c, B)) return i8_az(c, B, (float*)c->d_out, (long long)c->L * c->M);
-  if (use_fgemm(c, B)) return fgemm_az<real>(c, B, (real*)c->d_out, (long long)c->L * c->M);
-  int rc = launch_dense_az<real>(c, B, 0, 0, 1);
+    if (p.sec == SA_SEC_DENSE_I8) return i8_az(c, B, (float*)c->d_out, (long long)c->L * c->M);
+  if (p.sec == SA_SEC_MATRIX) return fgemm_az<real>(c, B, (real*)c->d_out, (long long)c->L * c->M);
+  int rc = launch_dense_az<real>(c, p, B, 0, 0, 1);
   if (rc) return rc;
   // the RS row-split partials into d_out
   k_dense_az_reduce<real><<<4096, 256, 0, c->at().stream>>>((const real*)c->d_azp, (real*)c->d_out, c->RS, c->lda,
@@ -693,14 +686,14 @@ int dense_az(sa_ctx* c, int B) {
   return SA_OK;
 }
 
-template int dense_start<float>(sa_ctx*, int, int);
-template int dense_start<double>(sa_ctx*, int, int);
-template int dense_iter<float>(sa_ctx*, int, int, int, int);
-template int dense_iter<double>(sa_ctx*, int, int, int, int);
-template int dense_ab<float>(sa_ctx*, int);
-template int dense_ab<double>(sa_ctx*, int);
-template int dense_az<float>(sa_ctx*, int);
-template int dense_az<double>(sa_ctx*, int);
+template int dense_start<float>(sa_ctx*, const Plan&, int);
+template int dense_start<double>(sa_ctx*, const Plan&, int);
+template int dense_iter<float>(sa_ctx*, const Plan&, int, int, int);
+template int dense_iter<double>(sa_ctx*, const Plan&, int, int, int);
+template int dense_ab<float>(sa_ctx*, const Plan&, int);
+template int dense_ab<double>(sa_ctx*, const Plan&, int);
+template int dense_az<float>(sa_ctx*, const Plan&, int);
+template int dense_az<double>(sa_ctx*, const Plan&, int);
 
 // A caller's matrix (SA_BACKEND_MATRIX, uploaded by sa_create_matrix): rows of
 // whole GEMM K stages (128 B), padded to whole 256-row tiles, zero padding
@@ -810,17 +803,17 @@ int check_host(sa_ctx* c, int B, const char* what) {
 template <typename real>
 int host_init_impl(sa_ctx* c, int B, const double* beta0, const double* ab0) {
   int rc;
-  pick_row(c, B);
+  const Plan p = plan_for(c, B);
   const sa_lane& ln = c->at();
   k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
   if (beta0) {  // z = y - Ab(beta0) with the caller's Ab(beta0) (sparc_ldpc.py:196-200)
     if ((rc = upload(c, ln.d_beta, beta0, (size_t)B * c->L * c->M))) return rc;
     if ((rc = upload(c, ln.d_abp, ab0, (size_t)B * c->n))) return rc;
-    return launch_row<real>(c, B, ROW_INIT, 0, 0, 1, c->Gd);
+    return launch_row<real>(c, p, B, ROW_INIT, 0, 0, 1, c->Gd);
   }
   const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
   k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, ln.stream>>>((uint32_t*)ln.d_beta, 0u, nw);
-  return launch_row<real>(c, B, ROW_INIT0, 0, 0, 1, c->Gd);
+  return launch_row<real>(c, p, B, ROW_INIT0, 0, 0, 1, c->Gd);
 }
 }  // namespace
 }  // extern "C++"
@@ -847,11 +840,12 @@ int sa_host_tau(sa_ctx* c, int B, int t, int flags, int* stopped) {
   HIP_TRY(hipSetDevice(c->device));
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
   const sa_lane& ln = c->at();
+  const int nz = plan_for(c, B).nz;
   if (c->prec == SA_PREC_F64)
-    k_tau<double><<<B, 64, 0, ln.stream>>>((const double*)ln.d_zzp, c->nz_cur, c->n, (double*)ln.d_tau, c->Tcap + 1,
+    k_tau<double><<<B, 64, 0, ln.stream>>>((const double*)ln.d_zzp, nz, c->n, (double*)ln.d_tau, c->Tcap + 1,
                                            t, es, ln.d_iters, c->d_stop);
   else
-    k_tau<float><<<B, 64, 0, ln.stream>>>((const float*)ln.d_zzp, c->nz_cur, c->n, (float*)ln.d_tau, c->Tcap + 1,
+    k_tau<float><<<B, 64, 0, ln.stream>>>((const float*)ln.d_zzp, nz, c->n, (float*)ln.d_tau, c->Tcap + 1,
                                           t, es, ln.d_iters, c->d_stop);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(stopped, c->d_stop, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ln.stream));
@@ -864,8 +858,9 @@ int sa_host_eta(sa_ctx* c, int B, int t, int flags, const double* az) {
   if (t < 0 || t >= c->Tcap || !az) return fail(SA_ERR_ARG, "sa_host_eta: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
+  const Plan p = plan_for(c, B);
   int rc = upload(c, c->d_azp, az, (size_t)B * c->L * c->M);
-  if (!rc) rc = c->prec == SA_PREC_F64 ? launch_dense_den<double>(c, B, t, es) : launch_dense_den<float>(c, B, t, es);
+  if (!rc) rc = c->prec == SA_PREC_F64 ? launch_dense_den<double>(c, p, B, t, es) : launch_dense_den<float>(c, p, B, t, es);
   return rc;
 }
 
@@ -874,10 +869,11 @@ int sa_host_residual(sa_ctx* c, int B, int t, int flags, const double* ab) {
   if (t < 0 || t >= c->Tcap || !ab) return fail(SA_ERR_ARG, "sa_host_residual: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
+  const Plan p = plan_for(c, B);
   int rc = upload(c, c->at().d_abp, ab, (size_t)B * c->n);
   if (!rc)
-    rc = c->prec == SA_PREC_F64 ? launch_row<double>(c, B, ROW_AMP, t, es, 1, c->Gd)
-                                : launch_row<float>(c, B, ROW_AMP, t, es, 1, c->Gd);
+    rc = c->prec == SA_PREC_F64 ? launch_row<double>(c, p, B, ROW_AMP, t, es, 1, c->Gd)
+                                : launch_row<float>(c, p, B, ROW_AMP, t, es, 1, c->Gd);
   return rc;
 }
 

@@ -111,14 +111,12 @@ struct sa_ctx {
   bool pt_on = false;  // row-block-major Ab partials between k_sec4 / k_sec43 and k_row2 (SecArgs::pt)
   bool sec4 = false;   // k_sec4 (4 waves per section) fits and is chosen
   size_t sec4_lds = 0;
-  int NZ16 = 0;        // k_row2 32-row blocks; nz_cur = z^2 partial count of the current decode
+  int NZ16 = 0;        // k_row2 32-row blocks
   int NZh = 0;         // k_row2 16-row blocks (row16)
   bool row16 = false;  // k_row2<16> after k_sec4 (row-block-major partials, NZh <= 320)
   int NZ4 = 0, NZ2 = 0;  // k_rowv<4> 256-row / k_rowv<2> 128-row blocks
-  int row_kind = 0;    // row kernel of the current decode: 0 k_row, 1 k_row2, 2 k_rowv<4>, 3 k_rowv<2>, 4 k_row2<16>, 5 k_rowc
   // (describes one lane's d_z, yet stays here: in the lane, sa_fetch_z after sa_mc_stage would answer differently)
   bool zil_last = false;  // the last decode left z codeword-interleaved ([NC][n][CB], zil_for)
-  int nz_cur = 0;
   size_t sec2_lds = 0;
   std::vector<uint32_t> ordering;
   uint16_t* d_inv = nullptr;
@@ -183,7 +181,6 @@ struct sa_ctx {
   int slot_cap = 0;
   int* h_mc_live = nullptr;  // pinned ring of the live-slot counts the host polls
   hipEvent_t mc_ev[4] = {};
-  const int* mc_tb = nullptr;  // the slots' t_b while an MC sequence is launched (SecArgs::tb)
   std::map<std::tuple<int, int, int, int>, hipGraphExec_t> mc_graphs;
   // host copies of the bucket table inv [L][w] and the Ab table fwd [G][n][4]
   // (build_tables), kept until the batched tables are built from them (ensure_invb)
@@ -207,6 +204,23 @@ void plaunch(sa_ctx* c, F kernel, dim3 grid, dim3 block, size_t lds, Args... arg
   for (int r = 0; r < nrep; ++r) kernel<<<grid, block, lds, c->at().stream>>>(args...);
 }
 
+// The launches seq() makes on stream s, captured and instantiated as a graph.
+template <typename F>
+int capture_graph(hipStream_t s, F seq, hipGraphExec_t* out) {
+  HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int rc = seq();
+  hipGraph_t g = nullptr;
+  hipError_t e = hipStreamEndCapture(s, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+  return SA_OK;
+}
 
 // ---- backend / kernel choice rules (shared by the units) --------------------
 constexpr int kI8MinB = 4;   // dense backend: batches at least this large take the int8 GEMM path
@@ -223,22 +237,6 @@ inline bool use_i8(const sa_ctx* c, int B) { return c->backend == SA_BACKEND_DEN
 inline bool use_fgemm(const sa_ctx* c, int B) { return c->backend == SA_BACKEND_MATRIX && B >= kFMinB; }
 inline bool use_batched(const sa_ctx* c, int B) { return c->CB > 0 && B >= 4; }
 
-// Two-waves-per-section kernel for the unbatched path when its G2 x B
-// workgroups fill at least half of the CUs (otherwise k_sec's row splits do).
-inline bool use_sec2(const sa_ctx* c, int B) {
-  return c->backend == SA_BACKEND_HADAMARD && !use_batched(c, B) && c->G2 > 0 && c->G2 * B * 2 >= c->n_cus;
-}
-
-// Ab / beta^2 partials per codeword of the unbatched multi-wave section kernels
-inline int sec2_parts(const sa_ctx* c) { return c->sec3 ? c->G3 : c->G2; }
-
-// Row splits for small batches: enough workgroups to cover every CU.
-inline int row_splits(const sa_ctx* c, int B) {
-  const int wgs = c->G * B;
-  int rs = (c->n_cus + wgs - 1) / wgs;
-  return rs < 1 ? 1 : (rs > 4 ? 4 : rs);
-}
-
 // The batched decode with z and the Ab partials interleaved by codeword chunk
 // (SecArgs::zil, 16-byte rows of CB codewords: binary32 CB = 4, binary64
 // CB = 2), row kernel k_rowc.  The default in binary32 (C3 +1.7 %, C4
@@ -251,39 +249,79 @@ inline bool zil_for(const sa_ctx* c, int B) {
   return on && c->backend == SA_BACKEND_HADAMARD && use_batched(c, B) && c->CB * (int)rsz(c) == 16;
 }
 
-// Row kernel for B codewords: k_row2 (32-row blocks) while B * ceil(n/64) <
-// 4 CUs, else in binary32 k_rowv<4> (n % 4 == 0) or k_rowv<2> (n even) when
-// their blocks cover the CUs twice, else k_row (64 rows); k_rowc behind the
-// codeword-interleaved k_secb.
-inline int row_kind_for(const sa_ctx* c, int B) {
-  if (zil_for(c, B)) return 5;
-  if ((long long)B * c->NZ < 4LL * c->n_cus) return (c->row16 && B == 1) ? 4 : 1;
+int dense_parts(const sa_ctx* c, int B);  // sa_dense.hip: Ab partials of the dense A beta (GEMM K splits or GEMV splits)
+
+// Which kernels a decode of B codewords runs, and the counts that follow from
+// the choice: everything (context, B) decides, filled by plan_for alone.  An
+// entry point that launches decode kernels computes it once and hands it to
+// the launchers; nothing of it is kept in the context.
+struct Plan {
+  sa_sec_path sec = SA_SEC_K_SEC;    // the section path of the iterations
+  sa_row_kernel row = SA_ROW_K_ROW;  // the row kernel of the decode (ROW_ABOUT: always k_row)
+  int nz = 0;          // z^2 partials per codeword: the row kernel's blocks per codeword
+  int G = 0, Gb = 0;   // partials per codeword of the loop's producer of abp (A beta) and bbp (beta^2)
+  int pt = 0;          // Ab partials of the loop row-block major (SecArgs::pt): rows per block, 0 for [G][n]
+  int rs = 1;          // row splits of a k_sec / k_secg launch (the loop's, the beta0 start's, sa_Ab / sa_Az)
+  int CB = 1;          // codewords per k_secb workgroup
+  bool zil = false;    // z and the Ab partials codeword-interleaved (zil_for)
+  bool dense() const { return sec == SA_SEC_DENSE || sec == SA_SEC_DENSE_I8 || sec == SA_SEC_MATRIX; }
+  bool batched() const { return sec == SA_SEC_K_SECB; }
+  bool multiwave() const { return sec == SA_SEC_K_SEC2 || sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43; }
+  // k_row2 launches can carry the iters writes (RowArgs::itset); the small-batch Hadamard decode uses them
+  bool row_sets_iters() const { return row == SA_ROW_K_ROW2 || row == SA_ROW_K_ROW2_16; }
+  bool it_row() const { return !dense() && !batched() && row_sets_iters(); }
+  // k_sec4 / k_sec43 can take the previous estimate as zero (SecArgs::bzero)
+  bool bzero() const { return sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43; }
+};
+
+// Row kernel for B codewords: k_row2 (32-row blocks, 16-row for one codeword
+// where row16) while B * ceil(n/64) < 4 CUs, else in binary32 k_rowv<4>
+// (n % 4 == 0) or k_rowv<2> (n even) when their blocks cover the CUs twice,
+// else k_row (64 rows); k_rowc behind the codeword-interleaved k_secb.
+// Section path: the GEMMs / GEMVs of a dense backend; k_secb from 4 codewords;
+// a multi-wave kernel (k_sec43 over k_sec4 over k_sec2) when its workgroups
+// fill at least half of the CUs; else k_sec's (k_secg's) row splits.
+inline Plan plan_for(const sa_ctx* c, int B) {
+  Plan p;
   const bool f32 = c->prec == SA_PREC_F32;
-  // 16-byte rows: binary32 n % 4 == 0 (256-row blocks) or binary64 n even (128)
-  if (c->n % (f32 ? 4 : 2) == 0 && (long long)B * (f32 ? c->NZ4 : c->NZ2) >= 2LL * c->n_cus) return 2;
-  if (f32 && c->n % 2 == 0 && (long long)B * c->NZ2 >= 2LL * c->n_cus) return 3;  // 8-byte rows
-  return 0;
-}
-inline int nz_for(const sa_ctx* c, int kind) {
-  const bool f32 = c->prec == SA_PREC_F32;
-  if (kind == 4) return c->NZh;
-  if (kind == 5) return c->NZ2;  // k_rowc: 128-row blocks
-  return kind == 1 ? c->NZ16 : (kind == 2 ? (f32 ? c->NZ4 : c->NZ2) : (kind == 3 ? c->NZ2 : c->NZ));
-}
-inline void pick_row(sa_ctx* c, int B) {
-  c->row_kind = row_kind_for(c, B);
-  c->nz_cur = nz_for(c, c->row_kind);  // z^2 partials per codeword
+  p.zil = zil_for(c, B);
+  if (p.zil) {
+    p.row = SA_ROW_K_ROWC; p.nz = c->NZ2;  // 128-row blocks
+  } else if ((long long)B * c->NZ < 4LL * c->n_cus) {
+    if (c->row16 && B == 1) { p.row = SA_ROW_K_ROW2_16; p.nz = c->NZh; }
+    else { p.row = SA_ROW_K_ROW2; p.nz = c->NZ16; }
+  } else if (c->n % (f32 ? 4 : 2) == 0 && (long long)B * (f32 ? c->NZ4 : c->NZ2) >= 2LL * c->n_cus) {
+    // 16-byte rows: binary32 n % 4 == 0 (256-row blocks) or binary64 n even (128)
+    p.row = SA_ROW_K_ROWV16; p.nz = f32 ? c->NZ4 : c->NZ2;
+  } else if (f32 && c->n % 2 == 0 && (long long)B * c->NZ2 >= 2LL * c->n_cus) {
+    p.row = SA_ROW_K_ROWV8; p.nz = c->NZ2;
+  } else {
+    p.row = SA_ROW_K_ROW; p.nz = c->NZ;
+  }
+  const int wgs = c->G * B;  // k_sec / k_secg: enough row splits to cover every CU
+  p.rs = std::min(4, std::max(1, (c->n_cus + wgs - 1) / wgs));
+  if (is_dense(c)) {
+    p.sec = use_i8(c, B) ? SA_SEC_DENSE_I8 : (use_fgemm(c, B) ? SA_SEC_MATRIX : SA_SEC_DENSE);
+    p.G = dense_parts(c, B);
+    p.Gb = c->Gd;
+  } else if (use_batched(c, B)) {
+    p.sec = SA_SEC_K_SECB;
+    p.G = p.Gb = c->Gb;
+    p.CB = c->CB;
+  } else if (c->backend == SA_BACKEND_HADAMARD && c->G2 > 0 && c->G2 * B * 2 >= c->n_cus) {
+    p.sec = c->sec3 ? SA_SEC_K_SEC43 : (c->sec4 ? SA_SEC_K_SEC4 : SA_SEC_K_SEC2);
+    p.G = p.Gb = c->sec3 ? c->G3 : c->G2;  // triples / pairs of sections
+    if (p.sec != SA_SEC_K_SEC2 && p.row_sets_iters() && c->pt_on) p.pt = p.row == SA_ROW_K_ROW2_16 ? 16 : kRow2Rows;
+  } else {
+    p.sec = c->big ? SA_SEC_K_SECG : SA_SEC_K_SEC;
+    p.G = p.Gb = c->G;
+  }
+  return p;
 }
 
-// Ab partial layout between the pair / triple kernels and k_row2 (SecArgs::pt):
-// rows per row-major block, 0 for the [G][n] layout
-inline int pt_for(const sa_ctx* c, int B, bool sec2) {
-  const int rk = row_kind_for(c, B);
-  return (sec2 && (c->sec3 || c->sec4) && (rk == 1 || rk == 4) && c->pt_on) ? (rk == 4 ? 16 : kRow2Rows) : 0;
-}
-
+// t_b: the Monte-Carlo stream's per-slot iteration indices (SecArgs::tb), else null
 template <typename real>
-SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
+SecArgs<real> sec_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop, const int* tb = nullptr) {
   SecArgs<real> a;
   const sa_lane& ln = c->at();
   a.inv = c->d_inv; a.inv32 = c->d_inv32; a.invb = c->d_invb; a.invl = c->d_invl; a.hs = c->d_hs;
@@ -292,7 +330,7 @@ SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
   a.z = (const real*)ln.d_z; a.beta = (real*)ln.d_beta; a.beta_out = (real*)ln.d_beta; a.out = (real*)c->d_out;
   a.abp = (real*)ln.d_abp; a.bbp = (real*)ln.d_bbp; a.zzp = (const real*)ln.d_zzp;
   a.tau = (real*)ln.d_tau; a.iters = ln.d_iters;
-  a.L = c->L; a.M = c->M; a.n = c->n; a.w = c->w; a.nhi = c->nhi; a.G = c->G; a.NZ = c->nz_cur;
+  a.L = c->L; a.M = c->M; a.n = c->n; a.w = c->w; a.nhi = c->nhi; a.G = c->G; a.NZ = p.nz;
   a.T1 = c->Tcap + 1; a.t = t; a.mode = mode; a.early_stop = early_stop;
   a.RS = 1;
   a.pt = 0;
@@ -300,20 +338,20 @@ SecArgs<real> sec_args(sa_ctx* c, int mode, int t, int early_stop) {
   a.cst = c->pb_on ? c->L : 0;
   if (c->pb_on) a.c = (const real*)c->d_cb;
   a.sqrt_n = (real)std::sqrt((double)c->n);
-  a.tb = c->mc_tb;
+  a.tb = tb;
   a.dead = c->dead;
   a.bzero = 0;
   return a;
 }
 
 template <typename real>
-RowArgs<real> row_args(sa_ctx* c, int mode, int t, int early_stop, int G, int Gb) {
+RowArgs<real> row_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop, int G, int Gb, const int* tb = nullptr) {
   RowArgs<real> a;
   const sa_lane& ln = c->at();
   a.y = (const real*)ln.d_y; a.z = (real*)ln.d_z; a.z_in = a.z; a.abp = (const real*)ln.d_abp;
   a.bbp = (const real*)ln.d_bbp; a.zzp = (real*)ln.d_zzp; a.tau = (const real*)ln.d_tau;
   a.out = (real*)c->d_out;
-  a.n = c->n; a.G = G; a.NZ = c->nz_cur;
+  a.n = c->n; a.G = G; a.NZ = p.nz;
   a.Gb = Gb; a.T1 = c->Tcap + 1; a.t = t; a.mode = mode;
   a.early_stop = early_stop;
   // the dense matrix already carries the 1/sqrt(n) of sparc_ldpc.py:143-146
@@ -322,7 +360,7 @@ RowArgs<real> row_args(sa_ctx* c, int mode, int t, int early_stop, int G, int Gb
   a.Pbst = c->pb_on ? 1 : 0;
   a.pt = 0;
   a.Bc = 0;
-  a.tb = c->mc_tb;
+  a.tb = tb;
   a.iters = ln.d_iters;
   a.itset = 0;
   return a;
@@ -351,7 +389,9 @@ int check_ctx(const sa_ctx* c);
 int check_tables(const sa_ctx* c, const char* what);
 int dev_alloc(sa_ctx* c, void** p, size_t bytes);
 void dev_free(void* p);
-void drop_graphs(sa_ctx* c);  // every lane's
+using GraphMap = std::map<std::tuple<int, int, int, int>, hipGraphExec_t>;
+void graphs_clear(GraphMap& m);
+void drop_graphs(sa_ctx* c);  // every lane's, and sa_mc_run's
 // decode lanes: wait for every lane; make lane k current; drop lane 1's buffers
 // (after waiting for every lane; lane 0 becomes current and keeps the staged y)
 int sync_all(sa_ctx* c);
@@ -385,36 +425,36 @@ extern __global__ void k_fill32(uint32_t* p, uint32_t v, size_t nw);
 
 // ---- sa_sec.hip: the single-codeword section kernels ---------------------------
 template <typename real>
-int launch_sec(sa_ctx* c, int B, int mode, int t, int es, void* bin = nullptr, void* bout = nullptr);
+int launch_sec(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, void* bin = nullptr, void* bout = nullptr);
 template <typename real>
-int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt = 0, int bzero = 0);
+int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero = 0);
 hipError_t sec_lds_attrs();
 
 // ---- sa_secb.hip: the batched section kernel ------------------------------------
 template <typename real>
-int launch_secb(sa_ctx* c, int B, int t, int es);
+int launch_secb(sa_ctx* c, const Plan& p, int B, int t, int es, const int* tb = nullptr);
 hipError_t secb_lds_attrs();
 bool secb_no_static_lds();
 
 // ---- sa_row.hip: row kernels, decisions ----------------------------------------
+// G, Gb: the partial counts of whatever produced abp / bbp for this launch
+// (the plan's for the loop; the beta0 start, the host loop and the
+// Monte-Carlo stream pass their own).  ROW_ABOUT is always k_row.
 template <typename real>
-int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt = 0, void* zin = nullptr,
-               void* zout = nullptr, int itset = 0);
-// k_row2 is the row kernel of the current decode: its launches can carry the iters writes (RowArgs::itset)
-inline bool row_sets_iters(const sa_ctx* c) { return c->row_kind == 1 || c->row_kind == 4; }
+int launch_row(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, int G, int Gb, int itset = 0,
+               const int* tb = nullptr);
 int launch_decide(sa_ctx* c, int B, int32_t* idx);  // idx: device-visible [B][L]
 
 // ---- sa_dense.hip: the materialised-matrix backends ----------------------------
-int dense_parts(const sa_ctx* c, int B);  // Ab partials of the dense A beta (GEMM K splits or GEMV splits)
 int dense_den_groups(const sa_ctx* c);
 template <typename real>
-int dense_start(sa_ctx* c, int B, int S);  // z = y - A beta0 (the beta0 start)
+int dense_start(sa_ctx* c, const Plan& p, int B);  // z = y - A beta0 (the beta0 start)
 template <typename real>
-int dense_iter(sa_ctx* c, int B, int t, int es, int S);  // A^T z -> denoiser -> A beta partials
+int dense_iter(sa_ctx* c, const Plan& p, int B, int t, int es);  // A^T z -> denoiser -> A beta partials
 template <typename real>
-int dense_ab(sa_ctx* c, int B);  // A beta of d_beta -> d_out
+int dense_ab(sa_ctx* c, const Plan& p, int B);  // A beta of d_beta -> d_out
 template <typename real>
-int dense_az(sa_ctx* c, int B);  // A^T z of d_z -> d_out
+int dense_az(sa_ctx* c, const Plan& p, int B);  // A^T z of d_z -> d_out
 int ensure_i8(sa_ctx* c, int B);
 int ensure_fgemm(sa_ctx* c, int B);
 int i8_set_bfix(sa_ctx* c);

@@ -338,18 +338,14 @@ int mc_encode_all(sa_ctx* c, const McArgs& a, int nreps) {
 // K iterations of the refilled batch: section kernel, row kernel, slot step,
 // turnover (all on the context's stream, captured once per (B, T, K, flags))
 template <typename real>
-int mc_iterations(sa_ctx* c, int B, int T, int K, int es) {
+int mc_iterations(sa_ctx* c, const Plan& p, int B, int T, int K, int es) {
   const McArgs a = mc_args(c, B, T);
-  c->mc_tb = a.tb;
-  int rc = SA_OK;
-  for (int k = 0; k < K && !rc; ++k) {
-    if ((rc = launch_secb<real>(c, B, 0, es))) break;
-    if ((rc = launch_row<real>(c, B, ROW_AMP, 0, es, c->Gb, c->Gb))) break;
+  for (int k = 0; k < K; ++k) {  // the kernels take each slot's iteration index from a.tb
+    if (int rc = launch_secb<real>(c, p, B, 0, es, a.tb)) return rc;
+    if (int rc = launch_row<real>(c, p, B, ROW_AMP, 0, es, c->Gb, c->Gb, 0, a.tb)) return rc;
     k_mc_step<<<1, kMcStepThreads, 0, c->at().stream>>>(a);
-    if ((rc = mc_turnover<real>(c, a))) break;
+    if (int rc = mc_turnover<real>(c, a)) return rc;
   }
-  c->mc_tb = nullptr;
-  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -357,8 +353,7 @@ int mc_iterations(sa_ctx* c, int B, int T, int K, int es) {
 int mc_ensure_slots(sa_ctx* c, int B) {
   if (c->slot_cap >= B) return SA_OK;
   HIP_TRY(hipStreamSynchronize(c->at().stream));
-  for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);
-  c->mc_graphs.clear();
+  graphs_clear(c->mc_graphs);
   dev_free(c->d_slots);
   c->d_slots = nullptr;
   c->slot_cap = 0;
@@ -373,8 +368,7 @@ int mc_ensure_slots(sa_ctx* c, int B) {
 hipError_t mc_lds_attrs() { return hipSuccess; }
 
 void mc_release(sa_ctx* c) {
-  for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);
-  c->mc_graphs.clear();
+  graphs_clear(c->mc_graphs);
   dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
   dev_free(c->d_mc_y); dev_free(c->d_mc_zzp);
   c->d_mc_y = c->d_mc_zzp = nullptr;
@@ -455,8 +449,7 @@ int sa_mc_stage(sa_ctx* c, int nreps, const int32_t* idx, const double* noise) {
     c->d_mc_noise = nullptr;
     c->d_mc_y = c->d_mc_zzp = nullptr;
     c->mc_cap = 0;
-    for (auto& kv : c->mc_graphs) (void)hipGraphExecDestroy(kv.second);  // they hold the old pointers
-    c->mc_graphs.clear();
+    graphs_clear(c->mc_graphs);  // they hold the old pointers
     int rc;
     if ((rc = dev_alloc(c, (void**)&c->d_mc_idx, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
     if ((rc = dev_alloc(c, (void**)&c->d_mc_dec, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
@@ -499,7 +492,7 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
   const bool f64 = c->prec == SA_PREC_F64;
   const int nreps = c->mc_nreps;
-  pick_row(c, B);
+  const Plan p = plan_for(c, B);  // k_secb + k_rowc (zil_for, checked above)
   c->zil_last = true;
   // the slots' start: the first min(B, reps) reps in slots 0.., the rest
   // empty; every slot's estimate zero (the turnover zeroes a refilled slot's
@@ -538,19 +531,11 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   const auto key = std::make_tuple(B, T, K, flags & 0xff);
   auto it = c->mc_graphs.find(key);
   if (it == c->mc_graphs.end()) {
-    HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
-    rc = f64 ? mc_iterations<double>(c, B, T, K, es) : mc_iterations<float>(c, B, T, K, es);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(ln.stream, &g);
-    if (rc) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     hipGraphExec_t ex = nullptr;
-    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    rc = capture_graph(ln.stream, [&] {
+      return f64 ? mc_iterations<double>(c, p, B, T, K, es) : mc_iterations<float>(c, p, B, T, K, es);
+    }, &ex);
+    if (rc) return rc;
     it = c->mc_graphs.emplace(key, ex).first;
   }
   // every rep takes at most T iterations and a slot refills in the iteration

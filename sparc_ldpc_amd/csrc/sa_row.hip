@@ -458,44 +458,43 @@ __global__ void __launch_bounds__(256) k_decide(const real* beta, int32_t* idx, 
 
 // ---- launchers ------------------------------------------------------------
 template <typename real>
-int launch_row(sa_ctx* c, int B, int mode, int t, int es, int G, int Gb, int pt, void* zin, void* zout, int itset) {
-  RowArgs<real> a = row_args<real>(c, mode, t, es, G, Gb);
-  a.pt = pt;
-  if (itset && !row_sets_iters(c)) return fail(SA_ERR_UNSUPPORTED, "launch_row: only k_row2 writes iters");
+int launch_row(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, int G, int Gb, int itset, const int* tb) {
+  RowArgs<real> a = row_args<real>(c, p, mode, t, es, G, Gb, tb);
+  a.pt = mode == ROW_AMP ? p.pt : 0;  // only the loop's producers write row-block major
+  if (itset && !p.row_sets_iters()) return fail(SA_ERR_UNSUPPORTED, "launch_row: only k_row2 writes iters");
   a.itset = itset;
-  // k_row2 takes its row-block count from RowArgs::NZ (no hidden grid argument)
-  if (row_sets_iters(c) && a.NZ != (c->row_kind == 4 ? c->NZh : c->NZ16))
-    return fail(SA_ERR_ARG, "launch_row: the z^2 partial count is not k_row2's row-block count");
-  if (zout) a.z = (real*)zout;
-  if (zin) a.z_in = (const real*)zin;
   if (c->prof) c->prof->begin(c->at().stream, K_ROW);
-  // small batch: 16-row workgroups cover the chip; many codewords: 64-row
-  // workgroups, 4 waves with deeper per-lane load streams
-  if (c->row_kind == 5 && mode != ROW_ABOUT) {
-    constexpr int CBz = 16 / (int)sizeof(real);  // codewords per 16-byte row
-    a.Bc = B;
-    // each wave's G / 4 partials in one batch of loads (U = 12: C4's 48 groups)
-    if ((a.G + 3) / 4 > 8 && (a.G + 3) / 4 <= 12)
-      plaunch(c, k_rowc<real, CBz, 12>, dim3(c->NZ2, (B + CBz - 1) / CBz), 256, 0, a, mode == ROW_AMP ? 1 : 0);
-    else
-      plaunch(c, k_rowc<real, CBz>, dim3(c->NZ2, (B + CBz - 1) / CBz), 256, 0, a, mode == ROW_AMP ? 1 : 0);
-  } else if (c->row_kind == 5) {  // A beta out of k_sec's [B][G][n] partials (sa_Ab after a batched decode)
-    plaunch(c, k_row<real, 4>, dim3(c->NZ, B), 4 * 64, 0, a);
-  } else if (c->row_kind == 1) {
-    plaunch(c, k_row2<real>, dim3(c->NZ16, B), 512, 0, a);
-  } else if (c->row_kind == 4) {
-    plaunch(c, k_row2<real, 16>, dim3(c->NZh, B), 512, 0, a);
-  } else if (c->row_kind == 2) {
-    constexpr int V = 16 / (int)sizeof(real);  // 16-byte rows
-    plaunch(c, k_rowv<real, V>, dim3(c->nz_cur, B), 256, 0, a);
-  } else if (c->row_kind == 3) {
-    if constexpr (sizeof(real) == 4) {
-      plaunch(c, k_rowv<float, 2>, dim3(c->NZ2, B), 256, 0, a);
-    } else {
-      return SA_ERR_UNSUPPORTED;  // never chosen for binary64 (row_kind_for)
+  // A beta out of [B][G][n] partials (sa_Ab): k_row whatever the plan's row
+  // kernel, so that the sum's order depends on no decode.  Else small batch:
+  // 16- / 32-row workgroups cover the chip; many codewords: 64-row workgroups,
+  // 4 waves with deeper per-lane load streams
+  switch (mode == ROW_ABOUT ? SA_ROW_K_ROW : p.row) {
+    case SA_ROW_K_ROWC: {
+      constexpr int CBz = 16 / (int)sizeof(real);  // codewords per 16-byte row
+      a.Bc = B;
+      // each wave's G / 4 partials in one batch of loads (U = 12: C4's 48 groups)
+      if ((a.G + 3) / 4 > 8 && (a.G + 3) / 4 <= 12)
+        plaunch(c, k_rowc<real, CBz, 12>, dim3(p.nz, (B + CBz - 1) / CBz), 256, 0, a, mode == ROW_AMP ? 1 : 0);
+      else
+        plaunch(c, k_rowc<real, CBz>, dim3(p.nz, (B + CBz - 1) / CBz), 256, 0, a, mode == ROW_AMP ? 1 : 0);
+      break;
     }
-  } else {
-    plaunch(c, k_row<real, 4>, dim3(c->NZ, B), 4 * 64, 0, a);
+    // k_row2 takes its row-block count from RowArgs::NZ (no hidden grid argument)
+    case SA_ROW_K_ROW2: plaunch(c, k_row2<real>, dim3(p.nz, B), 512, 0, a); break;
+    case SA_ROW_K_ROW2_16: plaunch(c, k_row2<real, 16>, dim3(p.nz, B), 512, 0, a); break;
+    case SA_ROW_K_ROWV16: {
+      constexpr int V = 16 / (int)sizeof(real);  // 16-byte rows
+      plaunch(c, k_rowv<real, V>, dim3(p.nz, B), 256, 0, a);
+      break;
+    }
+    case SA_ROW_K_ROWV8:
+      if constexpr (sizeof(real) == 4) {
+        plaunch(c, k_rowv<float, 2>, dim3(p.nz, B), 256, 0, a);
+        break;
+      } else {
+        return SA_ERR_UNSUPPORTED;  // never chosen for binary64 (plan_for)
+      }
+    case SA_ROW_K_ROW: plaunch(c, k_row<real, 4>, dim3(c->NZ, B), 4 * 64, 0, a); break;
   }
   if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
@@ -518,7 +517,7 @@ int launch_decide(sa_ctx* c, int B, int32_t* idx) {
   return SA_OK;
 }
 
-template int launch_row<float>(sa_ctx*, int, int, int, int, int, int, int, void*, void*, int);
-template int launch_row<double>(sa_ctx*, int, int, int, int, int, int, int, void*, void*, int);
+template int launch_row<float>(sa_ctx*, const Plan&, int, int, int, int, int, int, int, const int*);
+template int launch_row<double>(sa_ctx*, const Plan&, int, int, int, int, int, int, int, const int*);
 
 }  // namespace sa

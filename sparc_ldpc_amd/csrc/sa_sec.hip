@@ -823,8 +823,8 @@ __global__ void __launch_bounds__(768) k_sec43(SecArgs<real> a) { secq_body<real
 
 // ---- launchers ------------------------------------------------------------
 template <typename real, int E>
-void launch_sec_e(sa_ctx* c, int B, SecArgs<real> a) {
-  a.RS = row_splits(c, B);
+void launch_sec_e(sa_ctx* c, const Plan& p, int B, SecArgs<real> a) {
+  a.RS = p.rs;
   dim3 grid(c->G * a.RS, B);
   if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   if (c->big)
@@ -834,77 +834,78 @@ void launch_sec_e(sa_ctx* c, int B, SecArgs<real> a) {
   if (c->prof) c->prof->end(c->at().stream);
 }
 
+// One iteration's section step on the plan's multi-wave kernel (pairs or triples of sections)
 template <typename real>
-int launch_sec2(sa_ctx* c, int B, int t, int es, void* bin, void* bout, int pt, int bzero) {
-  SecArgs<real> a = sec_args<real>(c, SEC_AMP, t, es);
-  a.pt = pt;
-  if (bzero && !(c->sec3 || c->sec4)) return fail(SA_ERR_UNSUPPORTED, "k_sec2 reads its previous estimate");
+int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero) {
+  SecArgs<real> a = sec_args<real>(c, p, SEC_AMP, t, es);
+  a.pt = p.pt;
+  if (bzero && !p.bzero()) return fail(SA_ERR_UNSUPPORTED, "k_sec2 reads its previous estimate");
   a.bzero = bzero;
   a.beta = (real*)bin;
   a.beta_out = (real*)bout;
-  a.G = sec2_parts(c);
+  a.G = p.G;
   dim3 grid(a.G, B);
   if (c->prof) c->prof->begin(c->at().stream, K_SEC);
-  if (c->sec3) {
-    switch (c->M / 256) {
-      case 1: plaunch(c, k_sec43<real, 1>, grid, 768, c->sec3_lds, a); break;
-      case 2: plaunch(c, k_sec43<real, 2>, grid, 768, c->sec3_lds, a); break;
-      default: return fail(SA_ERR_UNSUPPORTED, "k_sec43: M");
-    }
-    if (c->prof) c->prof->end(c->at().stream);
-    HIP_TRY(hipGetLastError());
-    return SA_OK;
-  }
-  if (c->sec4) {
-    switch (c->M / 256) {
-      case 1: plaunch(c, k_sec4<real, 1>, grid, 512, c->sec4_lds, a); break;
-      case 2: plaunch(c, k_sec4<real, 2>, grid, 512, c->sec4_lds, a); break;
-      case 4: plaunch(c, k_sec4<real, 4>, grid, 512, c->sec4_lds, a); break;
-      case 8: plaunch(c, k_sec4<real, 8>, grid, 512, c->sec4_lds, a); break;
-      case 16: plaunch(c, k_sec4<real, 16>, grid, 512, c->sec4_lds, a); break;
-      default: return fail(SA_ERR_UNSUPPORTED, "k_sec4: M");
-    }
-    if (c->prof) c->prof->end(c->at().stream);
-    HIP_TRY(hipGetLastError());
-    return SA_OK;
-  }
-  switch (c->M / 128) {
-    case 1: plaunch(c, k_sec2<real, 1>, grid, 256, c->sec2_lds, a); break;
-    case 2: plaunch(c, k_sec2<real, 2>, grid, 256, c->sec2_lds, a); break;
-    case 4: plaunch(c, k_sec2<real, 4>, grid, 256, c->sec2_lds, a); break;
-    case 8: plaunch(c, k_sec2<real, 8>, grid, 256, c->sec2_lds, a); break;
-    case 16: plaunch(c, k_sec2<real, 16>, grid, 256, c->sec2_lds, a); break;
-    case 32: plaunch(c, k_sec2<real, 32>, grid, 256, c->sec2_lds, a); break;
-    default: return fail(SA_ERR_UNSUPPORTED, "k_sec2: M");
+  switch (p.sec) {
+    case SA_SEC_K_SEC43:
+      switch (c->M / 256) {
+        case 1: plaunch(c, k_sec43<real, 1>, grid, 768, c->sec3_lds, a); break;
+        case 2: plaunch(c, k_sec43<real, 2>, grid, 768, c->sec3_lds, a); break;
+        default: return fail(SA_ERR_UNSUPPORTED, "k_sec43: M");
+      }
+      break;
+    case SA_SEC_K_SEC4:
+      switch (c->M / 256) {
+        case 1: plaunch(c, k_sec4<real, 1>, grid, 512, c->sec4_lds, a); break;
+        case 2: plaunch(c, k_sec4<real, 2>, grid, 512, c->sec4_lds, a); break;
+        case 4: plaunch(c, k_sec4<real, 4>, grid, 512, c->sec4_lds, a); break;
+        case 8: plaunch(c, k_sec4<real, 8>, grid, 512, c->sec4_lds, a); break;
+        case 16: plaunch(c, k_sec4<real, 16>, grid, 512, c->sec4_lds, a); break;
+        default: return fail(SA_ERR_UNSUPPORTED, "k_sec4: M");
+      }
+      break;
+    case SA_SEC_K_SEC2:
+      switch (c->M / 128) {
+        case 1: plaunch(c, k_sec2<real, 1>, grid, 256, c->sec2_lds, a); break;
+        case 2: plaunch(c, k_sec2<real, 2>, grid, 256, c->sec2_lds, a); break;
+        case 4: plaunch(c, k_sec2<real, 4>, grid, 256, c->sec2_lds, a); break;
+        case 8: plaunch(c, k_sec2<real, 8>, grid, 256, c->sec2_lds, a); break;
+        case 16: plaunch(c, k_sec2<real, 16>, grid, 256, c->sec2_lds, a); break;
+        case 32: plaunch(c, k_sec2<real, 32>, grid, 256, c->sec2_lds, a); break;
+        default: return fail(SA_ERR_UNSUPPORTED, "k_sec2: M");
+      }
+      break;
+    default: return fail(SA_ERR_ARG, "launch_sec2: the plan runs no multi-wave section kernel");
   }
   if (c->prof) c->prof->end(c->at().stream);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
 
+// k_sec / k_secg in any mode (SEC_AMP, SEC_AB, SEC_AZ)
 template <typename real>
-int launch_sec(sa_ctx* c, int B, int mode, int t, int es, void* bin, void* bout) {
-  SecArgs<real> a = sec_args<real>(c, mode, t, es);
+int launch_sec(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, void* bin, void* bout) {
+  SecArgs<real> a = sec_args<real>(c, p, mode, t, es);
   if (bin) a.beta = (real*)bin;
   if (bout) a.beta_out = (real*)bout;
   switch (c->E) {
-    case 1: launch_sec_e<real, 1>(c, B, a); break;
-    case 2: launch_sec_e<real, 2>(c, B, a); break;
-    case 4: launch_sec_e<real, 4>(c, B, a); break;
-    case 8: launch_sec_e<real, 8>(c, B, a); break;
-    case 16: launch_sec_e<real, 16>(c, B, a); break;
-    case 32: launch_sec_e<real, 32>(c, B, a); break;
-    case 64: launch_sec_e<real, 64>(c, B, a); break;
+    case 1: launch_sec_e<real, 1>(c, p, B, a); break;
+    case 2: launch_sec_e<real, 2>(c, p, B, a); break;
+    case 4: launch_sec_e<real, 4>(c, p, B, a); break;
+    case 8: launch_sec_e<real, 8>(c, p, B, a); break;
+    case 16: launch_sec_e<real, 16>(c, p, B, a); break;
+    case 32: launch_sec_e<real, 32>(c, p, B, a); break;
+    case 64: launch_sec_e<real, 64>(c, p, B, a); break;
     default: return fail(SA_ERR_UNSUPPORTED, "bad E");
   }
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
 
-template int launch_sec<float>(sa_ctx*, int, int, int, int, void*, void*);
-template int launch_sec<double>(sa_ctx*, int, int, int, int, void*, void*);
-template int launch_sec2<float>(sa_ctx*, int, int, int, void*, void*, int, int);
-template int launch_sec2<double>(sa_ctx*, int, int, int, void*, void*, int, int);
+template int launch_sec<float>(sa_ctx*, const Plan&, int, int, int, int, void*, void*);
+template int launch_sec<double>(sa_ctx*, const Plan&, int, int, int, int, void*, void*);
+template int launch_sec2<float>(sa_ctx*, const Plan&, int, int, int, void*, void*, int);
+template int launch_sec2<double>(sa_ctx*, const Plan&, int, int, int, void*, void*, int);
 
 // Every single-codeword section-kernel instantiation may use the full 160 KB LDS.
 template <typename real>

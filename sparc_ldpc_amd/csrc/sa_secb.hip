@@ -624,11 +624,11 @@ __global__ void __launch_bounds__(W * 64, (E <= 8 ? 4 : 1)) k_secb(SecArgs<real>
 
 // Batched section kernel: grid = Gb groups x ceil(B / CB) chunks (1-D, XCD-grouped).
 template <typename real, int E, int CB>
-void launch_secb_e(sa_ctx* c, int B, SecArgs<real> a) {
+void launch_secb_e(sa_ctx* c, const Plan& p, int B, SecArgs<real> a) {
   a.G = c->Gb;
   a.B = B;
   a.NC = (B + CB - 1) / CB;
-  a.zil = zil_for(c, B) ? 1 : 0;
+  a.zil = p.zil ? 1 : 0;
   a.gpx = c->gpx;
   if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   const dim3 grid(c->Gb * a.NC);
@@ -652,39 +652,40 @@ void launch_secb_e(sa_ctx* c, int B, SecArgs<real> a) {
 }
 
 template <typename real, int CB>
-int launch_secb_cb(sa_ctx* c, int B, const SecArgs<real>& a) {
+int launch_secb_cb(sa_ctx* c, const Plan& p, int B, const SecArgs<real>& a) {
   switch (c->E) {
-    case 1: launch_secb_e<real, 1, CB>(c, B, a); break;
-    case 2: launch_secb_e<real, 2, CB>(c, B, a); break;
-    case 4: launch_secb_e<real, 4, CB>(c, B, a); break;
-    case 8: launch_secb_e<real, 8, CB>(c, B, a); break;
-    case 16: launch_secb_e<real, 16, CB>(c, B, a); break;
+    case 1: launch_secb_e<real, 1, CB>(c, p, B, a); break;
+    case 2: launch_secb_e<real, 2, CB>(c, p, B, a); break;
+    case 4: launch_secb_e<real, 4, CB>(c, p, B, a); break;
+    case 8: launch_secb_e<real, 8, CB>(c, p, B, a); break;
+    case 16: launch_secb_e<real, 16, CB>(c, p, B, a); break;
     default: return fail(SA_ERR_UNSUPPORTED, "batched kernel: M > 1024");
   }
   return SA_OK;
 }
 
 template <typename real>
-int launch_secb(sa_ctx* c, int B, int t, int es) {
-  SecArgs<real> a = sec_args<real>(c, SEC_AMP, t, es);
+int launch_secb(sa_ctx* c, const Plan& p, int B, int t, int es, const int* tb) {
+  if (!p.batched()) return fail(SA_ERR_ARG, "launch_secb: the plan does not run k_secb");
+  SecArgs<real> a = sec_args<real>(c, p, SEC_AMP, t, es, tb);
   int rc;
   if constexpr (sizeof(real) == 4) {
-    if (c->CB == 4) {
-      rc = launch_secb_cb<real, 4>(c, B, a);
+    if (p.CB == 4) {
+      rc = launch_secb_cb<real, 4>(c, p, B, a);
       if (rc) return rc;
       HIP_TRY(hipGetLastError());
       return SA_OK;
     }
   }
-  if (c->CB == 2) rc = launch_secb_cb<real, 2>(c, B, a);
-  else rc = launch_secb_cb<real, 1>(c, B, a);
+  if (p.CB == 2) rc = launch_secb_cb<real, 2>(c, p, B, a);
+  else rc = launch_secb_cb<real, 1>(c, p, B, a);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
 
-template int launch_secb<float>(sa_ctx*, int, int, int);
-template int launch_secb<double>(sa_ctx*, int, int, int);
+template int launch_secb<float>(sa_ctx*, const Plan&, int, int, int, const int*);
+template int launch_secb<double>(sa_ctx*, const Plan&, int, int, int, const int*);
 
 // Every k_secb instantiation may use the full 160 KB LDS.
 template <typename real>

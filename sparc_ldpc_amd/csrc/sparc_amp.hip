@@ -213,7 +213,7 @@ static bool lane_shape(const sa_ctx* c, int B) {
   return c->backend == SA_BACKEND_HADAMARD && !use_batched(c, B) && !(c->plan & (SA_PLAN_EAGER | SA_PLAN_NO_LANES));
 }
 
-static void graphs_clear(std::map<std::tuple<int, int, int, int>, hipGraphExec_t>& m) {
+void graphs_clear(GraphMap& m) {
   for (auto& kv : m) (void)hipGraphExecDestroy(kv.second);
   m.clear();
 }
@@ -346,17 +346,18 @@ int download(sa_ctx* c, sa_lane& l, double* dst, const void* src, size_t count) 
 // Ab of the batch staged in d_beta -> d_out  (B x n)
 template <typename real>
 int seq_ab(sa_ctx* c, int B) {
-  if (is_dense(c)) return dense_ab<real>(c, B);
-  int rc;
-  if ((rc = launch_sec<real>(c, B, SEC_AB, 0, 0))) return rc;
-  return launch_row<real>(c, B, ROW_ABOUT, 0, 0, c->G, c->G);
+  const Plan p = plan_for(c, B);
+  if (p.dense()) return dense_ab<real>(c, p, B);
+  if (int rc = launch_sec<real>(c, p, B, SEC_AB, 0, 0)) return rc;
+  return launch_row<real>(c, p, B, ROW_ABOUT, 0, 0, c->G, c->G);
 }
 
 // Az of the batch staged in d_z -> d_out  (B x L*M)
 template <typename real>
 int seq_az(sa_ctx* c, int B) {
-  if (is_dense(c)) return dense_az<real>(c, B);
-  return launch_sec<real>(c, B, SEC_AZ, 0, 0);
+  const Plan p = plan_for(c, B);
+  if (p.dense()) return dense_az<real>(c, p, B);
+  return launch_sec<real>(c, p, B, SEC_AZ, 0, 0);
 }
 
 // Whole AMP decode of the staged batch: y in d_y, beta0 in d_beta if has_b0.
@@ -364,16 +365,9 @@ template <typename real>
 int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
   sa_lane& ln = c->at();  // (nothing below changes lanes)
-  const bool dense = is_dense(c);
-  const bool batched = !dense && use_batched(c, B);
-  const bool sec2 = use_sec2(c, B);
-  pick_row(c, B);  // row kernel and its z^2 partial count
-  c->zil_last = zil_for(c, B);
-  // Ab partials row-block major between the pair / triple kernels and k_row2
-  const int pt = pt_for(c, B, sec2);
-  // partial counts of the producer of abp (Ab) and bbp (beta^2)
-  const int G = dense ? dense_parts(c, B) : (batched ? c->Gb : (sec2 ? sec2_parts(c) : c->G));
-  const int Gb = dense ? c->Gd : (batched ? c->Gb : (sec2 ? sec2_parts(c) : c->G));
+  const Plan p = plan_for(c, B);  // the kernels of this decode and their partial counts
+  const bool dense = p.dense(), batched = p.batched();
+  c->zil_last = p.zil;
   int rc;
   // The fixed launches around the T iterations.  Behind k_row2 (the small-batch
   // path) the iters writes ride on row launches the decode makes anyway: -1
@@ -383,40 +377,39 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   // off the final estimate's buffer is known here: without beta0 the ping-pong
   // starts on the side that ends in d_beta, and k_beta_final is launched only
   // where the estimate ends in d_beta2.
-  const bool it_row = !dense && !batched && row_sets_iters(c) && T > 0;
-  const bool bzero = !has_b0 && !dense && !batched && sec2 && (c->sec3 || c->sec4) && T > 0;
+  const bool it_row = p.it_row() && T > 0;
+  const bool bzero = !has_b0 && p.bzero() && T > 0;
   const int flip = (bzero && !es) ? (T & 1) : 0;  // beta0 lies in d_beta: no choice of side
   if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
   if (has_b0) {
     if (dense) {
-      if ((rc = dense_start<real>(c, B, G))) return rc;
-    } else {
-      if ((rc = launch_sec<real>(c, B, SEC_AB, 0, 0))) return rc;
-      if ((rc = launch_row<real>(c, B, ROW_INIT, 0, 0, c->G, c->G, 0, nullptr, nullptr, it_row ? -1 : 0))) return rc;
+      if ((rc = dense_start<real>(c, p, B))) return rc;
+    } else {  // A beta0 by k_sec: its c->G partials, whatever the loop's producer
+      if ((rc = launch_sec<real>(c, p, B, SEC_AB, 0, 0))) return rc;
+      if ((rc = launch_row<real>(c, p, B, ROW_INIT, 0, 0, c->G, c->G, it_row ? -1 : 0))) return rc;
     }
   } else {
     if (!bzero) {
       const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
       k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, ln.stream>>>((uint32_t*)ln.d_beta, 0u, nw);
     }
-    if ((rc = launch_row<real>(c, B, ROW_INIT0, 0, 0, G, Gb, 0, nullptr, nullptr, it_row ? -1 : 0))) return rc;
+    if ((rc = launch_row<real>(c, p, B, ROW_INIT0, 0, 0, p.G, p.Gb, it_row ? -1 : 0))) return rc;
   }
   for (int t = 0; t < T; ++t) {
     if (dense) {
-      if ((rc = dense_iter<real>(c, B, t, es, G))) return rc;
+      if ((rc = dense_iter<real>(c, p, B, t, es))) return rc;
     } else if (batched) {
-      if ((rc = launch_secb<real>(c, B, t, es))) return rc;
+      if ((rc = launch_secb<real>(c, p, B, t, es))) return rc;
     } else {
       void* pin = ((t ^ flip) & 1) ? ln.d_beta2 : ln.d_beta;
       void* pout = ((t ^ flip) & 1) ? ln.d_beta : ln.d_beta2;
-      if (sec2) {
-        if ((rc = launch_sec2<real>(c, B, t, es, pin, pout, pt, bzero && t == 0))) return rc;
-      } else if ((rc = launch_sec<real>(c, B, SEC_AMP, t, es, pin, pout))) {
+      if (p.multiwave()) {
+        if ((rc = launch_sec2<real>(c, p, B, t, es, pin, pout, bzero && t == 0))) return rc;
+      } else if ((rc = launch_sec<real>(c, p, B, SEC_AMP, t, es, pin, pout))) {
         return rc;
       }
     }
-    if ((rc = launch_row<real>(c, B, ROW_AMP, t, es, G, Gb, pt, nullptr, nullptr, it_row && t == T - 1 ? T : 0)))
-      return rc;
+    if ((rc = launch_row<real>(c, p, B, ROW_AMP, t, es, p.G, p.Gb, it_row && t == T - 1 ? T : 0))) return rc;
   }
   if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, ln.stream>>>(ln.d_iters, B, T);
   HIP_TRY(hipGetLastError());
@@ -475,21 +468,8 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const auto key = std::make_tuple(B, T, flags | (c->pb_on ? 0x10000 : 0), has_b0);
   auto it = ln.graphs.find(key);
   if (it == ln.graphs.end()) {
-    hipGraph_t g = nullptr;
-    HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
-    int rc = seq_amp<real>(c, B, T, flags, has_b0);
-    hipGraph_t cap = nullptr;
-    hipError_t e = hipStreamEndCapture(ln.stream, &cap);
-    if (rc) {
-      if (cap) (void)hipGraphDestroy(cap);
-      return rc;
-    }
-    if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    g = cap;
     hipGraphExec_t ex = nullptr;
-    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) return fail(SA_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    if (int rc = capture_graph(ln.stream, [&] { return seq_amp<real>(c, B, T, flags, has_b0); }, &ex)) return rc;
     it = ln.graphs.emplace(key, ex).first;
   }
   HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
@@ -1136,7 +1116,6 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
   c->NZh = (n + 15) / 16;
   c->NZ4 = (n + 255) / 256;
   c->NZ2 = (n + 127) / 128;
-  c->nz_cur = c->NZ;
   // section kernel LDS: z slots + 4 sections x M + 4 beta^2 partials
   const size_t s = rsz(c);
   const size_t zbytes = ((size_t)(n + 1) * s + 15) / 16 * 16;
@@ -1663,18 +1642,14 @@ int sa_decide_collect(sa_ctx* c, int B, int slot, int32_t* idx_out) {
 
 int sa_plan(sa_ctx* c, int B, int64_t* o) {
   if (check_ctx(c) || !o || B <= 0) return fail(SA_ERR_ARG, "sa_plan: bad arguments");
-  const bool dense = is_dense(c);
-  const bool batched = !dense && use_batched(c, B);
-  const bool sec2 = use_sec2(c, B);
-  const bool i8 = use_i8(c, B);
-  const bool fg = use_fgemm(c, B);
-  o[0] = i8 ? 6 : (fg ? 7 : (dense ? 3 : (batched ? 2 : (sec2 ? (c->sec3 ? 5 : (c->sec4 ? 4 : 1)) : (c->big ? 8 : 0)))));
-  o[1] = dense ? dense_parts(c, B) : (batched ? c->Gb : (sec2 ? sec2_parts(c) : c->G));
-  o[2] = (!dense && !batched && !sec2) ? row_splits(c, B) : 1;
-  o[3] = batched ? c->CB : 1;
-  o[4] = nz_for(c, row_kind_for(c, B));
+  const Plan p = plan_for(c, B);
+  o[0] = p.sec;
+  o[1] = p.G;
+  o[2] = (p.sec == SA_SEC_K_SEC || p.sec == SA_SEC_K_SECG) ? p.rs : 1;  // the loop's k_sec / k_secg launches
+  o[3] = p.CB;
+  o[4] = p.nz;
   o[5] = c->w;
-  o[6] = row_kind_for(c, B);
+  o[6] = p.row;
   o[7] = c->n_cus;
   return SA_OK;
 }

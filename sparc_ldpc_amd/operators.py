@@ -300,8 +300,10 @@ class SparcOperator:
         check(self._lib.sa_fetch(self._ctx, B, None, it.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int))))
         return it
 
+    # indexed by sparc_amp.h's SA_SEC_* / SA_ROW_* (sa_plan's out8[0] / out8[6])
     SECTION_KERNELS = ("k_sec", "k_sec2", "k_secb", "dense", "k_sec4", "k_sec43", "dense_mfma", "matrix_mfma",
                        "k_secg")
+    ROW_KERNELS = ("k_row", "k_row2", "k_rowv16B", "k_rowv8B", "k_row2_16", "k_rowc")
 
     def fetch_z(self, B):
         """Residual z after the last decode's final iteration, (B, n)."""
@@ -322,7 +324,7 @@ class SparcOperator:
         check(self._lib.sa_plan(self._ctx, int(B), o.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int64))))
         return dict(section_kernel=self.SECTION_KERNELS[int(o[0])], partials=int(o[1]), row_splits=int(o[2]),
                     codewords_per_wg=int(o[3]), zz_partials=int(o[4]), w=int(o[5]),
-                    row_kernel={1: "k_row2", 2: "k_rowv16B", 3: "k_rowv8B", 4: "k_row2_16", 5: "k_rowc"}.get(int(o[6]), "k_row"), cus=int(o[7]))
+                    row_kernel=self.ROW_KERNELS[int(o[6])], cus=int(o[7]))
 
     # ---- Monte-Carlo rep stream (sa_mc_stage / sa_mc_run) -------------------
     def mc_supported(self, B):

@@ -887,18 +887,20 @@ def test_cached_operator_two_powers(sp, prec):
 
 
 def test_row16_general_loop_for_kernel_partials(sp):
-    """k_row2 in 16-row blocks after a one-codeword decode must still read the
-    [G][n] partials of k_sec (sa_Ab; the beta0 start) through its general
-    loop: at ceil(L / 4) = 256 partials (L = 1024) its constant-stride fast
-    path, which assumes row-block-major partials, used to be taken (ADVICE r03
-    high).  Ab(beta) and a beta0 decode against the oracle."""
+    """k_row2 in 16-row blocks must read the [G][n] partials of k_sec (the
+    beta0 start) through its general loop: at ceil(L / 4) = 256 partials
+    (L = 1024) its constant-stride fast path, which assumes row-block-major
+    partials, used to be taken, by sa_Ab too while its row
+    step ran the last decode's row kernel.  sa_Ab's row step is k_row now
+    whatever ran before: Ab(beta) behind a one-codeword decode, and a beta0
+    decode, against the oracle."""
     L, M, n, P = 1024, 256, 4096, 4.0
     op = sp.SparcOperator(L, M, n, sp.make_ordering(L, M, n), precision="fp32")
     assert op.plan(1)["row_kernel"] == "k_row2_16"
     oAb, oAz, _ = orc.sparc_transforms(L, M, n)
     Pl = P / L * np.ones(L)
     _, y = orc.rep_inputs(L, M, n, Pl, 0.8, oAb, 41)
-    b1, _ = op.amp_batch(y.reshape(1, -1), Pl, 3, early_stop=False)  # leaves row_kind = 16-row k_row2
+    b1, _ = op.amp_batch(y.reshape(1, -1), Pl, 3, early_stop=False)  # a 16-row k_row2 decode in front of sa_Ab
     ref3 = orc._amp_core(y.reshape(-1, 1), Pl, L, M, 3, oAb, oAz, None, early_stop=False)[0]
     assert rel(b1[0], ref3) <= TOL["fp32"]
     rs = np.random.RandomState(3)
@@ -908,6 +910,37 @@ def test_row16_general_loop_for_kernel_partials(sp):
     bb, _ = op.amp_batch(y.reshape(1, -1), Pl, 2, beta0=b0.reshape(1, -1), early_stop=False)
     ref = orc._amp_core(y.reshape(-1, 1), Pl, L, M, 2, oAb, oAz, b0, early_stop=False)[0]
     assert rel(bb[0], ref) <= TOL["fp32"]
+
+
+@pytest.mark.parametrize("backend,prec,L,M,n,Bb,row1,secb,rowb", [
+    ("hadamard", "fp32", 128, 256, 1024, 8, "k_row2_16", "k_secb", "k_rowc"),
+    ("hadamard", "fp64", 128, 256, 1024, 8, "k_row2", "k_secb", "k_rowc"),
+    ("dense", "fp32", 32, 64, 192, 4, "k_row2", "dense_mfma", "k_row2")])
+def test_Ab_independent_of_decode_history(sp, backend, prec, L, M, n, Bb, row1, secb, rowb):
+    """sa_Ab is a function of its inputs: the same batch on a fresh operator,
+    behind a one-codeword decode (k_row2 / 16-row k_row2) and behind a batched
+    decode (k_secb + k_rowc; dense backend: the int8 GEMM path) gives the
+    same bits, within TOL of the oracle.  Its row step is k_row always; it
+    used to run the row kernel the last decode left, whose sum has another
+    order."""
+    op = sp.SparcOperator(L, M, n, sp.make_ordering(L, M, n), backend=backend, precision=prec)
+    assert op.plan(1)["row_kernel"] == row1  # (else the test is vacuous)
+    assert (op.plan(Bb)["section_kernel"], op.plan(Bb)["row_kernel"]) == (secb, rowb)
+    oAb, _, _ = orc.sparc_transforms(L, M, n)
+    Pl = 2.0 / L * np.ones(L)
+    ys = np.stack([orc.rep_inputs(L, M, n, Pl, 0.6, oAb, 500 + i)[1].reshape(-1) for i in range(Bb)])
+    x = np.random.RandomState(3).randn(3, L * M)
+    a0 = op.Ab_batch(x)
+    op.amp_batch(ys[:1], Pl, 3, early_stop=False)
+    a1 = op.Ab_batch(x)
+    op.amp_batch(ys, Pl, 3, early_stop=False)
+    ab = op.Ab_batch(x)
+    ref = np.stack([oAb(x[i].reshape(-1, 1)).reshape(-1) for i in range(3)])
+    print(f"rel(a0, oracle) = {rel(a0, ref):.3e}; max |a1 - a0| = {np.abs(a1 - a0).max():.3e}; "
+          f"max |ab - a0| = {np.abs(ab - a0).max():.3e}")
+    assert np.array_equal(a1, a0)
+    assert np.array_equal(ab, a0)
+    assert rel(a0, ref) <= TOL[prec]
 
 
 def test_fetch_z_layout_follows_every_run(sp):
