@@ -130,6 +130,23 @@ int lb_encode(lb_ctx* ctx, int B, const unsigned char* u, unsigned char* x);
 int lb_mc_run(lb_ctx* ctx, int nblk, const unsigned char* u, const double* w, double a, int kind, int batch,
               int algo, double corr_factor, int max_iter, int* errs, int* iters);
 
+/* lb_mc_run with every batch's bits and noise drawn on the device from the
+ * blocks' seeds (NumPy's legacy generator, one workgroup per block), on the
+ * context's stream in front of the encoder: only the seeds go up.  K: the
+ * bits drawn per block, Nv - Nc (encoded; needs lb_mc_set_code) or 0 (the
+ * all-zero word, no randint).  The bits and the random_sample values (kind 1)
+ * are bit for bit lb_draw_blocks'; the randn values (kind 0) are its values up
+ * to the device library's log against the C library's (both within an ulp: a
+ * few values in a thousand differ, by under 2^-49 relative).
+ *
+ * lb_draw_blocks_device: the same kernel with the arrays copied back, the
+ * device twin of lb_draw_blocks (u[nblk][K], w[nblk][N], host arrays; any K
+ * and N).  Blocking. */
+int lb_mc_run_seeds(lb_ctx* ctx, int nblk, const unsigned int* seeds, int K, double a, int kind, int batch,
+                    int algo, double corr_factor, int max_iter, int* errs, int* iters);
+int lb_draw_blocks_device(lb_ctx* ctx, const unsigned int* seeds, int nblk, int K, int N, int kind,
+                          unsigned char* u, double* w);
+
 int lb_device_count(void);
 const char* lb_last_error(void);
 const char* lb_version(void);

@@ -351,6 +351,21 @@ int sa_draw_reps(const uint32_t* seeds, int count, int L, int M, int n, double s
 int sa_mc_stage(sa_ctx* ctx, int nreps, const int32_t* idx, const double* noise);
 int sa_mc_run(sa_ctx* ctx, int B, int T, int flags, int32_t* dec_out, int32_t* iters_out, int32_t* errs_out,
               double* ms_out);
+/* sa_mc_draw stages `nreps` reps drawn on the device from their seeds: rep i
+ * is sa_draw_reps' rep of seeds[i] at sigma[i] (one sigma per rep, so the
+ * points of a sweep share a stream), NumPy's legacy generator run by one
+ * workgroup per rep.  Only the seeds and sigmas go up.  The section indices
+ * are bit for bit the host's; the noise is the host's up to the device
+ * library's log against the C library's (both within an ulp: a few values in
+ * a thousand differ, by under 2^-49 relative).  M must be a power of two
+ * (randint(0, M) then rejects no draw), else SA_ERR_UNSUPPORTED.  Afterwards
+ * sa_mc_run decodes the reps as after sa_mc_stage.  ms_out: the device time of
+ * the draw (events), or NULL.  Blocking.
+ *
+ * sa_mc_fetch_draws reads the first `nreps` staged reps back, whichever call
+ * staged them: idx_out [nreps][L], noise_out [nreps][n]; either may be NULL. */
+int sa_mc_draw(sa_ctx* ctx, int nreps, const uint32_t* seeds, const double* sigma, double* ms_out);
+int sa_mc_fetch_draws(sa_ctx* ctx, int nreps, int32_t* idx_out, double* noise_out);
 /* The design's row sub-sampling table (sparc_ldpc.py:107-117): NumPy's
  * RandomState(seed) shuffling arange(1, w) once per section, cumulatively,
  * the first n of each kept, w = 2^ceil(log2(max(M+1, n+1))); out [L][n]. */

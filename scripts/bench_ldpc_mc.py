@@ -5,7 +5,13 @@ sigma = sqrt(1 / (2 * 10**(5.33/20))): exactly 8192 blocks each (MIN_ERRORS out
 of reach, MAX_BLOCKS = 8192), batch 1024.  One warm-up of each, then the two
 alternate three times in one process; every wall time is taken around a device
 synchronise.  Prints one JSON line and writes it to results/ldpc_mc.json
-(or --out): medians, spread, blocks/s, and the new path's split."""
+(or --out): medians, spread, blocks/s, and the new path's split.
+
+--draws device: the same protocol for sim_ldpc_mc with host draws against
+sim_ldpc_mc(draws="device") (the blocks drawn on the GPU from their seeds), five
+alternating rounds after a warm-up of each, written to
+results/ldpc_mc_draws.json.  The bar: every device-draw run below every
+host-draw run."""
 import argparse
 import json
 import os
@@ -23,8 +29,12 @@ BLOCKS, BATCH, REPS = 8192, 1024, 3
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "results", "ldpc_mc.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--draws", default=None, choices=["device"],
+                    help="time sim_ldpc_mc's host draws against its device draws instead")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "results", "ldpc_mc_draws.json" if args.draws else "ldpc_mc.json")
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import ldpc
     lib = ldpc.load_bp_library()
@@ -43,16 +53,19 @@ def main():
         sync()
         return time.perf_counter() - t0, ber
 
-    def new(seed0):
+    def new(seed0, draws="host"):
         tm = {}
+        kw = {} if draws == "host" else {"draws": draws}
         sync()
         t0 = time.perf_counter()
-        r = sp.sim_ldpc_mc(lp, sigma, MIN_ERRORS=never, MAX_BLOCKS=BLOCKS, seed0=seed0, batch=BATCH, timings=tm)
+        r = sp.sim_ldpc_mc(lp, sigma, MIN_ERRORS=never, MAX_BLOCKS=BLOCKS, seed0=seed0, batch=BATCH, timings=tm, **kw)
         sync()
         wall = time.perf_counter() - t0
         assert r["blocks"] == BLOCKS
         return wall, r, tm
 
+    if args.draws:
+        return draws_leg(args, new, sigma)
     old(1)
     new(1)
     t_old, t_new, bers_old, res_new, splits = [], [], [], [], []
@@ -82,6 +95,35 @@ def main():
     line = json.dumps(out)
     print(line)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+def draws_leg(args, new, sigma):
+    rounds = 5
+    new(1, "host")
+    new(1, "device")
+    runs = {"host": [], "device": []}
+    for k in range(rounds):
+        for draws in ("host", "device"):
+            w, r, tm = new(100_000 * (k + 1), draws)
+            runs[draws].append(dict(wall_s=w, draw_s=tm["draw_s"], device_ms=tm["device_ms"],
+                                    rest_s=w - tm["device_ms"] / 1e3, ber=r["ber"], block_errors=r["block_errors"],
+                                    nit_total=r["nit_total"]))
+    med = {d: statistics.median(x["wall_s"] for x in runs[d]) for d in runs}
+    out = dict(
+        workload="802.16 5/6 z=192, sigma=%.6f, %d blocks, batch %d" % (sigma, BLOCKS, BATCH),
+        host_draws=dict(runs=runs["host"], median_s=med["host"], blocks_per_s=BLOCKS / med["host"]),
+        device_draws=dict(runs=runs["device"], median_s=med["device"], blocks_per_s=BLOCKS / med["device"]),
+        split_note="device_ms: events around the whole run (host draws: encode + BP + count; device draws: the "
+                   "draw kernels too); draw_s: the host draws' wall time, in a worker thread (0 for device draws); "
+                   "rest_s: wall minus device time",
+        speedup=med["host"] / med["device"],
+        bar_every_device_run_below_every_host_run=bool(
+            max(x["wall_s"] for x in runs["device"]) < min(x["wall_s"] for x in runs["host"])),
+    )
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         fh.write(json.dumps(out, indent=1) + "\n")
 

@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="codewords per batch (default 64; l768: 256 slots)")
     ap.add_argument("--no-stream", dest="stream", action="store_false",
                     help="l768: decode batch by batch instead of one refilled stream")
+    ap.add_argument("--draws", default="host", choices=["host", "device"],
+                    help="l768 stream: draw the reps on the host cores (default) or on the device from their seeds")
     ap.add_argument("--out", default="gpurun_out/waterfall")
     ap.add_argument("--precision", default=None, help="fp32 | fp64 (default: fp32 plain sweeps, fp64 joint)")
     args = ap.parse_args()
@@ -126,8 +128,11 @@ def main():
         seeds = [[j for j in range(i * 100000, i * 100000 + reps) if j % world == rank] for i in range(len(sigmas))]
         cnt = [len(s) for s in seeds]
         off = np.concatenate([[0], np.cumsum(cnt)])
-        idx = np.empty((off[-1], L), dtype=np.int32)
-        noise = np.empty((off[-1], n))
+        dev_draws = args.draws == "device"
+        if dev_draws and not args.stream:
+            ap.error("--draws device decodes the reps as one stream")
+        idx = None if dev_draws else np.empty((off[-1], L), dtype=np.int32)
+        noise = None if dev_draws else np.empty((off[-1], n))
         drawn = {}
 
         def draw_all():  # the native draws release the GIL: they run beside the operator set-up
@@ -137,7 +142,7 @@ def main():
             drawn["s"] = time.time() - t
 
         import threading
-        drawer = threading.Thread(target=draw_all) if args.stream else None
+        drawer = threading.Thread(target=draw_all) if args.stream and not dev_draws else None
         if drawer is not None:
             drawer.start()
         ta = time.time()
@@ -149,7 +154,22 @@ def main():
         tc = time.time()
         if drawer is not None:
             drawer.join()
-        if args.stream and op.mc_supported(args.batch):
+        if dev_draws:
+            # every point's reps in ONE stream, drawn on the device: only seeds and sigmas go up
+            if not op.mc_supported(args.batch):
+                ap.error("--draws device needs the stream (mc_supported)")
+            t2 = time.time()
+            phases = {}
+            all_seeds = [s for pt in seeds for s in pt]
+            all_sigma = np.repeat(sigmas, cnt)
+            be_all, it_all, dev_ms = sp.mc_stream_seeds(op, Pl, T, all_seeds, all_sigma, batch=args.batch,
+                                                        timings=phases)
+            t3 = time.time()
+            parts = [(be_all[off[i]:off[i + 1]], it_all[off[i]:off[i + 1]]) for i in range(len(sigmas))]
+            split = dict(ordering_s=tb - ta, operator_s=tc - tb, draws="device", draw_device_ms=phases["draw_ms"],
+                         stream_s=t3 - t2, stream_phases=phases, decode_device_ms=dev_ms, batch=args.batch,
+                         codeword_iterations=int(it_all.sum()), slot_iterations=int(np.minimum(it_all + 1, T).sum()))
+        elif args.stream and op.mc_supported(args.batch):
             # every point's reps in ONE stream through the refilled slots (AMP
             # never reads sigma: it is in the noise), drawn natively on the host
             t2 = time.time()

@@ -12,14 +12,14 @@ from .operators import (SparcOperator, AbOp, AzOp, make_ordering, sub_fht, block
                         sparc_transforms, sparc_transforms_shorter, default_device)
 from .amp import amp, amp_test, amp_batch, operator_of
 from .harness import (SPARCParams, LDPCParams, pa_parameterised, bits2indices, ber_of,
-                      amp_ldpc_sim, mc_decode, mc_decode_batched, mc_stream, draw_reps, ebno_to_sigma, ber_point, waterfall_plain,
+                      amp_ldpc_sim, mc_decode, mc_decode_batched, mc_stream, mc_stream_seeds, draw_reps, ebno_to_sigma, ber_point, waterfall_plain,
                       amp_test_reps, amp_init_test)
 from . import ldpc
 from .ldpc import code, LdpcBpError
 from .joint import (JointDecoder, joint_decoder, soft_amp_ldpc_sim, hardinitbeta_amp_ldpc_sim, sim_ldpc, soft_hard_plot,
                     waterfall, sp2bp, bp2sp, mc_joint)
 from . import ldpc_mc, ldpc_awgn, ldpc_bsc
-from .ldpc_mc import draw_blocks, mc_ldpc, sim_ldpc_mc
+from .ldpc_mc import draw_blocks, draw_blocks_device, mc_ldpc, sim_ldpc_mc
 from . import threshold
 from .threshold import (hard_initialisation, prep_y, calc_E, hist_E, calc_I_e, J, J_inverse,
                         soft_amp_ldpc_hardinit, ber_from_LLRs, soft_hardinit_plot, calc_E_batch, amp_exit_curve)

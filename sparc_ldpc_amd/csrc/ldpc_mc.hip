@@ -18,6 +18,10 @@
 //  * lb_mc_run: the blocks in batches; the next batch's bits and noise go up
 //    on a second stream through a second pinned staging buffer while the
 //    current batch is encoded, decoded and counted.
+//  * lb_mc_run_seeds / lb_draw_blocks_device: the blocks drawn on the device
+//    from their seeds (k_mc_draw_blocks, legacy_mt_dev.h: one workgroup per
+//    block) on the context's stream, in front of k_mc_prep; only the seeds go
+//    up, through no staging buffer and no second stream.
 
 #include <algorithm>
 #include <cmath>
@@ -27,6 +31,7 @@
 
 #include "ldpc_bp_int.h"
 #include "legacy_mt.h"
+#include "legacy_mt_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -34,7 +39,11 @@ struct lb_mc {
   int Mp = 0, Np = 0, z = 0;  // base matrix shape and lifting size; Mp == 0: no encoder
   int off = 0;                // the single offset column Kp's shifts reduce to
   int* d_proto = nullptr;     // [Mp][Np] shifts mod z, -1: no block
-  int cap = 0;                // words the staging buffers hold
+  int cap = 0;                // words the device staging buffers (d_u, d_w, d_x) hold
+  int hcap = 0;               // words the pinned staging buffers hold
+  uint32_t* d_seeds = nullptr;  // lb_mc_run_seeds: the blocks' seeds [capSeeds]
+  int* d_err = nullptr;         // the device generator's error flag
+  int capSeeds = 0;
   uint8_t* h_u[2] = {nullptr, nullptr};  // pinned staging, two batches
   double* h_w[2] = {nullptr, nullptr};
   uint8_t* d_u[2] = {nullptr, nullptr};
@@ -149,14 +158,47 @@ __global__ void __launch_bounds__(kCountThreads) k_mc_count(const double* app, c
 double (*volatile libm_pow)(double, double) = static_cast<double (*)(double, double)>(::pow);
 double (*volatile libm_log)(double) = static_cast<double (*)(double)>(::log);
 
-void free_staging(lb_mc* m) {
+// Rep-for-rep lb_draw_blocks on the device (legacy_mt_dev.h): block b draws
+// RandomState(seeds[b]).randint(0, 2, K) into u[b] (word k & 1), then randn(N)
+// (kind 0) or random_sample(N) (kind 1) into w[b].  A block whose randn runs
+// into the chunk cap sets *err.
+__global__ void __launch_bounds__(legacy_rng_dev::kThreads) k_mc_draw_blocks(const uint32_t* __restrict__ seeds,
+                                                                             int K, int N, int kind,
+                                                                             uint8_t* __restrict__ u,
+                                                                             double* __restrict__ w, int max_chunks,
+                                                                             int* err) {
+  __shared__ legacy_rng_dev::State st;
+  const int b = blockIdx.x;
+  legacy_rng_dev::seed_state(st, seeds[b]);
+  int have = 0;
+  uint8_t* ub = u + (size_t)b * K;
+  legacy_rng_dev::draw_masked(st, have, K, 1u, [&](int k, uint32_t v) { ub[k] = (uint8_t)v; });
+  double* wb = w + (size_t)b * N;
+  if (kind == 0) {
+    const bool ok = legacy_rng_dev::draw_randn(st, have, K, N, false, 1.0, wb, max_chunks);
+    if (!ok && threadIdx.x == 0) *err = 1;
+  } else {
+    legacy_rng_dev::draw_samples(st, have, K, N, wb);
+  }
+}
+
+void free_pinned(lb_mc* m) {
   for (int i = 0; i < 2; ++i) {
     if (m->h_u[i]) (void)hipHostFree(m->h_u[i]);
     if (m->h_w[i]) (void)hipHostFree(m->h_w[i]);
+    m->h_u[i] = nullptr;
+    m->h_w[i] = nullptr;
+  }
+  m->hcap = 0;
+}
+
+void free_staging(lb_mc* m) {
+  free_pinned(m);
+  for (int i = 0; i < 2; ++i) {
     (void)hipFree(m->d_u[i]);
     (void)hipFree(m->d_w[i]);
-    m->h_u[i] = m->d_u[i] = nullptr;
-    m->h_w[i] = m->d_w[i] = nullptr;
+    m->d_u[i] = nullptr;
+    m->d_w[i] = nullptr;
   }
   (void)hipFree(m->d_x);
   m->d_x = nullptr;
@@ -180,28 +222,46 @@ int ensure_state(lb_ctx* c) {
 }
 
 // staging for `B` words: two pinned and two device buffers of bits and noise, the codeword bits
-int ensure_staging(lb_ctx* c, int B) {
+int ensure_staging(lb_ctx* c, int B, bool pinned = true) {
   lb_mc* m = c->mc;
-  if (B <= m->cap) return LB_OK;
-  free_staging(m);
   const size_t K = (size_t)(c->Nv - c->Nc), N = (size_t)c->Nv;
   int rc;
-  for (int i = 0; i < 2; ++i) {
-    if (K > 0) {
-      if (hipHostMalloc((void**)&m->h_u[i], B * K, hipHostMallocDefault) != hipSuccess) {
+  if (B > m->cap) {
+    free_staging(m);
+    for (int i = 0; i < 2; ++i) {
+      if (K > 0 && (rc = lb::dev_alloc((void**)&m->d_u[i], B * K))) return rc;
+      if ((rc = lb::dev_alloc((void**)&m->d_w[i], B * N * sizeof(double)))) return rc;
+    }
+    if ((rc = lb::dev_alloc((void**)&m->d_x, B * N))) return rc;
+    m->cap = B;
+  }
+  if (pinned && B > m->hcap) {  // (the device-draw path stages nothing through the host)
+    free_pinned(m);
+    for (int i = 0; i < 2; ++i) {
+      if (K > 0 && hipHostMalloc((void**)&m->h_u[i], B * K, hipHostMallocDefault) != hipSuccess) {
         m->h_u[i] = nullptr;
         return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
       }
-      if ((rc = lb::dev_alloc((void**)&m->d_u[i], B * K))) return rc;
+      if (hipHostMalloc((void**)&m->h_w[i], B * N * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        m->h_w[i] = nullptr;
+        return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
+      }
     }
-    if (hipHostMalloc((void**)&m->h_w[i], B * N * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-      m->h_w[i] = nullptr;
-      return fail(LB_ERR_NOMEM, "hipHostMalloc failed");
-    }
-    if ((rc = lb::dev_alloc((void**)&m->d_w[i], B * N * sizeof(double)))) return rc;
+    m->hcap = B;
   }
-  if ((rc = lb::dev_alloc((void**)&m->d_x, B * N))) return rc;
-  m->cap = B;
+  return LB_OK;
+}
+
+// the seeds of lb_mc_run_seeds and the generator's error flag
+int ensure_seeds(lb_mc* m, int nblk) {
+  int rc;
+  if (!m->d_err && (rc = lb::dev_alloc((void**)&m->d_err, sizeof(int)))) return rc;
+  if (nblk <= m->capSeeds) return LB_OK;
+  (void)hipFree(m->d_seeds);
+  m->d_seeds = nullptr;
+  m->capSeeds = 0;
+  if ((rc = lb::dev_alloc((void**)&m->d_seeds, (size_t)nblk * sizeof(uint32_t)))) return rc;
+  m->capSeeds = nblk;
   return LB_OK;
 }
 
@@ -263,6 +323,8 @@ void mc_release(lb_ctx* c) {
   free_staging(m);
   (void)hipFree(m->d_proto);
   (void)hipFree(m->d_res);
+  (void)hipFree(m->d_seeds);
+  (void)hipFree(m->d_err);
   if (m->h_res) (void)hipHostFree(m->h_res);
   for (hipEvent_t e : {m->ev_up[0], m->ev_up[1], m->ev_prep[0], m->ev_prep[1]})
     if (e) (void)hipEventDestroy(e);
@@ -427,6 +489,104 @@ int lb_mc_run(lb_ctx* c, int nblk, const uint8_t* u, const double* w, double a, 
   HIP_TRY(hipStreamSynchronize(c->stream));
   std::memcpy(errs, m->h_res, (size_t)nblk * sizeof(int));
   std::memcpy(iters, m->h_res + nblk, (size_t)nblk * sizeof(int));
+  return LB_OK;
+}
+
+int lb_mc_run_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a, int kind, int batch, int algo,
+                    double corr, int max_iter, int* errs, int* iters) {
+  if (!c) return fail(LB_ERR_ARG, "lb_mc_run_seeds: null context");
+  if (nblk < 0 || batch <= 0 || (kind != 0 && kind != 1) || (nblk > 0 && (!seeds || !errs || !iters)))
+    return fail(LB_ERR_ARG, "lb_mc_run_seeds: bad arguments");
+  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0))
+    return fail(LB_ERR_ARG, "lb_mc_run_seeds: sigma must be > 0, p in (0, 1)");
+  if (K != 0 && K != c->Nv - c->Nc) return fail(LB_ERR_ARG, "lb_mc_run_seeds: K must be Nv - Nc, or 0 for no bits");
+  const bool enc = K > 0;
+  if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_run_seeds: the BSC sends the all-zero word (K must be 0)");
+  if (enc && (!c->mc || c->mc->Mp == 0))
+    return fail(LB_ERR_ARG, "lb_mc_run_seeds: no encoder set (lb_mc_set_code)");
+  if (nblk == 0) return LB_OK;
+  batch = std::min(batch, nblk);
+  HIP_TRY(hipSetDevice(c->dev));
+  int rc;
+  if ((rc = ensure_state(c))) return rc;
+  if ((rc = lb::ensure_io(c, batch))) return rc;
+  if ((rc = ensure_staging(c, batch, false))) return rc;
+  lb_mc* m = c->mc;
+  if ((rc = ensure_results(m, nblk))) return rc;
+  if ((rc = ensure_seeds(m, nblk))) return rc;
+  const int N = c->Nv;
+  PrepArgs p{};
+  fill_prep(p, c, enc);
+  p.ch = c->d_ch;
+  p.x = m->d_x;
+  p.kind = kind;
+  p.a = a;
+  p.c0 = kind == 0 ? 2.0 / libm_pow(a, 2.0) : libm_log((1.0 - a) / a);
+  p.u = m->d_u[0];
+  p.w = m->d_w[0];
+  const int cap = legacy_rng_dev::randn_chunk_cap(N);
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  HIP_TRY(hipMemcpyAsync(m->d_seeds, seeds, (size_t)nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(m->d_err, 0, sizeof(int), c->stream));
+  // one stream: a batch's draw follows the prep kernel that read the last one's
+  for (int b0 = 0; b0 < nblk; b0 += batch) {
+    const int B = std::min(batch, nblk - b0);
+    hipLaunchKernelGGL(k_mc_draw_blocks, dim3(B), dim3(legacy_rng_dev::kThreads), 0, c->stream, m->d_seeds + b0, K,
+                       N, kind, m->d_u[0], m->d_w[0], cap, m->d_err);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), c->stream, p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr, max_iter, false))) return rc;
+    hipLaunchKernelGGL(k_mc_count, dim3(B), dim3(kCountThreads), 0, c->stream, c->d_app, m->d_x, c->d_it, N,
+                       m->d_res + b0, m->d_res + nblk + b0);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, m->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(m->h_res, m->d_res, (size_t)2 * nblk * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (err) return fail(LB_ERR_HIP, "lb_mc_run_seeds: a block's randn ran into the chunk cap");
+  std::memcpy(errs, m->h_res, (size_t)nblk * sizeof(int));
+  std::memcpy(iters, m->h_res + nblk, (size_t)nblk * sizeof(int));
+  return LB_OK;
+}
+
+int lb_draw_blocks_device(lb_ctx* c, const uint32_t* seeds, int nblk, int K, int N, int kind, uint8_t* u, double* w) {
+  if (!c) return fail(LB_ERR_ARG, "lb_draw_blocks_device: null context");
+  if (nblk < 0 || K < 0 || N < 0 || K > (1 << 27) || N > (1 << 27) || (kind != 0 && kind != 1) ||
+      (nblk > 0 && (!seeds || (K > 0 && !u) || (N > 0 && !w))))
+    return fail(LB_ERR_ARG, "lb_draw_blocks_device: bad arguments");
+  if (nblk == 0 || (K == 0 && N == 0)) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  struct Bufs {  // this call's own arrays, whatever N and K
+    uint32_t* seeds = nullptr;
+    uint8_t* u = nullptr;
+    double* w = nullptr;
+    int* err = nullptr;
+    ~Bufs() {
+      (void)hipFree(seeds);
+      (void)hipFree(u);
+      (void)hipFree(w);
+      (void)hipFree(err);
+    }
+  } d;
+  int rc;
+  if ((rc = lb::dev_alloc((void**)&d.seeds, (size_t)nblk * sizeof(uint32_t)))) return rc;
+  if (K > 0 && (rc = lb::dev_alloc((void**)&d.u, (size_t)nblk * K))) return rc;
+  if (N > 0 && (rc = lb::dev_alloc((void**)&d.w, (size_t)nblk * N * sizeof(double)))) return rc;
+  if ((rc = lb::dev_alloc((void**)&d.err, sizeof(int)))) return rc;
+  HIP_TRY(hipMemcpyAsync(d.seeds, seeds, (size_t)nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(d.err, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_mc_draw_blocks, dim3(nblk), dim3(legacy_rng_dev::kThreads), 0, c->stream, d.seeds, K, N, kind,
+                     d.u, d.w, legacy_rng_dev::randn_chunk_cap(N), d.err);
+  HIP_TRY(hipGetLastError());
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, d.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (K > 0) HIP_TRY(hipMemcpyAsync(u, d.u, (size_t)nblk * K, hipMemcpyDeviceToHost, c->stream));
+  if (N > 0) HIP_TRY(hipMemcpyAsync(w, d.w, (size_t)nblk * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (err) return fail(LB_ERR_HIP, "lb_draw_blocks_device: a block's randn ran into the chunk cap");
   return LB_OK;
 }
 

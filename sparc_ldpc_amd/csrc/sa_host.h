@@ -177,6 +177,11 @@ struct sa_ctx {
   int32_t *d_mc_idx = nullptr, *d_mc_dec = nullptr, *d_mc_its = nullptr;
   double* d_mc_noise = nullptr;
   void *d_mc_y = nullptr, *d_mc_zzp = nullptr;  // the staged reps encoded: y [mc_cap][n], z^2 partials [mc_cap][NZ2]
+  // sa_mc_draw: the reps' seeds and sigmas [mc_seed_cap], the generator's error flag
+  uint32_t* d_mc_seeds = nullptr;
+  double* d_mc_sigma = nullptr;
+  int* d_mc_err = nullptr;
+  int mc_seed_cap = 0;
   int* d_slots = nullptr;   // [4][slot_cap]: rep, t, done rep, fresh; then ctl {next, live, nreps}
   int slot_cap = 0;
   int* h_mc_live = nullptr;  // pinned ring of the live-slot counts the host polls

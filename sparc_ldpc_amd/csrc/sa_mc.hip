@@ -18,6 +18,7 @@
 //    decisions and stop index equal those of the batched decode (sa_run).
 #include "sa_host.h"
 #include "legacy_mt.h"
+#include "legacy_mt_dev.h"
 
 #include <thread>
 
@@ -284,6 +285,25 @@ __global__ void __launch_bounds__(256) k_mc_turnover(McArgs a, real* beta, int g
   else mc_fill_blocks<real, CB>(a, y_all, zzp_all, y, z, zzp, blockIdx.x - gto, gridDim.x - gto);
 }
 
+// Rep r drawn from its seed (legacy_mt_dev.h): RandomState(seeds[r])
+// .randint(0, M, L) into idx[r] (M a power of two: word l & (M - 1)), then
+// .randn(n) * sigma[r] into noise[r].  A rep whose randn runs into the chunk
+// cap sets *err.
+__global__ void __launch_bounds__(legacy_rng_dev::kThreads) k_mc_draw(const uint32_t* __restrict__ seeds,
+                                                                      const double* __restrict__ sigma,
+                                                                      int32_t* __restrict__ idx,
+                                                                      double* __restrict__ noise, int L, int M, int n,
+                                                                      int max_chunks, int* err) {
+  __shared__ legacy_rng_dev::State st;
+  const int rep = blockIdx.x;
+  legacy_rng_dev::seed_state(st, seeds[rep]);
+  int have = 0;
+  int32_t* ix = idx + (size_t)rep * L;
+  legacy_rng_dev::draw_masked(st, have, L, (uint32_t)(M - 1), [&](int l, uint32_t v) { ix[l] = (int32_t)v; });
+  const bool ok = legacy_rng_dev::draw_randn(st, have, L, n, true, sigma[rep], noise + (size_t)rep * n, max_chunks);
+  if (!ok && threadIdx.x == 0) *err = 1;
+}
+
 // ---- host side ------------------------------------------------------------------
 
 namespace {
@@ -362,6 +382,48 @@ int mc_ensure_slots(sa_ctx* c, int B) {
   return SA_OK;
 }
 
+// the staged reps' arrays sized for nreps (sa_mc_stage, sa_mc_draw)
+int mc_ensure_reps(sa_ctx* c, int nreps) {
+  if (nreps <= c->mc_cap) return SA_OK;
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
+  dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
+  dev_free(c->d_mc_y); dev_free(c->d_mc_zzp);
+  c->d_mc_idx = c->d_mc_dec = c->d_mc_its = nullptr;
+  c->d_mc_noise = nullptr;
+  c->d_mc_y = c->d_mc_zzp = nullptr;
+  c->mc_cap = 0;
+  graphs_clear(c->mc_graphs);  // they hold the old pointers
+  int rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_idx, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_dec, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
+  // stop indices, then the bit errors
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_its, 2 * (size_t)nreps * sizeof(int32_t)))) return rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_noise, (size_t)nreps * c->n * sizeof(double)))) return rc;
+  // the encoded reps (k_mc_encode): y [nreps][n] and z^2 partials [nreps][NZ2], in the context precision
+  if ((rc = dev_alloc(c, &c->d_mc_y, (size_t)nreps * c->n * rsz(c)))) return rc;
+  if ((rc = dev_alloc(c, &c->d_mc_zzp, (size_t)nreps * c->NZ2 * rsz(c)))) return rc;
+  c->mc_cap = nreps;
+  return SA_OK;
+}
+
+// the seeds, sigmas and error flag of sa_mc_draw, sized for nreps
+int mc_ensure_seeds(sa_ctx* c, int nreps) {
+  if (!c->d_mc_err) {
+    if (int rc = dev_alloc(c, (void**)&c->d_mc_err, sizeof(int))) return rc;
+  }
+  if (nreps <= c->mc_seed_cap) return SA_OK;
+  HIP_TRY(hipStreamSynchronize(c->at().stream));
+  dev_free(c->d_mc_seeds); dev_free(c->d_mc_sigma);
+  c->d_mc_seeds = nullptr;
+  c->d_mc_sigma = nullptr;
+  c->mc_seed_cap = 0;
+  int rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_seeds, (size_t)nreps * sizeof(uint32_t)))) return rc;
+  if ((rc = dev_alloc(c, (void**)&c->d_mc_sigma, (size_t)nreps * sizeof(double)))) return rc;
+  c->mc_seed_cap = nreps;
+  return SA_OK;
+}
+
 }  // namespace
 
 // (the stream's kernels use at most 64 KB of LDS: nothing to raise)
@@ -372,6 +434,11 @@ void mc_release(sa_ctx* c) {
   dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
   dev_free(c->d_mc_y); dev_free(c->d_mc_zzp);
   c->d_mc_y = c->d_mc_zzp = nullptr;
+  dev_free(c->d_mc_seeds); dev_free(c->d_mc_sigma); dev_free(c->d_mc_err);
+  c->d_mc_seeds = nullptr;
+  c->d_mc_sigma = nullptr;
+  c->d_mc_err = nullptr;
+  c->mc_seed_cap = 0;
   dev_free(c->d_slots);
   c->d_mc_idx = c->d_mc_dec = c->d_mc_its = nullptr;
   c->d_mc_noise = nullptr;
@@ -441,31 +508,62 @@ int sa_mc_stage(sa_ctx* c, int nreps, const int32_t* idx, const double* noise) {
     if (idx[i] < 0 || idx[i] >= c->M) return fail(SA_ERR_ARG, "sa_mc_stage: index outside [0, M)");
   HIP_TRY(hipSetDevice(c->device));
   lane_switch(c, 0);  // the stream and its graphs live with lane 0 (the batched decode's lane)
-  if (nreps > c->mc_cap) {
-    HIP_TRY(hipStreamSynchronize(c->at().stream));
-    dev_free(c->d_mc_idx); dev_free(c->d_mc_noise); dev_free(c->d_mc_dec); dev_free(c->d_mc_its);
-    dev_free(c->d_mc_y); dev_free(c->d_mc_zzp);
-    c->d_mc_idx = c->d_mc_dec = c->d_mc_its = nullptr;
-    c->d_mc_noise = nullptr;
-    c->d_mc_y = c->d_mc_zzp = nullptr;
-    c->mc_cap = 0;
-    graphs_clear(c->mc_graphs);  // they hold the old pointers
-    int rc;
-    if ((rc = dev_alloc(c, (void**)&c->d_mc_idx, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc(c, (void**)&c->d_mc_dec, (size_t)nreps * c->L * sizeof(int32_t)))) return rc;
-    // stop indices, then the bit errors
-    if ((rc = dev_alloc(c, (void**)&c->d_mc_its, 2 * (size_t)nreps * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc(c, (void**)&c->d_mc_noise, (size_t)nreps * c->n * sizeof(double)))) return rc;
-    // the encoded reps (k_mc_encode): y [nreps][n] and z^2 partials [nreps][NZ2], in the context precision
-    if ((rc = dev_alloc(c, &c->d_mc_y, (size_t)nreps * c->n * rsz(c)))) return rc;
-    if ((rc = dev_alloc(c, &c->d_mc_zzp, (size_t)nreps * c->NZ2 * rsz(c)))) return rc;
-    c->mc_cap = nreps;
-  }
+  if (int rc = mc_ensure_reps(c, nreps)) return rc;
   HIP_TRY(hipMemcpyAsync(c->d_mc_idx, idx, (size_t)nreps * c->L * sizeof(int32_t), hipMemcpyHostToDevice, c->at().stream));
   HIP_TRY(hipMemcpyAsync(c->d_mc_noise, noise, (size_t)nreps * c->n * sizeof(double), hipMemcpyHostToDevice,
                          c->at().stream));
   HIP_TRY(hipStreamSynchronize(c->at().stream));
   c->mc_nreps = nreps;
+  return SA_OK;
+}
+
+int sa_mc_draw(sa_ctx* c, int nreps, const uint32_t* seeds, const double* sigma, double* ms_out) {
+  if (int rc = check_tables(c, "sa_mc_draw")) return rc;
+  if (nreps <= 0 || !seeds || !sigma) return fail(SA_ERR_ARG, "sa_mc_draw: bad arguments");
+  // the legacy generator's bounded integers reject draws above M - 1 unless
+  // M - 1 is its own mask; the device generator takes draw l from word l
+  if (!c->pow2 || c->M < 2)  // (a padded section's c->M is not the caller's M)
+    return fail(SA_ERR_UNSUPPORTED, "sa_mc_draw: the device generator draws randint(0, M) for M a power of two only");
+  if (c->n > (1 << 27) || c->L > (1 << 27)) return fail(SA_ERR_UNSUPPORTED, "sa_mc_draw: n or L above 2^27");
+  HIP_TRY(hipSetDevice(c->device));
+  lane_switch(c, 0);  // as sa_mc_stage
+  int rc;
+  if ((rc = mc_ensure_reps(c, nreps))) return rc;
+  if ((rc = mc_ensure_seeds(c, nreps))) return rc;
+  c->mc_nreps = 0;  // until the draw has succeeded
+  sa_lane& ln = c->at();
+  HIP_TRY(hipMemcpyAsync(c->d_mc_seeds, seeds, (size_t)nreps * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
+  HIP_TRY(hipMemcpyAsync(c->d_mc_sigma, sigma, (size_t)nreps * sizeof(double), hipMemcpyHostToDevice, ln.stream));
+  HIP_TRY(hipMemsetAsync(c->d_mc_err, 0, sizeof(int), ln.stream));
+  HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
+  k_mc_draw<<<nreps, legacy_rng_dev::kThreads, 0, ln.stream>>>(c->d_mc_seeds, c->d_mc_sigma, c->d_mc_idx,
+                                                                c->d_mc_noise, c->L, c->M, c->n,
+                                                                legacy_rng_dev::randn_chunk_cap(c->n), c->d_mc_err);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, c->d_mc_err, sizeof(int), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
+  if (err) return fail(SA_ERR_HIP, "sa_mc_draw: a rep's randn ran into the chunk cap");
+  if (ms_out) {
+    float ms = -1.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ln.ev0, ln.ev1));
+    *ms_out = ms;
+  }
+  c->mc_nreps = nreps;
+  return SA_OK;
+}
+
+int sa_mc_fetch_draws(sa_ctx* c, int nreps, int32_t* idx_out, double* noise_out) {
+  if (check_ctx(c)) return SA_ERR_ARG;
+  if (nreps <= 0 || nreps > c->mc_nreps) return fail(SA_ERR_ARG, "sa_mc_fetch_draws: nreps outside the staged reps");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->lane[0].stream;
+  if (idx_out)
+    HIP_TRY(hipMemcpyAsync(idx_out, c->d_mc_idx, (size_t)nreps * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (noise_out)
+    HIP_TRY(hipMemcpyAsync(noise_out, c->d_mc_noise, (size_t)nreps * c->n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return SA_OK;
 }
 

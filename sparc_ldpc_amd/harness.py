@@ -24,7 +24,7 @@ from .operators import SparcOperator, make_ordering, sparc_transforms, sparc_tra
 
 __all__ = [
     "SPARCParams", "LDPCParams", "pa_parameterised", "bits2indices", "ber_of",
-    "amp_ldpc_sim", "mc_decode", "mc_decode_batched", "mc_stream", "draw_reps", "ebno_to_sigma", "ber_point", "waterfall_plain", "amp_test_reps", "amp_init_test",
+    "amp_ldpc_sim", "mc_decode", "mc_decode_batched", "mc_stream", "mc_stream_seeds", "draw_reps", "ebno_to_sigma", "ber_point", "waterfall_plain", "amp_test_reps", "amp_init_test",
 ]
 
 
@@ -184,7 +184,33 @@ def mc_stream(op: SparcOperator, Pl, T, idx, noise, batch=256, early_stop=True, 
     return errs.astype(np.int64), its.astype(np.int64), ms
 
 
-def mc_decode(op: SparcOperator, Pl, sigma, T, seeds, batch=256, early_stop=True, stream=None):
+def mc_stream_seeds(op: SparcOperator, Pl, T, seeds, sigma, batch=256, early_stop=True, timings=None):
+    """mc_stream on reps drawn on the device from their seeds
+    (SparcOperator.mc_draw): rep i is _draw_reps' rep of seeds[i] at sigma[i]
+    (a scalar sigma: every rep's), so only 4 bytes of seed and 8 of sigma go
+    up per rep.  The section indices are the host's bit for bit and the noise
+    is the host's up to the device library's log (a few values in a thousand
+    differ, by under 2**-49 relative); mc_fetch_draws returns what was
+    decoded.  Seeds outside [0, 2**32) raise ValueError.  Returns per-rep
+    int64 (bit_errors, iters) and the stream's device milliseconds;
+    ``timings`` (a dict) receives the host wall seconds of its phases and the
+    draw's device milliseconds."""
+    import time
+    from .operators import seed_array
+    seeds = seed_array(seeds)
+    t0 = time.perf_counter()
+    op.reserve(batch, T)
+    op.stage_power(batch, np.asarray(Pl, dtype=np.float64))
+    t1 = time.perf_counter()
+    draw_ms = op.mc_draw(seeds, sigma)
+    t2 = time.perf_counter()
+    _, its, errs, ms = op.mc_run(batch, T, early_stop=early_stop, decisions=False)
+    if timings is not None:
+        timings.update(setup_s=t1 - t0, stage_s=t2 - t1, run_s=time.perf_counter() - t2, draw_ms=draw_ms)
+    return errs.astype(np.int64), its.astype(np.int64), ms
+
+
+def mc_decode(op: SparcOperator, Pl, sigma, T, seeds, batch=256, early_stop=True, stream=None, draws="host"):
     """Monte-Carlo reps on one device (the rep body of sparc_ldpc.py:423-462
     on SURVEY §8d's synthetic inputs, ``_draw_reps``).  Returns per-rep int64
     arrays (bit_errors, iters) in seed order.
@@ -193,8 +219,24 @@ def mc_decode(op: SparcOperator, Pl, sigma, T, seeds, batch=256, early_stop=True
     reps drawn natively on the host cores (draw_reps) and decoded as one
     stream through ``batch`` refilled slots (mc_stream); else batch by batch
     (mc_decode_batched).  The per-rep results are the same either way
-    (tests/test_gpu_mc_stream.py)."""
+    (tests/test_gpu_mc_stream.py).
+
+    draws="device": the reps are drawn on the device from their seeds and
+    decoded as one stream (mc_stream_seeds); the operator must support the
+    stream and have M a power of two.  A rep whose device-drawn noise equals
+    the host's bit for bit has the host-draw result."""
+    if draws not in ("host", "device"):
+        raise ValueError('draws must be "host" or "device"')
     seeds = list(seeds)
+    if draws == "device":
+        from .operators import seed_array
+        seeds = seed_array(seeds)
+        if stream is not None and not stream:
+            raise ValueError('draws="device" decodes the reps as one stream')
+        if not len(seeds):
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        be, it, _ = mc_stream_seeds(op, Pl, T, seeds, sigma, batch, early_stop)
+        return be, it
     if stream is None:
         stream = op.mc_supported(batch)
     if not stream or not seeds:

@@ -34,7 +34,7 @@ EXPORTS = (
     "lb_create", "lb_destroy", "lb_decode", "lb_decode_device", "lb_stage", "lb_run", "lb_wait",
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
     "lb_buffers", "lb_set_tail",
-    "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run",
+    "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
 )
 
 _P, _I, _D = ct.c_void_p, ct.c_int, ct.POINTER(ct.c_double)
@@ -65,6 +65,9 @@ _SIG = {
     "lb_mc_set_code": (_I, [_P, _IP, _I, _I, _I]),
     "lb_encode": (_I, [_P, _I, _U8, _U8]),
     "lb_mc_run": (_I, [_P, _I, _U8, _D, ct.c_double, _I, _I, _I, ct.c_double, _I, _IP, _IP]),
+    "lb_mc_run_seeds": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _I, ct.c_double, _I, _I, _I, ct.c_double, _I, _IP,
+                             _IP]),
+    "lb_draw_blocks_device": (_I, [_P, ct.POINTER(ct.c_uint32), _I, _I, _I, _I, _U8, _D]),
 }
 
 _lib = None
@@ -335,6 +338,31 @@ class code:
         _check(load_bp_library().lb_mc_run(self._context(), B, up, w.ctypes.data_as(_D), float(a),
                                             _CHANNELS[channel], int(batch), _ALGOS[dectype], float(corr_factor),
                                             int(max_iter), errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP)))
+        return errs.astype(np.int64), it.astype(np.int64)
+
+    def mc_blocks_seeds(self, seeds, a, channel="awgn", batch=1024, dectype="sumprod2", corr_factor=0.7,
+                        max_iter=MAX_ITCOUNT):
+        """mc_blocks on blocks drawn on the device from their seeds
+        (lb_mc_run_seeds; the blocks of ldpc_mc.draw_blocks_device): only the
+        seeds go up.  The information bits are drawn where ldpc_mc.info_bits
+        says the reference encodes, else the all-zero word is sent.  Returns
+        int64 (bit_errors, iters) in seed order."""
+        from .ldpc_mc import _seed_array, info_bits
+        if dectype not in _ALGOS:
+            raise NameError("Decoder type unknonwn")
+        if channel not in _CHANNELS:
+            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
+        seeds = _seed_array(seeds)
+        B = len(seeds)
+        K = info_bits(self, channel)
+        if K:
+            self._set_encoder()
+        errs = np.empty(B, dtype=np.intc)
+        it = np.empty(B, dtype=np.intc)
+        _check(load_bp_library().lb_mc_run_seeds(self._context(), B, seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)),
+                                                  K, float(a), _CHANNELS[channel], int(batch), _ALGOS[dectype],
+                                                  float(corr_factor), int(max_iter), errs.ctypes.data_as(_IP),
+                                                  it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
 
     def mc_event_ms(self):

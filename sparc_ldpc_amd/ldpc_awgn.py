@@ -29,14 +29,16 @@ sim_param = _grid(3)  # ldpc_awgn.py:6-43
 
 
 def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_STEP=100.0,
-        MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None):
+        MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None, draws="host"):
     """ldpc_awgn.py:60-123.  Starts C_AWGN_OFFSET dB above the SNR of the AWGN
     rate, and per point: sigma2 = 1 / 10**(SNR/10), blocks until MIN_ERRORS
     block errors or MAX_BLOCKS, then SNR += sqrt(P_STEP / nblocks).  Point d
     decodes the blocks seed0 + d * 10_000_000, ... (ldpc_mc's seed contract with
     sigma = sqrt(sigma2)).  Returns the reference's tuples (standard, rate, z,
     SNR, nblocks, nblockerrors, nblocks*K, nbiterrors, nit_total) and appends
-    them to ``results_file`` in its line format when given."""
+    them to ``results_file`` in its line format when given.  draws="device":
+    the blocks are drawn on the GPU from their seeds (ldpc_mc)."""
+    ldpc_mc._check_draws(draws)
     if rate not in _RATES:
         raise NameError("Rate unsupported")
     R = _RATES[rate]
@@ -47,7 +49,7 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     for datapoint in range(N_MEASUREMENTS):
         sigma2 = 1 / np.power(10, SNR / 10.0)
         r = ldpc_mc._mc_point(code, float(np.sqrt(sigma2)), "awgn", MIN_ERRORS, MAX_BLOCKS,
-                              seed0 + datapoint * 10_000_000, batch)
+                              seed0 + datapoint * 10_000_000, batch, draws=draws)
         nblocks = r["blocks"]
         output = (standard, rate, z, SNR, nblocks, r["block_errors"], nblocks * K, r["bit_errors"], r["iters_total"])
         res.append(output)

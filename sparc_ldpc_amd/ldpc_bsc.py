@@ -17,11 +17,13 @@ _P0 = {"1/2": 0.11, "2/3": 0.06, "5/6": 0.02459, "3/4": 0.0415}
 sim_param = _grid(100)  # ldpc_bsc.py:6-43
 
 
-def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0):
+def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host"):
     """ldpc_bsc.py:63-113: (res, parray) with parray = linspace(p0, 0.001, 10)
     and res[i] the mean bit error rate of ``repeats`` blocks at parray[i].
     Point i decodes the blocks seed0 + i * 10_000_000, ... (ldpc_mc's BSC
-    contract: random_sample(N) < p flips the bit)."""
+    contract: random_sample(N) < p flips the bit).  draws="device": the
+    uniform values are drawn on the GPU from the seeds (the same values)."""
+    ldpc_mc._check_draws(draws)
     if rate not in _P0:
         raise NameError("Rate unsupported")
     p = _P0[rate]
@@ -31,7 +33,8 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0):
     parray = np.linspace(p, 0.001, 10)
     for i, q in enumerate(parray):
         base = seed0 + i * 10_000_000
-        be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc")
+        be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc",
+                                **({} if draws == "host" else {"draws": draws}))
         errors = [int(b) / N for b in be]
         res.append(np.sum(errors) / repeats)
     return res, parray

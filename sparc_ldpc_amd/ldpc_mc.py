@@ -19,6 +19,13 @@ A block is its seed ``s`` in [0, 2**32).  With ``rs = np.random.RandomState(s)``
 ``_draw_blocks`` is that definition in NumPy; ``draw_blocks`` is its native
 twin on the host cores (lb_draw_blocks), bit for bit.  Results do not depend
 on the batch size, the rank count or the order the blocks are decoded in.
+
+``draws="device"`` (mc_ldpc and everything above it) draws the blocks on the
+GPU from their seeds instead (lb_mc_run_seeds: only the seeds go up);
+``draw_blocks_device`` returns those blocks.  The bits and the BSC's uniform
+values are the host's bit for bit; the AWGN noise is the host's up to the
+device library's ``log`` (a few values in a thousand differ, by under 2**-49
+relative), so an AWGN block's result may differ from its host-drawn one.
 """
 from __future__ import annotations
 
@@ -30,22 +37,18 @@ import numpy as np
 
 from . import ldpc as _ldpc
 from .harness import LDPCParams, ber_point, draw_threads
+from .operators import seed_array as _seed_array  # uint32 seeds; ValueError outside [0, 2**32), no masking
 
-__all__ = ["draw_blocks", "mc_ldpc", "sim_ldpc_mc", "info_bits"]
+__all__ = ["draw_blocks", "draw_blocks_device", "mc_ldpc", "sim_ldpc_mc", "info_bits"]
 
 _STANDARD = ("802.11n", "802.16")  # the codes the reference encodes (sparc_ldpc.py:1098)
 _RATES = {"1/2": .5, "2/3": 0.6667, "3/4": 0.75, "5/6": 0.83333, "0.45": 0.45}  # sparc_ldpc.py:1075-1086
 
 
-def _seed_array(seeds) -> np.ndarray:
-    """Seeds as uint32; outside [0, 2**32) NumPy's RandomState raises
-    ValueError, and so does this (no masking)."""
-    out = np.empty(len(seeds), dtype=np.uint32)
-    for i, s in enumerate(seeds):
-        if not 0 <= int(s) < 2 ** 32:
-            raise ValueError("Seed must be between 0 and 2**32 - 1")
-        out[i] = int(s)
-    return out
+def _check_draws(draws) -> str:
+    if draws not in ("host", "device"):
+        raise ValueError('draws must be "host" or "device"')
+    return draws
 
 
 def info_bits(code, channel="awgn") -> int:
@@ -88,24 +91,67 @@ def draw_blocks(seeds, K, N, channel="awgn", threads=None):
     return u, w
 
 
-def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None):
+def draw_blocks_device(code, seeds, channel="awgn"):
+    """The blocks mc_ldpc(draws="device") decodes: _draw_blocks' (u, w) for
+    ``code`` (K = info_bits, N = code.N) drawn on the GPU from their seeds
+    (lb_draw_blocks_device) and copied back."""
+    if channel not in _ldpc._CHANNELS:
+        raise ValueError(f"channel must be one of {sorted(_ldpc._CHANNELS)}")
+    seeds = _seed_array(seeds)
+    K, N = info_bits(code, channel), int(code.N)
+    u = np.empty((len(seeds), K), dtype=np.uint8) if K else None
+    w = np.empty((len(seeds), N))
+    lib = _ldpc.load_bp_library()
+    _ldpc._check(lib.lb_draw_blocks_device(code._context(), seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), len(seeds),
+                                           K, N, _ldpc._CHANNELS[channel],
+                                           None if u is None else u.ctypes.data_as(_ldpc._U8),
+                                           w.ctypes.data_as(_ldpc._D)))
+    return u, w
+
+
+def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, draws="host"):
     """Blocks ``seeds`` of ``code`` at sigma (AWGN) or p (BSC) ``a``: per-block
     int64 (bit_errors, iters) in seed order.  ``drawn``: the blocks' (u, w)
-    when the caller has drawn them already (draw_blocks)."""
+    when the caller has drawn them already (draw_blocks).  draws="device":
+    the blocks are drawn on the GPU from their seeds (code.mc_blocks_seeds)."""
+    _check_draws(draws)
     seeds = list(seeds)
-    if not seeds:
+    if draws == "device":
+        if drawn is not None:
+            raise ValueError('drawn blocks go with draws="host"')
+        seeds = _seed_array(seeds)
+    if not len(seeds):
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    if draws == "device":
+        return code.mc_blocks_seeds(seeds, a, channel, batch, dectype)
     u, w = draw_blocks(seeds, info_bits(code, channel), code.N, channel) if drawn is None else drawn
     return code.mc_blocks(u, w, a, channel, batch, dectype)
 
 
 def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectype="sumprod2", rank=0, world=1,
-              allreduce=None, timings=None):
+              allreduce=None, timings=None, draws="host"):
     """One operating point by the reference's stopping rule (harness.ber_point)
     over the blocks seed_base, seed_base + 1, ...: round r + 1 is drawn in a
     worker thread while round r decodes.  ``timings`` (a dict) receives the
-    seconds spent drawing and the device milliseconds of the decodes."""
+    seconds spent drawing and the device milliseconds of the decodes.
+    draws="device": every round is drawn on the GPU in front of its decode,
+    and no worker thread is started."""
+    _check_draws(draws)
     from .dist import shard_seeds
+    if draws == "device":
+        ms = [0.0]
+
+        def decode_seeds(seeds):
+            out = mc_ldpc(code, a, seeds, channel, batch, dectype, draws="device")
+            ms[0] += code.mc_event_ms()
+            return out
+
+        res = ber_point(decode_seeds, code.N, min_errors, max_blocks, batch, rank, world, allreduce,
+                        seed_base=seed_base)
+        if timings is not None:
+            timings["draw_s"] = timings.get("draw_s", 0.0)  # (inside device_ms)
+            timings["device_ms"] = timings.get("device_ms", 0.0) + ms[0]
+        return res
     K, N = info_bits(code, channel), code.N
     max_rounds = -(-int(max_blocks) // (batch * world))
     pending = {}
@@ -138,16 +184,18 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
 
 
 def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, seed0=0, batch=1024, rank=0,
-                world=1, allreduce=None, timings=None):
+                world=1, allreduce=None, timings=None, draws="host"):
     """sim_ldpc (sparc_ldpc.py:1064-1124) over the blocks seed0, seed0 + 1, ...
     with everything but the draws on the device: blocks until MIN_ERRORS block
     errors or MAX_BLOCKS blocks, consumed in seed order whatever ``batch`` and
     ``world``.  Returns dict(ber, blocks, block_errors, bit_errors, nit_total)
-    with ber = bit_errors / (blocks * N) from the integer counts (:1119)."""
+    with ber = bit_errors / (blocks * N) from the integer counts (:1119).
+    draws="device": the draws on the device too (only the seeds go up)."""
+    _check_draws(draws)
     if ldpcparams.r_ldpc not in _RATES:
         raise NameError("Rate unsupported")
     code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype)
     r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, "sumprod2", rank, world,
-                  allreduce, timings)
+                  allreduce, timings, draws)
     return dict(ber=r["bit_errors"] / (r["blocks"] * code.N), blocks=r["blocks"], block_errors=r["block_errors"],
                 bit_errors=r["bit_errors"], nit_total=r["iters_total"])

@@ -42,6 +42,17 @@ def default_device() -> int:
     return d if 0 <= d < ndev else 0
 
 
+def seed_array(seeds) -> np.ndarray:
+    """Seeds as uint32; outside [0, 2**32) NumPy's RandomState raises
+    ValueError, and so does this (no masking)."""
+    out = np.empty(len(seeds), dtype=np.uint32)
+    for i, s in enumerate(seeds):
+        if not 0 <= int(s) < 2 ** 32:
+            raise ValueError("Seed must be between 0 and 2**32 - 1")
+        out[i] = int(s)
+    return out
+
+
 def _w_of(n: int, m: int) -> int:
     # sparc_ldpc.py:52 / :110
     return 2 ** int(np.ceil(np.log2(max(m + 1, n + 1))))
@@ -345,6 +356,32 @@ class SparcOperator:
         check(self._lib.sa_mc_stage(self._ctx, R, idx.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int32)), dptr(noise)))
         self._mc_reps = R
         return R
+
+    def mc_draw(self, seeds, sigma):
+        """Stage reps for mc_run by drawing them on the device from their
+        seeds (sa_mc_draw): rep i is harness._draw_reps' rep of seeds[i] at
+        sigma[i] (a scalar sigma: the same for every rep).  Only the seeds and
+        sigmas go up.  Needs M a power of two.  Returns the device
+        milliseconds of the draw."""
+        seeds = seed_array(seeds)
+        R = len(seeds)
+        sig = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (R,)))
+        ms = np.zeros(1)
+        self._mc_reps = 0
+        check(self._lib.sa_mc_draw(self._ctx, R, seeds.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_uint32)), dptr(sig),
+                                   dptr(ms)))
+        self._mc_reps = R
+        return float(ms[0])
+
+    def mc_fetch_draws(self):
+        """The staged reps read back, whichever of mc_stage / mc_draw staged
+        them: (idx (R, L) int32, noise (R, n) fp64)."""
+        R = int(getattr(self, "_mc_reps", 0))
+        idx = np.empty((R, self.L), dtype=np.int32)
+        noise = np.empty((R, self.n))
+        check(self._lib.sa_mc_fetch_draws(self._ctx, R, idx.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int32)),
+                                          dptr(noise)))
+        return idx, noise
 
     def mc_run(self, B, T, early_stop=True, decisions=True):
         """Decode the staged reps through B slots with per-slot refill:
