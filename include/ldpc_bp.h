@@ -58,7 +58,11 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
 void lb_destroy(lb_ctx* ctx);
 
 /* Decode B words: ch[B][Nv] channel LLRs -> app[B][Nv] a-posteriori LLRs and
- * iters[B] (the reference's return value per word).  Host pointers; blocking. */
+ * iters[B] (the reference's return value per word).  Host pointers; blocking.
+ * max_iter = 0 (here and in lb_decode_device, lb_run, lb_mc_run and
+ * lb_mc_run_seeds) runs no iteration: app = ch, the variable phase on zero
+ * messages (the uncoded hard decision), and iters = 0 for every word.
+ * max_iter < 0 is LB_ERR_ARG. */
 int lb_decode(lb_ctx* ctx, int B, const double* ch, double* app, int* iters, int algo,
               double corr_factor, int max_iter);
 

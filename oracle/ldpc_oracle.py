@@ -24,8 +24,14 @@ encoder and C-decoder KATs; ``tests/test_ldpc_oracle.py``) and, when
 One deliberate difference: the reference ``minsum`` advances its message
 offset by ``cdeg[j+1]`` instead of ``cdeg[j]`` (c_ldpc.c:364), which only
 agrees with the intended rule for check-regular codes; this restatement (and
-the HIP decoder) use the aligned offsets, and minsum parity is asserted on
-check-regular codes only.
+the HIP decoder) use the aligned offsets, and minsum parity with the reference
+is asserted on check-regular codes only (the HIP decoder is held to this
+restatement on irregular codes too).
+
+For the iteration-by-iteration tests of the HIP decoder the decoders take
+``max_it``, ``_decode(..., trace=True)`` records every iteration's app and
+stop margin (``truncated`` cuts such a run at any smaller ``max_it``), and
+``lxor_ld`` is Lxor in long double.
 """
 from __future__ import annotations
 
@@ -124,6 +130,17 @@ def lxor(L1, L2, corr=True):
     return L
 
 
+def lxor_ld(L1, L2):
+    """Lxor with the correction, in np.longdouble with log1p / exp: the
+    high-precision reference for the float64 ``lxor`` and the device's Lxor."""
+    a = np.asarray(L1, dtype=np.longdouble)
+    b = np.asarray(L2, dtype=np.longdouble)
+    s = np.where(np.signbit(a) == np.signbit(b), np.longdouble(1), np.longdouble(-1))
+    L = s * np.fmin(np.abs(a), np.abs(b))
+    with np.errstate(over="ignore", under="ignore"):
+        return L + np.log1p(np.exp(-np.abs(a + b))) - np.log1p(np.exp(-np.abs(a - b)))
+
+
 def lxfb(Lm, corr=True):
     """c_ldpc.c:294-314 on the rows of Lm (n_nodes x dc), in place; returns b[0]."""
     dc = Lm.shape[1]
@@ -160,12 +177,31 @@ class _Graph:
             self.cgroups.append((nodes, E))
 
 
-def _decode(ch, vdeg, cdeg, intrlv, algo, corr_factor=0.7, max_it=MAX_ITCOUNT):
+def _decode(ch, vdeg, cdeg, intrlv, algo, corr_factor=0.7, max_it=MAX_ITCOUNT, trace=False):
+    """(app, it) as the reference returns them: a word whose checks are all
+    satisfied in iteration i (counted from 0) returns that iteration's app and
+    i; a word that runs out returns the last iteration's app and max_it.
+    max_it = 0 runs nothing: (ch, 0), the variable phase on zero messages.
+
+    trace=True returns (app, it, trace_app, trace_margin) with one row per
+    iteration run: app as that iteration's variable phase wrote it, and the
+    iteration's stop margin, the smallest |aggregate LLR| over all checks (how
+    far the stop decision was from flipping).  ``truncated`` reads the decode
+    cut at any smaller max_it off the trace."""
     g = _Graph(vdeg, cdeg, intrlv)
     ch = np.asarray(ch, dtype=np.float64)
     msg = np.zeros(len(g.intrlv))
     app = np.zeros(len(g.vdeg))
-    it = 0
+    tr_app, tr_margin = [], []
+
+    def out(it):
+        if not trace:
+            return app, it
+        return (app, it, np.array(tr_app).reshape(len(tr_app), len(app)), np.array(tr_margin))
+
+    if max_it == 0:
+        app = ch.copy()
+        return out(0)
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         for it in range(max_it):
             # variable nodes (c_ldpc.c:171-178): sequential sum in port order
@@ -177,6 +213,7 @@ def _decode(ch, vdeg, cdeg, intrlv, algo, corr_factor=0.7, max_it=MAX_ITCOUNT):
                 msg[E] = aggr[:, None] - old
                 app[nodes] = aggr
             unsat = False
+            margin = np.inf
             for nodes, E in g.cgroups:
                 Lm = msg[E]
                 if algo == "sumprod":  # c_ldpc.c:76-102
@@ -184,33 +221,51 @@ def _decode(ch, vdeg, cdeg, intrlv, algo, corr_factor=0.7, max_it=MAX_ITCOUNT):
                     aggr = np.ones(len(nodes))
                     for k in range(Lm.shape[1]):
                         aggr = aggr * Lm[:, k]
-                    unsat |= bool(np.any(2.0 * np.arctanh(aggr) <= 0.0))
+                    full = 2.0 * np.arctanh(aggr)
+                    unsat |= bool(np.any(full <= 0.0))
                     Lm = 2.0 * np.arctanh(aggr[:, None] / Lm)
                 elif algo == "sumprod2":
-                    aggr = lxfb(Lm, True)
-                    unsat |= bool(np.any(aggr <= 0.0))
+                    full = lxfb(Lm, True)
+                    unsat |= bool(np.any(full <= 0.0))
                 elif algo == "minsum":
-                    aggr = lxfb(Lm, False)
-                    unsat |= bool(np.any(aggr <= 0.0))
+                    full = lxfb(Lm, False)
+                    unsat |= bool(np.any(full <= 0.0))
                     Lm = Lm * corr_factor
                 else:
                     raise NameError("Decoder type unknonwn")
                 msg[E] = Lm
+                if trace:
+                    margin = np.min([margin, np.min(np.abs(full))])  # NaN propagates
+            if trace:
+                tr_app.append(app.copy())
+                tr_margin.append(margin)
             if not unsat:
-                return app, it
-    return app, max_it
+                return out(it)
+    return out(max_it)
 
 
-def sumprod2(ch, vdeg, cdeg, intrlv):
-    return _decode(ch, vdeg, cdeg, intrlv, "sumprod2")
+def truncated(ch, it, trace_app, k):
+    """(app, it) of the decode cut at max_it = k, from the trace of a run with
+    max_it >= k that returned ``it``: the cut run stops at iteration ``it`` as
+    well when it gets there (k > it), otherwise it runs iterations 0..k-1 and
+    returns the last one's app with k."""
+    if k == 0:
+        return np.asarray(ch, dtype=np.float64).copy(), 0
+    if it < len(trace_app) and k > it:  # the traced run converged in iteration ``it``
+        return trace_app[it], it
+    return trace_app[k - 1], k
 
 
-def sumprod(ch, vdeg, cdeg, intrlv):
-    return _decode(ch, vdeg, cdeg, intrlv, "sumprod")
+def sumprod2(ch, vdeg, cdeg, intrlv, max_it=MAX_ITCOUNT):
+    return _decode(ch, vdeg, cdeg, intrlv, "sumprod2", max_it=max_it)
 
 
-def minsum(ch, vdeg, cdeg, intrlv, corr_factor=0.7):
-    return _decode(ch, vdeg, cdeg, intrlv, "minsum", corr_factor)
+def sumprod(ch, vdeg, cdeg, intrlv, max_it=MAX_ITCOUNT):
+    return _decode(ch, vdeg, cdeg, intrlv, "sumprod", max_it=max_it)
+
+
+def minsum(ch, vdeg, cdeg, intrlv, corr_factor=0.7, max_it=MAX_ITCOUNT):
+    return _decode(ch, vdeg, cdeg, intrlv, "minsum", corr_factor, max_it=max_it)
 
 
 # ---- SPARC <-> bits glue ---------------------------------------------------------

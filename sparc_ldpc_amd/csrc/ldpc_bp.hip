@@ -648,6 +648,13 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
   if (algo < LB_SUMPROD2 || algo > LB_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
   if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
   if (B == 0) return LB_OK;
+  if (max_iter == 0) {
+    // no iteration: the variable phase on zero messages, app = ch (the uncoded
+    // hard decision), 0 iterations; k_bp would leave app unwritten
+    HIP_TRY(hipMemcpyAsync(d_app, d_ch, (size_t)B * c->Nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
+    return LB_OK;
+  }
   // the tail's variable kernel puts the words on the grid's y dimension (<= 65535)
   const bool tail = c->tail_at > 0 && max_iter > c->tail_at && B <= 65535;
   int rc;

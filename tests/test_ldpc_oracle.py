@@ -140,3 +140,69 @@ def test_sp2bp_bp2sp_llr_against_reference():
         if M <= 64:
             np.testing.assert_allclose(lo.bp2sp(g[f"bp2sp|{L}|{M}|v"], L, M), g[f"bp2sp|{L}|{M}|sp"],
                                        rtol=1e-14, atol=0)
+
+
+# ---- traced / truncated decodes, Lxor in long double, synthetic graphs -----------------
+import ldpc_cases as lc  # noqa: E402
+
+
+@pytest.mark.parametrize("algo", lc.ALGOS)
+@pytest.mark.parametrize("cell", ["16_1/2_z24", "16_5/6_z24", "syn_dc8"])
+def test_trace_equals_separate_truncated_runs(cell, algo):
+    """One traced run to 12 iterations gives the decode cut at every k <= 12, bit for bit."""
+    ref = lc.reference(cell, algo)
+    c = ref.c
+    fn = {"sumprod2": lo.sumprod2, "sumprod": lo.sumprod, "minsum": lo.minsum}[algo]
+    for i, ch in enumerate(ref.CH):
+        assert len(ref.apps[i]) == len(ref.margins[i]) == min(ref.its[i] + 1, lc.K_TRACE)
+        for k in range(lc.K_TRACE + 1):
+            app, it = fn(ch, c.vdeg, c.cdeg, c.intrlv, max_it=k)
+            tapp, tit = lo.truncated(ch, ref.its[i], ref.apps[i], k)
+            assert it == tit and np.array_equal(app, tapp, equal_nan=True), (ref.labels[i], k)
+            if k == 0:
+                assert it == 0 and np.array_equal(app, ch) and app is not ch
+
+
+@pytest.mark.parametrize("cell", list(lc.CELLS))
+def test_case_words_meet_their_preconditions(cell):
+    """What the GPU trajectory tests assume of their inputs, from the oracle alone."""
+    for algo in lc.ALGOS:
+        ref = lc.reference(cell, algo)
+        ref.check_preconditions(cell, algo)
+        assert len(ref.CH) == (2 if cell in lc.TWO_WORDS else 6 if algo == "sumprod" else 8)
+
+
+def test_lxor_float64_against_long_double():
+    a, b = lc.lxor_points()
+    assert 1200 <= len(a) <= 1800
+    ref = lo.lxor_ld(a, b)
+    err = np.abs(lo.lxor(a, b).astype(np.longdouble) - ref).astype(np.float64)
+    worst = np.max(err / lc.lxor_bar(a, b)) * 4
+    print(f"float64 lxor: worst error {worst:.3f} * 2^-52 * max(1, min(|a|, |b|))")
+    assert np.all(err <= lc.lxor_bar(a, b)), worst
+    # the edges are in the set: the branch switch, a = +-b, zeros, 1 + exp(-x) == 1, exp underflow
+    s, d = np.abs(a + b), np.abs(a - b)
+    assert (s == lc.LN_SW).any() and (d == lc.LN_SW).any() and (a == b).any() and (a == -b).any()
+    assert ((a == 0) & np.signbit(a)).any() and ((b == 0) & ~np.signbit(b)).any()
+    assert (np.abs(s - 37.0) < 1e-9).any() and (np.abs(d - 750.0) < 1e-9).any()
+    assert ((a != 0) & (np.abs(a) < 2.3e-308)).any()
+
+
+@pytest.mark.parametrize("name", list(lc.SYNTH))
+def test_synthetic_graphs_product_against_oracle(name):
+    from sparc_ldpc_amd import ldpc
+    rw, ncols, heavy, _ = lc.SYNTH[name]
+    proto = lc.synth_proto(name)
+    assert np.array_equal(proto, lc.synth_proto(name))  # seeded
+    assert proto.shape == (len(rw), ncols) and (proto < lc.SYNTH_Z).all()
+    assert np.array_equal((proto != -1).sum(1), rw) and (proto != -1).any(0).all()
+    if heavy:
+        assert (proto[:, heavy[0]] != -1).sum() == heavy[1] == 13
+    got = ldpc.tanner_graph(proto, lc.SYNTH_Z)
+    want = lo.prepare_decoder(proto, lc.SYNTH_Z)
+    for g, w in zip(got, want):
+        assert np.array_equal(g, w)
+    c = lc.make_code("syn_" + name)
+    assert np.array_equal(c.proto, proto) and np.array_equal(c.intrlv, want[2]) and c.cdeg.max() == max(rw)
+    H = lo.pcmat(proto, lc.SYNTH_Z)
+    assert np.array_equal(H.sum(0), c.vdeg) and np.array_equal(H.sum(1), c.cdeg)
