@@ -35,7 +35,8 @@ enum {
   LB_ERR_NO_DEVICE = -6    /* no HIP device: there is no CPU fallback */
 };
 
-enum { LB_SUMPROD2 = 0, LB_SUMPROD = 1, LB_MINSUM = 2 };
+/* 3, 4: the layered schedule (see lb_set_layers) with sumprod2's / minsum's check rule */
+enum { LB_SUMPROD2 = 0, LB_SUMPROD = 1, LB_MINSUM = 2, LB_LAYERED_SUMPROD2 = 3, LB_LAYERED_MINSUM = 4 };
 
 #define LB_MAX_ITCOUNT 200 /* c_ldpc.c:7 */
 
@@ -101,8 +102,46 @@ int lb_info(lb_ctx* ctx, long long* out);
  * max_iter is queued, sized from the previous tail's word count, and a
  * launch past the last running word returns at once.  tail_at < 0: the
  * default chosen at lb_create (8, or the environment's LDPC_BP_TAIL); 0: off.
- * Needs variable degrees <= 12 (LB_ERR_UNSUPPORTED otherwise). */
+ * Needs variable degrees <= 12 (LB_ERR_UNSUPPORTED otherwise).  The layered
+ * decoders take no part in the tail launches: they ignore tail_at. */
 int lb_set_tail(lb_ctx* ctx, int tail_at);
+
+/* ---- layered schedule (row-layered / turbo-decoding message passing) ---------- */
+/* algo = LB_LAYERED_SUMPROD2 / LB_LAYERED_MINSUM, wherever algo is taken
+ * (lb_decode, lb_decode_device, lb_run, lb_mc_run, lb_mc_run_seeds), decodes
+ * with the layered schedule: layer l is the consecutive checks first_check[l] ..
+ * first_check[l+1] - 1 (for a quasi-cyclic code its protograph rows,
+ * first_check = 0, z, 2z, .., Nc).  With app = ch and r = 0 (one message per
+ * edge, in check order), a sweep takes the layers in order; per layer, for
+ * each check and each of its edges e on variable v: q[e] = app[v] - r[e]; the
+ * check rule on the check's q gives its new r (Lxfb with the correction
+ * terms, or Lxfb without them times corr_factor); app[v] = q[e] + r[e].
+ * Before each sweep the stop test: every check has an even number of
+ * variables with app < 0 and none with app == 0 or NaN.  iters = i: the test
+ * passed after i sweeps (0: the channel word is a codeword already);
+ * max_iter: it had not passed before the last sweep.  One launch, one
+ * workgroup per word; lb_run and lb_decode_device never wait.
+ *
+ * lb_set_layers checks on the host, before anything is uploaded or changed,
+ * that first_check[0..nlayers] increases strictly from 0 to Nc and that no
+ * variable occurs twice in a layer (the checks of a layer are then independent
+ * and the result does not depend on the order they are taken in): otherwise
+ * LB_ERR_GRAPH, with a message naming the layer and the variable, and the
+ * context is left as it was.  A layered algo on a context without layers is
+ * LB_ERR_ARG.
+ *
+ * lb_layer_info: out[0..3] = nlayers (0: none set), the largest layer's
+ * checks, where the messages live (2: r and app in LDS, 1: app in LDS and r in
+ * HBM, 0: both in HBM) and threads per workgroup.  r and app live in LDS when
+ * they fit, and the workgroup has a thread per edge of the largest layer (at
+ * most 1024; 768 for check-regular codes of degree 20).
+ *
+ * Measurement switches, read from the environment by lb_set_layers:
+ * LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app in HBM although they would
+ * fit; LDPC_BP_LAYERED_THREADS = the threads per workgroup (the results are
+ * the same bits either way). */
+int lb_set_layers(lb_ctx* ctx, int nlayers, const int* first_check);
+int lb_layer_info(lb_ctx* ctx, long long* out);
 
 /* ---- LDPC-only Monte-Carlo (sim_ldpc sparc_ldpc.py:1064-1124, ldpc_awgn.py, ldpc_bsc.py) ---- */
 /* Block s is its seed: RandomState(seeds[i]) draws randint(0, 2, K) into

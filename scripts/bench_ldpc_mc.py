@@ -11,7 +11,17 @@ synchronise.  Prints one JSON line and writes it to results/ldpc_mc.json
 sim_ldpc_mc(draws="device") (the blocks drawn on the GPU from their seeds), five
 alternating rounds after a warm-up of each, written to
 results/ldpc_mc_draws.json.  The bar: every device-draw run below every
-host-draw run."""
+host-draw run.
+
+--dectype layered_sumprod2: sim_ldpc_mc(draws="device") with the flooding
+sumprod2 against the layered decoder on the same seeds, as the library lays it
+out itself (leg "layered": r and app in LDS, a thread per edge of a layer),
+with r held in HBM (LDPC_BP_LAYERED_LDS = 1), and both at a thread per check
+(LDPC_BP_LAYERED_THREADS = 192; "layouts" records each leg's), five
+alternating rounds after a warm-up of each, written to
+results/ldpc_mc_layered.json: per leg the median end-to-end and device
+milliseconds, blocks/s, mean iterations or sweeps a block, bit and block
+errors.  The flooding leg of the same session is the yardstick."""
 import argparse
 import json
 import os
@@ -32,9 +42,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--draws", default=None, choices=["device"],
                     help="time sim_ldpc_mc's host draws against its device draws instead")
+    ap.add_argument("--dectype", default=None, choices=["layered_sumprod2", "layered_minsum"],
+                    help="time the flooding decoder against this layered one instead (device draws)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "results", "ldpc_mc_draws.json" if args.draws else "ldpc_mc.json")
+        name = "ldpc_mc_layered.json" if args.dectype else "ldpc_mc_draws.json" if args.draws else "ldpc_mc.json"
+        args.out = os.path.join(ROOT, "results", name)
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import ldpc
     lib = ldpc.load_bp_library()
@@ -53,9 +66,11 @@ def main():
         sync()
         return time.perf_counter() - t0, ber
 
-    def new(seed0, draws="host"):
+    def new(seed0, draws="host", dectype=None):
         tm = {}
         kw = {} if draws == "host" else {"draws": draws}
+        if dectype:
+            kw["dectype"] = dectype
         sync()
         t0 = time.perf_counter()
         r = sp.sim_ldpc_mc(lp, sigma, MIN_ERRORS=never, MAX_BLOCKS=BLOCKS, seed0=seed0, batch=BATCH, timings=tm, **kw)
@@ -64,6 +79,8 @@ def main():
         assert r["blocks"] == BLOCKS
         return wall, r, tm
 
+    if args.dectype:
+        return layered_leg(args, new, sigma, lp)
     if args.draws:
         return draws_leg(args, new, sigma)
     old(1)
@@ -122,6 +139,69 @@ def draws_leg(args, new, sigma):
         bar_every_device_run_below_every_host_run=bool(
             max(x["wall_s"] for x in runs["device"]) < min(x["wall_s"] for x in runs["host"])),
     )
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+def layered_leg(args, new, sigma, lp):
+    from sparc_ldpc_amd import ldpc
+    rounds = 5
+    flooding = args.dectype[len("layered_"):]
+    # leg -> (dectype, LDPC_BP_LAYERED_LDS, LDPC_BP_LAYERED_THREADS read when the run's code sets its layers)
+    legs = {"flooding": (flooding, None, None), "layered": (args.dectype, None, None),
+            "layered_192": (args.dectype, None, "192"), "layered_r_hbm": (args.dectype, "1", None),
+            "layered_r_hbm_192": (args.dectype, "1", "192")}
+    names = ("LDPC_BP_LAYERED_LDS", "LDPC_BP_LAYERED_THREADS")
+
+    def setenv(knobs):
+        for name, val in zip(names, knobs):
+            os.environ.pop(name, None)
+            if val is not None:
+                os.environ[name] = val
+
+    def run(leg, seed0):
+        dectype, *knobs = legs[leg]
+        setenv(knobs)
+        try:
+            return new(seed0, "device", dectype)
+        finally:
+            setenv((None, None))
+
+    layout = {}
+    for leg, (dectype, *knobs) in legs.items():
+        if leg == "flooding":
+            continue
+        setenv(knobs)
+        c = ldpc.code(lp.standard, lp.r_ldpc, lp.z, lp.ptype)
+        c.decode_batch(np.ones((1, c.N)), dectype, max_iter=1)
+        layout[leg] = c.layer_info()
+        setenv((None, None))
+    for leg in legs:
+        run(leg, 1)
+    runs = {leg: [] for leg in legs}
+    for k in range(rounds):
+        for leg in legs:
+            w, r, tm = run(leg, 100_000 * (k + 1))
+            runs[leg].append(dict(wall_ms=w * 1e3, device_ms=tm["device_ms"], bit_errors=r["bit_errors"],
+                                  block_errors=r["block_errors"], nit_total=r["nit_total"]))
+    out = dict(workload="802.16 5/6 z=192, sigma=%.6f, %d blocks, batch %d, draws on the device, %s" %
+               (sigma, BLOCKS, BATCH, args.dectype), rounds=rounds, layouts=layout)
+    for leg in legs:
+        wall = statistics.median(x["wall_ms"] for x in runs[leg])
+        dev = statistics.median(x["device_ms"] for x in runs[leg])
+        nit = statistics.mean(x["nit_total"] for x in runs[leg]) / BLOCKS
+        out[leg] = dict(median_wall_ms=wall, median_device_ms=dev, blocks_per_s=BLOCKS / (wall / 1e3),
+                        mean_iterations_or_sweeps=nit, device_us_per_block_iteration=dev * 1e3 / (BLOCKS * nit),
+                        bit_errors=[x["bit_errors"] for x in runs[leg]],
+                        block_errors=[x["block_errors"] for x in runs[leg]],
+                        wall_ms=[x["wall_ms"] for x in runs[leg]], device_ms=[x["device_ms"] for x in runs[leg]])
+    for leg in legs:
+        if leg == "flooding":
+            continue
+        out[leg]["speedup_wall"] = out["flooding"]["median_wall_ms"] / out[leg]["median_wall_ms"]
+        out[leg]["speedup_device"] = out["flooding"]["median_device_ms"] / out[leg]["median_device_ms"]
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:

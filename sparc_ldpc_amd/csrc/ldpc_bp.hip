@@ -284,6 +284,96 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bp(Bp
 }
 
 // ---------------------------------------------------------------------------
+// Layered schedule (row-layered / turbo-decoding message passing)
+// ---------------------------------------------------------------------------
+// One workgroup per word, app on chip for the whole decode.  A sweep walks the
+// layers (for a quasi-cyclic code its protograph rows: z consecutive checks
+// that share no variable) in order; per layer, over the layer's contiguous
+// edges e (v = evar[e]):
+//   gather:  app[v] -= r[e]; r[e] = app[v]     (q, rounded once)    all threads
+//   check:   check_rule in place on each check's slice of r         thread per check
+//   scatter: app[v] += r[e]                                         all threads
+// so a later layer sees what the earlier ones have just written.  No variable
+// occurs twice in a layer (lb_set_layers checks it): every app[v] has one
+// owner per phase, and the result does not depend on the order the checks of
+// a layer are taken in.  Before each sweep the stop test: every check has an
+// even number of variables with app < 0 and none with app == 0 or NaN.
+// iters = the sweeps run before the test passed, or maxit.
+// MODE 2: r and app in LDS; 1: app in LDS, r in the word's HBM slice; 0: both
+// in HBM (app in the output array itself).
+struct BplArgs {
+  const double* ch;   // [B][Nv]
+  double* app;        // [B][Nv]
+  int* iters;         // [B]
+  double* gmsg;       // [B][Nmsg] (MODE < 2)
+  const int* evar;    // [Nmsg] variable node of each edge
+  const int* cstart;  // [Nc+1] first message of each check node
+  const int* lfirst;  // [nlayers+1] first check of each layer
+  int Nv, Nc, Nmsg, nlayers, maxit;
+  double corr;
+};
+
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(BplArgs a) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int Nv = a.Nv, Nc = a.Nc;
+  const double* ch = a.ch + (size_t)b * Nv;
+  double* out = a.app + (size_t)b * Nv;
+  double* app = MODE >= 1 ? lds_l : out;
+  double* r = MODE == 2 ? lds_l + Nv : a.gmsg + (size_t)b * a.Nmsg;
+
+  for (int i = tid; i < Nv; i += nt) app[i] = ch[i];
+  for (int i = tid; i < a.Nmsg; i += nt) r[i] = 0.0;
+  if (tid < 2) unsat[tid] = 0;
+  __syncthreads();
+
+  int it = 0;
+  for (; it < a.maxit; ++it) {
+    // stop test on the hard decisions
+    for (int c = tid; c < Nc; c += nt) {
+      const int s = a.cstart[c], e1 = a.cstart[c + 1];
+      bool odd = false, undecided = false;
+      for (int e = s; e < e1; ++e) {
+        const double x = app[a.evar[e]];
+        odd ^= x < 0.0;
+        undecided |= !(x > 0.0 || x < 0.0);  // +-0 or NaN
+      }
+      if (odd || undecided) unsat[it & 1] = 1;
+    }
+    __syncthreads();
+    if (!unsat[it & 1]) break;
+    // the other flag was last read in sweep it-1, before the barrier above
+    if (tid == 0) unsat[(it + 1) & 1] = 0;
+    for (int l = 0; l < a.nlayers; ++l) {
+      const int c0 = a.lfirst[l], c1 = a.lfirst[l + 1];
+      const int e0 = a.cstart[c0], e1 = a.cstart[c1];
+      for (int e = e0 + tid; e < e1; e += nt) {
+        const int v = a.evar[e];
+        const double q = app[v] - r[e];
+        app[v] = q;
+        r[e] = q;
+      }
+      __syncthreads();
+      for (int c = c0 + tid; c < c1; c += nt) {
+        const int s = a.cstart[c], dc = a.cstart[c + 1] - s;
+        (void)check_rule<ALGO, DCMAX, DCFIX>(r + s, dc, a.corr);
+      }
+      __syncthreads();
+      for (int e = e0 + tid; e < e1; e += nt) {
+        const int v = a.evar[e];
+        app[v] = app[v] + r[e];
+      }
+      __syncthreads();
+    }
+  }
+  if (MODE >= 1)
+    for (int i = tid; i < Nv; i += nt) out[i] = app[i];
+  if (tid == 0) a.iters[b] = it;
+}
+
+// ---------------------------------------------------------------------------
 // Tail: the iterations after the first `tail_at`, for the words still running
 // ---------------------------------------------------------------------------
 // One workgroup holds one word's whole decode above, so the words that do not
@@ -497,6 +587,27 @@ KernelFn pick_kernel(int algo, int maxdc, bool lds, bool fixed = false) {
   }
 }
 
+using LayeredFn = void (*)(BplArgs);
+
+template <int ALGO, int MODE>
+LayeredFn pick_layered_dc(int maxdc, bool fixed) {
+  if (fixed) return k_bpl<ALGO, 32, 20, MODE>;
+  if (maxdc <= 8) return k_bpl<ALGO, 8, 0, MODE>;
+  if (maxdc <= 16) return k_bpl<ALGO, 16, 0, MODE>;
+  return k_bpl<ALGO, 32, 0, MODE>;
+}
+
+// algo: LB_LAYERED_SUMPROD2 or LB_LAYERED_MINSUM; the check rules are the flooding decoders'
+LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode) {
+  if (algo == LB_LAYERED_SUMPROD2)
+    return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(maxdc, fixed)
+           : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(maxdc, fixed)
+                       : pick_layered_dc<LB_SUMPROD2, 0>(maxdc, fixed);
+  return mode == 2   ? pick_layered_dc<LB_MINSUM, 2>(maxdc, fixed)
+         : mode == 1 ? pick_layered_dc<LB_MINSUM, 1>(maxdc, fixed)
+                     : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed);
+}
+
 using TailFn = void (*)(TailArgs);
 
 template <int ALGO>
@@ -552,6 +663,7 @@ void release(lb_ctx* c) {
   (void)hipFree(c->d_msg);
   (void)hipFree(c->d_it);
   (void)hipFree(c->d_evar);
+  (void)hipFree(c->d_lfirst);
   (void)hipFree(c->d_active);
   (void)hipFree(c->d_nact);
   (void)hipFree(c->d_done);
@@ -592,8 +704,7 @@ int ensure_io(lb_ctx* c, int B) {
 
 // message slices: one per word without LDS, two per word (r_{t-1}, r_t)
 // for the tail launches; capMsgB counts word slices
-int ensure_msg(lb_ctx* c, int B, bool tail) {
-  const int need = tail ? 2 * B : (c->lds ? 0 : B);
+int ensure_slices(lb_ctx* c, int need) {
   if (need <= c->capMsgB) return LB_OK;
   (void)hipFree(c->d_msg);
   c->d_msg = nullptr;
@@ -601,6 +712,43 @@ int ensure_msg(lb_ctx* c, int B, bool tail) {
   int rc;
   if ((rc = dev_alloc((void**)&c->d_msg, (size_t)need * c->Nmsg * sizeof(double)))) return rc;
   c->capMsgB = need;
+  return LB_OK;
+}
+
+int ensure_msg(lb_ctx* c, int B, bool tail) { return ensure_slices(c, tail ? 2 * B : (c->lds ? 0 : B)); }
+
+// the layered schedule: one launch, one workgroup per word, no tail (never waits)
+int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
+                   int max_iter) {
+  const int mode = c->lmode;
+  int rc;
+  if ((rc = ensure_slices(c, mode == 2 ? 0 : B))) return rc;
+  const LayeredFn fn = pick_layered(algo, c->maxdc, c->lfixed, mode);
+  const size_t shm = mode == 2   ? (size_t)(c->Nv + c->Nmsg) * sizeof(double)
+                     : mode == 1 ? (size_t)c->Nv * sizeof(double)
+                                 : 0;
+  const unsigned bit = 1u << (algo - LB_LAYERED_SUMPROD2);
+  if (shm && !(c->lattrs & bit)) {
+    // the whole budget, whatever this code needs: contexts of other codes share the instance
+    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
+    c->lattrs |= bit;
+  }
+  BplArgs a;
+  a.ch = d_ch;
+  a.app = d_app;
+  a.iters = d_it;
+  a.gmsg = c->d_msg;
+  a.evar = c->d_evar;
+  a.cstart = c->d_cstart;
+  a.lfirst = c->d_lfirst;
+  a.Nv = c->Nv;
+  a.Nc = c->Nc;
+  a.Nmsg = c->Nmsg;
+  a.nlayers = c->nlayers;
+  a.maxit = max_iter;
+  a.corr = corr;
+  hipLaunchKernelGGL(fn, dim3(B), dim3(c->lnt), shm, c->stream, a);
+  HIP_TRY(hipGetLastError());
   return LB_OK;
 }
 
@@ -645,8 +793,10 @@ int set_attrs(lb_ctx* c) {
 // queued without waiting (see TailArgs)
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
            int max_iter, bool sized_on_host) {
-  if (algo < LB_SUMPROD2 || algo > LB_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
   if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
+  if (algo >= LB_LAYERED_SUMPROD2 && !c->nlayers)
+    return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
   if (B == 0) return LB_OK;
   if (max_iter == 0) {
     // no iteration: the variable phase on zero messages, app = ch (the uncoded
@@ -655,6 +805,7 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
     HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
     return LB_OK;
   }
+  if (algo >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, algo, corr, max_iter);
   // the tail's variable kernel puts the words on the grid's y dimension (<= 65535)
   const bool tail = c->tail_at > 0 && max_iter > c->tail_at && B <= 65535;
   int rc;
@@ -900,11 +1051,11 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
   }
   cs[0] = 0;
   for (int j = 0; j < Nc; ++j) cs[j + 1] = cs[j] + (int)cdeg[j];
-  // tail edge table: the variable node of each edge
+  // edge table of the tail and the layered kernels: the variable node of each edge
+  // (kept on the host as well: lb_set_layers checks its layers against it)
   const int nq = maxdv <= 12 ? std::max(1, (maxdv + 3) / 4) : 0;
-  std::vector<int> evar;
-  if (nq) {
-    evar.resize(Nmsg);
+  std::vector<int> evar(Nmsg);
+  {
     long q = 0;
     for (int j = 0; j < Nv; ++j)
       for (int k = 0; k < vdeg[j]; ++k) evar[intrlv[q++]] = j;
@@ -917,6 +1068,8 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
   c->Nmsg = Nmsg;
   c->maxdv = maxdv;
   c->maxdc = maxdc;
+  c->h_evar = evar;
+  c->h_cstart = cs;
   c->lds = (size_t)Nmsg * sizeof(double) <= kLdsBytes - 64;
   // one thread per check node when possible (the check phase dominates)
   c->nt = std::min(kMaxThreads, std::max(256, (Nc + 63) / 64 * 64));
@@ -935,7 +1088,7 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
   if ((rc = dev_alloc((void**)&c->d_vedge, vedge.size() * sizeof(int)))) return bail(rc);
   if ((rc = dev_alloc((void**)&c->d_vdeg, (size_t)Nv))) return bail(rc);
   if ((rc = dev_alloc((void**)&c->d_cstart, (size_t)(Nc + 1) * sizeof(int)))) return bail(rc);
-  if (c->nq && (rc = dev_alloc((void**)&c->d_evar, evar.size() * sizeof(int)))) return bail(rc);
+  if ((rc = dev_alloc((void**)&c->d_evar, evar.size() * sizeof(int)))) return bail(rc);
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
@@ -951,7 +1104,7 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
   if (hipMemcpyAsync(c->d_vedge, vedge.data(), vedge.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(c->d_vdeg, vd.data(), (size_t)Nv, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(c->d_cstart, cs.data(), (size_t)(Nc + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (c->nq && hipMemcpyAsync(c->d_evar, evar.data(), evar.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      hipMemcpyAsync(c->d_evar, evar.data(), evar.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return bail(fail(LB_ERR_HIP, "graph upload failed"));
   *out = c;
@@ -1057,6 +1210,71 @@ int lb_set_tail(lb_ctx* c, int tail_at) {
   if (!c) return fail(LB_ERR_ARG, "null context");
   if (tail_at > 0 && !c->nq) return fail(LB_ERR_UNSUPPORTED, "tail launches need variable degrees <= 12");
   c->tail_at = tail_at < 0 ? c->tail_default : tail_at;
+  return LB_OK;
+}
+
+int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
+  if (!c || nlayers < 1 || !first_check) return fail(LB_ERR_ARG, "bad layer arguments");
+  // on the host, before anything is uploaded or changed
+  if (first_check[0] != 0) return fail(LB_ERR_GRAPH, "first_check[0] must be 0");
+  int maxlayer = 0;
+  for (int l = 0; l < nlayers; ++l) {
+    if (first_check[l + 1] <= first_check[l] || first_check[l + 1] > c->Nc)
+      return fail(LB_ERR_GRAPH, "first_check must increase strictly from 0 to Nc (layer " + std::to_string(l) + ")");
+    maxlayer = std::max(maxlayer, first_check[l + 1] - first_check[l]);
+  }
+  int maxedges = 0;
+  for (int l = 0; l < nlayers; ++l)
+    maxedges = std::max(maxedges, c->h_cstart[first_check[l + 1]] - c->h_cstart[first_check[l]]);
+  if (first_check[nlayers] != c->Nc)
+    return fail(LB_ERR_GRAPH, "first_check[nlayers] = " + std::to_string(first_check[nlayers]) + " is not Nc = " +
+                                  std::to_string(c->Nc));
+  std::vector<int> owner(c->Nv, -1);
+  for (int l = 0; l < nlayers; ++l)
+    for (int e = c->h_cstart[first_check[l]]; e < c->h_cstart[first_check[l + 1]]; ++e) {
+      const int v = c->h_evar[e];
+      if (owner[v] == l)
+        return fail(LB_ERR_GRAPH, "layer " + std::to_string(l) + ": variable " + std::to_string(v) + " occurs twice");
+      owner[v] = l;
+    }
+  HIP_TRY(hipSetDevice(c->dev));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // a decode may still read the old table
+  int* d = nullptr;
+  int rc;
+  if ((rc = dev_alloc((void**)&d, (size_t)(nlayers + 1) * sizeof(int)))) return rc;
+  if (hipMemcpyAsync(d, first_check, (size_t)(nlayers + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(d);
+    return fail(LB_ERR_HIP, "layer upload failed");
+  }
+  (void)hipFree(c->d_lfirst);
+  c->d_lfirst = d;
+  c->nlayers = nlayers;
+  c->maxlayer = maxlayer;
+  const size_t app_bytes = (size_t)c->Nv * sizeof(double), r_bytes = (size_t)c->Nmsg * sizeof(double);
+  c->lmode = app_bytes + r_bytes <= kLdsBytes - 64 ? 2 : (app_bytes <= kLdsBytes - 64 ? 1 : 0);
+  // measurement and test switches: LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app out of LDS
+  // although they would fit; LDPC_BP_LAYERED_THREADS = the workgroup's threads (a multiple of 64
+  // within the instance's bound)
+  if (const char* e = getenv("LDPC_BP_LAYERED_LDS"); e && *e) c->lmode = std::min(c->lmode, std::max(0, atoi(e)));
+  c->lfixed = c->mindc == c->maxdc && c->maxdc == 20;
+  // a thread per edge of the largest layer: gather and scatter take one pass where the bound
+  // allows, the check chains run on the first waves (measured against a thread per check at
+  // 802.16 5/6 z=192)
+  const int ntmax = c->lfixed ? kFixThreads : kMaxThreads;
+  c->lnt = std::min(ntmax, std::max(128, (maxedges + 63) / 64 * 64));
+  if (const char* e = getenv("LDPC_BP_LAYERED_THREADS"); e && *e)
+    c->lnt = std::min(ntmax, std::max(64, atoi(e) / 64 * 64));
+  c->lattrs = 0;
+  return LB_OK;
+}
+
+int lb_layer_info(lb_ctx* c, long long* out) {
+  if (!c || !out) return fail(LB_ERR_ARG, "null argument");
+  out[0] = c->nlayers;
+  out[1] = c->maxlayer;
+  out[2] = c->lmode;
+  out[3] = c->lnt;
   return LB_OK;
 }
 

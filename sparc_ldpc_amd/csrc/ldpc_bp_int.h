@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "ldpc_bp.h"
 
@@ -38,6 +39,14 @@ struct lb_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool attrs_set = false;
+  // layered schedule (k_bpl), set by lb_set_layers: the layers' first checks on
+  // the device, where the messages live (2: r + app in LDS, 1: app in LDS,
+  // 0: HBM), threads per workgroup; host copies of the edge tables for its checks
+  std::vector<int> h_evar, h_cstart;
+  int* d_lfirst = nullptr;
+  int nlayers = 0, maxlayer = 0, lmode = 0, lnt = 0;
+  bool lfixed = false;
+  unsigned lattrs = 0;        // layered instances whose dynamic LDS size has been raised (bit per algorithm)
   lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
 };
 

@@ -24,8 +24,10 @@ MAX_ITCOUNT = 200  # ldpc.py:4 / c_ldpc.c:7
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_BP_LIB") or os.path.join(_HERE, "libldpc_bp.so")
 
-LB_SUMPROD2, LB_SUMPROD, LB_MINSUM = 0, 1, 2
-_ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM}
+LB_SUMPROD2, LB_SUMPROD, LB_MINSUM, LB_LAYERED_SUMPROD2, LB_LAYERED_MINSUM = 0, 1, 2, 3, 4
+_ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM,
+          "layered_sumprod2": LB_LAYERED_SUMPROD2, "layered_minsum": LB_LAYERED_MINSUM}
+_REFERENCE_ALGOS = ("sumprod2", "sumprod", "minsum")  # code.decode's names (ldpc.py:855-930)
 _CHANNELS = {"awgn": 0, "bsc": 1}  # lb_mc_run / lb_draw_blocks kinds
 
 # Every symbol include/ldpc_bp.h declares (tests check the export table).
@@ -33,7 +35,7 @@ EXPORTS = (
     "sumprod", "sumprod2", "minsum", "Lxor", "Lxfb",
     "lb_create", "lb_destroy", "lb_decode", "lb_decode_device", "lb_stage", "lb_run", "lb_wait",
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
-    "lb_buffers", "lb_set_tail",
+    "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info",
     "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
 )
 
@@ -58,6 +60,8 @@ _SIG = {
     "lb_run_event_ms": (ct.c_double, [_P]),
     "lb_info": (_I, [_P, ct.POINTER(ct.c_int64)]),
     "lb_set_tail": (_I, [_P, _I]),
+    "lb_set_layers": (_I, [_P, _I, _IP]),
+    "lb_layer_info": (_I, [_P, ct.POINTER(ct.c_int64)]),
     "lb_device_count": (_I, []),
     "lb_last_error": (ct.c_char_p, []),
     "lb_version": (ct.c_char_p, []),
@@ -97,6 +101,14 @@ def load_bp_library(path: str = LIB_PATH) -> ct.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def _layered_entry(name):
+    """An entry point of the layered decoder; an older libldpc_bp.so has none."""
+    fn = getattr(load_bp_library(), name, None)
+    if fn is None:
+        raise LdpcBpError(-5, f"this libldpc_bp.so has no layered decoder ({name})")
+    return fn
 
 
 def _check(rc: int) -> None:
@@ -201,7 +213,12 @@ class code:
     and methods (assign_proto, pcmat, prepare_decoder, encode, decode, Lxor,
     Lxfb), plus ``encode_batch`` / ``decode_batch`` for Monte-Carlo and the
     device-side ``encode_device`` / ``mc_blocks`` (encode, channel, decode and
-    error count without a host round trip)."""
+    error count without a host round trip).
+
+    ``decode_batch``, ``run_buffers``, ``mc_blocks`` and ``mc_blocks_seeds``
+    also take dectype "layered_sumprod2" / "layered_minsum": the layered
+    schedule over the protograph rows (include/ldpc_bp.h, lb_set_layers), whose
+    ``it`` counts sweeps."""
 
     def __init__(self, standard="802.11n", rate="1/2", z=27, ptype="A", device=None):
         self.standard = standard
@@ -221,6 +238,7 @@ class code:
         self._device = device
         self._ctx = None
         self._encoder_set = False
+        self._layers_set = False
 
     # -- construction ---------------------------------------------------------
     def assign_proto(self):
@@ -264,10 +282,34 @@ class code:
             self._ctx = ctx
         return self._ctx
 
-    def decode_batch(self, CH, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
-        """Decode B words (rows of CH, channel LLRs) -> (app (B, N) float64, it (B,) int)."""
+    def _algo(self, dectype):
+        """The library's number of a decoder type; a layered one sets the
+        context's layers (the protograph rows) on first use."""
         if dectype not in _ALGOS:
             raise NameError("Decoder type unknonwn")
+        if dectype.startswith("layered_") and not self._layers_set:
+            self.set_layers(np.arange(0, self.Nc + 1, self.z))
+        return _ALGOS[dectype]
+
+    def set_layers(self, first_check):
+        """Layer l = the checks first_check[l] .. first_check[l+1]-1
+        (lb_set_layers; LdpcBpError -4 when they do not increase strictly from
+        0 to Nc or a variable occurs twice in a layer)."""
+        fc = np.ascontiguousarray(first_check, dtype=np.intc)
+        _check(_layered_entry("lb_set_layers")(self._context(), len(fc) - 1, fc.ctypes.data_as(_IP)))
+        self._layers_set = True
+
+    def layer_info(self):
+        """lb_layer_info: layers, the largest layer's checks, where the layered
+        decoder keeps its messages (2: r and app in LDS, 1: app in LDS, 0: HBM)
+        and its threads per workgroup."""
+        out = (ct.c_int64 * 4)()
+        _check(_layered_entry("lb_layer_info")(self._context(), out))
+        return dict(zip(("nlayers", "max_layer", "lds_messages", "threads"), list(out)))
+
+    def decode_batch(self, CH, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
+        """Decode B words (rows of CH, channel LLRs) -> (app (B, N) float64, it (B,) int)."""
+        algo = self._algo(dectype)
         CH = np.ascontiguousarray(np.atleast_2d(CH), dtype=np.float64)
         if CH.shape[1] != self.Nv:
             raise NameError("Channel inputs not consistent with variable degrees")
@@ -276,7 +318,7 @@ class code:
         it = np.empty(B, dtype=np.intc)
         lib = load_bp_library()
         _check(lib.lb_decode(self._context(), B, CH.ctypes.data_as(_D), app.ctypes.data_as(_D),
-                             it.ctypes.data_as(ct.POINTER(ct.c_int)), _ALGOS[dectype],
+                             it.ctypes.data_as(ct.POINTER(ct.c_int)), algo,
                              float(corr_factor), int(max_iter)))
         return app, it.astype(np.int64)
 
@@ -316,8 +358,7 @@ class code:
         encode, ch = (2/sigma**2) * ((1 - 2x) + sigma*w) or -/+ log((1-p)/p)
         where w < p / elsewhere, decode, count.  Returns int64 (bit_errors,
         iters); only those come back from the device."""
-        if dectype not in _ALGOS:
-            raise NameError("Decoder type unknonwn")
+        algo = self._algo(dectype)
         if channel not in _CHANNELS:
             raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
         w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
@@ -336,7 +377,7 @@ class code:
         errs = np.empty(B, dtype=np.intc)
         it = np.empty(B, dtype=np.intc)
         _check(load_bp_library().lb_mc_run(self._context(), B, up, w.ctypes.data_as(_D), float(a),
-                                            _CHANNELS[channel], int(batch), _ALGOS[dectype], float(corr_factor),
+                                            _CHANNELS[channel], int(batch), algo, float(corr_factor),
                                             int(max_iter), errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
 
@@ -348,8 +389,7 @@ class code:
         says the reference encodes, else the all-zero word is sent.  Returns
         int64 (bit_errors, iters) in seed order."""
         from .ldpc_mc import _seed_array, info_bits
-        if dectype not in _ALGOS:
-            raise NameError("Decoder type unknonwn")
+        algo = self._algo(dectype)
         if channel not in _CHANNELS:
             raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
         seeds = _seed_array(seeds)
@@ -360,7 +400,7 @@ class code:
         errs = np.empty(B, dtype=np.intc)
         it = np.empty(B, dtype=np.intc)
         _check(load_bp_library().lb_mc_run_seeds(self._context(), B, seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)),
-                                                  K, float(a), _CHANNELS[channel], int(batch), _ALGOS[dectype],
+                                                  K, float(a), _CHANNELS[channel], int(batch), algo,
                                                   float(corr_factor), int(max_iter), errs.ctypes.data_as(_IP),
                                                   it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
@@ -378,7 +418,9 @@ class code:
     def run_buffers(self, B, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
         """Decode the B words in the device ch buffer into the app buffer (blocking)."""
         lib = load_bp_library()
-        _check(lib.lb_run(self._context(), int(B), _ALGOS[dectype], float(corr_factor), int(max_iter)))
+        if dectype not in _ALGOS:
+            raise KeyError(dectype)  # as before the layered names
+        _check(lib.lb_run(self._context(), int(B), self._algo(dectype), float(corr_factor), int(max_iter)))
         _check(lib.lb_wait(self._context()))
 
     def fetch_buffers(self, B, app=True):
@@ -391,6 +433,8 @@ class code:
 
     def decode(self, ch, dectype="sumprod2", corr_factor=0.7):
         """ldpc.py:855-930: (app, it) for one word of channel LLRs."""
+        if dectype not in _REFERENCE_ALGOS:
+            raise NameError("Decoder type unknonwn")
         ch = np.asarray(ch, dtype=np.float64).reshape(-1)
         if len(ch) != len(self.vdeg):
             raise NameError("Channel inputs not consistent with variable degrees")

@@ -29,7 +29,8 @@ sim_param = _grid(3)  # ldpc_awgn.py:6-43
 
 
 def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_STEP=100.0,
-        MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None, draws="host"):
+        MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None, draws="host",
+        dectype="sumprod2"):
     """ldpc_awgn.py:60-123.  Starts C_AWGN_OFFSET dB above the SNR of the AWGN
     rate, and per point: sigma2 = 1 / 10**(SNR/10), blocks until MIN_ERRORS
     block errors or MAX_BLOCKS, then SNR += sqrt(P_STEP / nblocks).  Point d
@@ -37,8 +38,12 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     sigma = sqrt(sigma2)).  Returns the reference's tuples (standard, rate, z,
     SNR, nblocks, nblockerrors, nblocks*K, nbiterrors, nit_total) and appends
     them to ``results_file`` in its line format when given.  draws="device":
-    the blocks are drawn on the GPU from their seeds (ldpc_mc)."""
+    the blocks are drawn on the GPU from their seeds (ldpc_mc).  dectype: the
+    decoder (code.decode_batch's names, the layered ones included; nit_total
+    then counts sweeps)."""
     ldpc_mc._check_draws(draws)
+    if dectype not in _ldpc._ALGOS:
+        raise NameError("Decoder type unknonwn")
     if rate not in _RATES:
         raise NameError("Rate unsupported")
     R = _RATES[rate]
@@ -49,7 +54,8 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     for datapoint in range(N_MEASUREMENTS):
         sigma2 = 1 / np.power(10, SNR / 10.0)
         r = ldpc_mc._mc_point(code, float(np.sqrt(sigma2)), "awgn", MIN_ERRORS, MAX_BLOCKS,
-                              seed0 + datapoint * 10_000_000, batch, draws=draws)
+                              seed0 + datapoint * 10_000_000, batch, draws=draws,
+                              **({} if dectype == "sumprod2" else {"dectype": dectype}))
         nblocks = r["blocks"]
         output = (standard, rate, z, SNR, nblocks, r["block_errors"], nblocks * K, r["bit_errors"], r["iters_total"])
         res.append(output)

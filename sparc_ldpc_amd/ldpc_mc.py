@@ -184,18 +184,22 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
 
 
 def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, seed0=0, batch=1024, rank=0,
-                world=1, allreduce=None, timings=None, draws="host"):
+                world=1, allreduce=None, timings=None, draws="host", dectype="sumprod2"):
     """sim_ldpc (sparc_ldpc.py:1064-1124) over the blocks seed0, seed0 + 1, ...
     with everything but the draws on the device: blocks until MIN_ERRORS block
     errors or MAX_BLOCKS blocks, consumed in seed order whatever ``batch`` and
     ``world``.  Returns dict(ber, blocks, block_errors, bit_errors, nit_total)
     with ber = bit_errors / (blocks * N) from the integer counts (:1119).
-    draws="device": the draws on the device too (only the seeds go up)."""
+    draws="device": the draws on the device too (only the seeds go up).
+    dectype: the decoder (code.decode_batch's names; with a layered one
+    nit_total counts sweeps)."""
     _check_draws(draws)
+    if dectype not in _ldpc._ALGOS:
+        raise NameError("Decoder type unknonwn")
     if ldpcparams.r_ldpc not in _RATES:
         raise NameError("Rate unsupported")
     code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype)
-    r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, "sumprod2", rank, world,
+    r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, dectype, rank, world,
                   allreduce, timings, draws)
     return dict(ber=r["bit_errors"] / (r["blocks"] * code.N), blocks=r["blocks"], block_errors=r["block_errors"],
                 bit_errors=r["bit_errors"], nit_total=r["iters_total"])
