@@ -14,7 +14,8 @@
  *  2. A context API for batches of B words sharing one graph (Monte-Carlo),
  *     with device-resident buffers for the joint SPARC/LDPC pipeline.
  *
- * All arithmetic is IEEE binary64 in the reference's per-node operation order.
+ * All arithmetic is IEEE binary64 in the reference's per-node operation order
+ * (the layered decoders also run in binary32 on request: LB_F32).
  * Graph arrays follow ldpc.py:694-786: vdeg[Nv], cdeg[Nc], intrlv[Nmsg]
  * (message index, in check-node order, of each variable-node port).
  */
@@ -37,6 +38,10 @@ enum {
 
 /* 3, 4: the layered schedule (see lb_set_layers) with sumprod2's / minsum's check rule */
 enum { LB_SUMPROD2 = 0, LB_SUMPROD = 1, LB_MINSUM = 2, LB_LAYERED_SUMPROD2 = 3, LB_LAYERED_MINSUM = 4 };
+/* Precision flag, OR-ed into algo: LB_LAYERED_SUMPROD2 | LB_F32 and
+ * LB_LAYERED_MINSUM | LB_F32 decode in binary32 (see "binary32" below).  On a
+ * flooding type it is LB_ERR_UNSUPPORTED. */
+#define LB_F32 0x100
 
 #define LB_MAX_ITCOUNT 200 /* c_ldpc.c:7 */
 
@@ -138,10 +143,35 @@ int lb_set_tail(lb_ctx* ctx, int tail_at);
  *
  * Measurement switches, read from the environment by lb_set_layers:
  * LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app in HBM although they would
- * fit; LDPC_BP_LAYERED_THREADS = the threads per workgroup (the results are
- * the same bits either way). */
+ * fit; LDPC_BP_LAYERED_THREADS = the threads per workgroup;
+ * LDPC_BP_LAYERED_F32_RESIDENT = 1 pads a binary32 workgroup's LDS so that it
+ * has its CU alone (the results are the same bits either way). */
 int lb_set_layers(lb_ctx* ctx, int nlayers, const int* first_check);
 int lb_layer_info(lb_ctx* ctx, long long* out);
+
+/* binary32: algo = LB_LAYERED_SUMPROD2 | LB_F32 or LB_LAYERED_MINSUM | LB_F32,
+ * wherever algo is taken, runs the same schedule with app, r, q, every Lxor
+ * and corr_factor held and rounded in binary32.  ch, app and iters keep their
+ * types and layouts: the kernel loads ch32 = (float)clip(ch, -2^100, 2^100)
+ * (NaN stays NaN, the sign of zero is kept; with variable degrees <= 255 |app|
+ * then stays below 2^108, so saturated inputs up to +-DBL_MAX or +-inf never
+ * meet as inf - inf) and stores app = (double)app32.  Layered minsum is the
+ * same IEEE operations as its statement in NumPy, bit for bit; layered
+ * sumprod2 evaluates log(1 + exp(-x)) with the hardware's binary32 exp2 and
+ * log2.  The stop test, the meaning of iters and max_iter = 0 (app = ch,
+ * unclamped) are the binary64 decoders'.  r and app live in LDS when
+ * (Nmsg + Nv) * 4 bytes fit, app alone when Nv * 4 bytes fit; r in HBM is kept
+ * in the context's message slices as floats.  LB_F32 on a flooding type is
+ * LB_ERR_UNSUPPORTED (binary32 exists for the layered types only); on a
+ * context without layers the layered types are LB_ERR_ARG in either precision.
+ *
+ * lb_layer_info_ex: precision 0 (binary64) or 1 (binary32); out[0..7] =
+ * nlayers, the largest layer's checks, where the messages live (2 / 1 / 0 as
+ * lb_layer_info's out[2]), threads per workgroup, dynamic LDS bytes,
+ * workgroups resident per CU of the sumprod2 and of the minsum instance (the
+ * runtime's occupancy figure at that thread count and LDS size; 0 before
+ * lb_set_layers), and the bytes per message (8 / 4). */
+int lb_layer_info_ex(lb_ctx* ctx, int precision, long long* out);
 
 /* ---- LDPC-only Monte-Carlo (sim_ldpc sparc_ldpc.py:1064-1124, ldpc_awgn.py, ldpc_bsc.py) ---- */
 /* Block s is its seed: RandomState(seeds[i]) draws randint(0, 2, K) into

@@ -21,7 +21,17 @@ with r held in HBM (LDPC_BP_LAYERED_LDS = 1), and both at a thread per check
 alternating rounds after a warm-up of each, written to
 results/ldpc_mc_layered.json: per leg the median end-to-end and device
 milliseconds, blocks/s, mean iterations or sweeps a block, bit and block
-errors.  The flooding leg of the same session is the yardstick."""
+errors.  The flooding leg of the same session is the yardstick.
+
+--dectype layered_sumprod2_f32 (or layered_minsum_f32), with --draws device:
+the binary32 layered decoder against the binary64 layered one and the flooding
+default on the same seeds, five alternating rounds after a warm-up of each,
+written to results/ldpc_mc_f32.json: per leg and round end-to-end and device
+milliseconds, sweeps a block, block and bit errors.  The bar of an opt-in
+path: every binary32 round's device time below every binary64 layered
+round's.  --sigma S runs the same legs at another noise level (fidelity: one
+at which the binary64 decoder leaves block errors in every round); those
+results are merged into the file under "fidelity", by sigma."""
 import argparse
 import json
 import os
@@ -42,11 +52,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--draws", default=None, choices=["device"],
                     help="time sim_ldpc_mc's host draws against its device draws instead")
-    ap.add_argument("--dectype", default=None, choices=["layered_sumprod2", "layered_minsum"],
-                    help="time the flooding decoder against this layered one instead (device draws)")
+    ap.add_argument("--dectype", default=None,
+                    choices=["layered_sumprod2", "layered_minsum", "layered_sumprod2_f32", "layered_minsum_f32"],
+                    help="time the flooding decoder against this layered one instead (device draws); _f32: "
+                         "the binary32 layered decoder against the binary64 one and flooding")
+    ap.add_argument("--sigma", type=float, default=None, help="noise level of the _f32 legs' fidelity run")
     args = ap.parse_args()
+    f32 = bool(args.dectype and args.dectype.endswith("_f32"))
     if args.out is None:
-        name = "ldpc_mc_layered.json" if args.dectype else "ldpc_mc_draws.json" if args.draws else "ldpc_mc.json"
+        name = "ldpc_mc_f32.json" if f32 else \
+            "ldpc_mc_layered.json" if args.dectype else "ldpc_mc_draws.json" if args.draws else "ldpc_mc.json"
         args.out = os.path.join(ROOT, "results", name)
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import ldpc
@@ -66,7 +81,7 @@ def main():
         sync()
         return time.perf_counter() - t0, ber
 
-    def new(seed0, draws="host", dectype=None):
+    def new(seed0, draws="host", dectype=None, sigma=sigma):
         tm = {}
         kw = {} if draws == "host" else {"draws": draws}
         if dectype:
@@ -79,6 +94,8 @@ def main():
         assert r["blocks"] == BLOCKS
         return wall, r, tm
 
+    if f32:
+        return f32_leg(args, new, sigma)
     if args.dectype:
         return layered_leg(args, new, sigma, lp)
     if args.draws:
@@ -141,6 +158,38 @@ def draws_leg(args, new, sigma):
     )
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+def f32_leg(args, new, sigma0):
+    rounds = 5
+    sigma = args.sigma if args.sigma is not None else sigma0
+    base = args.dectype[:-len("_f32")]
+    legs = {"flooding": base[len("layered_"):], "layered_f64": base, "layered_f32": args.dectype}
+    for dectype in legs.values():
+        new(1, "device", dectype, sigma)
+    runs = {leg: [] for leg in legs}
+    for k in range(rounds):
+        for leg, dectype in legs.items():
+            w, r, tm = new(100_000 * (k + 1), "device", dectype, sigma)
+            runs[leg].append(dict(wall_ms=w * 1e3, device_ms=tm["device_ms"], sweeps_per_block=r["nit_total"] / BLOCKS,
+                                  block_errors=r["block_errors"], bit_errors=r["bit_errors"]))
+    out = dict(workload="802.16 5/6 z=192, sigma=%.6f, %d blocks, batch %d, draws on the device, %s" %
+               (sigma, BLOCKS, BATCH, args.dectype), rounds=rounds)
+    for leg in legs:
+        out[leg] = dict(median_wall_ms=statistics.median(x["wall_ms"] for x in runs[leg]),
+                        median_device_ms=statistics.median(x["device_ms"] for x in runs[leg]), runs=runs[leg])
+    out["speedup_device_f32_over_f64"] = out["layered_f64"]["median_device_ms"] / out["layered_f32"]["median_device_ms"]
+    out["bar_every_f32_device_time_below_every_f64"] = bool(
+        max(x["device_ms"] for x in runs["layered_f32"]) < min(x["device_ms"] for x in runs["layered_f64"]))
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.sigma is not None and os.path.exists(args.out):  # the fidelity run joins the timing run's file
+        with open(args.out) as fh:
+            whole = json.load(fh)
+        whole.setdefault("fidelity", {})["sigma_%g" % sigma] = out
+        out = whole
     with open(args.out, "w") as fh:
         fh.write(json.dumps(out, indent=1) + "\n")
 

@@ -11,6 +11,17 @@ leg records its layout.  Prints one JSON line and writes it to
 results/bp_sweep_time.json (or the second argument).
 
     python scripts/bp_sweep_time.py [B,B,... [out.json]]
+
+--f32 (first argument): the binary32 layered decoders (LB_F32) against the
+binary64 ones instead, sumprod2 and minsum: as the library lays them out (two
+768-thread workgroups resident on a CU), held to one resident workgroup
+(LDPC_BP_LAYERED_F32_RESIDENT = 1) and at 384 threads.  One context per leg,
+a warm-up of each, then five rounds with the legs interleaved; written to
+results/bp_sweep_time_f32.json.  The library is the one LDPC_BP_LIB names
+(recorded as "library"): run it once more on a -DLB_F32_OCML build (make
+f32_ocml) for the device library's expf / logf against the hardware's.
+
+    python scripts/bp_sweep_time.py --f32 [B,B,... [out.json]]
 """
 import ctypes as ct
 import json
@@ -26,9 +37,65 @@ from sparc_ldpc_amd import ldpc  # noqa: E402
 D = ct.POINTER(ct.c_double)
 lib = ldpc.load_bp_library()
 assert lib.lb_device_count() > 0, "no HIP device visible"
+F32 = len(sys.argv) > 1 and sys.argv[1] == "--f32"
+if F32:
+    del sys.argv[1]
 BS = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [256, 1024]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "results", "bp_sweep_time.json")
+OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(
+    ROOT, "results", "bp_sweep_time_f32.json" if F32 else "bp_sweep_time.json")
+
+
+def f32_legs():
+    env = ("LDPC_BP_LAYERED_F32_RESIDENT", "LDPC_BP_LAYERED_THREADS")
+    legs = {}
+    for a in ("sumprod2", "minsum"):
+        legs[f"{a}_f64"] = (f"layered_{a}", None, None)
+        legs[f"{a}_f32"] = (f"layered_{a}_f32", None, None)
+        legs[f"{a}_f32_one_resident"] = (f"layered_{a}_f32", "1", None)
+        legs[f"{a}_f32_384"] = (f"layered_{a}_f32", None, "384")
+        legs[f"{a}_f64_384"] = (f"layered_{a}", None, "384")
+    codes = {}
+    for leg, (dectype, *knobs) in legs.items():
+        for name, val in zip(env, knobs):
+            os.environ.pop(name, None)
+            if val is not None:
+                os.environ[name] = val
+        c = ldpc.code("802.16", "5/6", 192)
+        c._algo(dectype)  # sets the layers under this leg's switches
+        codes[leg] = c
+    for name in env:
+        os.environ.pop(name, None)
+    out = {"library": os.path.basename(ldpc.LIB_PATH), "rounds": 5}
+    for B in BS:
+        CH = np.ascontiguousarray(3.0 * np.random.RandomState(B).randn(B, codes["sumprod2_f64"].N))
+        for leg, c in codes.items():
+            assert lib.lb_stage(c._context(), B, CH.ctypes.data_as(D)) == 0
+            for k in (4, 12):
+                c.run_buffers(B, legs[leg][0], max_iter=k)  # warm-up
+        t = {leg: {4: [], 12: []} for leg in legs}
+        for _ in range(5):
+            for leg, c in codes.items():
+                for k in (4, 12):
+                    c.run_buffers(B, legs[leg][0], max_iter=k)
+                    t[leg][k].append(c.mc_event_ms())
+                    assert (c.fetch_buffers(B, app=False)[1] == k).all()  # no word stopped early
+        for leg in legs:
+            sweeps = [(b - a) / 8 * 1e3 for a, b in zip(t[leg][4], t[leg][12])]
+            out.setdefault(leg, {})[str(B)] = dict(ms_at_4=t[leg][4], ms_at_12=t[leg][12], us_per_launch_sweep=sweeps,
+                                                   median_us_per_launch_sweep=statistics.median(sweeps))
+    for leg, c in codes.items():
+        out[leg]["layout"] = c.layer_info("f32" if "_f32" in leg else "f64")
+    return out
+
+
+if F32:
+    out = f32_legs()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    with open(OUT, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+    sys.exit(0)
 L = "layered_sumprod2"
 # leg -> (decoder, LDPC_BP_LAYERED_LDS, LDPC_BP_LAYERED_THREADS), read when the leg's code sets its layers
 LEGS = {"flooding": ("sumprod2", None, None), "layered": (L, None, None), "layered_192": (L, None, "192"),

@@ -30,6 +30,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "ldpc_bp_int.h"
@@ -110,31 +111,59 @@ __device__ __forceinline__ double lxor(double a, double b) {
   return L;
 }
 
+// Binary32 twin (the layered decoders with LB_F32; tests/ldpc_f32_ref.py is its
+// statement): the same sign rule and minimum, and the corrections c(|a + b|) -
+// c(|a - b|), c(x) = log(1 + exp(-x)), every operation rounded to binary32.
+// exp and log are the hardware's v_exp_f32 / v_log_f32 (base 2, the constants
+// folded in): about ten instructions an Lxor against the binary64 rule's 140.
+// 1 + exp(-x) lies in [1, 2], so v_log_f32 sees no subnormal, and a v_exp_f32
+// result under 2^-126 (flushed) is lost in 1 + . anyway.  -DLB_F32_OCML takes
+// the device library's expf / logf instead (DESIGN.md section 10 has both timed).
+__device__ __forceinline__ float corr32(float x) {
+#ifdef LB_F32_OCML
+  return logf(1.0f + expf(-x));
+#else
+  return 0.693147180559945f * __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * x));
+#endif
+}
+
+template <bool CORR>
+__device__ __forceinline__ float lxor(float a, float b) {
+  float L = (signbit(a) == signbit(b)) ? 1.0f : -1.0f;
+  L *= fminf(fabsf(a), fabsf(b));
+  if (CORR) {
+    L += corr32(fabsf(a + b));
+    L -= corr32(fabsf(a - b));
+  }
+  return L;
+}
+
 // Lxfb (c_ldpc.c:294-314) in place on one check node's dc messages:
 // f[k] = Lxor(f[k-1], L[k]); b[k] = Lxor(b[k+1], L[k]);
 // out[0] = b[1], out[dc-1] = f[dc-2], out[k] = Lxor(f[k-1], b[k+1]).
 // f stays in registers (unrolled to DCMAX with guards); b is carried down.
 // Returns b[0], the LLR of the XOR of all inputs (stopping rule).
 template <int DCMAX, bool CORR, typename P>
-__device__ __forceinline__ double lxfb(P L, int dc) {
-  double f[DCMAX];
+__device__ __forceinline__ auto lxfb(P L, int dc) {
+  using T = std::remove_cv_t<std::remove_reference_t<decltype(L[0])>>;  // double, or float (LB_F32)
+  T f[DCMAX];
   f[0] = L[0];
 #pragma unroll
   for (int k = 1; k < DCMAX; ++k)
     if (k < dc) f[k] = lxor<CORR>(f[k - 1], L[k]);
-  double b = 0.0;
+  T b = 0;
 #pragma unroll
   for (int k = DCMAX - 1; k >= 1; --k) {
     if (k == dc - 1) {
       b = L[k];
       L[k] = f[k - 1];
     } else if (k < dc - 1) {
-      const double lk = L[k];
+      const T lk = L[k];
       L[k] = lxor<CORR>(f[k - 1], b);
       b = lxor<CORR>(b, lk);
     }
   }
-  const double l0 = L[0];
+  const T l0 = L[0];
   L[0] = b;
   return lxor<CORR>(b, l0);
 }
@@ -148,10 +177,10 @@ __device__ __forceinline__ double lxfb(P L, int dc) {
 // dc - 1 Lxor latencies plus one, against 2 (dc - 2) in lxfb's
 // forward-then-backward form.  The same operations on the same operands:
 // bit-identical to lxfb.
-template <int DC, bool CORR>
-__device__ __forceinline__ double lxfb_fixed_regs(const double (&l)[DC], double (&o)[DC]) {
+template <int DC, bool CORR, typename T>
+__device__ __forceinline__ T lxfb_fixed_regs(const T (&l)[DC], T (&o)[DC]) {
   static_assert(DC >= 3, "fixed-degree checks");
-  double f[DC - 1], b[DC];
+  T f[DC - 1], b[DC];
   f[0] = l[0];
   b[DC - 1] = l[DC - 1];
 #pragma unroll
@@ -166,12 +195,12 @@ __device__ __forceinline__ double lxfb_fixed_regs(const double (&l)[DC], double 
   return b[0];  // = Lxor(b[1], L[0]), lxfb's return value
 }
 
-template <int DC, bool CORR>
-__device__ __forceinline__ double lxfb_fixed(double* L) {
-  double l[DC], o[DC];
+template <int DC, bool CORR, typename T>
+__device__ __forceinline__ T lxfb_fixed(T* L) {
+  T l[DC], o[DC];
 #pragma unroll
   for (int k = 0; k < DC; ++k) l[k] = L[k];
-  const double r = lxfb_fixed_regs<DC, CORR>(l, o);
+  const T r = lxfb_fixed_regs<DC, CORR>(l, o);
 #pragma unroll
   for (int k = 0; k < DC; ++k) L[k] = o[k];
   return r;
@@ -179,8 +208,10 @@ __device__ __forceinline__ double lxfb_fixed(double* L) {
 
 // One check node's rule on its dc messages at L (in place): the reference's
 // three decoders.  Returns whether the check is unsatisfied (the stopping rule).
+// On binary32 messages (sumprod2 and minsum only) corr is rounded to binary32 once.
 template <int ALGO, int DCMAX, int DCFIX, typename P>
 __device__ __forceinline__ bool check_rule(P L, int dc, double corr) {
+  using T = std::remove_cv_t<std::remove_reference_t<decltype(L[0])>>;
   bool bad;
   if (ALGO == LB_SUMPROD) {  // c_ldpc.c:76-102
     double aggr = 1.0;
@@ -192,12 +223,13 @@ __device__ __forceinline__ bool check_rule(P L, int dc, double corr) {
     bad = 2.0 * atanh(aggr) <= 0.0;
     for (int k = 0; k < dc; ++k) L[k] = 2.0 * atanh(aggr / L[k]);
   } else if (ALGO == LB_SUMPROD2) {  // c_ldpc.c:183-194
-    if constexpr (DCFIX > 0) bad = lxfb_fixed<DCFIX, true>(L) <= 0.0;
-    else bad = lxfb<DCMAX, true>(L, dc) <= 0.0;
+    if constexpr (DCFIX > 0) bad = lxfb_fixed<DCFIX, true>(L) <= T(0);
+    else bad = lxfb<DCMAX, true>(L, dc) <= T(0);
   } else {  // minsum, c_ldpc.c:364-372 with node-aligned offsets
-    if constexpr (DCFIX > 0) bad = lxfb_fixed<DCFIX, false>(L) <= 0.0;
-    else bad = lxfb<DCMAX, false>(L, dc) <= 0.0;
-    for (int k = 0; k < dc; ++k) L[k] *= corr;
+    if constexpr (DCFIX > 0) bad = lxfb_fixed<DCFIX, false>(L) <= T(0);
+    else bad = lxfb<DCMAX, false>(L, dc) <= T(0);
+    const T cf = (T)corr;
+    for (int k = 0; k < dc; ++k) L[k] *= cf;
   }
   return bad;
 }
@@ -301,6 +333,13 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bp(Bp
 // iters = the sweeps run before the test passed, or maxit.
 // MODE 2: r and app in LDS; 1: app in LDS, r in the word's HBM slice; 0: both
 // in HBM (app in the output array itself).
+//
+// T = float (LB_F32): app, r, q and every Lxor in binary32, the statement being
+// tests/ldpc_f32_ref.py.  ch is converted on load, clamped to +-2^100 (NaN and
+// the sign of zero kept): with variable degrees up to 255 |app| stays under
+// 2^108, so no inf - inf arises from saturated inputs; app is converted back on
+// store.  The word's HBM slice of gmsg (Nmsg doubles) holds r as Nmsg floats
+// and, in MODE 0, app as Nv <= Nmsg floats behind it.
 struct BplArgs {
   const double* ch;   // [B][Nv]
   double* app;        // [B][Nv]
@@ -313,19 +352,27 @@ struct BplArgs {
   double corr;
 };
 
-template <int ALGO, int DCMAX, int DCFIX, int MODE>
-__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(BplArgs a) {
-  extern __shared__ double lds_l[];
-  __shared__ int unsat[2];
+__device__ __forceinline__ void ch_load(double& dst, double x) { dst = x; }
+__device__ __forceinline__ void ch_load(float& dst, double x) {
+  const double lim = 0x1p100;
+  dst = (float)(x > lim ? lim : (x < -lim ? -lim : x));  // NaN passes both tests
+}
+
+template <typename T, int ALGO, int DCMAX, int DCFIX, int MODE>
+__device__ __forceinline__ void bpl_word(const BplArgs& a, T* lds, int* unsat) {
+  constexpr bool F32 = sizeof(T) == 4;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int Nv = a.Nv, Nc = a.Nc;
   const double* ch = a.ch + (size_t)b * Nv;
   double* out = a.app + (size_t)b * Nv;
-  double* app = MODE >= 1 ? lds_l : out;
-  double* r = MODE == 2 ? lds_l + Nv : a.gmsg + (size_t)b * a.Nmsg;
+  T* slice = reinterpret_cast<T*>(a.gmsg + (size_t)b * a.Nmsg);
+  T* app;
+  if constexpr (F32) app = MODE >= 1 ? lds : slice + a.Nmsg;
+  else app = MODE >= 1 ? lds : out;
+  T* r = MODE == 2 ? lds + Nv : slice;
 
-  for (int i = tid; i < Nv; i += nt) app[i] = ch[i];
-  for (int i = tid; i < a.Nmsg; i += nt) r[i] = 0.0;
+  for (int i = tid; i < Nv; i += nt) ch_load(app[i], ch[i]);
+  for (int i = tid; i < a.Nmsg; i += nt) r[i] = 0;
   if (tid < 2) unsat[tid] = 0;
   __syncthreads();
 
@@ -336,9 +383,9 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(B
       const int s = a.cstart[c], e1 = a.cstart[c + 1];
       bool odd = false, undecided = false;
       for (int e = s; e < e1; ++e) {
-        const double x = app[a.evar[e]];
-        odd ^= x < 0.0;
-        undecided |= !(x > 0.0 || x < 0.0);  // +-0 or NaN
+        const T x = app[a.evar[e]];
+        odd ^= x < T(0);
+        undecided |= !(x > T(0) || x < T(0));  // +-0 or NaN
       }
       if (odd || undecided) unsat[it & 1] = 1;
     }
@@ -351,7 +398,7 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(B
       const int e0 = a.cstart[c0], e1 = a.cstart[c1];
       for (int e = e0 + tid; e < e1; e += nt) {
         const int v = a.evar[e];
-        const double q = app[v] - r[e];
+        const T q = app[v] - r[e];
         app[v] = q;
         r[e] = q;
       }
@@ -368,9 +415,28 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(B
       __syncthreads();
     }
   }
-  if (MODE >= 1)
+  if (F32 || MODE >= 1)
     for (int i = tid; i < Nv; i += nt) out[i] = app[i];
   if (tid == 0) a.iters[b] = it;
+}
+
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(BplArgs a) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  bpl_word<double, ALGO, DCMAX, DCFIX, MODE>(a, lds_l, unsat);
+}
+
+// The binary32 instances.  The straight-line dc = 20 instance's second bound
+// asks for registers that allow two workgroups' waves on a CU (2 x 768 threads:
+// 6 waves per SIMD, at most 80 VGPRs): the 802.16 5/6 z=192 image is 78 KB, so
+// two words share a CU.  The general instances keep what 1024 threads imply
+// (4 waves per SIMD): DCMAX = 32 holds 32 forward values in registers.
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads, DCFIX > 0 ? 6 : 4) k_bpl32(BplArgs a) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  bpl_word<float, ALGO, DCMAX, DCFIX, MODE>(a, reinterpret_cast<float*>(lds_l), unsat);
 }
 
 // ---------------------------------------------------------------------------
@@ -590,7 +656,13 @@ KernelFn pick_kernel(int algo, int maxdc, bool lds, bool fixed = false) {
 using LayeredFn = void (*)(BplArgs);
 
 template <int ALGO, int MODE>
-LayeredFn pick_layered_dc(int maxdc, bool fixed) {
+LayeredFn pick_layered_dc(int maxdc, bool fixed, bool f32) {
+  if (f32) {
+    if (fixed) return k_bpl32<ALGO, 32, 20, MODE>;
+    if (maxdc <= 8) return k_bpl32<ALGO, 8, 0, MODE>;
+    if (maxdc <= 16) return k_bpl32<ALGO, 16, 0, MODE>;
+    return k_bpl32<ALGO, 32, 0, MODE>;
+  }
   if (fixed) return k_bpl<ALGO, 32, 20, MODE>;
   if (maxdc <= 8) return k_bpl<ALGO, 8, 0, MODE>;
   if (maxdc <= 16) return k_bpl<ALGO, 16, 0, MODE>;
@@ -598,14 +670,14 @@ LayeredFn pick_layered_dc(int maxdc, bool fixed) {
 }
 
 // algo: LB_LAYERED_SUMPROD2 or LB_LAYERED_MINSUM; the check rules are the flooding decoders'
-LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode) {
+LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
   if (algo == LB_LAYERED_SUMPROD2)
-    return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(maxdc, fixed)
-           : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(maxdc, fixed)
-                       : pick_layered_dc<LB_SUMPROD2, 0>(maxdc, fixed);
-  return mode == 2   ? pick_layered_dc<LB_MINSUM, 2>(maxdc, fixed)
-         : mode == 1 ? pick_layered_dc<LB_MINSUM, 1>(maxdc, fixed)
-                     : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed);
+    return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(maxdc, fixed, f32)
+           : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(maxdc, fixed, f32)
+                       : pick_layered_dc<LB_SUMPROD2, 0>(maxdc, fixed, f32);
+  return mode == 2   ? pick_layered_dc<LB_MINSUM, 2>(maxdc, fixed, f32)
+         : mode == 1 ? pick_layered_dc<LB_MINSUM, 1>(maxdc, fixed, f32)
+                     : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
 }
 
 using TailFn = void (*)(TailArgs);
@@ -718,21 +790,35 @@ int ensure_slices(lb_ctx* c, int need) {
 int ensure_msg(lb_ctx* c, int B, bool tail) { return ensure_slices(c, tail ? 2 * B : (c->lds ? 0 : B)); }
 
 // the layered schedule: one launch, one workgroup per word, no tail (never waits)
-int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
-                   int max_iter) {
-  const int mode = c->lmode;
-  int rc;
-  if ((rc = ensure_slices(c, mode == 2 ? 0 : B))) return rc;
-  const LayeredFn fn = pick_layered(algo, c->maxdc, c->lfixed, mode);
-  const size_t shm = mode == 2   ? (size_t)(c->Nv + c->Nmsg) * sizeof(double)
-                     : mode == 1 ? (size_t)c->Nv * sizeof(double)
-                                 : 0;
-  const unsigned bit = 1u << (algo - LB_LAYERED_SUMPROD2);
-  if (shm && !(c->lattrs & bit)) {
+// The layered instance of a decoder type (algo without LB_F32) and precision on this context, and
+// its dynamic LDS bytes; raises the instance's LDS limit on first use.
+int layered_instance(lb_ctx* c, int algo, bool f32, LayeredFn* fn, size_t* shm) {
+  const int mode = f32 ? c->lmode32 : c->lmode;
+  const size_t el = f32 ? sizeof(float) : sizeof(double);
+  *fn = pick_layered(algo, c->maxdc, c->lfixed, mode, f32);
+  *shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
+  // measurement switch: more than half a CU's LDS, so that a binary32 workgroup has its CU alone
+  if (f32 && c->lone32) *shm = std::max(*shm, kLdsBytes / 2 + 64);
+  const unsigned bit = 1u << (algo - LB_LAYERED_SUMPROD2 + (f32 ? 2 : 0));
+  if (*shm && !(c->lattrs & bit)) {
     // the whole budget, whatever this code needs: contexts of other codes share the instance
-    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
+    HIP_TRY(hipFuncSetAttribute((const void*)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
     c->lattrs |= bit;
   }
+  return LB_OK;
+}
+
+int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, bool f32, double corr,
+                   int max_iter) {
+  const int mode = f32 ? c->lmode32 : c->lmode;
+  // binary32 with app in HBM keeps it behind r in the word's slice of d_msg (Nmsg doubles)
+  if (f32 && mode == 0 && c->Nv > c->Nmsg)
+    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
+  int rc;
+  if ((rc = ensure_slices(c, mode == 2 ? 0 : B))) return rc;
+  LayeredFn fn;
+  size_t shm;
+  if ((rc = layered_instance(c, algo, f32, &fn, &shm))) return rc;
   BplArgs a;
   a.ch = d_ch;
   a.app = d_app;
@@ -793,7 +879,11 @@ int set_attrs(lb_ctx* c) {
 // queued without waiting (see TailArgs)
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
            int max_iter, bool sized_on_host) {
+  const bool f32 = algo >= 0 && (algo & LB_F32);
+  if (f32) algo &= ~LB_F32;
   if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  if (f32 && algo < LB_LAYERED_SUMPROD2)
+    return fail(LB_ERR_UNSUPPORTED, "binary32 (LB_F32) exists for the layered decoder types only");
   if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
   if (algo >= LB_LAYERED_SUMPROD2 && !c->nlayers)
     return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
@@ -805,7 +895,7 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
     HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
     return LB_OK;
   }
-  if (algo >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, algo, corr, max_iter);
+  if (algo >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, algo, f32, corr, max_iter);
   // the tail's variable kernel puts the words on the grid's y dimension (<= 65535)
   const bool tail = c->tail_at > 0 && max_iter > c->tail_at && B <= 65535;
   int rc;
@@ -1253,10 +1343,16 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   c->maxlayer = maxlayer;
   const size_t app_bytes = (size_t)c->Nv * sizeof(double), r_bytes = (size_t)c->Nmsg * sizeof(double);
   c->lmode = app_bytes + r_bytes <= kLdsBytes - 64 ? 2 : (app_bytes <= kLdsBytes - 64 ? 1 : 0);
+  // binary32 (LB_F32): the same choice at the element size 4
+  const size_t app32 = (size_t)c->Nv * sizeof(float), r32 = (size_t)c->Nmsg * sizeof(float);
+  c->lmode32 = app32 + r32 <= kLdsBytes - 64 ? 2 : (app32 <= kLdsBytes - 64 ? 1 : 0);
   // measurement and test switches: LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app out of LDS
   // although they would fit; LDPC_BP_LAYERED_THREADS = the workgroup's threads (a multiple of 64
   // within the instance's bound)
-  if (const char* e = getenv("LDPC_BP_LAYERED_LDS"); e && *e) c->lmode = std::min(c->lmode, std::max(0, atoi(e)));
+  if (const char* e = getenv("LDPC_BP_LAYERED_LDS"); e && *e) {
+    c->lmode = std::min(c->lmode, std::max(0, atoi(e)));
+    c->lmode32 = std::min(c->lmode32, std::max(0, atoi(e)));
+  }
   c->lfixed = c->mindc == c->maxdc && c->maxdc == 20;
   // a thread per edge of the largest layer: gather and scatter take one pass where the bound
   // allows, the check chains run on the first waves (measured against a thread per check at
@@ -1265,6 +1361,10 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   c->lnt = std::min(ntmax, std::max(128, (maxedges + 63) / 64 * 64));
   if (const char* e = getenv("LDPC_BP_LAYERED_THREADS"); e && *e)
     c->lnt = std::min(ntmax, std::max(64, atoi(e) / 64 * 64));
+  // LDPC_BP_LAYERED_F32_RESIDENT = 1: one binary32 workgroup per CU (padded dynamic LDS), to time
+  // against the two that share a CU at 802.16 5/6 z=192
+  if (const char* e = getenv("LDPC_BP_LAYERED_F32_RESIDENT"); e && *e) c->lone32 = atoi(e) == 1;
+  else c->lone32 = false;
   c->lattrs = 0;
   return LB_OK;
 }
@@ -1275,6 +1375,29 @@ int lb_layer_info(lb_ctx* c, long long* out) {
   out[1] = c->maxlayer;
   out[2] = c->lmode;
   out[3] = c->lnt;
+  return LB_OK;
+}
+
+int lb_layer_info_ex(lb_ctx* c, int precision, long long* out) {
+  if (!c || !out || precision < 0 || precision > 1) return fail(LB_ERR_ARG, "bad layer info arguments");
+  const bool f32 = precision == 1;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = c->nlayers;
+  out[1] = c->maxlayer;
+  out[2] = f32 ? c->lmode32 : c->lmode;
+  out[3] = c->lnt;
+  out[7] = f32 ? sizeof(float) : sizeof(double);
+  if (!c->nlayers) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  for (int k = 0; k < 2; ++k) {  // the sumprod2 and the minsum instance
+    LayeredFn fn;
+    size_t shm;
+    int rc, n = 0;
+    if ((rc = layered_instance(c, LB_LAYERED_SUMPROD2 + k, f32, &fn, &shm))) return rc;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
+    out[4] = (long long)shm;
+    out[5 + k] = n;
+  }
   return LB_OK;
 }
 

@@ -45,8 +45,11 @@ struct lb_ctx {
   std::vector<int> h_evar, h_cstart;
   int* d_lfirst = nullptr;
   int nlayers = 0, maxlayer = 0, lmode = 0, lnt = 0;
+  int lmode32 = 0;            // lmode of the binary32 instances (LB_F32): the same choice at 4 bytes a message
   bool lfixed = false;
-  unsigned lattrs = 0;        // layered instances whose dynamic LDS size has been raised (bit per algorithm)
+  bool lone32 = false;        // LDPC_BP_LAYERED_F32_RESIDENT = 1: binary32 workgroups padded to one per CU
+  unsigned lattrs = 0;        // layered instances whose dynamic LDS size has been raised (bit per algorithm
+                              // and precision)
   lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
 };
 

@@ -25,8 +25,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_BP_LIB") or os.path.join(_HERE, "libldpc_bp.so")
 
 LB_SUMPROD2, LB_SUMPROD, LB_MINSUM, LB_LAYERED_SUMPROD2, LB_LAYERED_MINSUM = 0, 1, 2, 3, 4
+LB_F32 = 0x100  # precision flag OR-ed into a layered type: binary32 messages
 _ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM,
-          "layered_sumprod2": LB_LAYERED_SUMPROD2, "layered_minsum": LB_LAYERED_MINSUM}
+          "layered_sumprod2": LB_LAYERED_SUMPROD2, "layered_minsum": LB_LAYERED_MINSUM,
+          "layered_sumprod2_f32": LB_LAYERED_SUMPROD2 | LB_F32, "layered_minsum_f32": LB_LAYERED_MINSUM | LB_F32}
 _REFERENCE_ALGOS = ("sumprod2", "sumprod", "minsum")  # code.decode's names (ldpc.py:855-930)
 _CHANNELS = {"awgn": 0, "bsc": 1}  # lb_mc_run / lb_draw_blocks kinds
 
@@ -35,7 +37,7 @@ EXPORTS = (
     "sumprod", "sumprod2", "minsum", "Lxor", "Lxfb",
     "lb_create", "lb_destroy", "lb_decode", "lb_decode_device", "lb_stage", "lb_run", "lb_wait",
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
-    "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info",
+    "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info", "lb_layer_info_ex",
     "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
 )
 
@@ -62,6 +64,7 @@ _SIG = {
     "lb_set_tail": (_I, [_P, _I]),
     "lb_set_layers": (_I, [_P, _I, _IP]),
     "lb_layer_info": (_I, [_P, ct.POINTER(ct.c_int64)]),
+    "lb_layer_info_ex": (_I, [_P, _I, ct.POINTER(ct.c_int64)]),
     "lb_device_count": (_I, []),
     "lb_last_error": (ct.c_char_p, []),
     "lb_version": (ct.c_char_p, []),
@@ -218,7 +221,9 @@ class code:
     ``decode_batch``, ``run_buffers``, ``mc_blocks`` and ``mc_blocks_seeds``
     also take dectype "layered_sumprod2" / "layered_minsum": the layered
     schedule over the protograph rows (include/ldpc_bp.h, lb_set_layers), whose
-    ``it`` counts sweeps."""
+    ``it`` counts sweeps; and "layered_sumprod2_f32" / "layered_minsum_f32":
+    the same schedule on binary32 messages (LB_F32; CH and app stay float64,
+    CH is clamped to +-2**100 on load)."""
 
     def __init__(self, standard="802.11n", rate="1/2", z=27, ptype="A", device=None):
         self.standard = standard
@@ -299,13 +304,23 @@ class code:
         _check(_layered_entry("lb_set_layers")(self._context(), len(fc) - 1, fc.ctypes.data_as(_IP)))
         self._layers_set = True
 
-    def layer_info(self):
+    def layer_info(self, precision="f64"):
         """lb_layer_info: layers, the largest layer's checks, where the layered
         decoder keeps its messages (2: r and app in LDS, 1: app in LDS, 0: HBM)
-        and its threads per workgroup."""
-        out = (ct.c_int64 * 4)()
-        _check(_layered_entry("lb_layer_info")(self._context(), out))
-        return dict(zip(("nlayers", "max_layer", "lds_messages", "threads"), list(out)))
+        and its threads per workgroup.  precision="f32" (lb_layer_info_ex) gives
+        these for the binary32 decoders and adds lds_bytes (dynamic LDS of a
+        workgroup), resident / resident_minsum (workgroups of the sumprod2 /
+        minsum instance a CU holds at once) and message_bytes."""
+        if precision not in ("f64", "f32"):
+            raise ValueError('precision must be "f64" or "f32"')
+        keys = ("nlayers", "max_layer", "lds_messages", "threads")
+        if precision == "f64":
+            out = (ct.c_int64 * 4)()
+            _check(_layered_entry("lb_layer_info")(self._context(), out))
+            return dict(zip(keys, list(out)))
+        out = (ct.c_int64 * 8)()
+        _check(_layered_entry("lb_layer_info_ex")(self._context(), 1, out))
+        return dict(zip(keys + ("lds_bytes", "resident", "resident_minsum", "message_bytes"), list(out)))
 
     def decode_batch(self, CH, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
         """Decode B words (rows of CH, channel LLRs) -> (app (B, N) float64, it (B,) int)."""

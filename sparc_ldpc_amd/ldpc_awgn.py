@@ -39,8 +39,8 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     SNR, nblocks, nblockerrors, nblocks*K, nbiterrors, nit_total) and appends
     them to ``results_file`` in its line format when given.  draws="device":
     the blocks are drawn on the GPU from their seeds (ldpc_mc).  dectype: the
-    decoder (code.decode_batch's names, the layered ones included; nit_total
-    then counts sweeps)."""
+    decoder (code.decode_batch's names, the layered ones and their binary32
+    "_f32" forms included; nit_total then counts sweeps)."""
     ldpc_mc._check_draws(draws)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")

@@ -23,7 +23,8 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
     Point i decodes the blocks seed0 + i * 10_000_000, ... (ldpc_mc's BSC
     contract: random_sample(N) < p flips the bit).  draws="device": the
     uniform values are drawn on the GPU from the seeds (the same values).
-    dectype: the decoder (code.decode_batch's names, the layered ones included)."""
+    dectype: the decoder (code.decode_batch's names, the layered ones and their
+    binary32 "_f32" forms included)."""
     ldpc_mc._check_draws(draws)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")

@@ -192,7 +192,8 @@ def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000
     with ber = bit_errors / (blocks * N) from the integer counts (:1119).
     draws="device": the draws on the device too (only the seeds go up).
     dectype: the decoder (code.decode_batch's names; with a layered one
-    nit_total counts sweeps)."""
+    nit_total counts sweeps; "layered_sumprod2_f32" / "layered_minsum_f32"
+    decode on binary32 messages)."""
     _check_draws(draws)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
