@@ -78,9 +78,9 @@ int sa_create(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
 enum {
   SA_PLAN_DEFAULT = 0,
   SA_PLAN_SEC3 = 1 << 0,      /* one codeword: three sections per workgroup (k_sec43) where it fits */
-  SA_PLAN_NO_SEC3 = 1 << 1,   /* one codeword: never k_sec43 (pairs, k_sec4) */
-  SA_PLAN_ROW16 = 1 << 2,     /* one codeword: 16-row k_row2 blocks where they fit */
-  SA_PLAN_NO_ROW16 = 1 << 3,  /* one codeword: 32-row k_row2 blocks */
+  SA_PLAN_NO_SEC3 = 1 << 1,   /* one codeword: never k_sec43 (pairs, k_sec4, in front of 16-row blocks in binary32) */
+  SA_PLAN_ROW16 = 1 << 2,     /* one codeword: 16-row k_row2 blocks where they fit (the binary32 default, except at L = 2 x CUs) */
+  SA_PLAN_NO_ROW16 = 1 << 3,  /* one codeword: 32-row k_row2 blocks (the default in binary64, and at L = 2 x CUs) */
   SA_PLAN_NO_PT = 1 << 4,     /* Ab partials [G][n] instead of row-block major (bit-identical) */
   SA_PLAN_ZIL = 1 << 5,       /* batched: z / Ab partials codeword-interleaved (the default since round 4) */
   SA_PLAN_NO_ZIL = 1 << 6,    /* batched: z / Ab partials [B][n] (binary32 too) */
@@ -90,7 +90,10 @@ enum {
   SA_PLAN_EAGER = 1 << 10,    /* sa_run launches eagerly instead of replaying a captured hipGraph */
   SA_PLAN_ONE_PASS = 1 << 11, /* batched: every section group of an XCD in one pass of the work order */
   SA_PLAN_NO_LANES = 1 << 12, /* every sa_run on one stream and one set of state buffers (no decode lanes) */
-  SA_PLAN_ALL = (1 << 13) - 1
+  SA_PLAN_SEC4Q = 1 << 13,    /* one codeword: four sections per workgroup (k_sec44) wherever pairs would run, M <= 512
+                                 (never chosen by the rules: faster with two decodes in flight, slower alone) */
+  SA_PLAN_NO_SEC4Q = 1 << 14, /* one codeword: never k_sec44 (the default; overrides SA_PLAN_SEC4Q) */
+  SA_PLAN_ALL = (1 << 15) - 1
 };
 int sa_create_ex(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
                  int backend, int precision, int device, int plan);
@@ -384,7 +387,8 @@ typedef enum sa_sec_path {
   SA_SEC_K_SEC43 = 5,  /* k_sec43: four waves per section, triples of sections */
   SA_SEC_DENSE_I8 = 6, /* dense int8 MFMA GEMMs */
   SA_SEC_MATRIX = 7,   /* caller-matrix f32 / f64 MFMA GEMMs */
-  SA_SEC_K_SECG = 8    /* k_secg: z from global memory, 32-bit bucket entries (n past the LDS image or >= 65535) */
+  SA_SEC_K_SECG = 8,   /* k_secg: z from global memory, 32-bit bucket entries (n past the LDS image or >= 65535) */
+  SA_SEC_K_SEC44 = 9   /* k_sec44: four waves per section, quads of sections (1024-thread workgroups) */
 } sa_sec_path;
 typedef enum sa_row_kernel {
   SA_ROW_K_ROW = 0,     /* k_row: 64-row blocks */

@@ -107,6 +107,9 @@ struct sa_ctx {
   int G3 = 0;          // k_sec43 triples of sections (used when sec3)
   bool sec3 = false;   // k_sec43 (three sections x 4 waves per workgroup) chosen over k_sec4
   size_t sec3_lds = 0;
+  int G4 = 0;          // k_sec44 quads of sections (used when sec4q)
+  bool sec4q = false;  // k_sec44 (four sections x 4 waves per workgroup, the pair table) chosen over k_sec4
+  size_t sec4q_lds = 0;
   uint32_t* d_fwd3 = nullptr;
   bool pt_on = false;  // row-block-major Ab partials between k_sec4 / k_sec43 and k_row2 (SecArgs::pt)
   bool sec4 = false;   // k_sec4 (4 waves per section) fits and is chosen
@@ -271,12 +274,14 @@ struct Plan {
   bool zil = false;    // z and the Ab partials codeword-interleaved (zil_for)
   bool dense() const { return sec == SA_SEC_DENSE || sec == SA_SEC_DENSE_I8 || sec == SA_SEC_MATRIX; }
   bool batched() const { return sec == SA_SEC_K_SECB; }
-  bool multiwave() const { return sec == SA_SEC_K_SEC2 || sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43; }
+  bool multiwave() const {
+    return sec == SA_SEC_K_SEC2 || sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43 || sec == SA_SEC_K_SEC44;
+  }
   // k_row2 launches can carry the iters writes (RowArgs::itset); the small-batch Hadamard decode uses them
   bool row_sets_iters() const { return row == SA_ROW_K_ROW2 || row == SA_ROW_K_ROW2_16; }
   bool it_row() const { return !dense() && !batched() && row_sets_iters(); }
-  // k_sec4 / k_sec43 can take the previous estimate as zero (SecArgs::bzero)
-  bool bzero() const { return sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43; }
+  // k_sec4 / k_sec43 / k_sec44 can take the previous estimate as zero (SecArgs::bzero)
+  bool bzero() const { return sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43 || sec == SA_SEC_K_SEC44; }
 };
 
 // Row kernel for B codewords: k_row2 (32-row blocks, 16-row for one codeword
@@ -284,7 +289,7 @@ struct Plan {
 // (n % 4 == 0) or k_rowv<2> (n even) when their blocks cover the CUs twice,
 // else k_row (64 rows); k_rowc behind the codeword-interleaved k_secb.
 // Section path: the GEMMs / GEMVs of a dense backend; k_secb from 4 codewords;
-// a multi-wave kernel (k_sec43 over k_sec4 over k_sec2) when its workgroups
+// a multi-wave kernel (k_sec43 over k_sec44 over k_sec4 over k_sec2) when its workgroups
 // fill at least half of the CUs; else k_sec's (k_secg's) row splits.
 inline Plan plan_for(const sa_ctx* c, int B) {
   Plan p;
@@ -314,8 +319,8 @@ inline Plan plan_for(const sa_ctx* c, int B) {
     p.G = p.Gb = c->Gb;
     p.CB = c->CB;
   } else if (c->backend == SA_BACKEND_HADAMARD && c->G2 > 0 && c->G2 * B * 2 >= c->n_cus) {
-    p.sec = c->sec3 ? SA_SEC_K_SEC43 : (c->sec4 ? SA_SEC_K_SEC4 : SA_SEC_K_SEC2);
-    p.G = p.Gb = c->sec3 ? c->G3 : c->G2;  // triples / pairs of sections
+    p.sec = c->sec3 ? SA_SEC_K_SEC43 : (c->sec4q ? SA_SEC_K_SEC44 : (c->sec4 ? SA_SEC_K_SEC4 : SA_SEC_K_SEC2));
+    p.G = p.Gb = c->sec3 ? c->G3 : (c->sec4q ? c->G4 : c->G2);  // triples / quads / pairs of sections
     if (p.sec != SA_SEC_K_SEC2 && p.row_sets_iters() && c->pt_on) p.pt = p.row == SA_ROW_K_ROW2_16 ? 16 : kRow2Rows;
   } else {
     p.sec = c->big ? SA_SEC_K_SECG : SA_SEC_K_SEC;

@@ -388,6 +388,16 @@ __global__ void __launch_bounds__(NT) k_row2(RowArgs<real> a) {
         tt[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
 #pragma unroll
       for (int u = 0; u < U; ++u) acc += tt[u];
+    } else if (pt && (R == 16 || sizeof(real) == 4) && G == NG * (U / 2)) {
+      // the same with G = 128 (c2 on k_sec44): half the loads per thread
+      constexpr int UH = U / 2;
+      const real* pb = abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R;
+      real tt[UH];
+#pragma unroll
+      for (int u = 0; u < UH; ++u)
+        tt[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
+#pragma unroll
+      for (int u = 0; u < UH; ++u) acc += tt[u];
     } else
     for (int g0 = pg; g0 < G; g0 += NG * U) {
       real tt[U];

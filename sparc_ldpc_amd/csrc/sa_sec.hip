@@ -1,5 +1,5 @@
 // sa_sec.hip — the single-codeword section kernels (k_sec, k_secg, k_sec2,
-// k_sec4, k_sec43) and their launchers.
+// k_sec4, k_sec43, k_sec44) and their launchers.
 #include "sa_host.h"
 
 namespace sa {
@@ -569,22 +569,27 @@ __device__ __forceinline__ real combine_q(const real* red, int w0, int f) {
   return x[0];
 }
 
-// The pair / triple section kernels' body (SPW sections x QW waves).
+// The pair / triple / quad section kernels' body (SPW sections x QW waves).
+// Quads (SPW = 4) have no table of their own: workgroup g reads the pair
+// table's rows 2g and 2g + 1, and a row's partial is the sum of its two pair
+// sums, (+-v0 +- v1) + (+-v2 +- v3).
 template <typename real, int EQ, int QW, int SPW = 2>
 __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
-  static_assert(SPW == 2 || SPW == 3, "sections per workgroup");
+  static_assert(SPW == 2 || SPW == 3 || SPW == 4, "sections per workgroup");
   STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = SPW * QW * 64;
   // bucket h-steps whose table loads are in flight together: triples take 8
   // (C4, 32 h-steps: half the first round trip's table bytes, the rest lands
   // during the gather; 961 -> 996 cw/s), pairs 16 (c2: all 16 up front; 8 neutral)
-  constexpr int KH = EQ >= 8 ? 4 : (SPW == 3 ? 8 : 16);
+  // (binary64 quads 8: all 16 up front spill at the 128 VGPRs of a 1024-thread workgroup)
+  constexpr int KH = EQ >= 8 ? 4 : ((SPW == 3 || (SPW == 4 && sizeof(real) == 8)) ? 8 : 16);
   constexpr int NQ = (EQ + 3) / 4;
   // rows per thread per pass, all Ab-table loads issued with the first loads: n <= 4608 (pairs,
   // C2) / 8448 (triples, C4 n = 8294) in one pass (a second pass reloads the table mid-phase:
-  // one more memory round trip)
+  // one more memory round trip); quads: 5 x 1024 rows, two table words per row
   constexpr int KR = ((SPW == 3 ? 8448 : 4608) + NT - 1) / NT;
+  constexpr int FW = SPW == 4 ? 2 : 1;  // table words per row
   const int g = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int sidx = wv / QW, q = wv % QW;
@@ -608,9 +613,13 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   // the HBM bucket tables as a workgroup-uniform base + this wave's 32-bit offset
   const uint16_t* ibase = a.inv + (size_t)g * SPW * a.w;
   const unsigned ioff = (unsigned)((lc - g * SPW) * a.w + eoff);
-  const uint32_t* fw = (SPW == 2 ? a.fwd2 : a.fwd3) + (size_t)g * n;
+  const uint32_t* fw = (SPW == 3 ? a.fwd3 : a.fwd2) + (size_t)(SPW == 4 ? 2 * g : g) * n;
+  // quads: the second pair's row of the pair table; where the last workgroup
+  // has no second pair (L % 4 in {1, 2}) its own first pair's row stands in
+  // (those sections' T is zero, whatever k the entries name)
+  const uint32_t* fw1 = a.fwd2 + (size_t)(2 * g + 1 < (a.L + 1) / 2 ? 2 * g + 1 : 2 * g) * n;
   ushort4 tb[KH][NQ];
-  uint32_t f[KR];  // Ab-table entries of this thread's rows
+  uint32_t f[KR][FW];  // Ab-table entries of this thread's rows
 
   // Load order: z's LDS-DMA first, then the z^2 partials and tau_{t-1}, then
   // the tables, all unconditional (straight-line).  While an LDS-DMA is in
@@ -690,7 +699,8 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #pragma unroll
   for (int u = 0; u < KR; ++u) {  // unconditional (clamped): see load_section
     const int r = u * NT + tid;
-    f[u] = ld_off(fw, (unsigned)(r < n ? r : 0) * 4u);  // uniform base + 32-bit offset
+    f[u][0] = ld_off(fw, (unsigned)(r < n ? r : 0) * 4u);  // uniform base + 32-bit offset
+    if constexpr (SPW == 4) f[u][1] = ld_off(fw1, (unsigned)(r < n ? r : 0) * 4u);
   }
   STAMP(3);
   fwht_wave<real, EQ>(v, lane, 64);
@@ -746,10 +756,11 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   STAMP(7);
   if (tid == 0) {
     real bsum = red[0 * 4 + 3] + red[QW * 4 + 3];
-    if constexpr (SPW == 3) bsum += red[2 * QW * 4 + 3];
+    if constexpr (SPW >= 3) bsum += red[2 * QW * 4 + 3];
+    if constexpr (SPW == 4) bsum += red[3 * QW * 4 + 3];
     a.bbp[(size_t)b * a.G + g] = bsum;
   }
-  // Ab partial of the pair (triple) for every row
+  // Ab partial of the pair (triple, quad) for every row
   real* abp = a.abp + ((size_t)b * a.G + g) * n;
   const int psh = a.pt == 16 ? 4 : 5;  // pt: rows per block 16 / 32
   const size_t npad = (size_t)((n + (1 << psh) - 1) >> psh) << psh;
@@ -765,7 +776,8 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #pragma unroll
       for (int u = 0; u < KR; ++u) {
         const int r = r0 + u * NT + tid;
-        f[u] = fw[r < n ? r : 0];
+        f[u][0] = fw[r < n ? r : 0];
+        if constexpr (SPW == 4) f[u][1] = fw1[r < n ? r : 0];
       }
     }
     real* const pbase = sbase + (size_t)((r0 + tid) >> sh) * gstride + ((r0 + tid) & smask);
@@ -773,13 +785,24 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
     auto row = [&](int u, int r) {
       real t;
       if constexpr (SPW == 2) {
-        const uint32_t e = f[u];
+        const uint32_t e = f[u][0];
         const real v0 = ts[e & 0x7fffu];
         const real v1 = ts[M + ((e >> 16) & 0x7fffu)];
         t = (e & 0x8000u) ? -v0 : v0;
         t += (e & 0x80000000u) ? -v1 : v1;
+      } else if constexpr (SPW == 4) {
+        const uint32_t e = f[u][0], e1 = f[u][1];
+        const real v0 = ts[e & 0x7fffu];
+        const real v1 = ts[M + ((e >> 16) & 0x7fffu)];
+        const real v2 = ts[2 * M + (e1 & 0x7fffu)];
+        const real v3 = ts[3 * M + ((e1 >> 16) & 0x7fffu)];
+        t = (e & 0x8000u) ? -v0 : v0;
+        t += (e & 0x80000000u) ? -v1 : v1;
+        real t1 = (e1 & 0x8000u) ? -v2 : v2;
+        t1 += (e1 & 0x80000000u) ? -v3 : v3;
+        t += t1;
       } else {
-        const uint32_t e = f[u];
+        const uint32_t e = f[u][0];
         const real v0 = ts[e & 0x1ffu];
         const real v1 = ts[M + ((e >> 10) & 0x1ffu)];
         const real v2 = ts[2 * M + ((e >> 20) & 0x1ffu)];
@@ -799,6 +822,11 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
       // LDS reads of several rows are in flight together (c2: n = 9 x 512)
 #pragma unroll
       for (int u = 0; u < KR; ++u) row(u, r0 + u * NT + tid);
+    } else if (SPW == 4 && r0 + NT * (KR - 1) <= n) {
+      // quads at c2 (n = 4.5 x 1024): only the last row of a thread may be missing
+#pragma unroll
+      for (int u = 0; u < KR - 1; ++u) row(u, r0 + u * NT + tid);
+      if (r0 + (KR - 1) * NT + tid < n) row(KR - 1, r0 + (KR - 1) * NT + tid);
     } else {
 #pragma unroll
       for (int u = 0; u < KR; ++u) {
@@ -820,6 +848,11 @@ __global__ void __launch_bounds__(512) k_sec4(SecArgs<real> a) { secq_body<real,
 // puts one workgroup on every CU where pairs leave half the CUs with two.
 template <typename real, int E4>
 __global__ void __launch_bounds__(768) k_sec43(SecArgs<real> a) { secq_body<real, E4, 4, 3>(a); }
+// Four sections per workgroup (16 waves): L = 4 x CUs / 2 (c2 on 256 CUs) gives
+// one launch half the chip, so the section kernels of two decodes in flight
+// (the decode lanes) share no CU, and half the pairs' Ab partials and z fills.
+template <typename real, int E4>
+__global__ void __launch_bounds__(1024) k_sec44(SecArgs<real> a) { secq_body<real, E4, 4, 4>(a); }
 
 // ---- launchers ------------------------------------------------------------
 template <typename real, int E>
@@ -834,7 +867,7 @@ void launch_sec_e(sa_ctx* c, const Plan& p, int B, SecArgs<real> a) {
   if (c->prof) c->prof->end(c->at().stream);
 }
 
-// One iteration's section step on the plan's multi-wave kernel (pairs or triples of sections)
+// One iteration's section step on the plan's multi-wave kernel (pairs, triples or quads of sections)
 template <typename real>
 int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero) {
   SecArgs<real> a = sec_args<real>(c, p, SEC_AMP, t, es);
@@ -852,6 +885,13 @@ int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void*
         case 1: plaunch(c, k_sec43<real, 1>, grid, 768, c->sec3_lds, a); break;
         case 2: plaunch(c, k_sec43<real, 2>, grid, 768, c->sec3_lds, a); break;
         default: return fail(SA_ERR_UNSUPPORTED, "k_sec43: M");
+      }
+      break;
+    case SA_SEC_K_SEC44:
+      switch (c->M / 256) {
+        case 1: plaunch(c, k_sec44<real, 1>, grid, 1024, c->sec4q_lds, a); break;
+        case 2: plaunch(c, k_sec44<real, 2>, grid, 1024, c->sec4q_lds, a); break;
+        default: return fail(SA_ERR_UNSUPPORTED, "k_sec44: M");
       }
       break;
     case SA_SEC_K_SEC4:
@@ -922,6 +962,7 @@ static hipError_t sec_lds_attrs_t() {
   SA_A((k_sec4<real, 1>)) SA_A((k_sec4<real, 2>)) SA_A((k_sec4<real, 4>)) SA_A((k_sec4<real, 8>))
   SA_A((k_sec4<real, 16>))
   SA_A((k_sec43<real, 1>)) SA_A((k_sec43<real, 2>))
+  SA_A((k_sec44<real, 1>)) SA_A((k_sec44<real, 2>))
 #undef SA_A
   return e;
 }

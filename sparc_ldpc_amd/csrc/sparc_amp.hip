@@ -1229,6 +1229,33 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
       c->G3 = G3;
       c->sec3_lds = need3;
     }
+    // k_sec44: four sections per workgroup on the pair table.  z + 4 sections'
+    // T + one exchange image per section + reductions.  SA_PLAN_SEC4Q runs it
+    // wherever pairs would run (SA_PLAN_SEC3 beside it keeps triples) and is
+    // never chosen otherwise.  At c2 (L = 2 x CUs) one launch takes half the
+    // CUs, so the section kernels of two decodes in flight (decode lanes) stop
+    // sharing CUs, and the Ab partials and z fills halve: +4.2 % to +4.8 % over
+    // pairs with lanes (as much as triples), but a lone decode, which leaves
+    // the other half of the chip idle, takes 0.74 ms against 0.68 ms (DESIGN.md
+    // section 8, "lane shapes"), so it stays an option for throughput callers
+    const size_t need4q = zbytes + 8 * (size_t)M * s + 64 * s;
+    // (M <= 512: the larger sections' instances spill at 128 VGPRs)
+    const bool fits4q = c->sec4 && backend == SA_BACKEND_HADAMARD && M <= 512 && need4q <= 160 * 1024;
+    if (fits4q && (plan & SA_PLAN_SEC4Q) && !(plan & (SA_PLAN_SEC3 | SA_PLAN_NO_SEC4Q))) {
+      c->sec4q = true;
+      c->sec3 = false;
+      c->G4 = (L + 3) / 4;
+      c->sec4q_lds = need4q;
+    }
+    // 32-row k_row2 blocks where pairs fill the chip exactly (L = 2 x CUs,
+    // c2): with two decodes in flight every CU already holds a section
+    // workgroup of each lane, and the 144 32-row workgroups of a row step
+    // disturb them less than 288 16-row ones: c2 +3 % with lanes, every run
+    // above every 16-row run, the lone decode inside its run-to-run range
+    // ("lane shapes").  SA_PLAN_ROW16
+    // keeps 16-row blocks, and so does SA_PLAN_NO_SEC3, which asks for the
+    // pair shape as it was (k_sec4 in front of 16-row blocks)
+    if (c->G2 == c->n_cus && !(plan & (SA_PLAN_ROW16 | SA_PLAN_NO_SEC3))) c->row16 = false;
   }
   if (lane_open(c->lane[0]) != SA_OK) {
     delete c;

@@ -313,7 +313,7 @@ class SparcOperator:
 
     # indexed by sparc_amp.h's SA_SEC_* / SA_ROW_* (sa_plan's out8[0] / out8[6])
     SECTION_KERNELS = ("k_sec", "k_sec2", "k_secb", "dense", "k_sec4", "k_sec43", "dense_mfma", "matrix_mfma",
-                       "k_secg")
+                       "k_secg", "k_sec44")
     ROW_KERNELS = ("k_row", "k_row2", "k_rowv16B", "k_rowv8B", "k_row2_16", "k_rowc")
 
     def fetch_z(self, B):
