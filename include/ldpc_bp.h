@@ -220,6 +220,43 @@ int lb_mc_run_seeds(lb_ctx* ctx, int nblk, const unsigned int* seeds, int K, dou
 int lb_draw_blocks_device(lb_ctx* ctx, const unsigned int* seeds, int nblk, int K, int N, int kind,
                           unsigned char* u, double* w);
 
+/* One operating point as a stream (opt-in; layered decoders only).  The blocks
+ * of lb_mc_run_seeds (same seeds, K, a, kind: the same draws, code words and
+ * channel values), in chunks of `chunk` blocks over two lanes (two streams,
+ * each with its own buffers).  Per chunk: the draw and the encoder / channel
+ * kernels over the whole chunk, then one persistent kernel of `slots`
+ * workgroups.  Each workgroup takes the chunk's next block by a ticket, decodes
+ * it with the layered decoder's arithmetic (per block the same errs and iters
+ * as lb_mc_run_seeds, bit for bit) and counts its bit errors itself, until the
+ * chunk is out of tickets; no workgroup waits for another.  Chunk k + 1's
+ * workgroups take the CUs that chunk k's last blocks leave, so a block that
+ * runs to max_iter holds one CU, not the launch.  Device memory for the
+ * decoder grows with `slots`, not with `chunk`.
+ *
+ * min_errors > 0: the stopping rule of a Monte-Carlo point, blocks in seed
+ * order until min_errors of them have errs > 0 (or nblk).  n* = the blocks
+ * that rule consumes.  The host consumes chunk k - 2 before it queues chunk k
+ * (at most two chunks in flight) and queues nothing once the rule is met; on
+ * the device a block is skipped when the block errors of the consumed chunks,
+ * of the chunk before and of its own chunk's finished blocks reach
+ * min_errors: all of them lie at smaller seed indices, so only blocks from n*
+ * on are ever skipped.  Blocks below n* are always decoded; which blocks from
+ * n* on are decoded depends on timing.  min_errors <= 0: every block is decoded.
+ *
+ * errs[nblk], iters[nblk] in seed order; iters = -1 (and errs = 0) marks a
+ * block that was not decoded.  out[0..3] = n* (nblk when the rule is off or
+ * never met), the blocks decoded, the slots per lane used, the chunks queued.
+ * slots <= 0: the workgroups the device holds at once (the instance's
+ * residency on a CU times the CU count); at most the chunk's blocks are used.
+ * algo: a flooding type is LB_ERR_UNSUPPORTED.  No layers set, chunk <= 0, or
+ * K / a / kind that lb_mc_run_seeds refuses: LB_ERR_ARG, and the context is
+ * left as it was.  max_iter = 0 as in lb_mc_run_seeds (errs of the channel's
+ * hard decision, iters = 0).  Host pointers; blocking; lb_run_event_ms gives
+ * the device time of the whole call, both lanes. */
+int lb_mc_stream_seeds(lb_ctx* ctx, int nblk, const unsigned int* seeds, int K, double a, int kind, int chunk,
+                       int slots, int min_errors, int algo, double corr_factor, int max_iter, int* errs,
+                       int* iters, long long* out);
+
 int lb_device_count(void);
 const char* lb_last_error(void);
 const char* lb_version(void);

@@ -31,7 +31,23 @@ milliseconds, sweeps a block, block and bit errors.  The bar of an opt-in
 path: every binary32 round's device time below every binary64 layered
 round's.  --sigma S runs the same legs at another noise level (fidelity: one
 at which the binary64 decoder leaves block errors in every round); those
-results are merged into the file under "fidelity", by sigma."""
+results are merged into the file under "fidelity", by sigma.
+
+--stream: one operating point as a stream of refilled decoder slots
+(code.mc_stream_seeds) against the batch path (code.mc_blocks_seeds) on the same
+8192 seeds, draws on the device, layered_sumprod2_f32 and layered_sumprod2, at
+sigma 0.5203 and 0.535, no stopping rule.  Legs: the batch path at batch 1024
+and at batch 8192, the stream at chunk 1024 / 2048 / 4096 / 8192 with the
+default slots, and at the default chunk with half and twice the slots.  After
+a warm-up of each leg five interleaved rounds; per round end-to-end and device
+milliseconds; every leg's per-block results are asserted equal to the batch
+path's.  The bar of an opt-in path: at sigma 0.535 every round of the default
+stream below every round of batch 1024, in device time, for both decoders.
+Then the rule: sim_ldpc_mc(MIN_ERRORS=100) at both sigmas, at 0.48 (no block
+fails) and at 0.56 (the rule is met within the first chunk) through batch
+1024, batch 8192 and the stream, the dicts asserted equal, with the blocks
+decoded against the blocks used.  Written to
+results/ldpc_mc_stream.json."""
 import argparse
 import json
 import os
@@ -57,7 +73,11 @@ def main():
                     help="time the flooding decoder against this layered one instead (device draws); _f32: "
                          "the binary32 layered decoder against the binary64 one and flooding")
     ap.add_argument("--sigma", type=float, default=None, help="noise level of the _f32 legs' fidelity run")
+    ap.add_argument("--stream", action="store_true",
+                    help="time the streamed operating point against the batch path instead")
     args = ap.parse_args()
+    if args.stream:
+        return stream_leg(args)
     f32 = bool(args.dectype and args.dectype.endswith("_f32"))
     if args.out is None:
         name = "ldpc_mc_f32.json" if f32 else \
@@ -191,6 +211,94 @@ def f32_leg(args, new, sigma0):
         whole.setdefault("fidelity", {})["sigma_%g" % sigma] = out
         out = whole
     with open(args.out, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+def stream_leg(args):
+    import sparc_ldpc_amd as sp
+    from sparc_ldpc_amd import ldpc
+    out_path = args.out or os.path.join(ROOT, "results", "ldpc_mc_stream.json")
+    lib = ldpc.load_bp_library()
+    assert lib.lb_device_count() > 0, "no HIP device visible"
+    rounds, seeds = 5, np.arange(100_000, 100_000 + BLOCKS)
+    lp = sp.LDPCParams("802.16", "5/6", 192)
+    code = ldpc.code(lp.standard, lp.r_ldpc, lp.z, lp.ptype)
+    default = ldpc.STREAM_CHUNK
+
+    def timed(fn):
+        assert lib.hipDeviceSynchronize() == 0
+        t0 = time.perf_counter()
+        r = fn()
+        assert lib.hipDeviceSynchronize() == 0
+        return (time.perf_counter() - t0) * 1e3, code.mc_event_ms(), r
+
+    out = dict(workload="802.16 5/6 z=192, %d blocks, draws on the device, no stopping rule" % BLOCKS, rounds=rounds,
+               default_chunk=default, points={})
+    for dectype in ("layered_sumprod2_f32", "layered_sumprod2"):
+        full =code.mc_stream_seeds(seeds, 0.5, "awgn", BLOCKS, dectype)[2]["slots"]
+        for sigma in (0.5203, 0.535):
+            legs = {"batch_1024": lambda: code.mc_blocks_seeds(seeds, sigma, "awgn", 1024, dectype),
+                    "batch_8192": lambda: code.mc_blocks_seeds(seeds, sigma, "awgn", 8192, dectype)}
+            for chunk in (1024, 2048, 4096, 8192):
+                legs["stream_%d" % chunk] = lambda chunk=chunk: code.mc_stream_seeds(seeds, sigma, "awgn", chunk, dectype)
+            for name, n in (("half", full // 2), ("twice", full * 2)):
+                legs["stream_%d_slots_%s" % (default, name)] = \
+                    lambda n=n: code.mc_stream_seeds(seeds, sigma, "awgn", default, dectype, slots=n)
+            ref = None
+            for leg, fn in legs.items():  # warm-up, and every leg against the batch path
+                r = fn()
+                ref = ref or r
+                assert np.array_equal(r[0], ref[0]) and np.array_equal(r[1], ref[1]), leg
+            runs = {leg: [] for leg in legs}
+            for _ in range(rounds):
+                for leg, fn in legs.items():
+                    wall, dev, _r = timed(fn)
+                    runs[leg].append(dict(wall_ms=wall, device_ms=dev))
+            pt = dict(default_slots=full, sweeps_per_block=float(ref[1].mean()), block_errors=int((ref[0] > 0).sum()))
+            for leg in legs:
+                pt[leg] = dict(median_device_ms=statistics.median(x["device_ms"] for x in runs[leg]),
+                               median_wall_ms=statistics.median(x["wall_ms"] for x in runs[leg]), runs=runs[leg])
+            dflt, a = runs["stream_%d" % default], runs["batch_1024"]
+            pt["bar_every_stream_device_time_below_every_batch_1024"] = bool(
+                max(x["device_ms"] for x in dflt) < min(x["device_ms"] for x in a))
+            pt["speedup_device_over_batch_1024"] = pt["batch_1024"]["median_device_ms"] / \
+                pt["stream_%d" % default]["median_device_ms"]
+            pt["speedup_device_over_batch_8192"] = pt["batch_8192"]["median_device_ms"] / \
+                pt["stream_%d" % default]["median_device_ms"]
+            out["points"]["%s sigma=%g" % (dectype, sigma)] = pt
+            print(dectype, sigma, {leg: round(pt[leg]["median_device_ms"], 3) for leg in legs}, flush=True)
+    # the stopping rule
+    out["rule"] = {}
+    for dectype in ("layered_sumprod2_f32", "layered_sumprod2"):
+        for sigma in (0.48, 0.5203, 0.535, 0.56):
+            row = {}
+            want = None
+            for leg, kw in (("batch_1024", dict(batch=1024)), ("batch_8192", dict(batch=8192)),
+                            ("stream", dict(batch=default, stream=True))):
+                res = []
+                for _ in range(3):
+                    tm = {}
+                    wall, _dev, r = timed(lambda: sp.sim_ldpc_mc(lp, sigma, MIN_ERRORS=100, MAX_BLOCKS=BLOCKS,
+                                                                  seed0=100_000, draws="device", dectype=dectype,
+                                                                  timings=tm, **kw))
+                    want = want or r
+                    assert r == want, (leg, r, want)
+                    used = r["blocks"]
+                    decoded = tm["stream"]["decoded"] if leg == "stream" else -(-used // kw["batch"]) * kw["batch"]
+                    res.append(dict(wall_ms=wall, device_ms=tm["device_ms"], blocks_decoded=min(decoded, BLOCKS)))
+                row[leg] = dict(median_wall_ms=statistics.median(x["wall_ms"] for x in res),
+                                median_device_ms=statistics.median(x["device_ms"] for x in res), runs=res[1:],
+                                first_run=res[0])
+            row["result"] = want
+            out["rule"]["%s sigma=%g" % (dectype, sigma)] = row
+            print(dectype, sigma, "rule", want["blocks"],
+                  {leg: (round(row[leg]["median_device_ms"], 3), row[leg]["runs"][-1]["blocks_decoded"])
+                   for leg in ("batch_1024", "batch_8192", "stream")}, flush=True)
+    out["bar_met"] = all(pt["bar_every_stream_device_time_below_every_batch_1024"]
+                         for name, pt in out["points"].items() if name.endswith("0.535"))
+    print(json.dumps({k: v for k, v in out.items() if k not in ("points", "rule")}))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
         fh.write(json.dumps(out, indent=1) + "\n")
 
 

@@ -358,14 +358,19 @@ __device__ __forceinline__ void ch_load(float& dst, double x) {
   dst = (float)(x > lim ? lim : (x < -lim ? -lim : x));  // NaN passes both tests
 }
 
+// `word` indexes ch; `slot` indexes what the decode owns while it runs: the app
+// output, the HBM message slice and iters.  One workgroup per word (k_bpl,
+// k_bpl32): both are blockIdx.x.  The persistent kernels (k_bpls, k_bpls32)
+// decode many words in one slot.  Returns the sweep count, the same in every
+// thread.
 template <typename T, int ALGO, int DCMAX, int DCFIX, int MODE>
-__device__ __forceinline__ void bpl_word(const BplArgs& a, T* lds, int* unsat) {
+__device__ __forceinline__ int bpl_word(const BplArgs& a, T* lds, int* unsat, int word, int slot) {
   constexpr bool F32 = sizeof(T) == 4;
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
   const int Nv = a.Nv, Nc = a.Nc;
-  const double* ch = a.ch + (size_t)b * Nv;
-  double* out = a.app + (size_t)b * Nv;
-  T* slice = reinterpret_cast<T*>(a.gmsg + (size_t)b * a.Nmsg);
+  const double* ch = a.ch + (size_t)word * Nv;
+  double* out = a.app + (size_t)slot * Nv;
+  T* slice = reinterpret_cast<T*>(a.gmsg + (size_t)slot * a.Nmsg);
   T* app;
   if constexpr (F32) app = MODE >= 1 ? lds : slice + a.Nmsg;
   else app = MODE >= 1 ? lds : out;
@@ -417,14 +422,15 @@ __device__ __forceinline__ void bpl_word(const BplArgs& a, T* lds, int* unsat) {
   }
   if (F32 || MODE >= 1)
     for (int i = tid; i < Nv; i += nt) out[i] = app[i];
-  if (tid == 0) a.iters[b] = it;
+  if (tid == 0) a.iters[slot] = it;
+  return it;
 }
 
 template <int ALGO, int DCMAX, int DCFIX, int MODE>
 __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpl(BplArgs a) {
   extern __shared__ double lds_l[];
   __shared__ int unsat[2];
-  bpl_word<double, ALGO, DCMAX, DCFIX, MODE>(a, lds_l, unsat);
+  (void)bpl_word<double, ALGO, DCMAX, DCFIX, MODE>(a, lds_l, unsat, blockIdx.x, blockIdx.x);
 }
 
 // The binary32 instances.  The straight-line dc = 20 instance's second bound
@@ -436,7 +442,102 @@ template <int ALGO, int DCMAX, int DCFIX, int MODE>
 __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads, DCFIX > 0 ? 6 : 4) k_bpl32(BplArgs a) {
   extern __shared__ double lds_l[];
   __shared__ int unsat[2];
-  bpl_word<float, ALGO, DCMAX, DCFIX, MODE>(a, reinterpret_cast<float*>(lds_l), unsat);
+  (void)bpl_word<float, ALGO, DCMAX, DCFIX, MODE>(a, reinterpret_cast<float*>(lds_l), unsat, blockIdx.x, blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------
+// Persistent layered decode-and-count (lb_mc_stream_seeds, ldpc_mc.hip)
+// ---------------------------------------------------------------------------
+// The grid is `slots` workgroups over one chunk of Monte-Carlo blocks.  Each
+// takes the chunk's next block by a ticket, decodes it with bpl_word in its
+// own slot (image in LDS, app / message slices in HBM indexed by blockIdx.x),
+// counts sum((app < 0) != x) and writes the block's two ints, until the chunk
+// is out of tickets.  No workgroup waits for another.
+//
+// Stop rule (min_errors > 0): a block is skipped (iters = -1, errs = 0) when
+// base + *eprev + *ecur >= min_errors: block errors of the chunks the host has
+// consumed, of the chunk before, and of this chunk's finished blocks.  The
+// counters are all one workgroup reads from another.  *ecur is read before the
+// ticket is taken (an acquire load, so that the ticket's atomic cannot be
+// issued ahead of it: a load and an L1 invalidate, no write-back): an error
+// seen there belongs to a block whose ticket was taken earlier, that is to a
+// smaller seed index, so the block asking lies behind the stopping block of
+// the sequential rule.  The sum only grows, so an old value only skips later.
+struct BplStreamArgs {
+  BplArgs w;          // ch: the chunk's words; app, gmsg, iters: one slice per slot
+  const uint8_t* x;   // [chunk][Nv] codeword bits
+  int* errs;          // [chunk] bit errors
+  int* iters;         // [chunk] sweeps, -1: skipped
+  int* ticket;        // the chunk's next block
+  const int* eprev;   // block errors of the chunk before
+  int* ecur;          // block errors among this chunk's finished blocks
+  int chunk, base, min_errors;
+};
+
+template <typename T, int ALGO, int DCMAX, int DCFIX, int MODE>
+__device__ __forceinline__ void bpl_stream(const BplStreamArgs& s, T* lds, int* unsat) {
+  __shared__ int next[3];  // ticket, skip, the word's bit errors
+  const int tid = threadIdx.x, nt = blockDim.x, slot = blockIdx.x, Nv = s.w.Nv;
+  for (;;) {
+    // the word before is done with next[], unsat[], its image and its slices:
+    // the next word's app = ch, r = 0 and unsat = 0 start behind this barrier
+    __syncthreads();
+    if (tid == 0) {
+      int skip = 0;
+      if (s.min_errors > 0) {
+        const int e0 = __hip_atomic_load(s.eprev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int e1 = __hip_atomic_load(s.ecur, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        skip = s.base + e0 + e1 >= s.min_errors;
+      }
+      next[0] = __hip_atomic_fetch_add(s.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      next[1] = skip;
+      next[2] = 0;
+    }
+    __syncthreads();
+    const int t = next[0];
+    if (t >= s.chunk) return;
+    if (next[1]) {
+      if (tid == 0) {
+        s.iters[t] = -1;
+        s.errs[t] = 0;
+      }
+      continue;
+    }
+    int it = 0;
+    const double* v = s.w.ch + (size_t)t * Nv;  // max_iter = 0: app = ch, unrounded, as the batch path has it
+    if (s.w.maxit > 0) {
+      it = bpl_word<T, ALGO, DCMAX, DCFIX, MODE>(s.w, lds, unsat, t, slot);
+      // every out[i] was written by this thread or in front of a barrier of bpl_word
+      v = s.w.app + (size_t)slot * Nv;
+    }
+    const uint8_t* xb = s.x + (size_t)t * Nv;
+    int cnt = 0;
+    for (int i = tid; i < Nv; i += nt) cnt += ((v[i] < 0.0) != (xb[i] != 0)) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if ((tid & 63) == 0 && cnt) atomicAdd(&next[2], cnt);
+    __syncthreads();
+    if (tid == 0) {
+      const int sum = next[2];
+      s.errs[t] = sum;
+      s.iters[t] = it;
+      if (sum) (void)__hip_atomic_fetch_add(s.ecur, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpls(BplStreamArgs s) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  bpl_stream<double, ALGO, DCMAX, DCFIX, MODE>(s, lds_l, unsat);
+}
+
+// (the bounds of k_bpl32: two workgroups of the dc = 20 instance share a CU)
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+__global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads, DCFIX > 0 ? 6 : 4) k_bpls32(BplStreamArgs s) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  bpl_stream<float, ALGO, DCMAX, DCFIX, MODE>(s, reinterpret_cast<float*>(lds_l), unsat);
 }
 
 // ---------------------------------------------------------------------------
@@ -680,6 +781,33 @@ LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
                      : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
 }
 
+// the persistent instances, over pick_layered's table
+using StreamFn = void (*)(BplStreamArgs);
+
+template <int ALGO, int MODE>
+StreamFn pick_stream_dc(int maxdc, bool fixed, bool f32) {
+  if (f32) {
+    if (fixed) return k_bpls32<ALGO, 32, 20, MODE>;
+    if (maxdc <= 8) return k_bpls32<ALGO, 8, 0, MODE>;
+    if (maxdc <= 16) return k_bpls32<ALGO, 16, 0, MODE>;
+    return k_bpls32<ALGO, 32, 0, MODE>;
+  }
+  if (fixed) return k_bpls<ALGO, 32, 20, MODE>;
+  if (maxdc <= 8) return k_bpls<ALGO, 8, 0, MODE>;
+  if (maxdc <= 16) return k_bpls<ALGO, 16, 0, MODE>;
+  return k_bpls<ALGO, 32, 0, MODE>;
+}
+
+StreamFn pick_stream(int algo, int maxdc, bool fixed, int mode, bool f32) {
+  if (algo == LB_LAYERED_SUMPROD2)
+    return mode == 2   ? pick_stream_dc<LB_SUMPROD2, 2>(maxdc, fixed, f32)
+           : mode == 1 ? pick_stream_dc<LB_SUMPROD2, 1>(maxdc, fixed, f32)
+                       : pick_stream_dc<LB_SUMPROD2, 0>(maxdc, fixed, f32);
+  return mode == 2   ? pick_stream_dc<LB_MINSUM, 2>(maxdc, fixed, f32)
+         : mode == 1 ? pick_stream_dc<LB_MINSUM, 1>(maxdc, fixed, f32)
+                     : pick_stream_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
+}
+
 using TailFn = void (*)(TailArgs);
 
 template <int ALGO>
@@ -834,6 +962,79 @@ int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_i
   a.maxit = max_iter;
   a.corr = corr;
   hipLaunchKernelGGL(fn, dim3(B), dim3(c->lnt), shm, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  return LB_OK;
+}
+
+// layered_instance for the persistent kernels (lattrs bits 4..7)
+int stream_instance(lb_ctx* c, int algo, bool f32, StreamFn* fn, size_t* shm) {
+  const int mode = f32 ? c->lmode32 : c->lmode;
+  const size_t el = f32 ? sizeof(float) : sizeof(double);
+  *fn = pick_stream(algo, c->maxdc, c->lfixed, mode, f32);
+  *shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
+  if (f32 && c->lone32) *shm = std::max(*shm, kLdsBytes / 2 + 64);
+  const unsigned bit = 16u << (algo - LB_LAYERED_SUMPROD2 + (f32 ? 2 : 0));
+  if (*shm && !(c->lattrs & bit)) {
+    HIP_TRY(hipFuncSetAttribute((const void*)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
+    c->lattrs |= bit;
+  }
+  return LB_OK;
+}
+
+// (lb::stream_plan, declared in ldpc_bp_int.h)
+int stream_plan(lb_ctx* c, int algo, int max_iter, int* resident) {
+  const bool f32 = algo >= 0 && (algo & LB_F32);
+  if (f32) algo &= ~LB_F32;
+  if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  if (algo < LB_LAYERED_SUMPROD2)
+    return fail(LB_ERR_UNSUPPORTED, "the block stream exists for the layered decoder types only");
+  if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
+  if (!c->nlayers) return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
+  if (f32 && c->lmode32 == 0 && c->Nv > c->Nmsg)
+    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
+  if (!resident) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  StreamFn fn;
+  size_t shm;
+  int rc, n = 0;
+  if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
+  *resident = std::max(1, n);
+  return LB_OK;
+}
+
+// (lb::launch_stream, declared in ldpc_bp_int.h; the arguments have passed stream_plan)
+int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter) {
+  const bool f32 = (algo & LB_F32) != 0;
+  algo &= ~LB_F32;
+  StreamFn fn;
+  size_t shm;
+  int rc;
+  if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
+  BplStreamArgs s;
+  s.w.ch = k.ch;
+  s.w.app = k.app;
+  s.w.iters = k.slot_iters;
+  s.w.gmsg = k.msg;
+  s.w.evar = c->d_evar;
+  s.w.cstart = c->d_cstart;
+  s.w.lfirst = c->d_lfirst;
+  s.w.Nv = c->Nv;
+  s.w.Nc = c->Nc;
+  s.w.Nmsg = c->Nmsg;
+  s.w.nlayers = c->nlayers;
+  s.w.maxit = max_iter;
+  s.w.corr = corr;
+  s.x = k.x;
+  s.errs = k.errs;
+  s.iters = k.iters;
+  s.ticket = k.ticket;
+  s.eprev = k.eprev;
+  s.ecur = k.ecur;
+  s.chunk = k.chunk;
+  s.base = k.base;
+  s.min_errors = k.min_errors;
+  hipLaunchKernelGGL(fn, dim3(slots), dim3(c->lnt), shm, st, s);
   HIP_TRY(hipGetLastError());
   return LB_OK;
 }

@@ -64,6 +64,27 @@ int ensure_io(lb_ctx* c, int B);
 // queue a decode of B words on the context's stream; sized_on_host = false never waits
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
            int max_iter, bool sized_on_host);
+// One chunk of lb_mc_stream_seeds for the persistent layered kernels (k_bpls,
+// k_bpls32 in ldpc_bp.hip): a grid of `slots` workgroups takes the chunk's
+// blocks by ticket, decodes and counts them.
+struct StreamChunk {
+  const double* ch;   // [chunk][Nv]
+  const uint8_t* x;   // [chunk][Nv]
+  double* app;        // [slots][Nv]
+  double* msg;        // [slots][Nmsg] (unused with r and app in LDS)
+  int* slot_iters;    // [slots]
+  int* errs;          // [chunk]
+  int* iters;         // [chunk], -1: skipped by the stop rule
+  int* ticket;        // zeroed
+  const int* eprev;   // block errors of the chunk before
+  int* ecur;          // zeroed: block errors of this chunk
+  int chunk, base, min_errors;
+};
+// Whether algo / max_iter can stream on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED; nothing is
+// changed then); resident (may be null): workgroups of the instance a CU holds at once
+int stream_plan(lb_ctx* c, int algo, int max_iter, int* resident);
+// queue one chunk on `st`; never waits
+int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter);
 // free the Monte-Carlo state of a context (ldpc_mc.hip)
 void mc_release(lb_ctx* c);
 

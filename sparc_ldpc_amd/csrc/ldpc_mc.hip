@@ -22,6 +22,19 @@
 //    from their seeds (k_mc_draw_blocks, legacy_mt_dev.h: one workgroup per
 //    block) on the context's stream, in front of k_mc_prep; only the seeds go
 //    up, through no staging buffer and no second stream.
+//  * lb_mc_stream_seeds: one operating point as a stream (opt-in, layered
+//    decoders).  The blocks in chunks over two lanes (the context's stream and
+//    `copy`, each lane with its own bits, noise, code words and channel LLRs):
+//    per chunk k_mc_draw_blocks and k_mc_prep over the whole chunk, unchanged,
+//    then one persistent kernel (k_bpls / k_bpls32, ldpc_bp.hip) of `slots`
+//    workgroups that take the chunk's blocks by ticket, decode them with the
+//    layered decoder's arithmetic and count their bit errors themselves, then
+//    an asynchronous copy of the chunk's two ints per block and an event.
+//    Chunk k + 1's workgroups take the CUs chunk k's last blocks leave.  The
+//    host consumes chunk k - 2 in seed order before it queues chunk k (two
+//    chunks in flight) and stops queuing once min_errors block errors are
+//    reached; the kernel skips blocks that are provably behind the stopping
+//    block.  Decoder memory grows with the slots, not with the chunk.
 
 #include <algorithm>
 #include <cmath>
@@ -55,6 +68,21 @@ struct lb_mc {
   hipStream_t copy = nullptr;
   hipEvent_t ev_up[2] = {nullptr, nullptr};    // staging buffer i has landed on the device
   hipEvent_t ev_prep[2] = {nullptr, nullptr};  // k_mc_prep has read device buffer i
+  // lb_mc_stream_seeds: lane 0 on the context's stream, lane 1 on `copy`; lane i draws into
+  // d_u[i] / d_w[i] and keeps its own codeword bits, channel LLRs and per-slot decoder slices
+  struct Lane {
+    uint8_t* x = nullptr;     // [capChunk][Nv]
+    double* ch = nullptr;     // [capChunk][Nv]
+    double* app = nullptr;    // [capSlots][Nv]
+    double* msg = nullptr;    // [capSlots][Nmsg]
+    int* it = nullptr;        // [capSlots]
+    hipEvent_t done = nullptr;  // the lane's last chunk has landed in h_res
+  } lane[2];
+  int capChunk = 0, capSlots = 0;
+  int* d_ctr = nullptr;       // a call's tickets [nchunks], then its block-error counters [nchunks + 1] (the first
+                              // stays 0); room for capCtr chunks
+  int capCtr = 0;
+  hipEvent_t ev_go = nullptr, ev_join = nullptr;  // the seeds and counters are up; lane 1 is through
 };
 
 namespace {
@@ -281,6 +309,55 @@ int ensure_results(lb_mc* m, int nblk) {
   return LB_OK;
 }
 
+void free_stream(lb_mc* m) {
+  for (lb_mc::Lane& l : m->lane) {
+    (void)hipFree(l.x);
+    (void)hipFree(l.ch);
+    (void)hipFree(l.app);
+    (void)hipFree(l.msg);
+    (void)hipFree(l.it);
+    l.x = nullptr;
+    l.ch = l.app = l.msg = nullptr;
+    l.it = nullptr;
+  }
+  m->capChunk = m->capSlots = 0;
+}
+
+// the lanes of lb_mc_stream_seeds for chunks of `chunk` blocks in `slots` slots, `nchunks` counters
+int ensure_stream(lb_ctx* c, int chunk, int slots, int nchunks, bool msg) {
+  lb_mc* m = c->mc;
+  const size_t N = (size_t)c->Nv;
+  int rc;
+  for (hipEvent_t* e : {&m->lane[0].done, &m->lane[1].done, &m->ev_go, &m->ev_join})
+    if (!*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) {
+      *e = nullptr;
+      return fail(LB_ERR_HIP, "hipEventCreate failed");
+    }
+  msg = msg || m->lane[0].msg;
+  if (chunk > m->capChunk || slots > m->capSlots || (msg && !m->lane[0].msg)) {
+    chunk = std::max(chunk, m->capChunk);
+    slots = std::max(slots, m->capSlots);
+    free_stream(m);
+    for (lb_mc::Lane& l : m->lane) {
+      if ((rc = lb::dev_alloc((void**)&l.x, chunk * N))) return rc;
+      if ((rc = lb::dev_alloc((void**)&l.ch, chunk * N * sizeof(double)))) return rc;
+      if ((rc = lb::dev_alloc((void**)&l.app, slots * N * sizeof(double)))) return rc;
+      if (msg && (rc = lb::dev_alloc((void**)&l.msg, (size_t)slots * c->Nmsg * sizeof(double)))) return rc;
+      if ((rc = lb::dev_alloc((void**)&l.it, (size_t)slots * sizeof(int)))) return rc;
+    }
+    m->capChunk = chunk;
+    m->capSlots = slots;
+  }
+  if (nchunks > m->capCtr) {
+    (void)hipFree(m->d_ctr);
+    m->d_ctr = nullptr;
+    m->capCtr = 0;
+    if ((rc = lb::dev_alloc((void**)&m->d_ctr, ((size_t)2 * nchunks + 1) * sizeof(int)))) return rc;
+    m->capCtr = nchunks;
+  }
+  return LB_OK;
+}
+
 // what ldpc.encode_batch checks (ldpc.py:815-822): the shifts of column Kp,
 // counted mod 2 by their value mod z, leave exactly one offset
 int surviving_offset(const int* proto, int Mp, int Np, int z, int* off) {
@@ -321,6 +398,10 @@ void mc_release(lb_ctx* c) {
   if (!m) return;
   (void)hipSetDevice(c->dev);
   free_staging(m);
+  free_stream(m);
+  (void)hipFree(m->d_ctr);
+  for (hipEvent_t e : {m->lane[0].done, m->lane[1].done, m->ev_go, m->ev_join})
+    if (e) (void)hipEventDestroy(e);
   (void)hipFree(m->d_proto);
   (void)hipFree(m->d_res);
   (void)hipFree(m->d_seeds);
@@ -549,6 +630,129 @@ int lb_mc_run_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a,
   if (err) return fail(LB_ERR_HIP, "lb_mc_run_seeds: a block's randn ran into the chunk cap");
   std::memcpy(errs, m->h_res, (size_t)nblk * sizeof(int));
   std::memcpy(iters, m->h_res + nblk, (size_t)nblk * sizeof(int));
+  return LB_OK;
+}
+
+int lb_mc_stream_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a, int kind, int chunk, int slots,
+                       int min_errors, int algo, double corr, int max_iter, int* errs, int* iters, long long* out) {
+  if (!c) return fail(LB_ERR_ARG, "lb_mc_stream_seeds: null context");
+  if (nblk < 0 || chunk <= 0 || (kind != 0 && kind != 1) || !out || (nblk > 0 && (!seeds || !errs || !iters)))
+    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: bad arguments");
+  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0))
+    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: sigma must be > 0, p in (0, 1)");
+  if (K != 0 && K != c->Nv - c->Nc)
+    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: K must be Nv - Nc, or 0 for no bits");
+  const bool enc = K > 0;
+  if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_stream_seeds: the BSC sends the all-zero word (K must be 0)");
+  if (enc && (!c->mc || c->mc->Mp == 0))
+    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: no encoder set (lb_mc_set_code)");
+  int rc, resident = 1;
+  if ((rc = lb::stream_plan(c, algo, max_iter, nullptr))) return rc;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (nblk == 0) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  if ((rc = lb::stream_plan(c, algo, max_iter, &resident))) return rc;
+  chunk = std::min(chunk, nblk);
+  // a slot beyond the chunk's blocks would find no ticket
+  slots = std::min(slots > 0 ? slots : resident * c->ncu, chunk);
+  const int nchunks = (nblk + chunk - 1) / chunk;
+  if ((rc = ensure_state(c))) return rc;
+  if ((rc = ensure_staging(c, chunk, false))) return rc;
+  const bool f32 = (algo & LB_F32) != 0;
+  if ((rc = ensure_stream(c, chunk, slots, nchunks, (f32 ? c->lmode32 : c->lmode) < 2))) return rc;
+  lb_mc* m = c->mc;
+  if ((rc = ensure_results(m, nblk))) return rc;
+  if ((rc = ensure_seeds(m, nblk))) return rc;
+  const int N = c->Nv;
+  PrepArgs p{};
+  fill_prep(p, c, enc);
+  p.kind = kind;
+  p.a = a;
+  p.c0 = kind == 0 ? 2.0 / libm_pow(a, 2.0) : libm_log((1.0 - a) / a);
+  const int cap = legacy_rng_dev::randn_chunk_cap(N);
+  hipStream_t st[2] = {c->stream, m->copy};
+  int* ticket = m->d_ctr;           // [nchunks]
+  int* ecnt = m->d_ctr + nchunks;   // [nchunks + 1]: chunk k counts in ecnt[k + 1]
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  HIP_TRY(hipMemcpyAsync(m->d_seeds, seeds, (size_t)nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(m->d_err, 0, sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(m->d_ctr, 0, ((size_t)2 * nchunks + 1) * sizeof(int), c->stream));
+  HIP_TRY(hipEventRecord(m->ev_go, c->stream));
+  HIP_TRY(hipStreamWaitEvent(m->copy, m->ev_go, 0));
+  // the sequential rule of harness.ber_point over the blocks that have landed
+  int used = 0, nerr = 0, decoded = 0, queued = 0, consumed = 0;
+  bool met = false;
+  auto consume = [&]() -> int {  // the oldest chunk in flight
+    const int k = consumed++;
+    HIP_TRY(hipEventSynchronize(m->lane[k & 1].done));
+    const int b0 = k * chunk, B = std::min(chunk, nblk - b0);
+    for (int j = b0; j < b0 + B; ++j) {
+      if (m->h_res[nblk + j] >= 0) ++decoded;
+      if (met) continue;
+      ++used;
+      if (m->h_res[j] > 0) ++nerr;
+      met = min_errors > 0 && nerr >= min_errors;
+    }
+    return LB_OK;
+  };
+  for (int k = 0; k < nchunks; ++k) {
+    if (k >= 2 && (rc = consume())) return rc;  // chunk k - 2: at most two in flight
+    if (met) break;
+    const int i = k & 1;
+    const int b0 = k * chunk, B = std::min(chunk, nblk - b0);
+    lb_mc::Lane& l = m->lane[i];
+    hipLaunchKernelGGL(k_mc_draw_blocks, dim3(B), dim3(legacy_rng_dev::kThreads), 0, st[i], m->d_seeds + b0, K, N,
+                       kind, m->d_u[i], m->d_w[i], cap, m->d_err);
+    HIP_TRY(hipGetLastError());
+    p.u = m->d_u[i];
+    p.w = m->d_w[i];
+    p.ch = l.ch;
+    p.x = l.x;
+    hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), st[i], p);
+    HIP_TRY(hipGetLastError());
+    lb::StreamChunk s;
+    s.ch = l.ch;
+    s.x = l.x;
+    s.app = l.app;
+    s.msg = l.msg;
+    s.slot_iters = l.it;
+    s.errs = m->d_res + b0;
+    s.iters = m->d_res + nblk + b0;
+    s.ticket = ticket + k;
+    s.eprev = ecnt + k;
+    s.ecur = ecnt + k + 1;
+    s.chunk = B;
+    s.base = nerr;  // the block errors of chunks <= k - 2, all consumed above
+    s.min_errors = min_errors;
+    if ((rc = lb::launch_stream(c, st[i], std::min(slots, B), s, algo, corr, max_iter))) return rc;
+    HIP_TRY(hipMemcpyAsync(m->h_res + b0, m->d_res + b0, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st[i]));
+    HIP_TRY(hipMemcpyAsync(m->h_res + nblk + b0, m->d_res + nblk + b0, (size_t)B * sizeof(int), hipMemcpyDeviceToHost,
+                           st[i]));
+    HIP_TRY(hipEventRecord(l.done, st[i]));
+    ++queued;
+  }
+  // lane 1 joins the context's stream: the run's time covers both lanes
+  HIP_TRY(hipEventRecord(m->ev_join, m->copy));
+  HIP_TRY(hipStreamWaitEvent(c->stream, m->ev_join, 0));
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, m->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (err) return fail(LB_ERR_HIP, "lb_mc_stream_seeds: a block's randn ran into the chunk cap");
+  // the chunks in flight when the loop ended (at most two), in seed order
+  while (consumed < queued)
+    if ((rc = consume())) return rc;
+  const int nq = (int)std::min<long long>(nblk, (long long)queued * chunk);
+  std::memcpy(errs, m->h_res, (size_t)nq * sizeof(int));
+  std::memcpy(iters, m->h_res + nblk, (size_t)nq * sizeof(int));
+  for (int j = nq; j < nblk; ++j) {  // never queued
+    errs[j] = 0;
+    iters[j] = -1;
+  }
+  out[0] = used;
+  out[1] = decoded;
+  out[2] = slots;
+  out[3] = queued;
   return LB_OK;
 }
 

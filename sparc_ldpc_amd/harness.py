@@ -333,6 +333,27 @@ def ber_point(decode_round, total_bits, min_errors, max_blocks, batch, rank=0, w
                 mean_iters=iters / nblocks, iters_total=iters)
 
 
+def consume_in_seed_order(be, it, total_bits, min_errors, max_blocks):
+    """ber_point's result from per-block arrays that are already in seed order
+    (the streamed point of ldpc_mc, one call over seed_base + arange(max_blocks)):
+    the same sequential arithmetic, block by block, until min_errors block
+    errors or max_blocks blocks.  Blocks behind the stopping block are not
+    read."""
+    ber_cum = 0.0
+    nerr = nblocks = iters = errbits = 0
+    while nerr < min_errors:
+        b = int(be[nblocks])
+        ber_cum += b / total_bits
+        errbits += b
+        iters += int(it[nblocks])
+        nerr += 1 if b > 0 else 0
+        nblocks += 1
+        if nblocks >= max_blocks:
+            break
+    return dict(BER=ber_cum / nblocks, blocks=nblocks, block_errors=nerr, bit_errors=errbits,
+                mean_iters=iters / nblocks, iters_total=iters)
+
+
 def waterfall_plain(L, M, P, R, T, ebno_dbs, min_errors=200, max_blocks=250, csv_filename=None,
                     batch=64, seed0=0, backend=None, precision=None, rank=0, world=1, allreduce=None):
     """BER_plain column of waterfall() (sparc_ldpc.py:1126-1282) on the GPU:

@@ -31,6 +31,7 @@ _ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM,
           "layered_sumprod2_f32": LB_LAYERED_SUMPROD2 | LB_F32, "layered_minsum_f32": LB_LAYERED_MINSUM | LB_F32}
 _REFERENCE_ALGOS = ("sumprod2", "sumprod", "minsum")  # code.decode's names (ldpc.py:855-930)
 _CHANNELS = {"awgn": 0, "bsc": 1}  # lb_mc_run / lb_draw_blocks kinds
+STREAM_CHUNK = 4096  # blocks per chunk of code.mc_stream_seeds
 
 # Every symbol include/ldpc_bp.h declares (tests check the export table).
 EXPORTS = (
@@ -39,6 +40,7 @@ EXPORTS = (
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
     "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info", "lb_layer_info_ex",
     "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
+    "lb_mc_stream_seeds",
 )
 
 _P, _I, _D = ct.c_void_p, ct.c_int, ct.POINTER(ct.c_double)
@@ -75,6 +77,8 @@ _SIG = {
     "lb_mc_run_seeds": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _I, ct.c_double, _I, _I, _I, ct.c_double, _I, _IP,
                              _IP]),
     "lb_draw_blocks_device": (_I, [_P, ct.POINTER(ct.c_uint32), _I, _I, _I, _I, _U8, _D]),
+    "lb_mc_stream_seeds": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _I, ct.c_double, _I, _I, _I, _I, _I, ct.c_double,
+                                _I, _IP, _IP, ct.POINTER(ct.c_int64)]),
 }
 
 _lib = None
@@ -223,7 +227,9 @@ class code:
     schedule over the protograph rows (include/ldpc_bp.h, lb_set_layers), whose
     ``it`` counts sweeps; and "layered_sumprod2_f32" / "layered_minsum_f32":
     the same schedule on binary32 messages (LB_F32; CH and app stay float64,
-    CH is clamped to +-2**100 on load)."""
+    CH is clamped to +-2**100 on load).  ``mc_stream_seeds`` runs
+    ``mc_blocks_seeds``' blocks, with a layered dectype, as a stream of refilled
+    decoder slots with an optional stopping rule (lb_mc_stream_seeds)."""
 
     def __init__(self, standard="802.11n", rate="1/2", z=27, ptype="A", device=None):
         self.standard = standard
@@ -419,6 +425,37 @@ class code:
                                                   float(corr_factor), int(max_iter), errs.ctypes.data_as(_IP),
                                                   it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
+
+    def mc_stream_seeds(self, seeds, a, channel="awgn", chunk=STREAM_CHUNK, dectype="layered_sumprod2",
+                        corr_factor=0.7, max_iter=MAX_ITCOUNT, min_errors=0, slots=0):
+        """mc_blocks_seeds as a stream of refilled decoder slots
+        (lb_mc_stream_seeds; layered decoders only): per chunk of ``chunk``
+        blocks one persistent kernel of ``slots`` workgroups (0: what the
+        device holds at once) that takes the blocks by ticket, decodes and
+        counts them; two chunks in flight on two lanes.  Per block the same
+        (bit_errors, iters) as mc_blocks_seeds.  min_errors > 0: the stopping
+        rule of harness.ber_point on the device and the host; blocks behind
+        the stopping block may come back undecoded (iters = -1, bit_errors
+        = 0).  Returns int64 (bit_errors, iters) in seed order and info =
+        dict(used: the blocks the rule consumes (all of them without a rule),
+        decoded, slots, chunks)."""
+        from .ldpc_mc import _seed_array, info_bits
+        algo = self._algo(dectype)  # (a flooding type: LdpcBpError -5 from the library)
+        if channel not in _CHANNELS:
+            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
+        seeds = _seed_array(seeds)
+        B = len(seeds)
+        K = info_bits(self, channel)
+        if K:
+            self._set_encoder()
+        errs = np.empty(B, dtype=np.intc)
+        it = np.empty(B, dtype=np.intc)
+        out = (ct.c_int64 * 4)()
+        _check(_layered_entry("lb_mc_stream_seeds")(
+            self._context(), B, seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), K, float(a), _CHANNELS[channel],
+            int(chunk), int(slots), int(min_errors), algo, float(corr_factor), int(max_iter),
+            errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP), out))
+        return errs.astype(np.int64), it.astype(np.int64), dict(zip(("used", "decoded", "slots", "chunks"), list(out)))
 
     def mc_event_ms(self):
         """Device milliseconds of the last mc_blocks / run_buffers (events on the context's stream)."""

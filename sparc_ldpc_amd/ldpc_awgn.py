@@ -30,7 +30,7 @@ sim_param = _grid(3)  # ldpc_awgn.py:6-43
 
 def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_STEP=100.0,
         MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None, draws="host",
-        dectype="sumprod2"):
+        dectype="sumprod2", stream=False):
     """ldpc_awgn.py:60-123.  Starts C_AWGN_OFFSET dB above the SNR of the AWGN
     rate, and per point: sigma2 = 1 / 10**(SNR/10), blocks until MIN_ERRORS
     block errors or MAX_BLOCKS, then SNR += sqrt(P_STEP / nblocks).  Point d
@@ -40,8 +40,11 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     them to ``results_file`` in its line format when given.  draws="device":
     the blocks are drawn on the GPU from their seeds (ldpc_mc).  dectype: the
     decoder (code.decode_batch's names, the layered ones and their binary32
-    "_f32" forms included; nit_total then counts sweeps)."""
+    "_f32" forms included; nit_total then counts sweeps).  stream=True
+    (draws="device", a layered dectype): every point as one stream of refilled
+    decoder slots (ldpc_mc._mc_point); the same tuples."""
     ldpc_mc._check_draws(draws)
+    ldpc_mc._check_stream(stream, draws, dectype)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
     if rate not in _RATES:
@@ -55,7 +58,8 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
         sigma2 = 1 / np.power(10, SNR / 10.0)
         r = ldpc_mc._mc_point(code, float(np.sqrt(sigma2)), "awgn", MIN_ERRORS, MAX_BLOCKS,
                               seed0 + datapoint * 10_000_000, batch, draws=draws,
-                              **({} if dectype == "sumprod2" else {"dectype": dectype}))
+                              **({} if dectype == "sumprod2" else {"dectype": dectype}),
+                              **({"stream": True} if stream else {}))
         nblocks = r["blocks"]
         output = (standard, rate, z, SNR, nblocks, r["block_errors"], nblocks * K, r["bit_errors"], r["iters_total"])
         res.append(output)

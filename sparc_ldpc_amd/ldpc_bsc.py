@@ -17,15 +17,18 @@ _P0 = {"1/2": 0.11, "2/3": 0.06, "5/6": 0.02459, "3/4": 0.0415}
 sim_param = _grid(100)  # ldpc_bsc.py:6-43
 
 
-def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dectype="sumprod2"):
+def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dectype="sumprod2", stream=False):
     """ldpc_bsc.py:63-113: (res, parray) with parray = linspace(p0, 0.001, 10)
     and res[i] the mean bit error rate of ``repeats`` blocks at parray[i].
     Point i decodes the blocks seed0 + i * 10_000_000, ... (ldpc_mc's BSC
     contract: random_sample(N) < p flips the bit).  draws="device": the
     uniform values are drawn on the GPU from the seeds (the same values).
     dectype: the decoder (code.decode_batch's names, the layered ones and their
-    binary32 "_f32" forms included)."""
+    binary32 "_f32" forms included).  stream=True (draws="device", a layered
+    dectype): the blocks through refilled decoder slots (ldpc_mc.mc_ldpc); the
+    same results."""
     ldpc_mc._check_draws(draws)
+    ldpc_mc._check_stream(stream, draws, dectype)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
     if rate not in _P0:
@@ -39,7 +42,8 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
         base = seed0 + i * 10_000_000
         be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc",
                                 **({} if draws == "host" else {"draws": draws}),
-                                **({} if dectype == "sumprod2" else {"dectype": dectype}))
+                                **({} if dectype == "sumprod2" else {"dectype": dectype}),
+                                **({"stream": True} if stream else {}))
         errors = [int(b) / N for b in be]
         res.append(np.sum(errors) / repeats)
     return res, parray

@@ -26,6 +26,14 @@ GPU from their seeds instead (lb_mc_run_seeds: only the seeds go up);
 values are the host's bit for bit; the AWGN noise is the host's up to the
 device library's ``log`` (a few values in a thousand differ, by under 2**-49
 relative), so an AWGN block's result may differ from its host-drawn one.
+
+``stream=True`` (with ``draws="device"``, a layered ``dectype`` and one rank)
+runs an operating point as one stream (code.mc_stream_seeds,
+lb_mc_stream_seeds): chunks of blocks on two lanes, each chunk decoded and
+counted by one persistent kernel whose workgroups take the blocks by ticket,
+so a block that does not converge holds one CU and not a batch.  The stopping
+rule runs on the device and the host; per block and per point the results are
+the batch path's.
 """
 from __future__ import annotations
 
@@ -36,7 +44,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import ldpc as _ldpc
-from .harness import LDPCParams, ber_point, draw_threads
+from .harness import LDPCParams, ber_point, consume_in_seed_order, draw_threads
 from .operators import seed_array as _seed_array  # uint32 seeds; ValueError outside [0, 2**32), no masking
 
 __all__ = ["draw_blocks", "draw_blocks_device", "mc_ldpc", "sim_ldpc_mc", "info_bits"]
@@ -49,6 +57,21 @@ def _check_draws(draws) -> str:
     if draws not in ("host", "device"):
         raise ValueError('draws must be "host" or "device"')
     return draws
+
+
+def _check_stream(stream, draws, dectype, world=1) -> bool:
+    """stream=True (the blocks through refilled decoder slots,
+    code.mc_stream_seeds) goes with device draws, a layered decoder and one
+    rank; checked before any library call."""
+    if not stream:
+        return False
+    if draws != "device":
+        raise ValueError('stream=True needs draws="device"')
+    if not str(dectype).startswith("layered_"):
+        raise ValueError("stream=True needs a layered dectype")
+    if world != 1:
+        raise ValueError("stream=True runs on one rank (world == 1)")
+    return True
 
 
 def info_bits(code, channel="awgn") -> int:
@@ -109,12 +132,15 @@ def draw_blocks_device(code, seeds, channel="awgn"):
     return u, w
 
 
-def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, draws="host"):
+def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, draws="host", stream=False):
     """Blocks ``seeds`` of ``code`` at sigma (AWGN) or p (BSC) ``a``: per-block
     int64 (bit_errors, iters) in seed order.  ``drawn``: the blocks' (u, w)
     when the caller has drawn them already (draw_blocks).  draws="device":
-    the blocks are drawn on the GPU from their seeds (code.mc_blocks_seeds)."""
+    the blocks are drawn on the GPU from their seeds (code.mc_blocks_seeds).
+    stream=True (device draws, a layered dectype): the same results through
+    code.mc_stream_seeds, ``batch`` being its chunk."""
     _check_draws(draws)
+    _check_stream(stream, draws, dectype)
     seeds = list(seeds)
     if draws == "device":
         if drawn is not None:
@@ -122,6 +148,8 @@ def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", draw
         seeds = _seed_array(seeds)
     if not len(seeds):
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    if stream:
+        return code.mc_stream_seeds(seeds, a, channel, batch, dectype)[:2]
     if draws == "device":
         return code.mc_blocks_seeds(seeds, a, channel, batch, dectype)
     u, w = draw_blocks(seeds, info_bits(code, channel), code.N, channel) if drawn is None else drawn
@@ -129,14 +157,29 @@ def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", draw
 
 
 def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectype="sumprod2", rank=0, world=1,
-              allreduce=None, timings=None, draws="host"):
+              allreduce=None, timings=None, draws="host", stream=False):
     """One operating point by the reference's stopping rule (harness.ber_point)
     over the blocks seed_base, seed_base + 1, ...: round r + 1 is drawn in a
     worker thread while round r decodes.  ``timings`` (a dict) receives the
     seconds spent drawing and the device milliseconds of the decodes.
     draws="device": every round is drawn on the GPU in front of its decode,
-    and no worker thread is started."""
+    and no worker thread is started.
+    stream=True (device draws, a layered dectype, world == 1): one call of
+    code.mc_stream_seeds over seed_base + arange(max_blocks) with the rule on
+    the device (``batch`` is its chunk), and the result from its first blocks
+    by the same sequential arithmetic (harness.consume_in_seed_order): the
+    same dict as stream=False.  ``timings["stream"]`` receives the call's
+    info (used, decoded, slots, chunks)."""
     _check_draws(draws)
+    if _check_stream(stream, draws, dectype, world):
+        nblk = max(1, int(max_blocks))
+        be, it, info = code.mc_stream_seeds(int(seed_base) + np.arange(nblk, dtype=np.int64), a, channel, batch,
+                                            dectype, min_errors=int(min_errors))
+        if timings is not None:
+            timings["draw_s"] = timings.get("draw_s", 0.0)  # (inside device_ms)
+            timings["device_ms"] = timings.get("device_ms", 0.0) + code.mc_event_ms()
+            timings["stream"] = info
+        return consume_in_seed_order(be, it, code.N, min_errors, max_blocks)
     from .dist import shard_seeds
     if draws == "device":
         ms = [0.0]
@@ -184,7 +227,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
 
 
 def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, seed0=0, batch=1024, rank=0,
-                world=1, allreduce=None, timings=None, draws="host", dectype="sumprod2"):
+                world=1, allreduce=None, timings=None, draws="host", dectype="sumprod2", stream=False):
     """sim_ldpc (sparc_ldpc.py:1064-1124) over the blocks seed0, seed0 + 1, ...
     with everything but the draws on the device: blocks until MIN_ERRORS block
     errors or MAX_BLOCKS blocks, consumed in seed order whatever ``batch`` and
@@ -193,14 +236,17 @@ def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000
     draws="device": the draws on the device too (only the seeds go up).
     dectype: the decoder (code.decode_batch's names; with a layered one
     nit_total counts sweeps; "layered_sumprod2_f32" / "layered_minsum_f32"
-    decode on binary32 messages)."""
+    decode on binary32 messages).
+    stream=True (draws="device", a layered dectype, world == 1): the point as
+    one stream of refilled decoder slots (_mc_point); the same dict."""
     _check_draws(draws)
+    _check_stream(stream, draws, dectype, world)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
     if ldpcparams.r_ldpc not in _RATES:
         raise NameError("Rate unsupported")
     code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype)
     r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, dectype, rank, world,
-                  allreduce, timings, draws)
+                  allreduce, timings, draws, stream)
     return dict(ber=r["bit_errors"] / (r["blocks"] * code.N), blocks=r["blocks"], block_errors=r["block_errors"],
                 bit_errors=r["bit_errors"], nit_total=r["iters_total"])
