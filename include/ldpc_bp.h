@@ -15,7 +15,8 @@
  *     with device-resident buffers for the joint SPARC/LDPC pipeline.
  *
  * All arithmetic is IEEE binary64 in the reference's per-node operation order
- * (the layered decoders also run in binary32 on request: LB_F32).
+ * (the layered decoders also run in binary32 on request, LB_F32, and layered
+ * min-sum on saturating integers of settable widths, LB_FIXED).
  * Graph arrays follow ldpc.py:694-786: vdeg[Nv], cdeg[Nc], intrlv[Nmsg]
  * (message index, in check-node order, of each variable-node port).
  */
@@ -32,7 +33,7 @@ enum {
   LB_ERR_HIP = -2,         /* HIP runtime failure */
   LB_ERR_NOMEM = -3,       /* device allocation failed (c_ldpc.c:40-42 returns -1) */
   LB_ERR_GRAPH = -4,       /* degrees do not sum to Nmsg, or intrlv is not a permutation */
-  LB_ERR_UNSUPPORTED = -5, /* check degree > 32 or variable degree > 255 */
+  LB_ERR_UNSUPPORTED = -5, /* check degree > 32 or variable degree > 255; a flag on a type it does not exist for */
   LB_ERR_NO_DEVICE = -6    /* no HIP device: there is no CPU fallback */
 };
 
@@ -42,6 +43,10 @@ enum { LB_SUMPROD2 = 0, LB_SUMPROD = 1, LB_MINSUM = 2, LB_LAYERED_SUMPROD2 = 3, 
  * LB_LAYERED_MINSUM | LB_F32 decode in binary32 (see "binary32" below).  On a
  * flooding type it is LB_ERR_UNSUPPORTED. */
 #define LB_F32 0x100
+/* Arithmetic flag, OR-ed into algo: LB_LAYERED_MINSUM | LB_FIXED decodes on
+ * integers of settable widths (see "fixed point" below).  On any other type it
+ * is LB_ERR_UNSUPPORTED; together with LB_F32 it is LB_ERR_ARG. */
+#define LB_FIXED 0x400
 
 #define LB_MAX_ITCOUNT 200 /* c_ldpc.c:7 */
 
@@ -172,6 +177,47 @@ int lb_layer_info(lb_ctx* ctx, long long* out);
  * runtime's occupancy figure at that thread count and LDS size; 0 before
  * lb_set_layers), and the bytes per message (8 / 4). */
 int lb_layer_info_ex(lb_ctx* ctx, int precision, long long* out);
+
+/* fixed point: algo = LB_LAYERED_MINSUM | LB_FIXED, wherever algo is taken
+ * (lb_decode, lb_decode_device, lb_run, lb_mc_run, lb_mc_run_seeds,
+ * lb_mc_stream_seeds), runs layered normalised min-sum on saturating integers,
+ * the decoder a receiver builds (tests/ldpc_fixed_ref.py is its statement; the
+ * kernel equals it bit for bit).  frac_bits F in 0..8, msg_bits MB in 2..8,
+ * app_bits AB in MB..16; rmax = 2^(MB-1) - 1, amax = 2^(AB-1) - 1,
+ * alpha = rint(16 corr_factor), which must lie in 1..16 (LB_ERR_ARG otherwise,
+ * and for a NaN).
+ *   app[v] = clip(rint(ch[v] 2^F), -rmax, rmax)   half to even; NaN -> 0; +-inf saturate; -0.0 -> 0
+ *   r[e] = 0; per sweep, after the layered decoders' stop test (every check even
+ *   in app < 0, no app == 0), per layer, per check, per edge e on variable v:
+ *     q[e]   = clip(app[v] - r[e], -amax, amax)
+ *     mag, neg = the minimum of |q| and the xor of (q < 0) over the check's other
+ *                edges (a check of degree 1: mag = amax)
+ *     m      = min((alpha mag + 8) >> 4, rmax);  r[e] = neg ? -m : m
+ *     app[v] = clip(q[e] + r[e], -amax, amax)
+ * ch, app and iters keep their types and layouts: app = (double)int 2^-F, so a
+ * zero is +0.  iters and max_iter mean what they mean for the other layered
+ * decoders; max_iter = 0 leaves app = ch, unquantised.  lb_set_tail does not
+ * apply.  app (int16) and r (int8) live in LDS for the whole decode, one
+ * workgroup per word, a group of lanes per check and one barrier per layer;
+ * there are no HBM layouts (no code this project builds needs them): when
+ * 2 Nv + Nmsg bytes do not fit a workgroup's LDS the call is LB_ERR_UNSUPPORTED.
+ * Errors leave app, iters and the context as they were: no layers set,
+ * alpha out of range, LB_FIXED | LB_F32: LB_ERR_ARG; LB_FIXED on another type
+ * than LB_LAYERED_MINSUM, or an image that does not fit: LB_ERR_UNSUPPORTED.
+ *
+ * lb_set_fixed sets the widths for the decodes that follow (any time between
+ * decodes; out of range: LB_ERR_ARG and the context unchanged; never called:
+ * 2, 6, 8).  lb_fixed_info: out[0..7] = frac_bits, msg_bits, app_bits, threads
+ * per workgroup, lanes per check, dynamic LDS bytes (2 Nv + Nmsg rounded up to
+ * 16), workgroups resident per CU (the runtime's occupancy figure) and whether
+ * the image fits (1 / 0); the last five are 0 before lb_set_layers.
+ *
+ * Measurement and test switches, read from the environment by lb_set_layers and
+ * lb_set_fixed: LDPC_BP_FIXED_LANES = the lanes per check (1, 2, 4, 8 or 16),
+ * LDPC_BP_FIXED_THREADS = the threads per workgroup (a multiple of 64 up to
+ * 1024).  The results are the same bits for every setting. */
+int lb_set_fixed(lb_ctx* ctx, int frac_bits, int msg_bits, int app_bits);
+int lb_fixed_info(lb_ctx* ctx, long long* out);
 
 /* ---- LDPC-only Monte-Carlo (sim_ldpc sparc_ldpc.py:1064-1124, ldpc_awgn.py, ldpc_bsc.py) ---- */
 /* Block s is its seed: RandomState(seeds[i]) draws randint(0, 2, K) into

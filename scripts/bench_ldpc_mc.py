@@ -47,7 +47,19 @@ Then the rule: sim_ldpc_mc(MIN_ERRORS=100) at both sigmas, at 0.48 (no block
 fails) and at 0.56 (the rule is met within the first chunk) through batch
 1024, batch 8192 and the stream, the dicts asserted equal, with the blocks
 decoded against the blocks used.  Written to
-results/ldpc_mc_stream.json."""
+results/ldpc_mc_stream.json.
+
+--quant F,MB,AB (with --dectype layered_minsum and --draws device): the
+fixed-point layered min-sum decoder (code.mc_blocks_seeds(quant=...)) against
+layered_minsum_f32 on the same 8192 seeds at sigma 0.5203 and 0.535, batch 1024,
+and with --stream also both through code.mc_stream_seeds at the default chunk;
+five interleaved rounds after a warm-up of each leg, per round end-to-end and
+device milliseconds.  The bar of an opt-in path: every fixed-point round below
+every binary32 round of the same form, in device time.  Then fidelity (reported,
+not gated): block and bit errors over the same seeds at sigma 0.5203, 0.535 and
+0.56 for the widths given, (1, 4, 6) and (3, 8, 16), beside binary32 and
+binary64 layered min-sum at the same corr_factor.  Written to
+results/ldpc_mc_fixed.json."""
 import argparse
 import json
 import os
@@ -75,7 +87,14 @@ def main():
     ap.add_argument("--sigma", type=float, default=None, help="noise level of the _f32 legs' fidelity run")
     ap.add_argument("--stream", action="store_true",
                     help="time the streamed operating point against the batch path instead")
+    ap.add_argument("--quant", default=None, metavar="F,MB,AB",
+                    help="with --dectype layered_minsum: time the fixed-point decoder of these widths against "
+                         "layered_minsum_f32 (batch 1024; with --stream also streamed)")
     args = ap.parse_args()
+    if args.quant:
+        if args.dectype != "layered_minsum":
+            ap.error("--quant goes with --dectype layered_minsum")
+        return fixed_leg(args)
     if args.stream:
         return stream_leg(args)
     f32 = bool(args.dectype and args.dectype.endswith("_f32"))
@@ -297,6 +316,79 @@ def stream_leg(args):
     out["bar_met"] = all(pt["bar_every_stream_device_time_below_every_batch_1024"]
                          for name, pt in out["points"].items() if name.endswith("0.535"))
     print(json.dumps({k: v for k, v in out.items() if k not in ("points", "rule")}))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
+
+
+def fixed_leg(args):
+    from sparc_ldpc_amd import ldpc
+    out_path = args.out or os.path.join(ROOT, "results", "ldpc_mc_fixed.json")
+    lib = ldpc.load_bp_library()
+    assert lib.lb_device_count() > 0, "no HIP device visible"
+    widths = tuple(int(x) for x in args.quant.split(","))
+    rounds, seeds, corr = 5, np.arange(100_000, 100_000 + BLOCKS), 0.7
+    code = ldpc.code("802.16", "5/6", 192)
+    F32, M = "layered_minsum_f32", "layered_minsum"
+
+    def timed(fn):
+        assert lib.hipDeviceSynchronize() == 0
+        t0 = time.perf_counter()
+        r = fn()
+        assert lib.hipDeviceSynchronize() == 0
+        return (time.perf_counter() - t0) * 1e3, code.mc_event_ms(), r
+
+    out = dict(workload="802.16 5/6 z=192, %d blocks, draws on the device, corr_factor %g, widths %s" %
+               (BLOCKS, corr, list(widths)), rounds=rounds, points={}, fidelity={})
+    for sigma in (0.5203, 0.535):
+        legs = {"f32_batch_1024": lambda: code.mc_blocks_seeds(seeds, sigma, "awgn", BATCH, F32, corr),
+                "fixed_batch_1024": lambda: code.mc_blocks_seeds(seeds, sigma, "awgn", BATCH, M, corr, quant=widths)}
+        if args.stream:
+            legs["f32_stream"] = lambda: code.mc_stream_seeds(seeds, sigma, "awgn", ldpc.STREAM_CHUNK, F32, corr)[:2]
+            legs["fixed_stream"] = lambda: code.mc_stream_seeds(seeds, sigma, "awgn", ldpc.STREAM_CHUNK, M, corr,
+                                                                quant=widths)[:2]
+        ref = {}
+        for leg, fn in legs.items():  # warm-up; the streamed results are the batch path's
+            r = fn()
+            kind = leg.split("_")[0]
+            ref.setdefault(kind, r)
+            assert np.array_equal(r[0], ref[kind][0]) and np.array_equal(r[1], ref[kind][1]), leg
+        runs = {leg: [] for leg in legs}
+        for _ in range(rounds):
+            for leg, fn in legs.items():
+                wall, dev, _r = timed(fn)
+                runs[leg].append(dict(wall_ms=wall, device_ms=dev))
+        pt = {}
+        for kind in ("f32", "fixed"):
+            pt[kind + "_sweeps_per_block"] = float(ref[kind][1].mean())
+            pt[kind + "_block_errors"] = int((ref[kind][0] > 0).sum())
+        for leg in legs:
+            pt[leg] = dict(median_device_ms=statistics.median(x["device_ms"] for x in runs[leg]),
+                           median_wall_ms=statistics.median(x["wall_ms"] for x in runs[leg]), runs=runs[leg])
+        for form in ("batch_1024",) + (("stream",) if args.stream else ()):
+            a, b = runs["fixed_" + form], runs["f32_" + form]
+            pt["bar_every_fixed_device_time_below_every_f32_" + form] = bool(
+                max(x["device_ms"] for x in a) < min(x["device_ms"] for x in b))
+            pt["speedup_device_over_f32_" + form] = pt["f32_" + form]["median_device_ms"] / \
+                pt["fixed_" + form]["median_device_ms"]
+        out["points"]["sigma=%g" % sigma] = pt
+        print(sigma, {leg: round(pt[leg]["median_device_ms"], 3) for leg in legs}, flush=True)
+    if args.stream:
+        out["fixed_info"] = code.fixed_info()
+        out["stream_slots"] = {"fixed": code.mc_stream_seeds(seeds[:1024], 0.5, quant=widths, dectype=M)[2]["slots"],
+                               "f32": code.mc_stream_seeds(seeds[:1024], 0.5, dectype=F32)[2]["slots"]}
+    # fidelity: the same seeds through every arithmetic (deterministic: a round repeats its counts)
+    decoders = {"binary64": (M, None), "binary32": (F32, None)}
+    for w in dict.fromkeys((widths, (1, 4, 6), (3, 8, 16))):
+        decoders["fixed_%d_%d_%d" % w] = (M, w)
+    for sigma in (0.5203, 0.535, 0.56):
+        row = {}
+        for name, (dectype, quant) in decoders.items():
+            be, it = code.mc_blocks_seeds(seeds, sigma, "awgn", BATCH, dectype, corr, quant=quant)
+            row[name] = dict(block_errors=int((be > 0).sum()), bit_errors=int(be.sum()), sweeps_per_block=float(it.mean()))
+        out["fidelity"]["sigma=%g" % sigma] = row
+        print(sigma, "fidelity", {k: (v["block_errors"], v["bit_errors"]) for k, v in row.items()}, flush=True)
+    print(json.dumps({k: v for k, v in out.items() if k != "points"}))
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as fh:
         fh.write(json.dumps(out, indent=1) + "\n")

@@ -22,6 +22,16 @@ results/bp_sweep_time_f32.json.  The library is the one LDPC_BP_LIB names
 f32_ocml) for the device library's expf / logf against the hardware's.
 
     python scripts/bp_sweep_time.py --f32 [B,B,... [out.json]]
+
+--fixed (first argument): the fixed-point layered min-sum decoder (LB_FIXED,
+widths 2, 6, 8) against binary64 and binary32 layered min-sum, corr_factor 0.75:
+as the library plans it (lanes per check and threads per workgroup of its own
+choice) and with the alternatives named by LDPC_BP_FIXED_LANES /
+LDPC_BP_FIXED_THREADS.  The --f32 protocol; every fixed-point leg records
+lb_fixed_info (threads, lanes, LDS bytes, resident workgroups).  Written to
+results/bp_sweep_time_fixed.json.
+
+    python scripts/bp_sweep_time.py --fixed [B,B,... [out.json]]
 """
 import ctypes as ct
 import json
@@ -38,12 +48,13 @@ D = ct.POINTER(ct.c_double)
 lib = ldpc.load_bp_library()
 assert lib.lb_device_count() > 0, "no HIP device visible"
 F32 = len(sys.argv) > 1 and sys.argv[1] == "--f32"
-if F32:
+FIXED = len(sys.argv) > 1 and sys.argv[1] == "--fixed"
+if F32 or FIXED:
     del sys.argv[1]
 BS = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [256, 1024]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(
-    ROOT, "results", "bp_sweep_time_f32.json" if F32 else "bp_sweep_time.json")
+    ROOT, "results", "bp_sweep_time_f32.json" if F32 else "bp_sweep_time_fixed.json" if FIXED else "bp_sweep_time.json")
 
 
 def f32_legs():
@@ -89,8 +100,63 @@ def f32_legs():
     return out
 
 
-if F32:
-    out = f32_legs()
+def fixed_legs():
+    env = ("LDPC_BP_FIXED_LANES", "LDPC_BP_FIXED_THREADS")
+    M, CORR, WIDTHS = "layered_minsum", 0.75, ldpc.FIXED_DEFAULT
+    # leg -> (decoder, quant, LDPC_BP_FIXED_LANES, LDPC_BP_FIXED_THREADS), read when the leg's code sets its layers
+    legs = {"minsum_f64": (M, None, None, None), "minsum_f32": (M + "_f32", None, None, None),
+            "fixed": (M, WIDTHS, None, None)}
+    for lanes, threads in ((1, None), (2, None), (8, None), (16, None), (2, "192"), (2, "768"), (4, "384"), (4, "768"),
+                           (1, "384")):
+        legs[f"fixed_lanes{lanes}" + (f"_threads{threads}" if threads else "")] = (M, WIDTHS, str(lanes), threads)
+    codes = {}
+    for leg, (dectype, quant, *knobs) in legs.items():
+        for name, val in zip(env, knobs):
+            os.environ.pop(name, None)
+            if val is not None:
+                os.environ[name] = val
+        codes[leg] = ldpc.code("802.16", "5/6", 192)
+    out = {"library": os.path.basename(ldpc.LIB_PATH), "rounds": 5, "corr_factor": CORR, "widths": list(WIDTHS)}
+    for B in BS:
+        CH = np.ascontiguousarray(3.0 * np.random.RandomState(B).randn(B, codes["fixed"].N))
+
+        def run(leg, k):
+            # the leg's switches stand while it runs: lb_set_layers and lb_set_fixed (every quant= call) read them
+            for name, val in zip(env, legs[leg][2:]):
+                os.environ.pop(name, None)
+                if val is not None:
+                    os.environ[name] = val
+            c = codes[leg]
+            c.run_buffers(B, legs[leg][0], CORR, k, quant=legs[leg][1])
+            return c.mc_event_ms()
+
+        for leg, c in codes.items():
+            assert lib.lb_stage(c._context(), B, CH.ctypes.data_as(D)) == 0
+            for k in (4, 12):
+                run(leg, k)  # warm-up
+        t = {leg: {4: [], 12: []} for leg in legs}
+        for _ in range(5):
+            for leg, c in codes.items():
+                for k in (4, 12):
+                    t[leg][k].append(run(leg, k))
+                    assert (c.fetch_buffers(B, app=False)[1] == k).all()  # no word stopped early
+        for leg in legs:
+            sweeps = [(b - a) / 8 * 1e3 for a, b in zip(t[leg][4], t[leg][12])]
+            out.setdefault(leg, {})[str(B)] = dict(ms_at_4=t[leg][4], ms_at_12=t[leg][12], us_per_launch_sweep=sweeps,
+                                                   median_us_per_launch_sweep=statistics.median(sweeps))
+        fx, f32 = out["fixed"][str(B)]["us_per_launch_sweep"], out["minsum_f32"][str(B)]["us_per_launch_sweep"]
+        out.setdefault("bar_every_fixed_round_below_every_f32_round", {})[str(B)] = bool(max(fx) < min(f32))
+        for leg, c in codes.items():  # (as the leg's last run planned it)
+            out[leg]["layout"] = c.fixed_info() if legs[leg][1] else c.layer_info("f32" if "_f32" in leg else "f64")
+            if legs[leg][1]:
+                assert legs[leg][2] in (None, str(out[leg]["layout"]["lanes"])), (leg, out[leg]["layout"])
+    for name in env:
+        os.environ.pop(name, None)
+    return out
+
+
+if F32 or FIXED:
+    out = fixed_legs() if FIXED else f32_legs()
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
     with open(OUT, "w") as fh:

@@ -474,8 +474,10 @@ struct BplStreamArgs {
   int chunk, base, min_errors;
 };
 
-template <typename T, int ALGO, int DCMAX, int DCFIX, int MODE>
-__device__ __forceinline__ void bpl_stream(const BplStreamArgs& s, T* lds, int* unsat) {
+// decode(t, slot): the sweep count of word t of the chunk, decoded in the
+// workgroup's slot with app left in the slot's slice of s.w.app
+template <typename Decode>
+__device__ __forceinline__ void stream_blocks(const BplStreamArgs& s, Decode decode) {
   __shared__ int next[3];  // ticket, skip, the word's bit errors
   const int tid = threadIdx.x, nt = blockDim.x, slot = blockIdx.x, Nv = s.w.Nv;
   for (;;) {
@@ -506,8 +508,8 @@ __device__ __forceinline__ void bpl_stream(const BplStreamArgs& s, T* lds, int* 
     int it = 0;
     const double* v = s.w.ch + (size_t)t * Nv;  // max_iter = 0: app = ch, unrounded, as the batch path has it
     if (s.w.maxit > 0) {
-      it = bpl_word<T, ALGO, DCMAX, DCFIX, MODE>(s.w, lds, unsat, t, slot);
-      // every out[i] was written by this thread or in front of a barrier of bpl_word
+      it = decode(t, slot);
+      // every out[i] was written by this thread or in front of a barrier of the decode
       v = s.w.app + (size_t)slot * Nv;
     }
     const uint8_t* xb = s.x + (size_t)t * Nv;
@@ -525,6 +527,11 @@ __device__ __forceinline__ void bpl_stream(const BplStreamArgs& s, T* lds, int* 
   }
 }
 
+template <typename T, int ALGO, int DCMAX, int DCFIX, int MODE>
+__device__ __forceinline__ void bpl_stream(const BplStreamArgs& s, T* lds, int* unsat) {
+  stream_blocks(s, [&](int t, int slot) { return bpl_word<T, ALGO, DCMAX, DCFIX, MODE>(s.w, lds, unsat, t, slot); });
+}
+
 template <int ALGO, int DCMAX, int DCFIX, int MODE>
 __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bpls(BplStreamArgs s) {
   extern __shared__ double lds_l[];
@@ -538,6 +545,167 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads, DCFIX >
   extern __shared__ double lds_l[];
   __shared__ int unsat[2];
   bpl_stream<float, ALGO, DCMAX, DCFIX, MODE>(s, reinterpret_cast<float*>(lds_l), unsat);
+}
+
+// ---------------------------------------------------------------------------
+// Fixed-point layered min-sum (LB_FIXED; tests/ldpc_fixed_ref.py is its statement)
+// ---------------------------------------------------------------------------
+// The layered schedule on saturating integers: app int16[Nv] and r int8[Nmsg]
+// in LDS for the whole decode (2 Nv + Nmsg bytes: 802.16 5/6 z=192 is 24 576
+// against binary32's 79 872), one workgroup per word.  The min-sum rule needs
+// two minima and a parity per check, not a chain of values, so a layer is not
+// bpl_word's gather / check-thread / scatter: a group of G lanes (a power of
+// two, within a wave) owns a check.  Lane j of the group reads its edges j,
+// j + G, .. once (app[v] and r[e]), keeps q and v in registers, the group folds
+// (min1, min2, parity) of |q| with __shfl_xor, packed in one word (15 + 15 + 1
+// bits), and every lane writes its own r[e] and app[v]:
+//   mag_e = |q_e| == min1 ? min2 : min1      (a tie of the two smallest gives min2 == min1)
+//   r[e]  = +-min((alpha mag_e + 8) >> 4, rmax);  app[v] = clip(q_e + r[e], +-amax)
+// No variable occurs twice in a layer, so every app[v] and r[e] has one reader
+// and one writer, the same lane, within a layer: one barrier per layer, none
+// inside.  EPL = the edges a lane may hold (G EPL >= the largest check degree).
+// The loops over checks run the same number of passes in every thread, so the
+// shuffles are never issued under divergence; a group without a check folds
+// neutral values.  A check of degree 1 sees mag = amax (the minimum over no edge).
+struct FixedPar {
+  int frac, rmax, amax, alpha;
+};
+
+template <int G, int EPL>
+__device__ __forceinline__ int bplq_word(const BplArgs& a, const FixedPar& p, unsigned char* lds, int* unsat, int word,
+                                         int slot) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int Nv = a.Nv, Nc = a.Nc;
+  const int j = tid & (G - 1), grp = tid / G, cpp = nt / G;  // lane of the group, group, checks per pass
+  const int rmax = p.rmax, amax = p.amax, alpha = p.alpha;
+  const double* ch = a.ch + (size_t)word * Nv;
+  double* out = a.app + (size_t)slot * Nv;
+  int16_t* app = reinterpret_cast<int16_t*>(lds);
+  int8_t* r = reinterpret_cast<int8_t*>(lds + 2 * (size_t)Nv);
+
+  const double up = (double)(1 << p.frac), down = 1.0 / up;
+  for (int i = tid; i < Nv; i += nt) {
+    double x = rint(ch[i] * up);  // half to even; +-inf stay
+    x = x > (double)rmax ? (double)rmax : (x < (double)-rmax ? (double)-rmax : x);
+    app[i] = (int16_t)(x == x ? (int)x : 0);  // NaN -> 0; -0.0 -> 0
+  }
+  for (int i = tid; i < a.Nmsg; i += nt) r[i] = 0;
+  if (tid < 2) unsat[tid] = 0;
+  __syncthreads();
+
+  int it = 0;
+  for (; it < a.maxit; ++it) {
+    // stop test on the hard decisions: bit 0 the check's parity, bit 1 an undecided variable
+    for (int cb = 0; cb < Nc; cb += cpp) {
+      const int c = cb + grp;
+      int w = 0;
+      if (c < Nc) {
+        const int e1 = a.cstart[c + 1];
+        for (int e = a.cstart[c] + j; e < e1; e += G) {
+          const int x = app[a.evar[e]];
+          w ^= x < 0 ? 1 : 0;
+          w |= x == 0 ? 2 : 0;
+        }
+      }
+#pragma unroll
+      for (int o = G / 2; o > 0; o >>= 1) {
+        const int y = __shfl_xor(w, o, 64);
+        w = ((w ^ y) & 1) | ((w | y) & 2);
+      }
+      if (w && j == 0) unsat[it & 1] = 1;
+    }
+    __syncthreads();
+    if (!unsat[it & 1]) break;
+    // the other flag was last read in sweep it-1, before the barrier above
+    if (tid == 0) unsat[(it + 1) & 1] = 0;
+    for (int l = 0; l < a.nlayers; ++l) {
+      const int c0 = a.lfirst[l], c1 = a.lfirst[l + 1];
+      for (int cb = c0; cb < c1; cb += cpp) {
+        const int c = cb + grp;
+        int s = 0, dc = 0;
+        if (c < c1) {
+          s = a.cstart[c];
+          dc = a.cstart[c + 1] - s;
+        }
+        int q[EPL], v[EPL];
+        int m1 = amax, m2 = amax, par = 0;
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+          const int i = j + k * G;
+          if (i < dc) {
+            v[k] = a.evar[s + i];
+            int x = (int)app[v[k]] - (int)r[s + i];
+            x = x > amax ? amax : (x < -amax ? -amax : x);
+            q[k] = x;
+            const int m = x < 0 ? -x : x;
+            par ^= x < 0 ? 1 : 0;
+            m2 = min(m2, max(m1, m));
+            m1 = min(m1, m);
+          }
+        }
+        int w = m1 | (m2 << 15) | (par << 30);
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) {
+          const int y = __shfl_xor(w, o, 64);
+          const int a1 = w & 0x7fff, a2 = (w >> 15) & 0x7fff, b1 = y & 0x7fff, b2 = (y >> 15) & 0x7fff;
+          w = min(a1, b1) | (min(max(a1, b1), min(a2, b2)) << 15) | ((w ^ y) & (1 << 30));
+        }
+        m1 = w & 0x7fff;
+        m2 = (w >> 15) & 0x7fff;
+        par = (w >> 30) & 1;
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+          const int i = j + k * G;
+          if (i < dc) {
+            const int x = q[k];
+            const int m = x < 0 ? -x : x;
+            const int mag = min((alpha * (m == m1 ? m2 : m1) + 8) >> 4, rmax);
+            const int rn = (par ^ (x < 0 ? 1 : 0)) ? -mag : mag;
+            r[s + i] = (int8_t)rn;
+            const int y = x + rn;
+            app[v[k]] = (int16_t)(y > amax ? amax : (y < -amax ? -amax : y));
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < Nv; i += nt) out[i] = (double)app[i] * down;
+  if (tid == 0) a.iters[slot] = it;
+  return it;
+}
+
+struct BplqArgs {
+  BplArgs w;  // (gmsg and corr unused)
+  FixedPar p;
+};
+
+struct BplqStreamArgs {
+  BplStreamArgs s;
+  FixedPar p;
+};
+
+// The second bound follows from the measured residency: the 802.16 5/6 z=192 plan (G = 4, five edges a
+// lane, 1024 threads, a 24 KB image) has two workgroups on a CU only at eight waves a SIMD, which the
+// persistent instance missed by its scalar registers (103: seven waves).  Instances of up to five
+// edges a lane are asked for eight (at most 64 VGPRs, which they use anyway: 35..61); the wider ones
+// (up to 105 VGPRs at 32 edges a lane) keep what 1024 threads imply.
+constexpr int fixed_waves(int epl) { return epl <= 5 ? 8 : 4; }
+
+template <int G, int EPL>
+__global__ void __launch_bounds__(kMaxThreads, fixed_waves(EPL)) k_bplq(BplqArgs a) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  (void)bplq_word<G, EPL>(a.w, a.p, reinterpret_cast<unsigned char*>(lds_l), unsat, blockIdx.x, blockIdx.x);
+}
+
+// the persistent ticketed form (lb_mc_stream_seeds)
+template <int G, int EPL>
+__global__ void __launch_bounds__(kMaxThreads, fixed_waves(EPL)) k_bplsq(BplqStreamArgs a) {
+  extern __shared__ double lds_l[];
+  __shared__ int unsat[2];
+  unsigned char* lds = reinterpret_cast<unsigned char*>(lds_l);
+  stream_blocks(a.s, [&](int t, int slot) { return bplq_word<G, EPL>(a.s.w, a.p, lds, unsat, t, slot); });
 }
 
 // ---------------------------------------------------------------------------
@@ -808,6 +976,55 @@ StreamFn pick_stream(int algo, int maxdc, bool fixed, int mode, bool f32) {
                      : pick_stream_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
 }
 
+// The fixed-point instances: lanes per check G x the check-degree class (8 / 16 / 20 / 32 edges over
+// the group's lanes; 20 is the 802.16 5/6 codes' degree and keeps their lanes at 10 edges, not 16).  fixed_index numbers them for the context's record of raised LDS limits.
+using FixedFn = void (*)(BplqArgs);
+using FixedStreamFn = void (*)(BplqStreamArgs);
+
+constexpr int edges_per_lane(int dcmax, int g) { return (dcmax + g - 1) / g; }
+
+template <int G>
+FixedFn pick_fixed_g(int maxdc) {
+  if (maxdc <= 8) return k_bplq<G, edges_per_lane(8, G)>;
+  if (maxdc <= 16) return k_bplq<G, edges_per_lane(16, G)>;
+  if (maxdc <= 20) return k_bplq<G, edges_per_lane(20, G)>;
+  return k_bplq<G, edges_per_lane(32, G)>;
+}
+
+template <int G>
+FixedStreamFn pick_fixed_stream_g(int maxdc) {
+  if (maxdc <= 8) return k_bplsq<G, edges_per_lane(8, G)>;
+  if (maxdc <= 16) return k_bplsq<G, edges_per_lane(16, G)>;
+  if (maxdc <= 20) return k_bplsq<G, edges_per_lane(20, G)>;
+  return k_bplsq<G, edges_per_lane(32, G)>;
+}
+
+FixedFn pick_fixed(int lanes, int maxdc) {
+  switch (lanes) {
+    case 1: return pick_fixed_g<1>(maxdc);
+    case 2: return pick_fixed_g<2>(maxdc);
+    case 4: return pick_fixed_g<4>(maxdc);
+    case 8: return pick_fixed_g<8>(maxdc);
+    default: return pick_fixed_g<16>(maxdc);
+  }
+}
+
+FixedStreamFn pick_fixed_stream(int lanes, int maxdc) {
+  switch (lanes) {
+    case 1: return pick_fixed_stream_g<1>(maxdc);
+    case 2: return pick_fixed_stream_g<2>(maxdc);
+    case 4: return pick_fixed_stream_g<4>(maxdc);
+    case 8: return pick_fixed_stream_g<8>(maxdc);
+    default: return pick_fixed_stream_g<16>(maxdc);
+  }
+}
+
+int fixed_index(int lanes, int maxdc) {
+  int lg = 0;
+  while ((1 << lg) < lanes) ++lg;
+  return lg * 4 + (maxdc <= 8 ? 0 : maxdc <= 16 ? 1 : maxdc <= 20 ? 2 : 3);
+}
+
 using TailFn = void (*)(TailArgs);
 
 template <int ALGO>
@@ -966,6 +1183,86 @@ int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_i
   return LB_OK;
 }
 
+// ---- fixed point (LB_FIXED) ----
+// LB_FIXED goes with layered min-sum alone (algo without its flags)
+int fixed_type(int algo, bool f32) {
+  if (f32) return fail(LB_ERR_ARG, "LB_FIXED | LB_F32: the fixed-point decoder has no binary32 form");
+  if (algo != LB_LAYERED_MINSUM)
+    return fail(LB_ERR_UNSUPPORTED, "fixed-point (LB_FIXED) exists for layered min-sum (LB_LAYERED_MINSUM) only");
+  return LB_OK;
+}
+
+// the kernel's parameters from the context's widths and corr_factor; the context has layers
+int fixed_par(lb_ctx* c, double corr, FixedPar* p) {
+  const double alpha = nearbyint(16.0 * corr);  // half to even, as rint in the statement
+  if (!(alpha >= 1.0 && alpha <= 16.0))
+    return fail(LB_ERR_ARG, "fixed-point min-sum needs rint(16 corr_factor) in 1..16");
+  if (!c->qfit)
+    return fail(LB_ERR_UNSUPPORTED, "fixed-point decoder: the image (" + std::to_string(c->qlds) +
+                                        " bytes) does not fit a workgroup's LDS, and there is no HBM layout");
+  p->frac = c->qfrac;
+  p->rmax = (1 << (c->qmsg - 1)) - 1;
+  p->amax = (1 << (c->qapp - 1)) - 1;
+  p->alpha = (int)alpha;
+  return LB_OK;
+}
+
+// threads per workgroup, lanes per check and LDS bytes of the fixed-point decoder (lb_set_layers,
+// lb_set_fixed).  Lanes: the largest power of two, at most the largest check degree and 16, at which
+// the largest layer's groups still fit 768 threads (measured at 802.16 5/6 z=192, DESIGN.md section
+// 10b: 4 lanes against 2 and 8); threads: a lane for every group of the largest layer, and all 1024
+// where that is more than a third of a CU's 2048 (two workgroups share a CU either way, and the
+// loops over all checks and variables take fewer passes).
+void plan_fixed(lb_ctx* c) {
+  int cap = 1;
+  while (cap * 2 <= c->maxdc && cap < 16) cap *= 2;
+  int g = 1;
+  while (g * 2 <= cap && (long long)c->maxlayer * g * 2 <= 768) g *= 2;
+  if (const char* e = getenv("LDPC_BP_FIXED_LANES"); e && *e) {
+    const int v = atoi(e);
+    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) g = v;
+  }
+  long long nt = std::min<long long>(kMaxThreads, ((long long)c->maxlayer * g + 63) / 64 * 64);
+  if (nt * 3 > 2048) nt = kMaxThreads;
+  if (const char* e = getenv("LDPC_BP_FIXED_THREADS"); e && *e) nt = std::min(kMaxThreads, atoi(e) / 64 * 64);
+  c->qlanes = g;
+  c->qnt = (int)std::max<long long>(64, nt);
+  const long long bytes = (2LL * c->Nv + c->Nmsg + 15) / 16 * 16;
+  c->qfit = bytes <= (long long)kLdsBytes - 64;
+  c->qlds = (int)std::min<long long>(bytes, INT32_MAX);
+}
+
+int raise_lds(const void* fn, unsigned long long* done, int index) {
+  if (*done & (1ull << index)) return LB_OK;
+  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
+  *done |= 1ull << index;
+  return LB_OK;
+}
+
+int launch_fixed(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const FixedPar& p, int max_iter) {
+  const FixedFn fn = pick_fixed(c->qlanes, c->maxdc);
+  int rc;
+  if ((rc = raise_lds((const void*)fn, &c->qattrs, fixed_index(c->qlanes, c->maxdc)))) return rc;
+  BplqArgs a;
+  a.w.ch = d_ch;
+  a.w.app = d_app;
+  a.w.iters = d_it;
+  a.w.gmsg = nullptr;
+  a.w.evar = c->d_evar;
+  a.w.cstart = c->d_cstart;
+  a.w.lfirst = c->d_lfirst;
+  a.w.Nv = c->Nv;
+  a.w.Nc = c->Nc;
+  a.w.Nmsg = c->Nmsg;
+  a.w.nlayers = c->nlayers;
+  a.w.maxit = max_iter;
+  a.w.corr = 0.0;
+  a.p = p;
+  hipLaunchKernelGGL(fn, dim3(B), dim3(c->qnt), (size_t)c->qlds, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  return LB_OK;
+}
+
 // layered_instance for the persistent kernels (lattrs bits 4..7)
 int stream_instance(lb_ctx* c, int algo, bool f32, StreamFn* fn, size_t* shm) {
   const int mode = f32 ? c->lmode32 : c->lmode;
@@ -982,35 +1279,45 @@ int stream_instance(lb_ctx* c, int algo, bool f32, StreamFn* fn, size_t* shm) {
 }
 
 // (lb::stream_plan, declared in ldpc_bp_int.h)
-int stream_plan(lb_ctx* c, int algo, int max_iter, int* resident) {
-  const bool f32 = algo >= 0 && (algo & LB_F32);
-  if (f32) algo &= ~LB_F32;
+int stream_plan(lb_ctx* c, int algo, double corr, int max_iter, int* resident) {
+  const bool f32 = algo >= 0 && (algo & LB_F32), fixed = algo >= 0 && (algo & LB_FIXED);
+  if (algo >= 0) algo &= ~(LB_F32 | LB_FIXED);
   if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  int rc;
+  if (fixed && (rc = fixed_type(algo, f32))) return rc;
   if (algo < LB_LAYERED_SUMPROD2)
     return fail(LB_ERR_UNSUPPORTED, "the block stream exists for the layered decoder types only");
   if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
   if (!c->nlayers) return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
+  FixedPar par;
+  if (fixed && (rc = fixed_par(c, corr, &par))) return rc;
   if (f32 && c->lmode32 == 0 && c->Nv > c->Nmsg)
     return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
   if (!resident) return LB_OK;
   HIP_TRY(hipSetDevice(c->dev));
-  StreamFn fn;
-  size_t shm;
-  int rc, n = 0;
-  if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
+  int n = 0;
+  if (fixed) {
+    const FixedStreamFn fn = pick_fixed_stream(c->qlanes, c->maxdc);
+    if ((rc = raise_lds((const void*)fn, &c->qattrs, 20 + fixed_index(c->qlanes, c->maxdc)))) return rc;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->qnt, (size_t)c->qlds));
+  } else {
+    StreamFn fn;
+    size_t shm;
+    if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
+  }
   *resident = std::max(1, n);
   return LB_OK;
 }
 
 // (lb::launch_stream, declared in ldpc_bp_int.h; the arguments have passed stream_plan)
 int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter) {
-  const bool f32 = (algo & LB_F32) != 0;
-  algo &= ~LB_F32;
-  StreamFn fn;
-  size_t shm;
+  const bool f32 = (algo & LB_F32) != 0, fixed = (algo & LB_FIXED) != 0;
+  algo &= ~(LB_F32 | LB_FIXED);
+  StreamFn fn = nullptr;
+  size_t shm = 0;
   int rc;
-  if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
+  if (!fixed && (rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
   BplStreamArgs s;
   s.w.ch = k.ch;
   s.w.app = k.app;
@@ -1034,6 +1341,16 @@ int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, in
   s.chunk = k.chunk;
   s.base = k.base;
   s.min_errors = k.min_errors;
+  if (fixed) {
+    BplqStreamArgs q;
+    q.s = s;
+    if ((rc = fixed_par(c, corr, &q.p))) return rc;
+    const FixedStreamFn qfn = pick_fixed_stream(c->qlanes, c->maxdc);
+    if ((rc = raise_lds((const void*)qfn, &c->qattrs, 20 + fixed_index(c->qlanes, c->maxdc)))) return rc;
+    hipLaunchKernelGGL(qfn, dim3(slots), dim3(c->qnt), (size_t)c->qlds, st, q);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+  }
   hipLaunchKernelGGL(fn, dim3(slots), dim3(c->lnt), shm, st, s);
   HIP_TRY(hipGetLastError());
   return LB_OK;
@@ -1080,14 +1397,18 @@ int set_attrs(lb_ctx* c) {
 // queued without waiting (see TailArgs)
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
            int max_iter, bool sized_on_host) {
-  const bool f32 = algo >= 0 && (algo & LB_F32);
-  if (f32) algo &= ~LB_F32;
+  const bool f32 = algo >= 0 && (algo & LB_F32), fixed = algo >= 0 && (algo & LB_FIXED);
+  if (algo >= 0) algo &= ~(LB_F32 | LB_FIXED);
   if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  int rcq;
+  if (fixed && (rcq = fixed_type(algo, f32))) return rcq;
   if (f32 && algo < LB_LAYERED_SUMPROD2)
     return fail(LB_ERR_UNSUPPORTED, "binary32 (LB_F32) exists for the layered decoder types only");
   if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
   if (algo >= LB_LAYERED_SUMPROD2 && !c->nlayers)
     return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
+  FixedPar par;
+  if (fixed && (rcq = fixed_par(c, corr, &par))) return rcq;
   if (B == 0) return LB_OK;
   if (max_iter == 0) {
     // no iteration: the variable phase on zero messages, app = ch (the uncoded
@@ -1096,6 +1417,7 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
     HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
     return LB_OK;
   }
+  if (fixed) return launch_fixed(c, B, d_ch, d_app, d_it, par, max_iter);
   if (algo >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, algo, f32, corr, max_iter);
   // the tail's variable kernel puts the words on the grid's y dimension (<= 65535)
   const bool tail = c->tail_at > 0 && max_iter > c->tail_at && B <= 65535;
@@ -1567,6 +1889,39 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   if (const char* e = getenv("LDPC_BP_LAYERED_F32_RESIDENT"); e && *e) c->lone32 = atoi(e) == 1;
   else c->lone32 = false;
   c->lattrs = 0;
+  plan_fixed(c);
+  return LB_OK;
+}
+
+int lb_set_fixed(lb_ctx* c, int frac_bits, int msg_bits, int app_bits) {
+  if (!c) return fail(LB_ERR_ARG, "null context");
+  if (frac_bits < 0 || frac_bits > 8 || msg_bits < 2 || msg_bits > 8 || app_bits < msg_bits || app_bits > 16)
+    return fail(LB_ERR_ARG, "fixed-point widths: frac_bits in 0..8, msg_bits in 2..8, app_bits in msg_bits..16");
+  c->qfrac = frac_bits;
+  c->qmsg = msg_bits;
+  c->qapp = app_bits;
+  if (c->nlayers) plan_fixed(c);  // (the switches of the environment, read again)
+  return LB_OK;
+}
+
+int lb_fixed_info(lb_ctx* c, long long* out) {
+  if (!c || !out) return fail(LB_ERR_ARG, "null argument");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = c->qfrac;
+  out[1] = c->qmsg;
+  out[2] = c->qapp;
+  if (!c->nlayers) return LB_OK;
+  out[3] = c->qnt;
+  out[4] = c->qlanes;
+  out[5] = c->qlds;
+  out[7] = c->qfit ? 1 : 0;
+  if (!c->qfit) return LB_OK;
+  HIP_TRY(hipSetDevice(c->dev));
+  const FixedFn fn = pick_fixed(c->qlanes, c->maxdc);
+  int rc, n = 0;
+  if ((rc = raise_lds((const void*)fn, &c->qattrs, fixed_index(c->qlanes, c->maxdc)))) return rc;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->qnt, (size_t)c->qlds));
+  out[6] = n;
   return LB_OK;
 }
 

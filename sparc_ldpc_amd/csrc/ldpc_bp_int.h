@@ -50,6 +50,12 @@ struct lb_ctx {
   bool lone32 = false;        // LDPC_BP_LAYERED_F32_RESIDENT = 1: binary32 workgroups padded to one per CU
   unsigned lattrs = 0;        // layered instances whose dynamic LDS size has been raised (bit per algorithm
                               // and precision)
+  // fixed-point layered min-sum (k_bplq), lb_set_fixed: the widths; the plan made by lb_set_layers /
+  // lb_set_fixed: threads per workgroup, lanes per check, dynamic LDS bytes, whether the image fits
+  int qfrac = 2, qmsg = 6, qapp = 8;
+  int qnt = 0, qlanes = 0, qlds = 0;
+  bool qfit = false;
+  unsigned long long qattrs = 0;  // fixed-point instances whose dynamic LDS size has been raised
   lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
 };
 
@@ -65,7 +71,7 @@ int ensure_io(lb_ctx* c, int B);
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
            int max_iter, bool sized_on_host);
 // One chunk of lb_mc_stream_seeds for the persistent layered kernels (k_bpls,
-// k_bpls32 in ldpc_bp.hip): a grid of `slots` workgroups takes the chunk's
+// k_bpls32, k_bplsq in ldpc_bp.hip): a grid of `slots` workgroups takes the chunk's
 // blocks by ticket, decodes and counts them.
 struct StreamChunk {
   const double* ch;   // [chunk][Nv]
@@ -80,9 +86,9 @@ struct StreamChunk {
   int* ecur;          // zeroed: block errors of this chunk
   int chunk, base, min_errors;
 };
-// Whether algo / max_iter can stream on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED; nothing is
+// Whether algo / corr / max_iter can stream on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED; nothing is
 // changed then); resident (may be null): workgroups of the instance a CU holds at once
-int stream_plan(lb_ctx* c, int algo, int max_iter, int* resident);
+int stream_plan(lb_ctx* c, int algo, double corr, int max_iter, int* resident);
 // queue one chunk on `st`; never waits
 int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter);
 // free the Monte-Carlo state of a context (ldpc_mc.hip)

@@ -647,19 +647,19 @@ int lb_mc_stream_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double
   if (enc && (!c->mc || c->mc->Mp == 0))
     return fail(LB_ERR_ARG, "lb_mc_stream_seeds: no encoder set (lb_mc_set_code)");
   int rc, resident = 1;
-  if ((rc = lb::stream_plan(c, algo, max_iter, nullptr))) return rc;
+  if ((rc = lb::stream_plan(c, algo, corr, max_iter, nullptr))) return rc;
   out[0] = out[1] = out[2] = out[3] = 0;
   if (nblk == 0) return LB_OK;
   HIP_TRY(hipSetDevice(c->dev));
-  if ((rc = lb::stream_plan(c, algo, max_iter, &resident))) return rc;
+  if ((rc = lb::stream_plan(c, algo, corr, max_iter, &resident))) return rc;
   chunk = std::min(chunk, nblk);
   // a slot beyond the chunk's blocks would find no ticket
   slots = std::min(slots > 0 ? slots : resident * c->ncu, chunk);
   const int nchunks = (nblk + chunk - 1) / chunk;
   if ((rc = ensure_state(c))) return rc;
   if ((rc = ensure_staging(c, chunk, false))) return rc;
-  const bool f32 = (algo & LB_F32) != 0;
-  if ((rc = ensure_stream(c, chunk, slots, nchunks, (f32 ? c->lmode32 : c->lmode) < 2))) return rc;
+  const bool f32 = (algo & LB_F32) != 0, fixed = (algo & LB_FIXED) != 0;  // (fixed point: no HBM messages)
+  if ((rc = ensure_stream(c, chunk, slots, nchunks, !fixed && (f32 ? c->lmode32 : c->lmode) < 2))) return rc;
   lb_mc* m = c->mc;
   if ((rc = ensure_results(m, nblk))) return rc;
   if ((rc = ensure_seeds(m, nblk))) return rc;

@@ -29,6 +29,8 @@ LB_F32 = 0x100  # precision flag OR-ed into a layered type: binary32 messages
 _ALGOS = {"sumprod2": LB_SUMPROD2, "sumprod": LB_SUMPROD, "minsum": LB_MINSUM,
           "layered_sumprod2": LB_LAYERED_SUMPROD2, "layered_minsum": LB_LAYERED_MINSUM,
           "layered_sumprod2_f32": LB_LAYERED_SUMPROD2 | LB_F32, "layered_minsum_f32": LB_LAYERED_MINSUM | LB_F32}
+LB_FIXED = 0x400  # arithmetic flag OR-ed into LB_LAYERED_MINSUM: saturating integers (the quant keyword)
+FIXED_DEFAULT = (2, 6, 8)  # frac_bits, msg_bits, app_bits of quant=True (lb_set_fixed's defaults)
 _REFERENCE_ALGOS = ("sumprod2", "sumprod", "minsum")  # code.decode's names (ldpc.py:855-930)
 _CHANNELS = {"awgn": 0, "bsc": 1}  # lb_mc_run / lb_draw_blocks kinds
 STREAM_CHUNK = 4096  # blocks per chunk of code.mc_stream_seeds
@@ -40,7 +42,7 @@ EXPORTS = (
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
     "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info", "lb_layer_info_ex",
     "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
-    "lb_mc_stream_seeds",
+    "lb_mc_stream_seeds", "lb_set_fixed", "lb_fixed_info",
 )
 
 _P, _I, _D = ct.c_void_p, ct.c_int, ct.POINTER(ct.c_double)
@@ -67,6 +69,8 @@ _SIG = {
     "lb_set_layers": (_I, [_P, _I, _IP]),
     "lb_layer_info": (_I, [_P, ct.POINTER(ct.c_int64)]),
     "lb_layer_info_ex": (_I, [_P, _I, ct.POINTER(ct.c_int64)]),
+    "lb_set_fixed": (_I, [_P, _I, _I, _I]),
+    "lb_fixed_info": (_I, [_P, ct.POINTER(ct.c_int64)]),
     "lb_device_count": (_I, []),
     "lb_last_error": (ct.c_char_p, []),
     "lb_version": (ct.c_char_p, []),
@@ -116,6 +120,23 @@ def _layered_entry(name):
     if fn is None:
         raise LdpcBpError(-5, f"this libldpc_bp.so has no layered decoder ({name})")
     return fn
+
+
+def _quant_widths(quant, dectype):
+    """The (frac_bits, msg_bits, app_bits) a ``quant`` keyword asks for, or None:
+    None: floating point as ever; True: FIXED_DEFAULT; a triple: those widths.
+    ValueError unless the decoder type is "layered_minsum" (needs no device)."""
+    if quant is None:
+        return None
+    if dectype != "layered_minsum":
+        raise ValueError('quant (fixed-point arithmetic) goes with dectype="layered_minsum" only')
+    if quant is True:
+        return FIXED_DEFAULT
+    try:
+        f, m, a = (int(x) for x in quant)
+    except (TypeError, ValueError):
+        raise ValueError("quant must be None, True or (frac_bits, msg_bits, app_bits)") from None
+    return f, m, a
 
 
 def _check(rc: int) -> None:
@@ -229,7 +250,15 @@ class code:
     the same schedule on binary32 messages (LB_F32; CH and app stay float64,
     CH is clamped to +-2**100 on load).  ``mc_stream_seeds`` runs
     ``mc_blocks_seeds``' blocks, with a layered dectype, as a stream of refilled
-    decoder slots with an optional stopping rule (lb_mc_stream_seeds)."""
+    decoder slots with an optional stopping rule (lb_mc_stream_seeds).
+
+    These five also take ``quant`` with dectype "layered_minsum": the
+    fixed-point decoder (LB_FIXED, include/ldpc_bp.h), layered normalised
+    min-sum on saturating integers.  None: floating point as ever; True:
+    FIXED_DEFAULT; (frac_bits, msg_bits, app_bits): those widths.  With any
+    other dectype it is a ValueError.  app stays float64 and holds
+    int * 2**-frac_bits exactly; ``decode`` (the reference's signature) does
+    not take it."""
 
     def __init__(self, standard="802.11n", rate="1/2", z=27, ptype="A", device=None):
         self.standard = standard
@@ -293,14 +322,34 @@ class code:
             self._ctx = ctx
         return self._ctx
 
-    def _algo(self, dectype):
+    def _algo(self, dectype, quant=None):
         """The library's number of a decoder type; a layered one sets the
-        context's layers (the protograph rows) on first use."""
+        context's layers (the protograph rows) on first use.  ``quant``: the
+        context's fixed-point widths are set and LB_FIXED is OR-ed in."""
         if dectype not in _ALGOS:
             raise NameError("Decoder type unknonwn")
+        widths = _quant_widths(quant, dectype)
         if dectype.startswith("layered_") and not self._layers_set:
             self.set_layers(np.arange(0, self.Nc + 1, self.z))
-        return _ALGOS[dectype]
+        if widths is None:
+            return _ALGOS[dectype]
+        self.set_fixed(*widths)
+        return _ALGOS[dectype] | LB_FIXED
+
+    def set_fixed(self, frac_bits=FIXED_DEFAULT[0], msg_bits=FIXED_DEFAULT[1], app_bits=FIXED_DEFAULT[2]):
+        """The widths of the fixed-point decoder for the decodes that follow
+        (lb_set_fixed: frac_bits 0..8, msg_bits 2..8, app_bits msg_bits..16;
+        AssertionError otherwise, and the widths stay as they were)."""
+        _check(_layered_entry("lb_set_fixed")(self._context(), int(frac_bits), int(msg_bits), int(app_bits)))
+
+    def fixed_info(self):
+        """lb_fixed_info: the widths, and (0 before the layers are set) threads
+        per workgroup, lanes per check, dynamic LDS bytes, workgroups resident
+        on a CU and whether the int16 / int8 image fits LDS."""
+        out = (ct.c_int64 * 8)()
+        _check(_layered_entry("lb_fixed_info")(self._context(), out))
+        keys = ("frac_bits", "msg_bits", "app_bits", "threads", "lanes", "lds_bytes", "resident", "fits")
+        return dict(zip(keys, list(out)))
 
     def set_layers(self, first_check):
         """Layer l = the checks first_check[l] .. first_check[l+1]-1
@@ -328,9 +377,9 @@ class code:
         _check(_layered_entry("lb_layer_info_ex")(self._context(), 1, out))
         return dict(zip(keys + ("lds_bytes", "resident", "resident_minsum", "message_bytes"), list(out)))
 
-    def decode_batch(self, CH, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
+    def decode_batch(self, CH, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT, quant=None):
         """Decode B words (rows of CH, channel LLRs) -> (app (B, N) float64, it (B,) int)."""
-        algo = self._algo(dectype)
+        algo = self._algo(dectype, quant)
         CH = np.ascontiguousarray(np.atleast_2d(CH), dtype=np.float64)
         if CH.shape[1] != self.Nv:
             raise NameError("Channel inputs not consistent with variable degrees")
@@ -372,14 +421,14 @@ class code:
         return X
 
     def mc_blocks(self, u, w, a, channel="awgn", batch=1024, dectype="sumprod2", corr_factor=0.7,
-                  max_iter=MAX_ITCOUNT):
+                  max_iter=MAX_ITCOUNT, quant=None):
         """Blocks through the device pipeline (lb_mc_run): u (B, K) 0/1 uint8
         information bits (None: the all-zero word), w (B, N) float64 draws
         (randn for "awgn", random_sample for "bsc"), a = sigma or p.  Per block:
         encode, ch = (2/sigma**2) * ((1 - 2x) + sigma*w) or -/+ log((1-p)/p)
         where w < p / elsewhere, decode, count.  Returns int64 (bit_errors,
         iters); only those come back from the device."""
-        algo = self._algo(dectype)
+        algo = self._algo(dectype, quant)
         if channel not in _CHANNELS:
             raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
         w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
@@ -403,14 +452,14 @@ class code:
         return errs.astype(np.int64), it.astype(np.int64)
 
     def mc_blocks_seeds(self, seeds, a, channel="awgn", batch=1024, dectype="sumprod2", corr_factor=0.7,
-                        max_iter=MAX_ITCOUNT):
+                        max_iter=MAX_ITCOUNT, quant=None):
         """mc_blocks on blocks drawn on the device from their seeds
         (lb_mc_run_seeds; the blocks of ldpc_mc.draw_blocks_device): only the
         seeds go up.  The information bits are drawn where ldpc_mc.info_bits
         says the reference encodes, else the all-zero word is sent.  Returns
         int64 (bit_errors, iters) in seed order."""
         from .ldpc_mc import _seed_array, info_bits
-        algo = self._algo(dectype)
+        algo = self._algo(dectype, quant)
         if channel not in _CHANNELS:
             raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
         seeds = _seed_array(seeds)
@@ -427,7 +476,7 @@ class code:
         return errs.astype(np.int64), it.astype(np.int64)
 
     def mc_stream_seeds(self, seeds, a, channel="awgn", chunk=STREAM_CHUNK, dectype="layered_sumprod2",
-                        corr_factor=0.7, max_iter=MAX_ITCOUNT, min_errors=0, slots=0):
+                        corr_factor=0.7, max_iter=MAX_ITCOUNT, min_errors=0, slots=0, quant=None):
         """mc_blocks_seeds as a stream of refilled decoder slots
         (lb_mc_stream_seeds; layered decoders only): per chunk of ``chunk``
         blocks one persistent kernel of ``slots`` workgroups (0: what the
@@ -440,7 +489,7 @@ class code:
         dict(used: the blocks the rule consumes (all of them without a rule),
         decoded, slots, chunks)."""
         from .ldpc_mc import _seed_array, info_bits
-        algo = self._algo(dectype)  # (a flooding type: LdpcBpError -5 from the library)
+        algo = self._algo(dectype, quant)  # (a flooding type: LdpcBpError -5 from the library)
         if channel not in _CHANNELS:
             raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
         seeds = _seed_array(seeds)
@@ -467,12 +516,13 @@ class code:
         _check(load_bp_library().lb_buffers(self._context(), int(B), ct.byref(ch), ct.byref(app), ct.byref(it)))
         return ch.value, app.value, it.value
 
-    def run_buffers(self, B, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT):
+    def run_buffers(self, B, dectype="sumprod2", corr_factor=0.7, max_iter=MAX_ITCOUNT, quant=None):
         """Decode the B words in the device ch buffer into the app buffer (blocking)."""
-        lib = load_bp_library()
         if dectype not in _ALGOS:
             raise KeyError(dectype)  # as before the layered names
-        _check(lib.lb_run(self._context(), int(B), self._algo(dectype), float(corr_factor), int(max_iter)))
+        algo = self._algo(dectype, quant)
+        lib = load_bp_library()
+        _check(lib.lb_run(self._context(), int(B), algo, float(corr_factor), int(max_iter)))
         _check(lib.lb_wait(self._context()))
 
     def fetch_buffers(self, B, app=True):

@@ -30,7 +30,7 @@ sim_param = _grid(3)  # ldpc_awgn.py:6-43
 
 def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_STEP=100.0,
         MIN_ERRORS=100, MAX_BLOCKS=400000, *, seed0=0, batch=1024, results_file=None, draws="host",
-        dectype="sumprod2", stream=False):
+        dectype="sumprod2", stream=False, quant=None):
     """ldpc_awgn.py:60-123.  Starts C_AWGN_OFFSET dB above the SNR of the AWGN
     rate, and per point: sigma2 = 1 / 10**(SNR/10), blocks until MIN_ERRORS
     block errors or MAX_BLOCKS, then SNR += sqrt(P_STEP / nblocks).  Point d
@@ -42,11 +42,14 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     decoder (code.decode_batch's names, the layered ones and their binary32
     "_f32" forms included; nit_total then counts sweeps).  stream=True
     (draws="device", a layered dectype): every point as one stream of refilled
-    decoder slots (ldpc_mc._mc_point); the same tuples."""
+    decoder slots (ldpc_mc._mc_point); the same tuples.  quant (None, True or
+    (frac_bits, msg_bits, app_bits), with dectype "layered_minsum"): the
+    fixed-point decoder (ldpc.code)."""
     ldpc_mc._check_draws(draws)
     ldpc_mc._check_stream(stream, draws, dectype)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
+    _ldpc._quant_widths(quant, dectype)
     if rate not in _RATES:
         raise NameError("Rate unsupported")
     R = _RATES[rate]
@@ -59,7 +62,8 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
         r = ldpc_mc._mc_point(code, float(np.sqrt(sigma2)), "awgn", MIN_ERRORS, MAX_BLOCKS,
                               seed0 + datapoint * 10_000_000, batch, draws=draws,
                               **({} if dectype == "sumprod2" else {"dectype": dectype}),
-                              **({"stream": True} if stream else {}))
+                              **({"stream": True} if stream else {}),
+                              **({} if quant is None else {"quant": quant}))
         nblocks = r["blocks"]
         output = (standard, rate, z, SNR, nblocks, r["block_errors"], nblocks * K, r["bit_errors"], r["iters_total"])
         res.append(output)

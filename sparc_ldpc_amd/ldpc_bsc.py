@@ -17,7 +17,8 @@ _P0 = {"1/2": 0.11, "2/3": 0.06, "5/6": 0.02459, "3/4": 0.0415}
 sim_param = _grid(100)  # ldpc_bsc.py:6-43
 
 
-def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dectype="sumprod2", stream=False):
+def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dectype="sumprod2", stream=False,
+        quant=None):
     """ldpc_bsc.py:63-113: (res, parray) with parray = linspace(p0, 0.001, 10)
     and res[i] the mean bit error rate of ``repeats`` blocks at parray[i].
     Point i decodes the blocks seed0 + i * 10_000_000, ... (ldpc_mc's BSC
@@ -26,11 +27,13 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
     dectype: the decoder (code.decode_batch's names, the layered ones and their
     binary32 "_f32" forms included).  stream=True (draws="device", a layered
     dectype): the blocks through refilled decoder slots (ldpc_mc.mc_ldpc); the
-    same results."""
+    same results.  quant (None, True or (frac_bits, msg_bits, app_bits), with
+    dectype "layered_minsum"): the fixed-point decoder (ldpc.code)."""
     ldpc_mc._check_draws(draws)
     ldpc_mc._check_stream(stream, draws, dectype)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
+    _ldpc._quant_widths(quant, dectype)
     if rate not in _P0:
         raise NameError("Rate unsupported")
     p = _P0[rate]
@@ -43,7 +46,8 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
         be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc",
                                 **({} if draws == "host" else {"draws": draws}),
                                 **({} if dectype == "sumprod2" else {"dectype": dectype}),
-                                **({"stream": True} if stream else {}))
+                                **({"stream": True} if stream else {}),
+                                **({} if quant is None else {"quant": quant}))
         errors = [int(b) / N for b in be]
         res.append(np.sum(errors) / repeats)
     return res, parray

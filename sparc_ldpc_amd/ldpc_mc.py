@@ -132,15 +132,19 @@ def draw_blocks_device(code, seeds, channel="awgn"):
     return u, w
 
 
-def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, draws="host", stream=False):
+def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, draws="host", stream=False,
+            quant=None):
     """Blocks ``seeds`` of ``code`` at sigma (AWGN) or p (BSC) ``a``: per-block
     int64 (bit_errors, iters) in seed order.  ``drawn``: the blocks' (u, w)
     when the caller has drawn them already (draw_blocks).  draws="device":
     the blocks are drawn on the GPU from their seeds (code.mc_blocks_seeds).
     stream=True (device draws, a layered dectype): the same results through
-    code.mc_stream_seeds, ``batch`` being its chunk."""
+    code.mc_stream_seeds, ``batch`` being its chunk.  quant (with dectype
+    "layered_minsum"): the fixed-point decoder, see ldpc.code."""
     _check_draws(draws)
     _check_stream(stream, draws, dectype)
+    _ldpc._quant_widths(quant, dectype)
+    q = {} if quant is None else {"quant": quant}
     seeds = list(seeds)
     if draws == "device":
         if drawn is not None:
@@ -149,15 +153,15 @@ def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", draw
     if not len(seeds):
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     if stream:
-        return code.mc_stream_seeds(seeds, a, channel, batch, dectype)[:2]
+        return code.mc_stream_seeds(seeds, a, channel, batch, dectype, **q)[:2]
     if draws == "device":
-        return code.mc_blocks_seeds(seeds, a, channel, batch, dectype)
+        return code.mc_blocks_seeds(seeds, a, channel, batch, dectype, **q)
     u, w = draw_blocks(seeds, info_bits(code, channel), code.N, channel) if drawn is None else drawn
-    return code.mc_blocks(u, w, a, channel, batch, dectype)
+    return code.mc_blocks(u, w, a, channel, batch, dectype, **q)
 
 
 def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectype="sumprod2", rank=0, world=1,
-              allreduce=None, timings=None, draws="host", stream=False):
+              allreduce=None, timings=None, draws="host", stream=False, quant=None):
     """One operating point by the reference's stopping rule (harness.ber_point)
     over the blocks seed_base, seed_base + 1, ...: round r + 1 is drawn in a
     worker thread while round r decodes.  ``timings`` (a dict) receives the
@@ -169,12 +173,13 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
     the device (``batch`` is its chunk), and the result from its first blocks
     by the same sequential arithmetic (harness.consume_in_seed_order): the
     same dict as stream=False.  ``timings["stream"]`` receives the call's
-    info (used, decoded, slots, chunks)."""
+    info (used, decoded, slots, chunks).  quant: as mc_ldpc."""
     _check_draws(draws)
+    q = {} if quant is None else {"quant": quant}
     if _check_stream(stream, draws, dectype, world):
         nblk = max(1, int(max_blocks))
         be, it, info = code.mc_stream_seeds(int(seed_base) + np.arange(nblk, dtype=np.int64), a, channel, batch,
-                                            dectype, min_errors=int(min_errors))
+                                            dectype, min_errors=int(min_errors), **q)
         if timings is not None:
             timings["draw_s"] = timings.get("draw_s", 0.0)  # (inside device_ms)
             timings["device_ms"] = timings.get("device_ms", 0.0) + code.mc_event_ms()
@@ -185,7 +190,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
         ms = [0.0]
 
         def decode_seeds(seeds):
-            out = mc_ldpc(code, a, seeds, channel, batch, dectype, draws="device")
+            out = mc_ldpc(code, a, seeds, channel, batch, dectype, draws="device", **q)
             ms[0] += code.mc_event_ms()
             return out
 
@@ -214,7 +219,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
             drawn = fut.result() if fut is not None else draw(seeds)
             if r + 1 < max_rounds:
                 pending[r + 1] = pool.submit(draw, shard_seeds(seed_base, r + 1, batch, rank, world))
-            out = mc_ldpc(code, a, seeds, channel, batch, dectype, drawn=drawn)
+            out = mc_ldpc(code, a, seeds, channel, batch, dectype, drawn=drawn, **q)
             if timings is not None:
                 state["device_ms"] += code.mc_event_ms()
             return out
@@ -227,7 +232,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
 
 
 def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, seed0=0, batch=1024, rank=0,
-                world=1, allreduce=None, timings=None, draws="host", dectype="sumprod2", stream=False):
+                world=1, allreduce=None, timings=None, draws="host", dectype="sumprod2", stream=False, quant=None):
     """sim_ldpc (sparc_ldpc.py:1064-1124) over the blocks seed0, seed0 + 1, ...
     with everything but the draws on the device: blocks until MIN_ERRORS block
     errors or MAX_BLOCKS blocks, consumed in seed order whatever ``batch`` and
@@ -238,15 +243,18 @@ def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000
     nit_total counts sweeps; "layered_sumprod2_f32" / "layered_minsum_f32"
     decode on binary32 messages).
     stream=True (draws="device", a layered dectype, world == 1): the point as
-    one stream of refilled decoder slots (_mc_point); the same dict."""
+    one stream of refilled decoder slots (_mc_point); the same dict.
+    quant (None, True or (frac_bits, msg_bits, app_bits), with dectype
+    "layered_minsum"): the fixed-point decoder (ldpc.code)."""
     _check_draws(draws)
     _check_stream(stream, draws, dectype, world)
     if dectype not in _ldpc._ALGOS:
         raise NameError("Decoder type unknonwn")
+    _ldpc._quant_widths(quant, dectype)
     if ldpcparams.r_ldpc not in _RATES:
         raise NameError("Rate unsupported")
     code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype)
     r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, dectype, rank, world,
-                  allreduce, timings, draws, stream)
+                  allreduce, timings, draws, stream, **({} if quant is None else {"quant": quant}))
     return dict(ber=r["bit_errors"] / (r["blocks"] * code.N), blocks=r["blocks"], block_errors=r["block_errors"],
                 bit_errors=r["bit_errors"], nit_total=r["iters_total"])
