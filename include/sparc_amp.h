@@ -73,7 +73,7 @@ int sa_create(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
  * (sa_plan reports the choice); these bits override a rule, e.g. to test a
  * kernel on shapes where the rule would not pick it.  Every option keeps the
  * results within the same parity bounds; SA_PLAN_NO_PT, SA_PLAN_EAGER,
- * SA_PLAN_ONE_PASS and SA_PLAN_NO_LANES are bit-identical to the default plan.  `sa_subset` contexts
+ * SA_PLAN_ONE_PASS, SA_PLAN_NO_LANES and SA_PLAN_NO_FUSED_TAIL are bit-identical to the default plan.  `sa_subset` contexts
  * inherit their parent's options. */
 enum {
   SA_PLAN_DEFAULT = 0,
@@ -93,7 +93,9 @@ enum {
   SA_PLAN_SEC4Q = 1 << 13,    /* one codeword: four sections per workgroup (k_sec44) wherever pairs would run, M <= 512
                                  (never chosen by the rules: faster with two decodes in flight, slower alone) */
   SA_PLAN_NO_SEC4Q = 1 << 14, /* one codeword: never k_sec44 (the default; overrides SA_PLAN_SEC4Q) */
-  SA_PLAN_ALL = (1 << 15) - 1
+  SA_PLAN_NO_FUSED_TAIL = 1 << 15, /* one codeword, early stop off: keep the decode's last k_row2 launch and decide
+                                      with k_decide (no decisions out of the last section launch; bit-identical) */
+  SA_PLAN_ALL = (1 << 16) - 1
 };
 int sa_create_ex(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
                  int backend, int precision, int device, int plan);
@@ -157,7 +159,10 @@ int sa_amp(sa_ctx* ctx, int B, const double* y, const double* Pl, int T,
  * buffers; sa_run decodes the staged batch asynchronously on the context's
  * stream (replayed hipGraph); sa_wait blocks until it is done; sa_fetch
  * copies the results back.  sa_run_event_ms returns the device time of the
- * last sa_run measured with HIP events on the context's stream.
+ * last sa_run measured with HIP events on the context's stream: from the start
+ * of its graph to the end of the graph's last kernel (with the fused tail, see
+ * sa_decide_async, the section decisions lie inside that span and the last
+ * residual update, deferred, outside it).
  *
  * Decode lanes.  A context holds two lanes, each a stream plus everything one
  * decode mutates (y, z, both beta buffers, the partials, tau, iters, the
@@ -201,7 +206,11 @@ int sa_stage_power_batch(sa_ctx* ctx, int B, const double* Pl);
 int sa_run(sa_ctx* ctx, int B, int T, int flags);
 int sa_wait(sa_ctx* ctx);
 int sa_fetch(sa_ctx* ctx, int B, double* beta_out, int* iters_out);
-/* The residual z of the last decode's final iteration, B x n (diagnostics). */
+/* The residual z of the last decode's final iteration, B x n (diagnostics).
+ * A one-codeword decode with the early stop off leaves its last residual
+ * update undone (nothing of the decode, its estimate or its decisions reads
+ * z_T); this call, and any call that changes what the update reads (a new y,
+ * a new power allocation), launches it first, and the lane's next sa_run drops it. */
 int sa_fetch_z(sa_ctx* ctx, int B, double* z_out);
 /* The staged y, B x n, widened to binary64: what the next sa_run would read
  * (sa_stage's, or what sa_encode, sa_hard_cancel with dst or sa_cancel left
@@ -246,7 +255,18 @@ int sa_decide(sa_ctx* ctx, int B, int32_t* idx_out);
  * returns at once; sa_decide_collect waits for that slot's copy only and
  * hands its indices to the caller (idx_out: B x L).  A decoder loop queues
  * decode k + 1 before it collects the decisions of decode k, so the device
- * never waits on the host. */
+ * never waits on the host.
+ *
+ * Fused tail.  A one-codeword decode on the pair / triple / quad section
+ * kernels with k_row2, SA_FLAG_NO_EARLY_STOP, T > 0 and M a power of two takes
+ * the decisions in its last section launch (the argmax of the estimate that
+ * launch stores, the same rule) and writes them into a pinned buffer of its
+ * lane: sa_decide_async then enqueues nothing, the slot remembers the lane, and
+ * sa_decide_collect waits for the end of that decode (the event
+ * sa_run_event_ms reads) and copies from the lane.  A later sa_run on that lane
+ * first moves uncollected decisions into the slot, on the lane's stream.  Any
+ * number of slots may be queued before the first collect; each yields its own
+ * step's decisions.  SA_PLAN_NO_FUSED_TAIL keeps the separate argmax launch. */
 enum { SA_DECIDE_SLOTS = 4 };
 int sa_decide_async(sa_ctx* ctx, int B, int slot);
 int sa_decide_collect(sa_ctx* ctx, int B, int slot, int32_t* idx_out);

@@ -24,7 +24,14 @@ how many of them overlap a decode of another stream, the overlapped share of
 their wall time and the decode period (the in-graph durations then measure a
 shared chip).
 
-Usage: graph_trace.py <kernel_trace.csv> [out.txt] [source-hash]
+Since the fused tail a one-codeword decode with the
+early stop off ends with its last section launch and no k_decide follows, so
+on one stream consecutive decodes form one unbroken run of loop kernels (row,
+section, row, ...).  The optional fourth argument gives the loop kernels of one
+decode (2 T); longer runs are cut into decodes of that many.  The summary also
+counts the k_decide dispatches of the whole trace.
+
+Usage: graph_trace.py <kernel_trace.csv> [out.txt] [source-hash] [loop kernels per decode]
 """
 import csv
 import statistics as st
@@ -61,6 +68,15 @@ def main():
                     runs.append(cur)
                     where.append(key)
                 cur = []
+    per_decode = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+    if per_decode:
+        cut, cut_where = [], []
+        for r, w in zip(runs, where):
+            for i in range(0, len(r), per_decode):
+                cut.append(r[i:i + per_decode])
+                cut_where.append(w)
+        runs, where = cut, cut_where
+
     def med_gap(r):
         return st.median([r[i + 1][1] - r[i][2] for i in range(len(r) - 1)]) if len(r) > 1 else 1e9
     timed = [(r, w) for r, w in zip(runs, where) if len(r) > 2 and med_gap(r) < 1000]
@@ -74,6 +90,8 @@ def main():
     if len(sys.argv) > 3:
         out.append(f"sources sha256 {sys.argv[3]}")
     out.append(f"{len(timed)} graph-replayed decodes of {n0} loop kernels each")
+    n_decide = sum(1 for seq in streams.values() for k in seq if k[0] == "k_decide")
+    out.append(f"k_decide dispatches in the whole trace: {n_decide}")
     per = {}
     for r in timed:
         for i, (k, s, e) in enumerate(r):

@@ -924,6 +924,12 @@ struct SecArgs {
   // k_sec4 / k_sec43: the previous estimate is zero whatever `beta` holds (the
   // first iteration of a decode without beta0: no zero fill of the buffer)
   int bzero;
+  // k_sec4 / k_sec43 / k_sec44, the last launch of a decode with the early
+  // stop off (fused tail, sa_host.h: fused_tail): the section decisions
+  // [B][L] (argmax of the new estimate, section_argmax's rule) go to `dec`, a
+  // device-visible buffer, and iters[b] = itset; null / 0 on every other launch
+  int32_t* dec;
+  int itset;
 };
 
 template <typename real>

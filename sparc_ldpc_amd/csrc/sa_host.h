@@ -72,6 +72,16 @@ struct sa_lane {
   hipEvent_t y_ev = nullptr;      // behind the last write of this lane's d_y (staging, or the copy from the other lane)
   unsigned long long y_ver = 0;   // version of the y this lane holds (sa_ctx::y_ver: the latest staged)
   bool y_read = false;            // this lane's last y copy read the other lane's d_y (that lane's next y write waits for y_ev)
+  // Fused tail (fused_tail below): the lane's last run ended with its last
+  // section launch, which wrote the decisions of fused_B codewords into h_dec
+  // (pinned, device-mapped at d_dec, Bcap x L; marked by ev1), and left the
+  // row step of iteration row_T - 1 of row_B codewords undone: nothing of the
+  // decode, its decisions or its estimate reads z_T.  row_flush launches that
+  // step for whoever reads d_z / d_zzp, or is about to change what it reads
+  // (y, the power, the partials); the lane's next run drops it.
+  int32_t *h_dec = nullptr, *d_dec = nullptr;
+  int fused_B = 0;
+  int row_B = 0, row_T = 0;
 };
 
 struct sa_ctx {
@@ -173,6 +183,9 @@ struct sa_ctx {
   size_t dec_cap = 0;
   hipEvent_t dec_ev[SA_DECIDE_SLOTS] = {};
   int dec_B[SA_DECIDE_SLOTS] = {};
+  // where a queued slot's decisions are: -1 the ring (behind dec_ev), else the
+  // h_dec of that lane (behind its ev1: the fused tail wrote them, sa_decide_async enqueued nothing)
+  int dec_lane[SA_DECIDE_SLOTS] = {-1, -1, -1, -1};
   // Monte-Carlo stream (sa_mc_stage / sa_mc_run, sa_mc.hip): the staged reps'
   // section indices [mc_cap][L] and noise [mc_cap][n], their decisions and stop
   // indices, the slot state of the refilled batch, and its captured graphs
@@ -329,6 +342,16 @@ inline Plan plan_for(const sa_ctx* c, int B) {
   return p;
 }
 
+// Fused tail of a decode: with the early stop off the last launch is known at
+// capture time, so the last section launch of the pair / triple / quad kernels
+// also writes the section decisions and iters (SecArgs::dec, itset), k_decide
+// is never launched, and the last k_row2 step, whose z_T only sa_fetch_z
+// reads, is deferred (sa_lane::row_B).  Depends on (context, B, T, flags) alone.
+inline bool fused_tail(const sa_ctx* c, const Plan& p, int T, int flags) {
+  return p.bzero() && p.it_row() && (flags & SA_FLAG_NO_EARLY_STOP) && T > 0 && c->dead == 0 && !c->prof &&
+         !(c->plan & SA_PLAN_NO_FUSED_TAIL);
+}
+
 // t_b: the Monte-Carlo stream's per-slot iteration indices (SecArgs::tb), else null
 template <typename real>
 SecArgs<real> sec_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop, const int* tb = nullptr) {
@@ -351,6 +374,8 @@ SecArgs<real> sec_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop
   a.tb = tb;
   a.dead = c->dead;
   a.bzero = 0;
+  a.dec = nullptr;
+  a.itset = 0;
   return a;
 }
 
@@ -407,6 +432,14 @@ void drop_graphs(sa_ctx* c);  // every lane's, and sa_mc_run's
 int sync_all(sa_ctx* c);
 inline void lane_switch(sa_ctx* c, int k) { c->cur = k; }
 int lanes_release(sa_ctx* c);
+// fused tail: launch lane k's deferred row step, if one is pending, on its
+// stream; tail_settle: that, and the lane's fused decisions no longer stand
+// for its d_beta (entry points that change the current lane's buffers)
+int row_flush(sa_ctx* c, int k);
+inline int tail_settle(sa_ctx* c) {
+  c->at().fused_B = 0;
+  return row_flush(c, c->cur);
+}
 // the staged y across lanes: y_sync brings lane k's d_y up to the latest
 // staged version (a device-to-device copy on its stream, behind the event
 // recorded after the staging); a writer of B codewords of lane k's d_y on
@@ -437,7 +470,8 @@ extern __global__ void k_fill32(uint32_t* p, uint32_t v, size_t nw);
 template <typename real>
 int launch_sec(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, void* bin = nullptr, void* bout = nullptr);
 template <typename real>
-int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero = 0);
+int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero = 0,
+                int32_t* dec = nullptr, int itset = 0);  // dec, itset: the fused tail's last launch (SecArgs::dec)
 hipError_t sec_lds_attrs();
 
 // ---- sa_secb.hip: the batched section kernel ------------------------------------

@@ -654,6 +654,8 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   if (g == 0 && tid == 0) {
     a.tau[(size_t)b * a.T1 + a.t] = tau;
     if (stop && a.iters[b] < 0) a.iters[b] = a.t;
+    // the decode's last launch (early stop off, so no stop fired): iters[b] = T
+    if (a.itset != 0 && !stop) a.iters[b] = a.itset;
   }
   if (stop) {  // uniform over the grid row
     if (dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA write may outlive the workgroup
@@ -741,6 +743,26 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   for (int i = 0; i < EQ; ++i) v[i] = have ? v[i] * scale : (real)0;
   if (have) store_section<real, EQ>(blo, v, lane, Mq);
   const real bb = have ? S2 * scale * scale : (real)0;
+  // The decode's last launch (SecArgs::dec): the section decision out of the
+  // estimate just stored, k_decide's argmax (section_argmax's rule: strictly
+  // greater wins, an equal value with a lower index wins, nothing comparable
+  // gives 0; index M stands for "none").  Here this wave's quarter; the QW
+  // waves of a section meet in red[] behind the T staging below.
+  real dbest = neg_inf<real>();
+  int dbi = M;
+  if (a.dec) {
+#pragma unroll
+    for (int i = 0; i < EQ; ++i) {
+      const int e = eoff + elem_index<EQ>(lane, i);
+      if (v[i] > dbest || (v[i] == dbest && e < dbi)) { dbest = v[i]; dbi = e; }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const real ob = __shfl_xor(dbest, m);
+      const int oi = __shfl_xor(dbi, m);
+      if (ob > dbest || (ob == dbest && oi < dbi)) { dbest = ob; dbi = oi; }
+    }
+  }
 
   STAMP(5);
   fwht_wave<real, EQ>(v, lane, 64);  // T_l = H_M beta_l
@@ -751,9 +773,27 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #pragma unroll
     for (int i = 0; i < EQ; ++i) tl[elem_index<EQ>(lane, i)] = v[i];
   }
-  if (lane == 0) red[wv * 4 + 3] = bb;
+  if (lane == 0) {
+    red[wv * 4 + 3] = bb;
+    // slots 0 (max) and 1 (S) were last read in front of the barriers of the transform above
+    if (a.dec) {
+      red[wv * 4] = dbest;
+      red[wv * 4 + 1] = (real)dbi;  // <= M <= 4096: exact
+    }
+  }
   __syncthreads();
   STAMP(7);
+  if (a.dec && have && q == 0 && lane == 0) {  // the section's QW quarters in q order; a missing section writes nothing
+    real best = red[wv * 4];
+    int bi = (int)red[wv * 4 + 1];
+#pragma unroll
+    for (int j = 1; j < QW; ++j) {
+      const real ob = red[(wv + j) * 4];
+      const int oi = (int)red[(wv + j) * 4 + 1];
+      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    a.dec[(size_t)b * a.L + l] = bi >= M ? 0 : bi;
+  }
   if (tid == 0) {
     real bsum = red[0 * 4 + 3] + red[QW * 4 + 3];
     if constexpr (SPW >= 3) bsum += red[2 * QW * 4 + 3];
@@ -869,11 +909,16 @@ void launch_sec_e(sa_ctx* c, const Plan& p, int B, SecArgs<real> a) {
 
 // One iteration's section step on the plan's multi-wave kernel (pairs, triples or quads of sections)
 template <typename real>
-int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero) {
+int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void* bout, int bzero, int32_t* dec,
+                int itset) {
   SecArgs<real> a = sec_args<real>(c, p, SEC_AMP, t, es);
   a.pt = p.pt;
   if (bzero && !p.bzero()) return fail(SA_ERR_UNSUPPORTED, "k_sec2 reads its previous estimate");
+  if ((dec || itset) && (!p.bzero() || es || c->dead))  // secq_body alone decides, and only where no stop can fire
+    return fail(SA_ERR_UNSUPPORTED, "launch_sec2: no fused decision on this path");
   a.bzero = bzero;
+  a.dec = dec;
+  a.itset = itset;
   a.beta = (real*)bin;
   a.beta_out = (real*)bout;
   a.G = p.G;
@@ -944,8 +989,8 @@ int launch_sec(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, void* b
 
 template int launch_sec<float>(sa_ctx*, const Plan&, int, int, int, int, void*, void*);
 template int launch_sec<double>(sa_ctx*, const Plan&, int, int, int, int, void*, void*);
-template int launch_sec2<float>(sa_ctx*, const Plan&, int, int, int, void*, void*, int);
-template int launch_sec2<double>(sa_ctx*, const Plan&, int, int, int, void*, void*, int);
+template int launch_sec2<float>(sa_ctx*, const Plan&, int, int, int, void*, void*, int, int32_t*, int);
+template int launch_sec2<double>(sa_ctx*, const Plan&, int, int, int, void*, void*, int, int32_t*, int);
 
 // Every single-codeword section-kernel instantiation may use the full 160 KB LDS.
 template <typename real>

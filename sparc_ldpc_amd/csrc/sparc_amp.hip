@@ -68,6 +68,12 @@ __global__ void k_iters_final(int* it, int B, int T) {
 }
 
 
+// Fused decisions of a lane moved into a ring slot (both pinned and device-mapped)
+__global__ void k_copy32(const int32_t* s, int32_t* d, size_t N) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < N; i += (size_t)gridDim.x * blockDim.x)
+    d[i] = s[i];
+}
+
 int dev_alloc(sa_ctx* c, void** p, size_t bytes) {
   if (bytes == 0) bytes = 16;
   hipError_t e = hipMalloc(p, bytes);
@@ -102,6 +108,14 @@ static int y_wait_reader(sa_ctx* c, int k, hipStream_t s) {
 }
 
 int y_begin_write(sa_ctx* c, int k, hipStream_t s, int B) {
+  if (c->lane[k].row_B) {  // a deferred row step reads the y about to go
+    sa_lane& l = c->lane[k];
+    if (int rc = row_flush(c, k)) return rc;
+    if (s != l.stream) {
+      HIP_TRY(hipEventRecord(l.y_ev, l.stream));  // (still behind the lane's last y write)
+      HIP_TRY(hipStreamWaitEvent(s, l.y_ev, 0));
+    }
+  }
   if (!c->lanes_on) return SA_OK;
   if (B < c->Bcap) {  // the rows past B keep the latest staged values
     if (int rc = y_sync(c, k)) return rc;
@@ -122,6 +136,7 @@ int y_sync(sa_ctx* c, int k) {
   sa_lane& l = c->lane[k];
   if (!c->lanes_on || l.y_ver == c->y_ver) return SA_OK;
   sa_lane& src = c->lane[c->y_lane];
+  if (int rcf = row_flush(c, k)) return rcf;  // a deferred row step reads the y about to go
   HIP_TRY(hipStreamWaitEvent(l.stream, src.y_ev, 0));
   if (int rc = y_wait_reader(c, k, l.stream)) return rc;
   HIP_TRY(hipMemcpyAsync(l.d_y, src.d_y, (size_t)c->Bcap * c->n * rsz(c), hipMemcpyDeviceToDevice, l.stream));
@@ -163,6 +178,13 @@ static int lane_alloc(sa_ctx* c, sa_lane& l, size_t nB, size_t nBp, int T, int G
   if ((rc = dev_alloc(c, &l.d_zzp, nB * c->NZh * s))) return rc;
   if ((rc = dev_alloc(c, &l.d_tau, nB * (T + 1) * s))) return rc;
   if ((rc = dev_alloc(c, (void**)&l.d_iters, nB * sizeof(int)))) return rc;
+  // the fused tail's decisions: written by the last section launch, read by the host behind ev1
+  if (hipHostMalloc((void**)&l.h_dec, nB * c->L * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&l.d_dec, l.h_dec, 0) != hipSuccess) {
+    if (l.h_dec) (void)hipHostFree(l.h_dec);
+    l.h_dec = l.d_dec = nullptr;
+    return fail(SA_ERR_NOMEM, "hipHostMalloc(lane decisions) failed");
+  }
   return beta2 ? beta2_alloc(c, l, nB) : SA_OK;
 }
 
@@ -173,6 +195,35 @@ static void lane_free(sa_lane& l) {
     *p = nullptr;
   }
   l.beta2_cap = 0;
+  if (l.h_dec) (void)hipHostFree(l.h_dec);
+  l.h_dec = l.d_dec = nullptr;
+  l.fused_B = l.row_B = l.row_T = 0;
+}
+
+// Lane k's buffers are about to go (every lane waited for): decisions that a
+// queued slot still expects in the lane's h_dec move into the ring.
+static void dec_rescue(sa_ctx* c, int k) {
+  for (int s = 0; s < SA_DECIDE_SLOTS; ++s)
+    if (c->dec_B[s] != 0 && c->dec_lane[s] == k && c->h_dec && c->lane[k].h_dec) {
+      std::memcpy(c->h_dec + (size_t)s * c->dec_cap, c->lane[k].h_dec, (size_t)c->dec_B[s] * c->L * sizeof(int32_t));
+      c->dec_lane[s] = -1;  // (dec_ev[s]: recorded long ago or never; waiting for it returns at once)
+    }
+}
+
+// Before a run re-records lane k's ev1 (and may overwrite its h_dec): decisions
+// a queued slot still expects there move into the slot on the lane's stream,
+// behind the run that wrote them, and the slot waits on its own event again.
+static int dec_spill(sa_ctx* c, int k) {
+  sa_lane& l = c->lane[k];
+  for (int s = 0; s < SA_DECIDE_SLOTS; ++s)
+    if (c->dec_B[s] != 0 && c->dec_lane[s] == k) {
+      const size_t N = (size_t)c->dec_B[s] * c->L;
+      k_copy32<<<(int)std::min<size_t>((N + 255) / 256, 1024), 256, 0, l.stream>>>(l.d_dec, c->d_dec + (size_t)s * c->dec_cap, N);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->dec_ev[s], l.stream));
+      c->dec_lane[s] = -1;
+    }
+  return SA_OK;
 }
 
 static void stage_free(sa_lane& l) {
@@ -221,6 +272,7 @@ void graphs_clear(GraphMap& m) {
 int lanes_release(sa_ctx* c) {
   int rc = sync_all(c);
   if (!c->lanes_on) return rc;
+  if (!rc) dec_rescue(c, 1);
   lane_switch(c, 0);
   sa_lane &l0 = c->lane[0], &l = c->lane[1];
   if (!rc) rc = y_sync(c, 0);  // the staged y stays with lane 0
@@ -275,6 +327,7 @@ int ensure_workspace(sa_ctx* c, int B, int T) {
   drop_graphs(c);
   const size_t nB = B > c->Bcap ? B : c->Bcap;
   const int nT = T > c->Tcap ? T : c->Tcap;
+  dec_rescue(c, 0);  // (lanes_release waited for every lane)
   free_workspace(c);
   const size_t s = rsz(c), LM = (size_t)c->L * c->M;
   int Gmax = c->G > c->KS ? c->G : c->KS;
@@ -380,6 +433,10 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
   const bool it_row = p.it_row() && T > 0;
   const bool bzero = !has_b0 && p.bzero() && T > 0;
   const int flip = (bzero && !es) ? (T & 1) : 0;  // beta0 lies in d_beta: no choice of side
+  // Fused tail: the last section launch also decides and sets iters = T, and
+  // the sequence ends with it: the row step behind it (z_T) is deferred
+  // (run_graph records it in the lane; row_flush launches it on demand)
+  const bool ft = fused_tail(c, p, T, flags);
   if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
   if (has_b0) {
     if (dense) {
@@ -404,11 +461,14 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
       void* pin = ((t ^ flip) & 1) ? ln.d_beta2 : ln.d_beta;
       void* pout = ((t ^ flip) & 1) ? ln.d_beta : ln.d_beta2;
       if (p.multiwave()) {
-        if ((rc = launch_sec2<real>(c, p, B, t, es, pin, pout, bzero && t == 0))) return rc;
+        const bool tail = ft && t == T - 1;
+        if ((rc = launch_sec2<real>(c, p, B, t, es, pin, pout, bzero && t == 0, tail ? ln.d_dec : nullptr, tail ? T : 0)))
+          return rc;
       } else if ((rc = launch_sec<real>(c, p, B, SEC_AMP, t, es, pin, pout))) {
         return rc;
       }
     }
+    if (ft && t == T - 1) break;
     if ((rc = launch_row<real>(c, p, B, ROW_AMP, t, es, p.G, p.Gb, it_row && t == T - 1 ? T : 0))) return rc;
   }
   if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, ln.stream>>>(ln.d_iters, B, T);
@@ -423,6 +483,29 @@ int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
     HIP_TRY(hipGetLastError());
   }
   return SA_OK;
+}
+
+int row_flush(sa_ctx* c, int k) {
+  sa_lane& l = c->lane[k];
+  if (!l.row_B) return SA_OK;
+  const int B = l.row_B, T = l.row_T, keep = c->cur;
+  l.row_B = l.row_T = 0;
+  const Plan p = plan_for(c, B);  // the run's own: (context, B) decide it
+  lane_switch(c, k);  // the launchers address the current lane
+  const int rc = c->prec == SA_PREC_F64 ? launch_row<double>(c, p, B, ROW_AMP, T - 1, 0, p.G, p.Gb, 0)
+                                        : launch_row<float>(c, p, B, ROW_AMP, T - 1, 0, p.G, p.Gb, 0);
+  lane_switch(c, keep);
+  return rc;
+}
+
+// What a run of (B, T, flags) leaves in its lane beside the results (the
+// captured graph does not run seq_amp again: set by every run)
+static void tail_mark(sa_ctx* c, int B, int T, int flags) {
+  sa_lane& ln = c->at();
+  const bool ft = fused_tail(c, plan_for(c, B), T, flags);
+  ln.fused_B = ft ? B : 0;
+  ln.row_B = ft ? B : 0;
+  ln.row_T = ft ? T : 0;
 }
 
 int ensure_beta2(sa_ctx* c, int B) {
@@ -452,13 +535,20 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   } else if (use_batched(c, B)) {
     lane_switch(c, 0);  // lane 1's buffers hold no batched layout (no chunk padding, no k_secb partials)
   }
+  {
+    sa_lane& l = c->at();  // the run's lane: cur is settled
+    l.row_B = l.row_T = 0;  // a deferred row step of the lane's previous run: dropped (z starts from y again)
+    if (int rcd = dec_spill(c, c->cur)) return rcd;
+    l.fused_B = 0;
+  }
   if (int rcy = y_sync(c)) return rcy;  // a lane whose y is older than the latest staged one
-  sa_lane& ln = c->at();  // the run's lane: cur is settled
+  sa_lane& ln = c->at();
   if (c->plan & SA_PLAN_EAGER) {  // eager launches instead of the captured graph
     HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
     int rc = seq_amp<real>(c, B, T, flags, has_b0);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
+    tail_mark(c, B, T, flags);
     c->last_B = B;
     c->last_T = T;
     c->zil_last = zil_for(c, B);
@@ -475,6 +565,7 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
   HIP_TRY(hipGraphLaunch(it->second, ln.stream));
   HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
+  tail_mark(c, B, T, flags);
   c->last_B = B;
   c->last_T = T;
   c->zil_last = zil_for(c, B);  // the layout d_z is left in by THIS run (a cached graph does not run seq_amp)
@@ -541,6 +632,9 @@ int set_power(sa_ctx* c, const double* Pl) {
     cl[l] = std::sqrt((double)c->n * Pl[l]);  // np.sqrt(n*Pl), sparc_ldpc.py:214
     P += Pl[l];                                // np.sum(Pl), sparc_ldpc.py:190
   }
+  // (a deferred row step reads P as its decode did: before any change of mode or value)
+  for (int k = 0; k < sa_ctx::kLanes; ++k)
+    if (int rcf = row_flush(c, k)) return rcf;
   // A decode in flight on either lane reads d_c / d_P1: an unchanged Pl (a
   // caller passing it with every stage) writes nothing, a new one waits for
   // every lane first.
@@ -579,6 +673,8 @@ int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   if (!Pl) return fail(SA_ERR_ARG, "Pl is NULL");
   if (is_dense(c)) return fail(SA_ERR_UNSUPPORTED, "per-codeword power: Hadamard backend only");
   const size_t L = (size_t)c->L;
+  for (int k = 0; k < sa_ctx::kLanes; ++k)
+    if (int rcf = row_flush(c, k)) return rcf;
   // as set_power: unchanged allocations write nothing, new ones wait for every lane
   if (c->h_Plb.size() == (size_t)B * L && std::memcmp(c->h_Plb.data(), Pl, (size_t)B * L * 8) == 0) {
     c->pb_on = true;
@@ -1387,6 +1483,7 @@ int sa_Ab(sa_ctx* c, int B, const double* beta, double* out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
+  if ((rc = tail_settle(c))) return rc;  // d_beta and the partials change
   if ((rc = upload_sections(c, c->at().d_beta, beta, B))) return rc;
   rc = c->prec == SA_PREC_F64 ? seq_ab<double>(c, B) : seq_ab<float>(c, B);
   if (rc) return rc;
@@ -1401,6 +1498,7 @@ int sa_Az(sa_ctx* c, int B, const double* z, double* out) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
   if (rc) return rc;
+  if ((rc = row_flush(c, c->cur))) return rc;  // in stream order in front of the new z, as the decode's last row step was
   if ((rc = upload(c, c->at().d_z, z, (size_t)B * c->n))) return rc;
   c->zil_last = false;  // d_z holds [B][n] now
   if (c->prec == SA_PREC_F64) {
@@ -1444,7 +1542,10 @@ int sa_stage(sa_ctx* c, int B, const double* y, const double* Pl, const double* 
     if (!rc) rc = y_mark(c, k);
     if (rc) return rc;
   }
-  if (beta0 && (rc = upload_sections(c, c->at().d_beta, beta0, B))) return rc;
+  if (beta0) {
+    c->at().fused_B = 0;  // d_beta no longer holds the estimate the fused decisions were taken from
+    if ((rc = upload_sections(c, c->at().d_beta, beta0, B))) return rc;
+  }
   return SA_OK;
 }
 
@@ -1490,6 +1591,7 @@ int sa_fetch_z(sa_ctx* c, int B, double* z_out) {
   if (B <= 0 || B > c->Bcap) return fail(SA_ERR_ARG, "sa_fetch_z: bad batch");
   HIP_TRY(hipSetDevice(c->device));
   int rc;
+  if ((rc = row_flush(c, c->cur))) return rc;  // z_T of a fused-tail decode: its last row step runs now
   if (c->zil_last) {  // [NC][n][CB] -> [B][n]
     const int CB = 16 / (int)rsz(c), NC = (B + CB - 1) / CB;
     std::vector<double> il((size_t)NC * CB * c->n);
@@ -1537,6 +1639,7 @@ int sa_amp(sa_ctx* c, int B, const double* y, const double* Pl, int T, const dou
   if ((rc = sa_stage(c, B, y, Pl, beta0))) return rc;
   if (T == 0) {
     // the loop body never runs: beta is beta0 (or zeros)
+    c->at().fused_B = 0;
     if (!beta0) HIP_TRY(hipMemsetAsync(c->at().d_beta, 0, (size_t)B * c->L * c->M * rsz(c), c->at().stream));
     HIP_TRY(hipMemsetAsync(c->at().d_iters, 0, (size_t)B * sizeof(int), c->at().stream));
   } else {
@@ -1559,6 +1662,8 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   if (int rcs = sync_all(c)) return rcs;  // the profiled decode has the chip to itself (it stays on the current lane)
   if (int rcb = ensure_beta2(c, B)) return rcb;
   if (use_batched(c, B)) lane_switch(c, 0);  // as sa_run
+  c->at().row_B = c->at().row_T = 0;  // as sa_run: a new decode of the lane (never a fused tail: fused_tail)
+  c->at().fused_B = 0;
   if (int rcy = y_sync(c)) return rcy;
   if (use_batched(c, B))
     if (int rci = ensure_invb(c)) return rci;
@@ -1614,6 +1719,11 @@ int sa_decide(sa_ctx* c, int B, int32_t* idx_out) {
   if (check_ctx(c)) return SA_ERR_ARG;
   if (B <= 0 || B > c->Bcap || !idx_out) return fail(SA_ERR_ARG, "sa_decide: bad arguments");
   HIP_TRY(hipSetDevice(c->device));
+  if (c->at().fused_B >= B) {  // the last section launch decided
+    HIP_TRY(hipStreamSynchronize(c->at().stream));
+    std::memcpy(idx_out, c->at().h_dec, (size_t)B * c->L * sizeof(int32_t));
+    return SA_OK;
+  }
   if (int rc = launch_decide(c, B, c->d_idx)) return rc;
   HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, c->at().stream));
   HIP_TRY(hipStreamSynchronize(c->at().stream));
@@ -1644,8 +1754,17 @@ int sa_decide_async(sa_ctx* c, int B, int slot) {
     for (int k = 0; k < SA_DECIDE_SLOTS; ++k) {
       if (!c->dec_ev[k]) HIP_TRY(hipEventCreateWithFlags(&c->dec_ev[k], hipEventDisableTiming));
       c->dec_B[k] = 0;
+      c->dec_lane[k] = -1;
     }
   }
+  if (c->at().fused_B >= B) {
+    // the run's last section launch wrote them into its lane's pinned buffer,
+    // marked by the lane's ev1: nothing to enqueue, the slot remembers the lane
+    c->dec_lane[slot] = c->cur;
+    c->dec_B[slot] = B;
+    return SA_OK;
+  }
+  c->dec_lane[slot] = -1;
   // k_decide writes the indices straight into the slot (the pinned ring is
   // mapped into the device's address space: no copy behind the kernel); the
   // host reads them after the event recorded behind it
@@ -1660,6 +1779,13 @@ int sa_decide_collect(sa_ctx* c, int B, int slot, int32_t* idx_out) {
   if (slot < 0 || slot >= SA_DECIDE_SLOTS || !idx_out || !c->h_dec || c->dec_B[slot] != B || B <= 0)
     return fail(SA_ERR_ARG, "sa_decide_collect: no decision of this batch queued in the slot");
   HIP_TRY(hipSetDevice(c->device));
+  if (const int k = c->dec_lane[slot]; k >= 0) {  // fused decisions, still in their lane
+    HIP_TRY(hipEventSynchronize(c->lane[k].ev1));
+    std::memcpy(idx_out, c->lane[k].h_dec, (size_t)B * c->L * sizeof(int32_t));
+    c->dec_B[slot] = 0;
+    c->dec_lane[slot] = -1;
+    return SA_OK;
+  }
   HIP_TRY(hipEventSynchronize(c->dec_ev[slot]));
   std::memcpy(idx_out, c->h_dec + (size_t)slot * c->dec_cap, (size_t)B * c->L * sizeof(int32_t));
   c->dec_B[slot] = 0;
