@@ -297,6 +297,18 @@ int sa_stage_onehot_scaled(sa_ctx* ctx, int B, const int32_t* idx, double scale)
  * context's precision counts as posterior 1, a decided section). */
 int sa_llr(sa_ctx* ctx, int B, int l0, int ns, double* llr, int flags);
 
+/* sa_llr with a choice of form and a clip on the magnitude.
+ *   mode  SA_LLR_REFERENCE: the expression above (sa_llr is this with no clip).
+ *         SA_LLR_TWO_SIDED: llr = nan_to_num(log(p0) - log(p1)), p1 the p above
+ *         and p0 the same ordered sum over the entries whose bit is clear.
+ *         Neither term is 1 - (a rounded sum): on a binary32 beta the
+ *         reference form is noise from |llr| = 16 and 0 (NaN) where p > 1.
+ *   clip  +inf or 0: none, +-inf -> +-DBL_MAX.  Finite > 0: the result is
+ *         bounded to [-clip, clip], +-inf -> +-clip; NaN -> 0 either way.
+ * An unknown mode, or a negative or NaN clip: SA_ERR_ARG, nothing is written. */
+enum { SA_LLR_REFERENCE = 0, SA_LLR_TWO_SIDED = 1 };
+int sa_llr_ex(sa_ctx* ctx, int B, int l0, int ns, double* llr, int flags, int mode, double clip);
+
 /* Soft exchange (sparc_ldpc.py:683-698): beta0 := beta with sections
  * [l0, l0+ns) replaced by c_l * bp2sp(1/(1+exp(app))), staged for the next
  * sa_run(..., SA_FLAG_BETA0); the staged y is kept. */

@@ -122,6 +122,36 @@ def cpu_baseline(sigma, soft_iter, procs):
     }
 
 
+def add_decoder_options(ap):
+    """--llr / --llr-clip / --bp-dectype / --bp-quant (joint.joint_options); the defaults are the reference's."""
+    ap.add_argument("--llr", default="reference", choices=["reference", "two_sided"],
+                    help="form of the section->bit LLRs (sa_llr_ex)")
+    ap.add_argument("--llr-clip", type=float, default=None, help="bound on |LLR| (default: none)")
+    ap.add_argument("--bp-dectype", default="sumprod2", help="the outer decoder's type (ldpc._ALGOS)")
+    ap.add_argument("--bp-quant", default=None,
+                    help="fixed-point widths of layered_minsum: 'default' or frac,msg,app")
+
+
+def decoder_options(args):
+    """The joint_options keywords of parsed arguments (absent attributes: the defaults)."""
+    q = getattr(args, "bp_quant", None)
+    if isinstance(q, str):
+        q = True if q == "default" else tuple(int(x) for x in q.split(","))
+    return dict(llr=getattr(args, "llr", "reference"), llr_clip=getattr(args, "llr_clip", None),
+                bp_dectype=getattr(args, "bp_dectype", "sumprod2"), bp_quant=q)
+
+
+def bp_kernel_name(o):
+    """The kernel(s) behind a BP call with joint_options o (csrc/ldpc_bp.hip)."""
+    d = o["bp_dectype"]
+    if not d.startswith("layered_"):
+        return f"k_bp<{d}> (8 iterations) + k_bp_tail_var / k_bp_tail_chk"
+    algo = d[len("layered_"):]
+    if o["bp_quant"] is not None:
+        return "k_bplq<minsum, frac,msg,app = %d,%d,%d>" % tuple(o["bp_quant"])
+    return f"k_bpl32<{algo[:-4]}>" if algo.endswith("_f32") else f"k_bpl<{algo}>"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -131,6 +161,7 @@ def main():
     ap.add_argument("--soft-iter", type=int, default=2)
     ap.add_argument("--precision", default="fp64", choices=["fp32", "fp64"])
     ap.add_argument("--plan", default="", help="comma-separated plan options (sa_create_ex)")
+    add_decoder_options(ap)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=0)
     ap.add_argument("--no-ref", action="store_true", help="skip the one-decoder reference decode (traces)")
@@ -140,6 +171,20 @@ def main():
                     help="concurrent slices of the batch, each on its own streams (joint.JointPipeline); 1: one decoder")
     args = ap.parse_args()
     print(json.dumps(measure(args)), flush=True)
+
+
+def llr_launch_ms(jd, B, reps=20):
+    """Host-clock milliseconds per call (launch + stream wait) of the two LLR
+    forms into the LDPC context's device buffer, on the current beta."""
+    d_ch = jd.code.device_buffers(B)[0]
+    out = {}
+    for name, kw in (("sa_llr", {}), ("sa_llr_ex_two_sided", dict(mode="two_sided", clip=jd.options["llr_clip"]))):
+        jd.op.llr(B, jd.l0, jd.ns, out=d_ch, **kw)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            jd.op.llr(B, jd.l0, jd.ns, out=d_ch, **kw)
+        out[name + "_ms"] = round((time.perf_counter() - t0) / reps * 1e3, 4)
+    return out
 
 
 def measure(args, device=None, rank=0, world=1):
@@ -154,7 +199,9 @@ def measure(args, device=None, rank=0, world=1):
     lp = sp.LDPCParams("802.16", "5/6", Z)
     R = 5 / 6
     sigma = ebno_to_sigma(args.ebno, P, R)
-    jd = joint.joint_decoder(L, M, N_SPARC, lp, T, precision=args.precision, device=device)
+    opts = joint.joint_options(**decoder_options(args))
+    default_opts = opts == joint.joint_options()
+    jd = joint.joint_decoder(L, M, N_SPARC, lp, T, precision=args.precision, device=device, **opts)
     if args.plan:  # A/B of plan options: the same design with sa_create_ex options
         jd.op = sp.SparcOperator(L, M, N_SPARC, sp.make_ordering(L, M, N_SPARC), precision=args.precision,
                                  plan=[p for p in args.plan.split(",") if p])
@@ -191,6 +238,7 @@ def measure(args, device=None, rank=0, world=1):
     kinds, amp_ms = op.profile(B, T)
     jd._bp(B)
     bp_ms = float(sp.ldpc.load_bp_library().lb_run_event_ms(code._context()))
+    llr_ms = None if default_opts else llr_launch_ms(jd, B)
     _, bp_it = code.fetch_buffers(B, app=False)
     # repeated-launch timing: 4 back-to-back launches per HIP-event pair; and
     # the dispatch-bound event pairs of an eager decode (bench.py measure_roofline)
@@ -267,16 +315,20 @@ def measure(args, device=None, rank=0, world=1):
             "amp_launches": {k: v[1] for k, v in kinds.items() if v[1]},
             "eager_amp_decode_ms": round(amp_ms, 3),
         },
-        "bp": {"kernel": "k_bp<sumprod2> (8 iterations) + k_bp_tail_var / k_bp_tail_chk", "launch_ms": round(bp_ms, 4),
+        "bp": {"kernel": bp_kernel_name(opts), "launch_ms": round(bp_ms, 4),
                "words": B,
                "mean_iterations": round(float(bp_it.mean()), 2), "max_iterations": int(bp_it.max()),
                "edges": nmsg, "edge_updates_per_s": round(float(bp_it.sum()) * nmsg / (bp_ms * 1e-3), 1),
                "bound": "fp64 VALU: the first iterations issue-bound (3 waves per SIMD), the tail one wave per "
-                        "SIMD on the dependent Lxor chain of each check"},
+                        "SIMD on the dependent Lxor chain of each check" if opts["bp_dectype"] == "sumprod2" else
+                        "not profiled in the joint step (scripts/bp_sweep_time.py times the layered decoders)"},
         "errors": {"amp_bits_per_round": r["amp"].sum(axis=0).tolist(),
                    "ldpc_bits_per_round": r["ldpc"].sum(axis=0).tolist(), "bits": int(B * L * 9)},
         "step_share_ms": {k: round(v, 3) for k, v in share.items()},
     }
+    if not default_opts:  # (the default line stays as it was)
+        result["config"]["decoder_options"] = opts
+        result["llr"] = {"kernel": "k_llr2" if opts["llr"] == "two_sided" else "k_llr", **llr_ms}
     if rank == 0 and not args.no_cpu:
         procs = args.cpu_procs or min(16, len(os.sched_getaffinity(0)))
         result["cpu_baseline"] = cpu_baseline(sigma, args.soft_iter, procs)

@@ -52,7 +52,16 @@ def main():
                     help="l768 stream: draw the reps on the host cores (default) or on the device from their seeds")
     ap.add_argument("--out", default="gpurun_out/waterfall")
     ap.add_argument("--precision", default=None, help="fp32 | fp64 (default: fp32 plain sweeps, fp64 joint)")
+    ap.add_argument("--min-errors", type=int, default=None, help="joint sweeps: MIN_ERRORS (default: the published run's)")
+    ap.add_argument("--max-blocks", type=int, default=None, help="joint sweeps: MAX_BLOCKS (default: the published run's)")
+    ap.add_argument("--no-bpsk", action="store_true", help="soft / hard / originalHard: skip the LDPC + BPSK column")
+    from bench_joint import add_decoder_options, decoder_options
+    add_decoder_options(ap)  # --llr, --llr-clip, --bp-dectype, --bp-quant: the joint sweeps' decoder
     args = ap.parse_args()
+    opts = decoder_options(args)
+    chosen = opts != decoder_options(argparse.Namespace())
+    if chosen and args.sweep in ("plain", "l768"):
+        ap.error("--llr / --llr-clip / --bp-dectype / --bp-quant go with the joint sweeps")
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import dist
     rank, world, _ = dist.init()
@@ -80,9 +89,10 @@ def main():
         lp = sp.LDPCParams("802.16", "5/6", None)
         ebno = np.linspace(3, 10, 10)[:args.points]
         rows = sp.waterfall(spp, lp, csv_filename=args.out + ".csv" if rank == 0 else None, init=args.sweep,
-                            MIN_ERRORS=cfg["MIN_ERRORS"], MAX_BLOCKS=cfg["MAX_BLOCKS"], sections=sections,
+                            MIN_ERRORS=args.min_errors or cfg["MIN_ERRORS"],
+                            MAX_BLOCKS=args.max_blocks or cfg["MAX_BLOCKS"], sections=sections,
                             batch=args.batch, precision=args.precision, rank=rank, world=world,
-                            allreduce=dist.allreduce_sum, ebno_dbs=ebno)
+                            allreduce=dist.allreduce_sum, ebno_dbs=ebno, bpsk=not args.no_bpsk, **opts)
         ref = pub["waterfall_joint"]["runs"][args.sweep]
         for i, r in enumerate(rows):
             r["reference"] = {k: ref[k][i] for k in ref if k not in ("file", "EbN0_dB")}
@@ -94,7 +104,7 @@ def main():
         rows = sp.soft_hard_plot(True, True, cfg["sec"], cfg["soft_iter"], spp, lp,
                                  args.out + ".csv" if rank == 0 else None, None, MIN_ERRORS=cfg["MIN_ERRORS"],
                                  MAX_BLOCKS=cfg["MAX_BLOCKS"], batch=args.batch, precision=args.precision,
-                                 rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig)
+                                 rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig, **opts)
         ps, ph = pub["soft_hard"]["soft"], pub["soft_hard"]["hard"]
         for i, r in enumerate(rows):
             r["reference"] = dict(BER_sparc=ps["BER_sparc"][i], BER_ldpc_soft=ps["BER_ldpc"][i],
@@ -109,7 +119,7 @@ def main():
                                      MIN_ERRORS=200, MAX_BLOCKS=200, soft_iter=cfg["soft_iter"],
                                      threshold=args.threshold, batch=args.batch, precision=args.precision or "fp64",
                                      rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig,
-                                     unit_cancel=args.unit_cancel)
+                                     unit_cancel=args.unit_cancel, **opts)
         refs = [r for r in pub["threshold_init"]["runs"] if r["threshold"] == args.threshold]
         for i, r in enumerate(rows):
             r["reference_runs"] = [{k: ref[k][i] for k in ("BER_amp", "BER_ldpc", "BER_plain")} for ref in refs]
@@ -198,6 +208,8 @@ def main():
                              reference=pub["soft_hard_BER_sparc"]["BER_sparc"][i]))
     if rank == 0:
         res = dict(sweep=args.sweep, world=world, seconds=time.time() - t0, rows=rows)
+        if chosen:
+            res["decoder_options"] = dict(opts, precision=args.precision)
         if split is not None:
             # the l768 stream: host draw / stream wall time, its device time and
             # the codeword-iterations it decoded (sum of min(stop index + 1, T))

@@ -33,6 +33,7 @@ SA_PREC_F64 = 1
 SA_FLAG_NO_EARLY_STOP = 1
 SA_FLAG_BETA0 = 0x100
 SA_PTR_DEVICE = 0x200
+SA_LLR_MODES = {"reference": 0, "two_sided": 1}  # sa_llr_ex: SA_LLR_REFERENCE, SA_LLR_TWO_SIDED
 
 # sa_create_ex plan options (include/sparc_amp.h): overrides of the built-in
 # kernel / layout choice rules, by name
@@ -66,7 +67,7 @@ EXPORTS = (
     "sa_reserve", "sa_stage", "sa_stage_power_batch", "sa_run", "sa_wait", "sa_fetch", "sa_fetch_z", "sa_fetch_y", "sa_run_event_ms",
     "sa_profile", "sa_profile_rep", "sa_profile_dispatch", "sa_profile_kinds", "sa_decide",
     "sa_decide_async", "sa_decide_collect", "sa_info", "sa_device_count", "sa_last_error", "sa_version",
-    "sa_encode", "sa_stage_onehot", "sa_llr", "sa_soft_beta0", "sa_hard_cancel",
+    "sa_encode", "sa_stage_onehot", "sa_llr", "sa_llr_ex", "sa_soft_beta0", "sa_hard_cancel",
     "sa_threshold", "sa_cancel", "sa_plan", "sa_plan_batched", "sa_stage_onehot_scaled", "sa_cancel_scaled",
     "sa_host_init", "sa_host_tau", "sa_host_eta", "sa_host_residual",
     "sa_draw_reps", "sa_mc_stage", "sa_mc_run", "sa_make_ordering", "sa_mc_draw", "sa_mc_fetch_draws",
@@ -115,6 +116,7 @@ _SIG = {
     "sa_stage_onehot_scaled": (_I, [_P, _I, ct.POINTER(ct.c_int32), ct.c_double]),
     "sa_cancel_scaled": (_I, [_P, _I, ct.POINTER(ct.c_int32), ct.c_double, _P]),
     "sa_llr": (_I, [_P, _I, _I, _I, _P, _I]),
+    "sa_llr_ex": (_I, [_P, _I, _I, _I, _P, _I, _I, ct.c_double]),
     "sa_soft_beta0": (_I, [_P, _I, _I, _I, _P, _I]),
     "sa_hard_cancel": (_I, [_P, _I, _I, _I, _P, _I, _P, ct.POINTER(ct.c_int32)]),
     "sa_host_init": (_I, [_P, _I, _I, _D, _D, _D, _D]),

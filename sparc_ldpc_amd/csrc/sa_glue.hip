@@ -94,6 +94,52 @@ __global__ void __launch_bounds__(64) k_llr(const real* __restrict__ beta, const
   llr[bl * lgM + t] = v;
 }
 
+// nan_to_num and the magnitude clip of an LLR: NaN -> 0; lim > 0 bounds the
+// value to [-lim, lim] (+-inf included); lim == 0 (no clip) sends +-inf to +-max.
+__device__ __forceinline__ double llr_finish(double v, double lim) {
+  if (v != v) return 0.0;
+  if (lim > 0.0) return fmin(fmax(v, -lim), lim);
+  if (isinf(v)) return v > 0 ? DBL_MAX : -DBL_MAX;
+  return v;
+}
+
+// The two-sided LLR (SA_LLR_TWO_SIDED), staged like k_llr: lane t < log2 M
+// forms p1_t as k_llr forms p, lane log2 M + t forms p0_t, the sum over the
+// entries whose bit (logM-1-t) is clear, also in ascending j;
+// llr = log(p0) - log(p1).  Neither sum is formed as 1 - (the other), so a beta
+// held in binary32, whose sums carry 6e-8 of rounding, keeps its LLR beyond
+// |LLR| = 16 and a sum that lands above 1 gives no NaN.
+template <typename real>
+__global__ void __launch_bounds__(64) k_llr2(const real* __restrict__ beta, const double* __restrict__ cd, int L,
+                                             int M, int lgM, int l0, int ns, double lim, double* __restrict__ llr) {
+  extern __shared__ double post[];
+  const size_t bl = blockIdx.x;  // b * ns + lp
+  const int l = l0 + (int)(bl % ns);
+  const real* bs = beta + ((bl / ns) * L + l) * M;
+  const double c = cd[l];
+  const real cr = (real)c;  // a decided section: posterior 1 (see k_llr)
+  for (int j = threadIdx.x; j < M; j += 64) post[j] = bs[j] == cr ? 1.0 : (double)bs[j] / c;
+  __syncthreads();
+  const int t = threadIdx.x;  // 2 log2 M <= 26 lanes sum (check_glue: M <= 8192)
+  double p = 0.0;
+  if (t < 2 * lgM) {
+    const int one = t < lgM, sh = lgM - 1 - (one ? t : t - lgM), lo = (1 << sh) - 1;
+    const int set = one ? lo + 1 : 0;
+    // i-th entry (ascending) whose bit sh is set / clear
+    p = lds_seq_sum(post, M >> 1, [=](int i) { return ((i >> sh) << (sh + 1)) | set | (i & lo); });
+  }
+  const double p0 = __shfl(p, (t + lgM) & 63);  // every lane of the wavefront takes part
+  if (t >= lgM) return;
+  llr[bl * lgM + t] = llr_finish(log(p0) - log(p), lim);
+}
+
+// The clip of SA_LLR_REFERENCE's output, in place: k_llr has already sent NaN
+// to 0 and +-inf to +-max.
+__global__ void k_llr_clip(double* __restrict__ llr, size_t cnt, double lim) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x)
+    llr[i] = fmin(fmax(llr[i], -lim), lim);
+}
+
 // bp2sp of the LDPC a-posteriori LLRs into beta0 (sparc_ldpc.py:683-696 ->
 // :283-314), one wavefront per (codeword, LDPC section): bp_t = 1/(1+exp(app_t));
 // sp_m = prod_t (bit_t(m) ? bp_t : 1 - bp_t), MSB first, in LDS; the
@@ -297,9 +343,16 @@ int sa_stage_onehot_scaled(sa_ctx* c, int B, const int32_t* idx, double scale) {
 }
 
 int sa_llr(sa_ctx* c, int B, int l0, int ns, double* llr, int flags) {
+  return sa_llr_ex(c, B, l0, ns, llr, flags, SA_LLR_REFERENCE, INFINITY);
+}
+
+int sa_llr_ex(sa_ctx* c, int B, int l0, int ns, double* llr, int flags, int mode, double clip) {
   int rc = check_glue(c, B, l0, ns);
   if (rc) return rc;
   if (!llr) return fail(SA_ERR_ARG, "sa_llr: llr is NULL");
+  if (mode != SA_LLR_REFERENCE && mode != SA_LLR_TWO_SIDED) return fail(SA_ERR_ARG, "sa_llr_ex: unknown mode");
+  if (!(clip >= 0.0)) return fail(SA_ERR_ARG, "sa_llr_ex: clip must be positive, or 0 / +inf for none");
+  const double lim = std::isinf(clip) ? 0.0 : clip;  // 0: no clip
   HIP_TRY(hipSetDevice(c->device));
   sa_lane& ln = c->at();
   const int lgM = ilog2(c->M);
@@ -310,10 +363,20 @@ int sa_llr(sa_ctx* c, int B, int l0, int ns, double* llr, int flags) {
     d_out = ln.d_stage;
   }
   const size_t lds = (size_t)c->M * sizeof(double);
-  if (c->prec == SA_PREC_F64)
-    k_llr<double><<<B * ns, 64, lds, ln.stream>>>((const double*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
-  else
-    k_llr<float><<<B * ns, 64, lds, ln.stream>>>((const float*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
+  if (mode == SA_LLR_TWO_SIDED) {
+    if (c->prec == SA_PREC_F64)
+      k_llr2<double><<<B * ns, 64, lds, ln.stream>>>((const double*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, lim,
+                                                     d_out);
+    else
+      k_llr2<float><<<B * ns, 64, lds, ln.stream>>>((const float*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, lim,
+                                                    d_out);
+  } else {
+    if (c->prec == SA_PREC_F64)
+      k_llr<double><<<B * ns, 64, lds, ln.stream>>>((const double*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
+    else
+      k_llr<float><<<B * ns, 64, lds, ln.stream>>>((const float*)ln.d_beta, c->d_cd, c->L, c->M, lgM, l0, ns, d_out);
+    if (lim > 0.0) k_llr_clip<<<grid_of(cnt), 256, 0, ln.stream>>>(d_out, cnt, lim);
+  }
   HIP_TRY(hipGetLastError());
   if (!(flags & SA_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(llr, d_out, cnt * 8, hipMemcpyDeviceToHost, ln.stream));
   HIP_TRY(hipStreamSynchronize(ln.stream));

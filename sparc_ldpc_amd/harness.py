@@ -90,7 +90,7 @@ def ber_of(sent, decided, total_bits):
 
 
 def amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams=None, a=None, f=None, C=None, *,
-                 backend=None, precision=None):
+                 backend=None, precision=None, **options):
     """sparc_ldpc.py:359-545: one Monte-Carlo rep.  With an LDPC code this is
     the original hard exchange (``joint.amp_ldpc_sim_ldpc``); without one,
     plain SPARC returning (ber_amp, None, None, R) like the reference.
@@ -99,7 +99,9 @@ def amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams=None, a=None, f=None, C=No
     """
     if ldpcparams is not None:
         from .joint import amp_ldpc_sim_ldpc
-        return amp_ldpc_sim_ldpc(sparcparams, ldpcparams, backend=backend, precision=precision)
+        return amp_ldpc_sim_ldpc(sparcparams, ldpcparams, backend=backend, precision=precision, **options)
+    if options:
+        raise TypeError(f"joint decoder options without an LDPC code: {sorted(options)}")
     L, M, P = sparcparams.L, sparcparams.M, sparcparams.p
     sigma, r_sparc, T = sparcparams.sigma, sparcparams.r, sparcparams.t
     a, f, C = sparcparams.a, sparcparams.f, sparcparams.C

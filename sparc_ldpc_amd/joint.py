@@ -25,6 +25,11 @@ Every step of a round runs on the device: encoding (``sa_encode``), AMP
 between the two libraries as device pointers.  The host draws the message
 bits and the noise and LDPC-encodes the protected bits (numpy), exactly in
 the reference's draw order, and counts bit errors.
+
+Opt-in (``joint_options``; nothing of it is a default): the two-sided form of
+the section->bit LLR and a bound on its magnitude (``sa_llr_ex``), with which
+the rounds also work on a binary32 AMP, and any of the LDPC decoder types for
+the BP calls.
 """
 from __future__ import annotations
 
@@ -36,12 +41,39 @@ import numpy as np
 
 from . import ldpc as _ldpc
 from .harness import SPARCParams, LDPCParams, pa_parameterised, ebno_to_sigma
-from .operators import SparcOperator, make_ordering
+from .operators import SparcOperator, llr_mode, make_ordering
 
-__all__ = ["JointDecoder", "JointPipeline", "joint_decoder", "draw_reps", "amp_ldpc_sim_ldpc", "soft_amp_ldpc_sim",
-           "hardinitbeta_amp_ldpc_sim", "sim_ldpc", "waterfall", "soft_hard_plot", "sp2bp", "bp2sp", "mc_joint"]
+__all__ = ["JointDecoder", "JointPipeline", "joint_decoder", "joint_options", "draw_reps", "amp_ldpc_sim_ldpc",
+           "soft_amp_ldpc_sim", "hardinitbeta_amp_ldpc_sim", "sim_ldpc", "waterfall", "soft_hard_plot", "sp2bp",
+           "bp2sp", "mc_joint"]
 
 MODES = ("originalHard", "soft", "hard", "threshold")
+
+
+def joint_options(llr="reference", llr_clip=None, bp_dectype="sumprod2", bp_corr_factor=0.7,
+                  bp_max_iter=_ldpc.MAX_ITCOUNT, bp_quant=None):
+    """The LLR and BP options of a JointDecoder, checked (ValueError) and in a
+    canonical, hashable form; with no argument, the reference's."""
+    llr_mode(llr)
+    if llr_clip is not None:
+        llr_clip = float(llr_clip)
+        if not llr_clip >= 0.0:
+            raise ValueError("llr_clip must be None or a bound >= 0 (0 and inf: none)")
+        if llr_clip == 0.0 or math.isinf(llr_clip):
+            llr_clip = None
+    if bp_dectype not in _ldpc._ALGOS:
+        raise ValueError(f"bp_dectype must be one of {sorted(_ldpc._ALGOS)}, not {bp_dectype!r}")
+    widths = _ldpc._quant_widths(bp_quant, bp_dectype)
+    return dict(llr=llr, llr_clip=llr_clip, bp_dectype=bp_dectype, bp_corr_factor=float(bp_corr_factor),
+                bp_max_iter=int(bp_max_iter), bp_quant=None if widths is None else tuple(widths))
+
+
+def option_keywords(o):
+    """joint_options' dict as the keywords of SparcOperator.llr and of the
+    LDPC code's run_buffers / decode_batch."""
+    return (dict(mode=o["llr"], clip=o["llr_clip"]),
+            dict(dectype=o["bp_dectype"], corr_factor=o["bp_corr_factor"], max_iter=o["bp_max_iter"],
+                 quant=o["bp_quant"]))
 
 
 def sp2bp(beta, L, M):
@@ -104,10 +136,16 @@ class JointDecoder:
     sections, for B-codeword batches of the joint schemes."""
 
     def __init__(self, L, M, n, code, T, backend=None, precision=None, device=None, seed=0, twin_of=None,
-                 ordering=None):
+                 ordering=None, **options):
         """twin_of: another JointDecoder whose operator tables this one shares
         (SparcOperator.twin: own stream and workspace, one copy of the tables).
-        ordering: the design's (L, n) ordering (default: make_ordering(..., seed))."""
+        ordering: the design's (L, n) ordering (default: make_ordering(..., seed)).
+        options (joint_options): llr / llr_clip, the form and the bound of the
+        section->bit LLRs (SparcOperator.llr), and bp_dectype / bp_corr_factor /
+        bp_max_iter / bp_quant, the outer decoder of every BP call (any type of
+        ldpc._ALGOS; the defaults are the reference's)."""
+        self.options = joint_options(**options)
+        self._llr_kw, self._bp_kw = option_keywords(self.options)
         self.L, self.M, self.n, self.T = int(L), int(M), int(n), int(T)
         self.logm = int(round(math.log2(M)))
         self.code = code
@@ -135,10 +173,10 @@ class JointDecoder:
         return draw_reps(self.code, self.L, self.M, self.n, rs, B, sigma)
 
     # -- one batch ------------------------------------------------------------------
-    def _bp(self, B, dectype="sumprod2"):
+    def _bp(self, B):
         d_ch, d_app, _ = self.code.device_buffers(B)
-        self.op.llr(B, self.l0, self.ns, out=d_ch)
-        self.code.run_buffers(B, dectype)
+        self.op.llr(B, self.l0, self.ns, out=d_ch, **self._llr_kw)
+        self.code.run_buffers(B, **self._bp_kw)
         return d_app
 
     def run(self, idx, noise, Pl, mode="soft", soft_iter=2, threshold=0.5, unit_cancel=False):
@@ -234,14 +272,14 @@ class JointDecoder:
         """The information-exchange rounds of soft_amp_ldpc_hardinit
         (sparc_ldpc.py:960-1041) for the batch; the first AMP has run on self.op."""
         op, T, L, logm, l0, ns = self.op, self.T, self.L, self.logm, self.l0, self.ns
-        LLR = op.llr(B, 0, L)  # :960-970, every section
+        LLR = op.llr(B, 0, L, **self._llr_kw)  # :960-970, every section
         if self._masked is None:
             self._masked = op.subset(np.arange(L))
         mk = self._masked
         mk.reserve(B, T)
         mk.stage_power(B, Pl)  # c_l of the LLR kernel
         for i in range(soft_iter):
-            app, it = self.code.decode_batch(LLR[:, l0 * logm:])  # :973
+            app, it = self.code.decode_batch(LLR[:, l0 * logm:], **self._bp_kw)  # :973
             bp_iters.append(it)
             LLR[:, l0 * logm:] = app
             errs_ldpc.append(self._llr_errs(idx, LLR))  # :977
@@ -259,7 +297,7 @@ class JointDecoder:
                 mk.stage_power_batch(B, np.where(undecided, np.asarray(Pl, np.float64)[None, :], 0.0))
                 mk.run(B, T)
                 mk.wait()
-                llr = mk.llr(B, 0, L).reshape(B, L, logm)
+                llr = mk.llr(B, 0, L, **self._llr_kw).reshape(B, L, logm)
                 LLR.reshape(B, L, logm)[undecided] = llr[undecided]
             errs_amp.append(self._llr_errs(idx, LLR))  # :1038
 
@@ -312,7 +350,8 @@ class JointPipeline:
             # every slice decodes against jd's design (its ordering, whatever
             # seed built it): the twin's shared tables or its own copy of them
             self.parts.append(JointDecoder(jd.L, jd.M, jd.n, c2, jd.T, op.backend, op.precision, op.device,
-                                           twin_of=jd if TWIN_SLICES else None, ordering=op.ordering))
+                                           twin_of=jd if TWIN_SLICES else None, ordering=op.ordering,
+                                           **jd.options))
         self._pool = ThreadPoolExecutor(max_workers=len(self.parts), thread_name_prefix="joint")
         self._slices = None
 
@@ -396,22 +435,30 @@ def _evict(jd: JointDecoder):
         jd._pipeline = None
 
 
-def joint_decoder(L, M, n, ldpcparams: LDPCParams, T, backend=None, precision=None, device=None):
-    """Cached JointDecoder (the operator tables and the LDPC graph are built once).
+def joint_decoder(L, M, n, ldpcparams: LDPCParams, T, backend=None, precision=None, device=None, **options):
+    """Cached JointDecoder (the operator tables and the LDPC graph are built once);
+    options: JointDecoder's LLR / BP options (joint_options), part of the cache key.
 
-    AMP runs in binary64 unless told otherwise: in fp32 the softmax of the
-    denoiser underflows below e^-87 (fp64: e^-745), so confident sections
-    give p in {0, 1} exactly and the LLRs saturate at +-DBL_MAX, including
-    for wrong decisions that BP could otherwise revise (measured: the fp32
-    soft waterfall's BER_ldpc stalls near 0.4 above 7 dB, the fp64 one
-    overlays the reference's published curve)."""
+    AMP runs in binary64 unless told otherwise.  With the reference LLR,
+    log(1 - p) - log(p), a binary32 beta is not enough: p carries the 6e-8
+    rounding of its terms, so 1 - p is noise from |LLR| = 16 upwards, and
+    where p lands above 1 the NaN becomes 0: a confident bit reaches BP as an
+    erasure (measured: the fp32 soft waterfall's BER_ldpc stalls near 0.4
+    above 7 dB, the fp64 one overlays the reference's published curve).
+    llr="two_sided" forms both sums instead; with it the fp32 soft waterfall
+    lies on the fp64 one (every column within 3e-5 over 10 points x 256
+    blocks, with and without llr_clip) and the configs[4] step takes 59-60 ms
+    against 106.  Nothing of this is a default."""
     precision = precision or "fp64"
+    options = joint_options(**options)
     key = (L, M, n, ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype, T,
            backend, precision, device)
+    if options != joint_options():  # (the key of a decoder without options stays as it was)
+        key += tuple(sorted(options.items()))
     jd = _JD_CACHE.get(key)
     if jd is None:
         code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype, device=device)
-        jd = JointDecoder(L, M, n, code, T, backend, precision, device)
+        jd = JointDecoder(L, M, n, code, T, backend, precision, device, **options)
         _JD_CACHE[key] = jd
         while len(_JD_CACHE) > 4:
             _evict(_JD_CACHE.popitem(last=False)[1])
@@ -431,10 +478,11 @@ def _setup(sparcparams: SPARCParams, ldpcparams: LDPCParams, uniform_only=False,
     return jd, Pl
 
 
-def amp_ldpc_sim_ldpc(sparcparams: SPARCParams, ldpcparams: LDPCParams, backend=None, precision=None):
+def amp_ldpc_sim_ldpc(sparcparams: SPARCParams, ldpcparams: LDPCParams, backend=None, precision=None, **options):
     """LDPC branch of amp_ldpc_sim (sparc_ldpc.py:359-545): one rep from the
-    global np.random stream.  Returns (ber_amp, ber_ldpc, ber_ldpc_amp | None, R)."""
-    jd, Pl = _setup(sparcparams, ldpcparams, backend=backend, precision=precision)
+    global np.random stream.  Returns (ber_amp, ber_ldpc, ber_ldpc_amp | None, R).
+    options: the decoder's LLR / BP options (joint_options), here and below."""
+    jd, Pl = _setup(sparcparams, ldpcparams, backend=backend, precision=precision, **options)
     idx, noise = jd.draw(np.random, 1, sparcparams.sigma)
     r = jd.run(idx, noise, Pl, "originalHard")
     tb = jd.total_bits
@@ -443,18 +491,19 @@ def amp_ldpc_sim_ldpc(sparcparams: SPARCParams, ldpcparams: LDPCParams, backend=
 
 
 def soft_amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams: LDPCParams, soft_iter, a=None, f=None, C=None,
-                      backend=None, precision=None):
+                      backend=None, precision=None, **options):
     """sparc_ldpc.py:547-712: (ber_amp list (soft_iter+1), ber_ldpc list (soft_iter), R)."""
-    jd, Pl = _setup(sparcparams, ldpcparams, backend=backend, precision=precision)
+    jd, Pl = _setup(sparcparams, ldpcparams, backend=backend, precision=precision, **options)
     idx, noise = jd.draw(np.random, 1, sparcparams.sigma)
     r = jd.run(idx, noise, Pl, "soft", soft_iter)
     tb = jd.total_bits
     return [float(e) / tb for e in r["amp"][0]], [float(e) / tb for e in r["ldpc"][0]], jd.R
 
 
-def hardinitbeta_amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams: LDPCParams, backend=None, precision=None):
+def hardinitbeta_amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams: LDPCParams, backend=None, precision=None,
+                              **options):
     """sparc_ldpc.py:715-860 (uniform power only): (ber_amp [2], ber_ldpc [1], R)."""
-    jd, Pl = _setup(sparcparams, ldpcparams, uniform_only=True, backend=backend, precision=precision)
+    jd, Pl = _setup(sparcparams, ldpcparams, uniform_only=True, backend=backend, precision=precision, **options)
     idx, noise = jd.draw(np.random, 1, sparcparams.sigma)
     r = jd.run(idx, noise, Pl, "hard")
     tb = jd.total_bits
@@ -517,14 +566,15 @@ def sim_ldpc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, b
 def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None, png_filename=None,
               init="soft", pa_param=False, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, bpsk=True,
               sections=512, batch=64, seed0=0, backend=None, precision=None, rank=0, world=1, allreduce=None,
-              ebno_dbs=None, bpsk_mc=False):
+              ebno_dbs=None, bpsk_mc=False, **options):
     """The reference's waterfall sweep on the GPU.  Per Eb/N0 point (20 log10
     convention): blocks of the joint scheme ``init`` and of plain SPARC at the
     same overall rate, consumed in seed order until MIN_ERRORS plain block
     errors or MAX_BLOCKS blocks (:1217-1245 counts the PLAIN block errors);
     BER_bpsk from sim_ldpc, or with ``bpsk_mc`` from the device-side
     ldpc_mc.sim_ldpc_mc (its own seeded blocks, sharded over ranks).  Reps are
-    sharded over ranks like ber_point.
+    sharded over ranks like ber_point.  options: the joint decoder's LLR / BP
+    options (joint_options); the BER_bpsk column keeps the reference's sumprod2.
     Returns the rows; writes the reference CSV schema (:1257-1264) on rank 0."""
     from .harness import mc_decode
     precision = precision or "fp64"  # see joint_decoder
@@ -539,7 +589,7 @@ def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=Non
     if ebno_dbs is None:
         ebno_dbs = np.linspace(3, 10, datapoints)
     n = int(L * np.log2(M) / r_sparc)
-    jd = joint_decoder(L, M, n, ldp, T, backend=backend, precision=precision)
+    jd = joint_decoder(L, M, n, ldp, T, backend=backend, precision=precision, **options)
     n_plain = int(L * np.log2(M) / R)
     plain = SparcOperator(L, M, n_plain, make_ordering(L, M, n_plain, 0), backend, precision)
     total_bits = L * logm
@@ -632,7 +682,7 @@ def _ber_point_multi(round_fn, total_bits, min_errors, max_blocks, batch, rank, 
 
 def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None,
                    png_filename=None, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, batch=64, seed0=0,
-                   backend=None, precision=None, rank=0, world=1, allreduce=None, sigmas=None):
+                   backend=None, precision=None, rank=0, world=1, allreduce=None, sigmas=None, **options):
     """Soft exchange vs the original hard exchange on the GPU.
 
     The LDPC code covers nl = log2(M) * sec bits with z = int(nl / 24)
@@ -646,7 +696,7 @@ def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcpar
     sharded over ranks like waterfall.  Returns rows (EbN0_dB, BER_sparc,
     BER_ldpc_soft [soft_iter], BER_amp_soft [soft_iter + 1], BER_ldpc_hard,
     BER_amp_hard [2], blocks); rank 0 appends the reference's two CSV blocks
-    (:1397-1413).  No plots."""
+    (:1397-1413).  No plots.  options: the joint decoder's LLR / BP options."""
     from .harness import mc_decode
     from .dist import shard_seeds
     precision = precision or "fp64"
@@ -661,7 +711,7 @@ def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcpar
     n_plain = int(L * np.log2(M) / R)
     total_bits = L * logm
     Pl = p / L * np.ones(L)
-    jd = joint_decoder(L, M, n, ldp, T, backend=backend, precision=precision)
+    jd = joint_decoder(L, M, n, ldp, T, backend=backend, precision=precision, **options)
     plain = SparcOperator(L, M, n_plain, make_ordering(L, M, n_plain, 0), backend, precision)
     SIGMA = np.linspace(0.8, 0.4, datapoints) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
     rows = []

@@ -42,6 +42,13 @@ def default_device() -> int:
     return d if 0 <= d < ndev else 0
 
 
+def llr_mode(mode) -> int:
+    """sa_llr_ex's number of an LLR form, "reference" or "two_sided" (ValueError otherwise)."""
+    if mode not in _lib.SA_LLR_MODES:
+        raise ValueError(f"llr must be one of {sorted(_lib.SA_LLR_MODES)}, not {mode!r}")
+    return _lib.SA_LLR_MODES[mode]
+
+
 def seed_array(seeds) -> np.ndarray:
     """Seeds as uint32; outside [0, 2**32) NumPy's RandomState raises
     ValueError, and so does this (no masking)."""
@@ -459,14 +466,24 @@ class SparcOperator:
         else:
             check(self._lib.sa_stage_onehot_scaled(self._ctx, idx.shape[0], p, float(scale)))
 
-    def llr(self, B, l0, ns, out=None):
+    def llr(self, B, l0, ns, out=None, mode="reference", clip=None):
         """LDPC-bit LLRs of sections [l0, l0+ns) of the current β (sparc_ldpc.py:470-479).
-        out: None (returns a (B, ns*log2 M) array) or a device pointer."""
+        out: None (returns a (B, ns*log2 M) array) or a device pointer.
+        mode: "reference", log(1 - p) - log(p) as the reference forms it, or
+        "two_sided", log(p0) - log(p1) with both sums formed (sa_llr_ex: the form
+        that keeps |LLR| > 16 on a binary32 β).  clip: bound on |LLR| (None: ±max)."""
+        m = llr_mode(mode)
         lgm = int(np.log2(self.M))
         if out is None:
             out = np.empty((B, ns * lgm))
         p, fl = self._ptr(out)
-        check(self._lib.sa_llr(self._ctx, int(B), int(l0), int(ns), p, fl))
+        if m == 0 and clip is None:
+            check(self._lib.sa_llr(self._ctx, int(B), int(l0), int(ns), p, fl))
+        else:
+            if not hasattr(self._lib, "sa_llr_ex"):
+                raise _lib.SparcAmpError(_lib.SA_ERR_UNSUPPORTED, "this build of the library has no sa_llr_ex")
+            check(self._lib.sa_llr_ex(self._ctx, int(B), int(l0), int(ns), p, fl, m,
+                                      float("inf") if clip is None else float(clip)))
         return out
 
     def soft_beta0(self, B, l0, ns, app):

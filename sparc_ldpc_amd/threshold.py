@@ -123,7 +123,7 @@ def prep_y(X, L, M, n, sigma_w, P, a=None, f=None, C=None):
     return (x + w).reshape(-1, 1), Ab, Az, Pl, ordering
 
 
-def _amp_on_undecided(op, idx_full, Pl, T, M):
+def _amp_on_undecided(op, idx_full, Pl, T, M, llr_kw=None):
     """Cancel decided sections (idx >= 0) from op's staged y and run AMP on the
     rest through a shortened operator; returns (amp_sections, LLRs (len*logm,))."""
     amp_sections = np.nonzero(idx_full[0] < 0)[0]
@@ -135,7 +135,7 @@ def _amp_on_undecided(op, idx_full, Pl, T, M):
     sub.stage_power(1, np.asarray(Pl)[amp_sections])
     sub.run(1, T)
     sub.wait()
-    return amp_sections, sub.llr(1, 0, amp_sections.size)[0]
+    return amp_sections, sub.llr(1, 0, amp_sections.size, **(llr_kw or {}))[0]
 
 
 def calc_E(X, I_a, snr_dB, sparcparams: SPARCParams, csv_filename=None, threshold=0.5, precision="fp64"):
@@ -218,9 +218,12 @@ def polynomial(I_a, I_e):
 
 
 def soft_amp_ldpc_hardinit(sparcparams: SPARCParams, ldpcparams: LDPCParams, soft_iter, threshold,
-                           precision="fp64"):
+                           precision="fp64", **options):
     """sparc_ldpc.py:862-1047: threshold-initialised exchange, one rep from the
-    global np.random stream.  Returns (ber_amp list, ber_ldpc list, R)."""
+    global np.random stream.  Returns (ber_amp list, ber_ldpc list, R).
+    options: the LLR / BP options of joint.joint_options."""
+    from .joint import joint_options, option_keywords
+    llr_kw, bp_kw = option_keywords(joint_options(**options))
     L, M, P, sigma, T = sparcparams.L, sparcparams.M, sparcparams.p, sparcparams.sigma, sparcparams.t
     n = int(L * np.log2(M) / sparcparams.r)
     logm = int(np.log2(M))
@@ -251,9 +254,10 @@ def soft_amp_ldpc_hardinit(sparcparams: SPARCParams, ldpcparams: LDPCParams, sof
     ber_ldpc = []
     ns = nl // logm
     l0 = L - ns
-    LLR = op.llr(1, 0, L)[0]
+    LLR = op.llr(1, 0, L, **llr_kw)[0]
     for i in range(soft_iter):
-        app, _ = code.decode(LLR[l0 * logm:])
+        app, _ = code.decode_batch(LLR[None, l0 * logm:], **bp_kw)  # (code.decode, with the chosen decoder)
+        app = app[0]
         LLR[l0 * logm:] = app
         ber_ldpc.append(ber_from_LLRs(M, LLR, idx, total_bits))
         if i == soft_iter - 1:
@@ -261,7 +265,7 @@ def soft_amp_ldpc_hardinit(sparcparams: SPARCParams, ldpcparams: LDPCParams, sof
         dec = op.threshold(1, l0, ns, app, threshold)
         full = -np.ones((1, L), dtype=np.int32)
         full[0, l0:] = dec[0]
-        amp_sections, llr = _amp_on_undecided(op, full, Pl, T, M)
+        amp_sections, llr = _amp_on_undecided(op, full, Pl, T, M, llr_kw)
         if llr is not None:
             pos = (np.arange(logm)[None, :] + logm * amp_sections[:, None]).reshape(-1)
             LLR[pos] = llr
@@ -273,7 +277,7 @@ def soft_amp_ldpc_hardinit(sparcparams: SPARCParams, ldpcparams: LDPCParams, sof
 def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None, png_filename=None,
                        sections=None, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, soft_iter=3, threshold=0.6,
                        batch=64, seed0=0, precision="fp64", rank=0, world=1, allreduce=None, sigmas=None,
-                       unit_cancel=False):
+                       unit_cancel=False, **options):
     """The threshold-initialised exchange sweep of sparc_ldpc.py:1435-1590 on the GPU.
 
     Per sigma of linspace(0.9, 1.4, datapoints) (:1488): blocks of
@@ -292,6 +296,7 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
     unit_cancel=True cancels decided sections with amplitude 1 (the
     reference's behaviour before the fix noted at amp_exit.py:97-98, which its
     published threshold-init CSVs reflect; batched path only).
+    options: the joint decoder's LLR / BP options (joint.joint_options).
     No plots (figure code is out of scope)."""
     from .harness import mc_decode, amp_ldpc_sim
     from .joint import joint_decoder, mc_joint, _ber_point_multi
@@ -318,7 +323,7 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
     Pl = p / L * np.ones(L)
     rows = []
     if std:
-        jd = joint_decoder(L, M, n, ldp, T, precision=precision)
+        jd = joint_decoder(L, M, n, ldp, T, precision=precision, **options)
         assert jd.ns == sections, "sections must match the LDPC code length"
         plain = SparcOperator(L, M, n_plain, make_ordering(L, M, n_plain, 0), None, precision)
     for pi, sigma in enumerate(SIGMA):
@@ -340,7 +345,7 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
             cum_amp, cum_ldpc, cum_plain = np.zeros(soft_iter), np.zeros(soft_iter), 0.0
             nerr = nblocks = 0
             while nerr < MIN_ERRORS:
-                ba, bl, _ = soft_amp_ldpc_hardinit(sp_c, ldp, soft_iter, threshold, precision=precision)
+                ba, bl, _ = soft_amp_ldpc_hardinit(sp_c, ldp, soft_iter, threshold, precision=precision, **options)
                 bpl = amp_ldpc_sim(sp_plain)[0]
                 cum_amp += np.asarray(ba[:soft_iter])
                 cum_ldpc += np.asarray(bl[:soft_iter])
