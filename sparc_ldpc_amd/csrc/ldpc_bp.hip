@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -567,10 +568,6 @@ __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads, DCFIX >
 // The loops over checks run the same number of passes in every thread, so the
 // shuffles are never issued under divergence; a group without a check folds
 // neutral values.  A check of degree 1 sees mag = amax (the minimum over no edge).
-struct FixedPar {
-  int frac, rmax, amax, alpha;
-};
-
 template <int G, int EPL>
 __device__ __forceinline__ int bplq_word(const BplArgs& a, const FixedPar& p, unsigned char* lds, int* unsat, int word,
                                          int slot) {
@@ -922,24 +919,29 @@ KernelFn pick_kernel(int algo, int maxdc, bool lds, bool fixed = false) {
   }
 }
 
-using LayeredFn = void (*)(BplArgs);
+// A layered instance: the kernel of one workgroup per word and the persistent kernel of the block
+// stream, of one template row, so that a class cannot differ between the two.
+struct LayeredInst {
+  void (*batch)(BplArgs);
+  void (*stream)(BplStreamArgs);
+};
+
+template <int ALGO, int DCMAX, int DCFIX, int MODE>
+LayeredInst layered_row(bool f32) {
+  if (f32) return {k_bpl32<ALGO, DCMAX, DCFIX, MODE>, k_bpls32<ALGO, DCMAX, DCFIX, MODE>};
+  return {k_bpl<ALGO, DCMAX, DCFIX, MODE>, k_bpls<ALGO, DCMAX, DCFIX, MODE>};
+}
 
 template <int ALGO, int MODE>
-LayeredFn pick_layered_dc(int maxdc, bool fixed, bool f32) {
-  if (f32) {
-    if (fixed) return k_bpl32<ALGO, 32, 20, MODE>;
-    if (maxdc <= 8) return k_bpl32<ALGO, 8, 0, MODE>;
-    if (maxdc <= 16) return k_bpl32<ALGO, 16, 0, MODE>;
-    return k_bpl32<ALGO, 32, 0, MODE>;
-  }
-  if (fixed) return k_bpl<ALGO, 32, 20, MODE>;
-  if (maxdc <= 8) return k_bpl<ALGO, 8, 0, MODE>;
-  if (maxdc <= 16) return k_bpl<ALGO, 16, 0, MODE>;
-  return k_bpl<ALGO, 32, 0, MODE>;
+LayeredInst pick_layered_dc(int maxdc, bool fixed, bool f32) {
+  if (fixed) return layered_row<ALGO, 32, 20, MODE>(f32);
+  if (maxdc <= 8) return layered_row<ALGO, 8, 0, MODE>(f32);
+  if (maxdc <= 16) return layered_row<ALGO, 16, 0, MODE>(f32);
+  return layered_row<ALGO, 32, 0, MODE>(f32);
 }
 
 // algo: LB_LAYERED_SUMPROD2 or LB_LAYERED_MINSUM; the check rules are the flooding decoders'
-LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
+LayeredInst pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
   if (algo == LB_LAYERED_SUMPROD2)
     return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(maxdc, fixed, f32)
            : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(maxdc, fixed, f32)
@@ -949,57 +951,29 @@ LayeredFn pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
                      : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
 }
 
-// the persistent instances, over pick_layered's table
-using StreamFn = void (*)(BplStreamArgs);
-
-template <int ALGO, int MODE>
-StreamFn pick_stream_dc(int maxdc, bool fixed, bool f32) {
-  if (f32) {
-    if (fixed) return k_bpls32<ALGO, 32, 20, MODE>;
-    if (maxdc <= 8) return k_bpls32<ALGO, 8, 0, MODE>;
-    if (maxdc <= 16) return k_bpls32<ALGO, 16, 0, MODE>;
-    return k_bpls32<ALGO, 32, 0, MODE>;
-  }
-  if (fixed) return k_bpls<ALGO, 32, 20, MODE>;
-  if (maxdc <= 8) return k_bpls<ALGO, 8, 0, MODE>;
-  if (maxdc <= 16) return k_bpls<ALGO, 16, 0, MODE>;
-  return k_bpls<ALGO, 32, 0, MODE>;
-}
-
-StreamFn pick_stream(int algo, int maxdc, bool fixed, int mode, bool f32) {
-  if (algo == LB_LAYERED_SUMPROD2)
-    return mode == 2   ? pick_stream_dc<LB_SUMPROD2, 2>(maxdc, fixed, f32)
-           : mode == 1 ? pick_stream_dc<LB_SUMPROD2, 1>(maxdc, fixed, f32)
-                       : pick_stream_dc<LB_SUMPROD2, 0>(maxdc, fixed, f32);
-  return mode == 2   ? pick_stream_dc<LB_MINSUM, 2>(maxdc, fixed, f32)
-         : mode == 1 ? pick_stream_dc<LB_MINSUM, 1>(maxdc, fixed, f32)
-                     : pick_stream_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
-}
-
 // The fixed-point instances: lanes per check G x the check-degree class (8 / 16 / 20 / 32 edges over
-// the group's lanes; 20 is the 802.16 5/6 codes' degree and keeps their lanes at 10 edges, not 16).  fixed_index numbers them for the context's record of raised LDS limits.
-using FixedFn = void (*)(BplqArgs);
-using FixedStreamFn = void (*)(BplqStreamArgs);
+// the group's lanes; 20 is the 802.16 5/6 codes' degree and keeps their lanes at 10 edges, not 16).
+struct FixedInst {
+  void (*batch)(BplqArgs);
+  void (*stream)(BplqStreamArgs);
+};
 
 constexpr int edges_per_lane(int dcmax, int g) { return (dcmax + g - 1) / g; }
 
-template <int G>
-FixedFn pick_fixed_g(int maxdc) {
-  if (maxdc <= 8) return k_bplq<G, edges_per_lane(8, G)>;
-  if (maxdc <= 16) return k_bplq<G, edges_per_lane(16, G)>;
-  if (maxdc <= 20) return k_bplq<G, edges_per_lane(20, G)>;
-  return k_bplq<G, edges_per_lane(32, G)>;
+template <int G, int DCMAX>
+FixedInst fixed_row() {
+  return {k_bplq<G, edges_per_lane(DCMAX, G)>, k_bplsq<G, edges_per_lane(DCMAX, G)>};
 }
 
 template <int G>
-FixedStreamFn pick_fixed_stream_g(int maxdc) {
-  if (maxdc <= 8) return k_bplsq<G, edges_per_lane(8, G)>;
-  if (maxdc <= 16) return k_bplsq<G, edges_per_lane(16, G)>;
-  if (maxdc <= 20) return k_bplsq<G, edges_per_lane(20, G)>;
-  return k_bplsq<G, edges_per_lane(32, G)>;
+FixedInst pick_fixed_g(int maxdc) {
+  if (maxdc <= 8) return fixed_row<G, 8>();
+  if (maxdc <= 16) return fixed_row<G, 16>();
+  if (maxdc <= 20) return fixed_row<G, 20>();
+  return fixed_row<G, 32>();
 }
 
-FixedFn pick_fixed(int lanes, int maxdc) {
+FixedInst pick_fixed(int lanes, int maxdc) {
   switch (lanes) {
     case 1: return pick_fixed_g<1>(maxdc);
     case 2: return pick_fixed_g<2>(maxdc);
@@ -1007,22 +981,6 @@ FixedFn pick_fixed(int lanes, int maxdc) {
     case 8: return pick_fixed_g<8>(maxdc);
     default: return pick_fixed_g<16>(maxdc);
   }
-}
-
-FixedStreamFn pick_fixed_stream(int lanes, int maxdc) {
-  switch (lanes) {
-    case 1: return pick_fixed_stream_g<1>(maxdc);
-    case 2: return pick_fixed_stream_g<2>(maxdc);
-    case 4: return pick_fixed_stream_g<4>(maxdc);
-    case 8: return pick_fixed_stream_g<8>(maxdc);
-    default: return pick_fixed_stream_g<16>(maxdc);
-  }
-}
-
-int fixed_index(int lanes, int maxdc) {
-  int lg = 0;
-  while ((1 << lg) < lanes) ++lg;
-  return lg * 4 + (maxdc <= 8 ? 0 : maxdc <= 16 ? 1 : maxdc <= 20 ? 2 : 3);
 }
 
 using TailFn = void (*)(TailArgs);
@@ -1134,41 +1092,103 @@ int ensure_slices(lb_ctx* c, int need) {
 
 int ensure_msg(lb_ctx* c, int B, bool tail) { return ensure_slices(c, tail ? 2 * B : (c->lds ? 0 : B)); }
 
-// the layered schedule: one launch, one workgroup per word, no tail (never waits)
-// The layered instance of a decoder type (algo without LB_F32) and precision on this context, and
-// its dynamic LDS bytes; raises the instance's LDS limit on first use.
-int layered_instance(lb_ctx* c, int algo, bool f32, LayeredFn* fn, size_t* shm) {
-  const int mode = f32 ? c->lmode32 : c->lmode;
-  const size_t el = f32 ? sizeof(float) : sizeof(double);
-  *fn = pick_layered(algo, c->maxdc, c->lfixed, mode, f32);
-  *shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
-  // measurement switch: more than half a CU's LDS, so that a binary32 workgroup has its CU alone
-  if (f32 && c->lone32) *shm = std::max(*shm, kLdsBytes / 2 + 64);
-  const unsigned bit = 1u << (algo - LB_LAYERED_SUMPROD2 + (f32 ? 2 : 0));
-  if (*shm && !(c->lattrs & bit)) {
-    // the whole budget, whatever this code needs: contexts of other codes share the instance
-    HIP_TRY(hipFuncSetAttribute((const void*)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
-    c->lattrs |= bit;
-  }
+// binary32 with app in HBM keeps it behind r in the word's slice of d_msg (Nmsg doubles)
+int f32_slice_fits(const lb_ctx* c, const DecType& t) {
+  if (t.f32 && c->lmode32 == 0 && c->Nv > c->Nmsg)
+    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
   return LB_OK;
 }
 
-int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, bool f32, double corr,
-                   int max_iter) {
-  const int mode = f32 ? c->lmode32 : c->lmode;
-  // binary32 with app in HBM keeps it behind r in the word's slice of d_msg (Nmsg doubles)
-  if (f32 && mode == 0 && c->Nv > c->Nmsg)
-    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
+// (lb::resolve, declared in ldpc_bp_int.h)
+int resolve(lb_ctx* c, int algo, double corr, int max_iter, bool for_stream, DecType* t) {
+  DecType d;
+  d.f32 = algo >= 0 && (algo & LB_F32);
+  d.fixed = algo >= 0 && (algo & LB_FIXED);
+  d.base = algo >= 0 ? algo & ~(LB_F32 | LB_FIXED) : algo;
+  if (d.base < LB_SUMPROD2 || d.base > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
+  const bool layered = d.base >= LB_LAYERED_SUMPROD2;
+  // LB_FIXED goes with layered min-sum alone
+  if (d.fixed && d.f32) return fail(LB_ERR_ARG, "LB_FIXED | LB_F32: the fixed-point decoder has no binary32 form");
+  if (d.fixed && d.base != LB_LAYERED_MINSUM)
+    return fail(LB_ERR_UNSUPPORTED, "fixed-point (LB_FIXED) exists for layered min-sum (LB_LAYERED_MINSUM) only");
+  if (d.f32 && !layered)
+    return fail(LB_ERR_UNSUPPORTED, "binary32 (LB_F32) exists for the layered decoder types only");
+  if (for_stream && !layered)
+    return fail(LB_ERR_UNSUPPORTED, "the block stream exists for the layered decoder types only");
+  if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
+  if (layered && !c->nlayers)
+    return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
+  if (d.fixed) {  // the kernel's parameters from the context's widths and corr_factor
+    const double alpha = nearbyint(16.0 * corr);  // half to even, as rint in the statement
+    if (!(alpha >= 1.0 && alpha <= 16.0))
+      return fail(LB_ERR_ARG, "fixed-point min-sum needs rint(16 corr_factor) in 1..16");
+    if (!c->qfit)
+      return fail(LB_ERR_UNSUPPORTED, "fixed-point decoder: the image (" + std::to_string(c->qlds) +
+                                          " bytes) does not fit a workgroup's LDS, and there is no HBM layout");
+    d.par = {c->qfrac, (1 << (c->qmsg - 1)) - 1, (1 << (c->qapp - 1)) - 1, (int)alpha};
+  }
   int rc;
-  if ((rc = ensure_slices(c, mode == 2 ? 0 : B))) return rc;
-  LayeredFn fn;
-  size_t shm;
-  if ((rc = layered_instance(c, algo, f32, &fn, &shm))) return rc;
+  if (for_stream && (rc = f32_slice_fits(c, d))) return rc;  // (lb::launch: once it has work)
+  d.hbm = layered && !d.fixed && (d.f32 ? c->lmode32 : c->lmode) < 2;
+  *t = d;
+  return LB_OK;
+}
+
+// Raise a kernel's dynamic LDS limit, once per context.  The layered instances ask for the whole
+// budget, whatever this code needs: contexts of other codes share the instance.
+int raise_lds(lb_ctx* c, const void* fn, size_t bytes = kLdsBytes - 64) {
+  if (std::find(c->raised.begin(), c->raised.end(), fn) != c->raised.end()) return LB_OK;
+  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  c->raised.push_back(fn);
+  return LB_OK;
+}
+
+// How a resolved layered type launches on this context: its batch / stream instance pair
+// (floating or fixed point), threads per workgroup and dynamic LDS bytes.
+struct LayeredShape {
+  LayeredInst fn{};
+  FixedInst qfn{};               // DecType::fixed
+  const void* kernel = nullptr;  // the one of the pair asked for
+  int nt = 0;
+  size_t shm = 0;
+};
+
+// stream: the persistent kernel of the pair.  Raises that kernel's LDS limit on first use.
+int layered_shape(lb_ctx* c, const DecType& t, bool stream, LayeredShape* s) {
+  if (t.fixed) {
+    s->qfn = pick_fixed(c->qlanes, c->maxdc);
+    s->kernel = stream ? (const void*)s->qfn.stream : (const void*)s->qfn.batch;
+    s->nt = c->qnt;
+    s->shm = (size_t)c->qlds;
+  } else {
+    const int mode = t.f32 ? c->lmode32 : c->lmode;
+    const size_t el = t.f32 ? sizeof(float) : sizeof(double);
+    s->fn = pick_layered(t.base, c->maxdc, c->lfixed, mode, t.f32);
+    s->kernel = stream ? (const void*)s->fn.stream : (const void*)s->fn.batch;
+    s->nt = c->lnt;
+    s->shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
+    // measurement switch: more than half a CU's LDS, so that a binary32 workgroup has its CU alone
+    if (t.f32 && c->lone32) s->shm = std::max(s->shm, kLdsBytes / 2 + 64);
+  }
+  return s->shm ? raise_lds(c, s->kernel) : LB_OK;
+}
+
+// workgroups of that kernel a CU holds at once
+int residency(lb_ctx* c, const DecType& t, bool stream, int* n, size_t* shm = nullptr) {
+  LayeredShape s;
+  int rc;
+  if ((rc = layered_shape(c, t, stream, &s))) return rc;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(n, s.kernel, s.nt, s.shm));
+  if (shm) *shm = s.shm;
+  return LB_OK;
+}
+
+BplArgs bpl_args(const lb_ctx* c, const double* ch, double* app, int* iters, double* gmsg, double corr, int max_iter) {
   BplArgs a;
-  a.ch = d_ch;
-  a.app = d_app;
-  a.iters = d_it;
-  a.gmsg = c->d_msg;
+  a.ch = ch;
+  a.app = app;
+  a.iters = iters;
+  a.gmsg = gmsg;
   a.evar = c->d_evar;
   a.cstart = c->d_cstart;
   a.lfirst = c->d_lfirst;
@@ -1178,34 +1198,29 @@ int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_i
   a.nlayers = c->nlayers;
   a.maxit = max_iter;
   a.corr = corr;
-  hipLaunchKernelGGL(fn, dim3(B), dim3(c->lnt), shm, c->stream, a);
+  return a;
+}
+
+// the layered schedule: one launch, one workgroup per word, no tail (never waits)
+int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const DecType& t, double corr,
+                   int max_iter) {
+  int rc;
+  if ((rc = f32_slice_fits(c, t))) return rc;
+  if ((rc = ensure_slices(c, t.hbm ? B : 0))) return rc;
+  LayeredShape s;
+  if ((rc = layered_shape(c, t, false, &s))) return rc;
+  if (t.fixed) {  // (gmsg and corr unused)
+    const BplqArgs q{bpl_args(c, d_ch, d_app, d_it, nullptr, 0.0, max_iter), t.par};
+    hipLaunchKernelGGL(s.qfn.batch, dim3(B), dim3(s.nt), s.shm, c->stream, q);
+  } else {
+    const BplArgs a = bpl_args(c, d_ch, d_app, d_it, c->d_msg, corr, max_iter);
+    hipLaunchKernelGGL(s.fn.batch, dim3(B), dim3(s.nt), s.shm, c->stream, a);
+  }
   HIP_TRY(hipGetLastError());
   return LB_OK;
 }
 
-// ---- fixed point (LB_FIXED) ----
-// LB_FIXED goes with layered min-sum alone (algo without its flags)
-int fixed_type(int algo, bool f32) {
-  if (f32) return fail(LB_ERR_ARG, "LB_FIXED | LB_F32: the fixed-point decoder has no binary32 form");
-  if (algo != LB_LAYERED_MINSUM)
-    return fail(LB_ERR_UNSUPPORTED, "fixed-point (LB_FIXED) exists for layered min-sum (LB_LAYERED_MINSUM) only");
-  return LB_OK;
-}
-
-// the kernel's parameters from the context's widths and corr_factor; the context has layers
-int fixed_par(lb_ctx* c, double corr, FixedPar* p) {
-  const double alpha = nearbyint(16.0 * corr);  // half to even, as rint in the statement
-  if (!(alpha >= 1.0 && alpha <= 16.0))
-    return fail(LB_ERR_ARG, "fixed-point min-sum needs rint(16 corr_factor) in 1..16");
-  if (!c->qfit)
-    return fail(LB_ERR_UNSUPPORTED, "fixed-point decoder: the image (" + std::to_string(c->qlds) +
-                                        " bytes) does not fit a workgroup's LDS, and there is no HBM layout");
-  p->frac = c->qfrac;
-  p->rmax = (1 << (c->qmsg - 1)) - 1;
-  p->amax = (1 << (c->qapp - 1)) - 1;
-  p->alpha = (int)alpha;
-  return LB_OK;
-}
+// ---- fixed point ----
 
 // threads per workgroup, lanes per check and LDS bytes of the fixed-point decoder (lb_set_layers,
 // lb_set_fixed).  Lanes: the largest power of two, at most the largest check degree and 16, at which
@@ -1232,126 +1247,38 @@ void plan_fixed(lb_ctx* c) {
   c->qlds = (int)std::min<long long>(bytes, INT32_MAX);
 }
 
-int raise_lds(const void* fn, unsigned long long* done, int index) {
-  if (*done & (1ull << index)) return LB_OK;
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
-  *done |= 1ull << index;
-  return LB_OK;
-}
-
-int launch_fixed(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const FixedPar& p, int max_iter) {
-  const FixedFn fn = pick_fixed(c->qlanes, c->maxdc);
-  int rc;
-  if ((rc = raise_lds((const void*)fn, &c->qattrs, fixed_index(c->qlanes, c->maxdc)))) return rc;
-  BplqArgs a;
-  a.w.ch = d_ch;
-  a.w.app = d_app;
-  a.w.iters = d_it;
-  a.w.gmsg = nullptr;
-  a.w.evar = c->d_evar;
-  a.w.cstart = c->d_cstart;
-  a.w.lfirst = c->d_lfirst;
-  a.w.Nv = c->Nv;
-  a.w.Nc = c->Nc;
-  a.w.Nmsg = c->Nmsg;
-  a.w.nlayers = c->nlayers;
-  a.w.maxit = max_iter;
-  a.w.corr = 0.0;
-  a.p = p;
-  hipLaunchKernelGGL(fn, dim3(B), dim3(c->qnt), (size_t)c->qlds, c->stream, a);
-  HIP_TRY(hipGetLastError());
-  return LB_OK;
-}
-
-// layered_instance for the persistent kernels (lattrs bits 4..7)
-int stream_instance(lb_ctx* c, int algo, bool f32, StreamFn* fn, size_t* shm) {
-  const int mode = f32 ? c->lmode32 : c->lmode;
-  const size_t el = f32 ? sizeof(float) : sizeof(double);
-  *fn = pick_stream(algo, c->maxdc, c->lfixed, mode, f32);
-  *shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
-  if (f32 && c->lone32) *shm = std::max(*shm, kLdsBytes / 2 + 64);
-  const unsigned bit = 16u << (algo - LB_LAYERED_SUMPROD2 + (f32 ? 2 : 0));
-  if (*shm && !(c->lattrs & bit)) {
-    HIP_TRY(hipFuncSetAttribute((const void*)*fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - 64)));
-    c->lattrs |= bit;
-  }
-  return LB_OK;
-}
-
 // (lb::stream_plan, declared in ldpc_bp_int.h)
-int stream_plan(lb_ctx* c, int algo, double corr, int max_iter, int* resident) {
-  const bool f32 = algo >= 0 && (algo & LB_F32), fixed = algo >= 0 && (algo & LB_FIXED);
-  if (algo >= 0) algo &= ~(LB_F32 | LB_FIXED);
-  if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
-  int rc;
-  if (fixed && (rc = fixed_type(algo, f32))) return rc;
-  if (algo < LB_LAYERED_SUMPROD2)
-    return fail(LB_ERR_UNSUPPORTED, "the block stream exists for the layered decoder types only");
-  if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
-  if (!c->nlayers) return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
-  FixedPar par;
-  if (fixed && (rc = fixed_par(c, corr, &par))) return rc;
-  if (f32 && c->lmode32 == 0 && c->Nv > c->Nmsg)
-    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
-  if (!resident) return LB_OK;
+int stream_plan(lb_ctx* c, const DecType& t, int* resident) {
   HIP_TRY(hipSetDevice(c->dev));
-  int n = 0;
-  if (fixed) {
-    const FixedStreamFn fn = pick_fixed_stream(c->qlanes, c->maxdc);
-    if ((rc = raise_lds((const void*)fn, &c->qattrs, 20 + fixed_index(c->qlanes, c->maxdc)))) return rc;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->qnt, (size_t)c->qlds));
-  } else {
-    StreamFn fn;
-    size_t shm;
-    if ((rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
-  }
+  int rc, n = 0;
+  if ((rc = residency(c, t, true, &n))) return rc;
   *resident = std::max(1, n);
   return LB_OK;
 }
 
-// (lb::launch_stream, declared in ldpc_bp_int.h; the arguments have passed stream_plan)
-int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter) {
-  const bool f32 = (algo & LB_F32) != 0, fixed = (algo & LB_FIXED) != 0;
-  algo &= ~(LB_F32 | LB_FIXED);
-  StreamFn fn = nullptr;
-  size_t shm = 0;
+// (lb::launch_stream, declared in ldpc_bp_int.h)
+int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, const DecType& t, double corr,
+                  int max_iter) {
+  LayeredShape s;
   int rc;
-  if (!fixed && (rc = stream_instance(c, algo, f32, &fn, &shm))) return rc;
-  BplStreamArgs s;
-  s.w.ch = k.ch;
-  s.w.app = k.app;
-  s.w.iters = k.slot_iters;
-  s.w.gmsg = k.msg;
-  s.w.evar = c->d_evar;
-  s.w.cstart = c->d_cstart;
-  s.w.lfirst = c->d_lfirst;
-  s.w.Nv = c->Nv;
-  s.w.Nc = c->Nc;
-  s.w.Nmsg = c->Nmsg;
-  s.w.nlayers = c->nlayers;
-  s.w.maxit = max_iter;
-  s.w.corr = corr;
-  s.x = k.x;
-  s.errs = k.errs;
-  s.iters = k.iters;
-  s.ticket = k.ticket;
-  s.eprev = k.eprev;
-  s.ecur = k.ecur;
-  s.chunk = k.chunk;
-  s.base = k.base;
-  s.min_errors = k.min_errors;
-  if (fixed) {
-    BplqStreamArgs q;
-    q.s = s;
-    if ((rc = fixed_par(c, corr, &q.p))) return rc;
-    const FixedStreamFn qfn = pick_fixed_stream(c->qlanes, c->maxdc);
-    if ((rc = raise_lds((const void*)qfn, &c->qattrs, 20 + fixed_index(c->qlanes, c->maxdc)))) return rc;
-    hipLaunchKernelGGL(qfn, dim3(slots), dim3(c->qnt), (size_t)c->qlds, st, q);
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
+  if ((rc = layered_shape(c, t, true, &s))) return rc;
+  BplStreamArgs a;
+  a.w = bpl_args(c, k.ch, k.app, k.slot_iters, k.msg, corr, max_iter);
+  a.x = k.x;
+  a.errs = k.errs;
+  a.iters = k.iters;
+  a.ticket = k.ticket;
+  a.eprev = k.eprev;
+  a.ecur = k.ecur;
+  a.chunk = k.chunk;
+  a.base = k.base;
+  a.min_errors = k.min_errors;
+  if (t.fixed) {
+    const BplqStreamArgs q{a, t.par};
+    hipLaunchKernelGGL(s.qfn.stream, dim3(slots), dim3(s.nt), s.shm, st, q);
+  } else {
+    hipLaunchKernelGGL(s.fn.stream, dim3(slots), dim3(s.nt), s.shm, st, a);
   }
-  hipLaunchKernelGGL(fn, dim3(slots), dim3(c->lnt), shm, st, s);
   HIP_TRY(hipGetLastError());
   return LB_OK;
 }
@@ -1382,43 +1309,20 @@ int ensure_tail(lb_ctx* c, int B) {
 }
 
 int set_attrs(lb_ctx* c) {
-  if (c->attrs_set || !c->lds) return LB_OK;
+  if (!c->lds) return LB_OK;
   const size_t bytes = (size_t)c->Nmsg * sizeof(double);
+  int rc;
   for (int algo = 0; algo < 3; ++algo)
-    HIP_TRY(hipFuncSetAttribute((const void*)pick_kernel(algo, c->maxdc, true, c->fixed),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  c->attrs_set = true;
+    if ((rc = raise_lds(c, (const void*)pick_kernel(algo, c->maxdc, true, c->fixed), bytes))) return rc;
   return LB_OK;
 }
 
-// (lb::launch, declared in ldpc_bp_int.h)
-// sized_on_host: the tail's shape from the number of words still running
-// (one read-back; the caller blocks anyway), else sized on the device and
-// queued without waiting (see TailArgs)
-int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
-           int max_iter, bool sized_on_host) {
-  const bool f32 = algo >= 0 && (algo & LB_F32), fixed = algo >= 0 && (algo & LB_FIXED);
-  if (algo >= 0) algo &= ~(LB_F32 | LB_FIXED);
-  if (algo < LB_SUMPROD2 || algo > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
-  int rcq;
-  if (fixed && (rcq = fixed_type(algo, f32))) return rcq;
-  if (f32 && algo < LB_LAYERED_SUMPROD2)
-    return fail(LB_ERR_UNSUPPORTED, "binary32 (LB_F32) exists for the layered decoder types only");
-  if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
-  if (algo >= LB_LAYERED_SUMPROD2 && !c->nlayers)
-    return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
-  FixedPar par;
-  if (fixed && (rcq = fixed_par(c, corr, &par))) return rcq;
-  if (B == 0) return LB_OK;
-  if (max_iter == 0) {
-    // no iteration: the variable phase on zero messages, app = ch (the uncoded
-    // hard decision), 0 iterations; k_bp would leave app unwritten
-    HIP_TRY(hipMemcpyAsync(d_app, d_ch, (size_t)B * c->Nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
-    return LB_OK;
-  }
-  if (fixed) return launch_fixed(c, B, d_ch, d_app, d_it, par, max_iter);
-  if (algo >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, algo, f32, corr, max_iter);
+int launch_tail(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr, int max_iter,
+                bool sized_on_host);
+
+// the flooding schedule's first phase: all of max_iter in one launch, or the iterations before the tail
+int launch_flooding(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
+                    int max_iter, bool sized_on_host) {
   // the tail's variable kernel puts the words on the grid's y dimension (<= 65535)
   const bool tail = c->tail_at > 0 && max_iter > c->tail_at && B <= 65535;
   int rc;
@@ -1455,8 +1359,14 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
   const size_t shm = c->lds ? (size_t)c->Nmsg * sizeof(double) : 0;
   hipLaunchKernelGGL(pick_kernel(algo, c->maxdc, c->lds, c->fixed), dim3(B), dim3(c->nt), shm, c->stream, a);
   HIP_TRY(hipGetLastError());
-  if (!tail) return LB_OK;
+  return tail ? launch_tail(c, B, d_ch, d_app, d_it, algo, corr, max_iter, sized_on_host) : LB_OK;
+}
 
+// The tail launches (k_bp_tail) from iteration tail_at on, over the words that phase one left
+// running.  sized_on_host: the tail's shape from the number of those words (one read-back; the
+// caller blocks anyway), else sized on the device and queued without waiting (see TailArgs)
+int launch_tail(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr, int max_iter,
+                bool sized_on_host) {
   int n = B;
   if (sized_on_host) {
     // how many words are left decides the tail's shape (one 4-byte read-back)
@@ -1477,11 +1387,11 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
   // cover the SIMDs once: S = ceil(Nc / 64m) workgroups per word
   // the straight-line check rule runs on lane pairs (32 checks per wave)
   const bool split = c->fixed && algo != LB_SUMPROD;
-  const long waves = (long)nsz * ((c->Nc + (split ? 31 : 63)) / (split ? 32 : 64));
-  const int mmax = c->fixed && algo != LB_SUMPROD ? kTailFixThreads / 64 : kTailThreads / 64;
+  const int cpt = split ? 32 : 64;  // checks per wave
+  const long waves = (long)nsz * ((c->Nc + cpt - 1) / cpt);
+  const int mmax = (split ? kTailFixThreads : kTailThreads) / 64;
   int m = (int)((waves + 4L * c->ncu - 1) / (4L * c->ncu));
   m = m < 1 ? 1 : (m > mmax ? mmax : m);
-  const int cpt = split ? 32 : 64;  // checks per wave
   const int S = (c->Nc + cpt * m - 1) / (cpt * m);
   TailArgs t;
   t.ch = d_ch;
@@ -1509,15 +1419,16 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
   const TailFn var = pick_tail_var(c->nq);
   const dim3 vgrid((c->Nv + 255) / 256, nsz);
   const dim3 cgrid((unsigned)nsz * S);
+  auto iterate = [&](int it) {
+    t.rold = slot[(it - c->tail_at) & 1];
+    t.rnew = slot[(it - c->tail_at + 1) & 1];
+    t.it = it;
+    hipLaunchKernelGGL(var, vgrid, dim3(256), 0, c->stream, t);
+    hipLaunchKernelGGL(chk, cgrid, dim3(64 * m), 0, c->stream, t);
+  };
   if (!sized_on_host) {
     // every iteration queued; a launch past the last running word returns at once
-    for (int it = c->tail_at; it < max_iter; ++it) {
-      t.rold = slot[(it - c->tail_at) & 1];
-      t.rnew = slot[(it - c->tail_at + 1) & 1];
-      t.it = it;
-      hipLaunchKernelGGL(var, vgrid, dim3(256), 0, c->stream, t);
-      hipLaunchKernelGGL(chk, cgrid, dim3(64 * m), 0, c->stream, t);
-    }
+    for (int it = c->tail_at; it < max_iter; ++it) iterate(it);
     // this tail's word count, for the next one's estimate (read when it has landed)
     HIP_TRY(hipMemcpyAsync(c->h_nact + 3, c->d_nact, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(c->evn, c->stream));
@@ -1533,13 +1444,7 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
         HIP_TRY(hipEventSynchronize(c->evc[k & 1]));
         if (c->h_nact[1 + (k & 1)] >= n) break;
       }
-      for (int it = it0; it < std::min(max_iter, it0 + kTailChunk); ++it) {
-        t.rold = slot[(it - c->tail_at) & 1];
-        t.rnew = slot[(it - c->tail_at + 1) & 1];
-        t.it = it;
-        hipLaunchKernelGGL(var, vgrid, dim3(256), 0, c->stream, t);
-        hipLaunchKernelGGL(chk, cgrid, dim3(64 * m), 0, c->stream, t);
-      }
+      for (int it = it0; it < std::min(max_iter, it0 + kTailChunk); ++it) iterate(it);
       HIP_TRY(hipMemcpyAsync(c->h_nact + 1 + (k & 1), c->d_nact + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipEventRecord(c->evc[k & 1], c->stream));
     }
@@ -1548,6 +1453,21 @@ int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int a
                      c->d_done, c->d_lastbad, B, max_iter);
   HIP_TRY(hipGetLastError());
   return LB_OK;
+}
+
+// (lb::launch, declared in ldpc_bp_int.h)
+int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const DecType& t, double corr,
+           int max_iter, bool sized_on_host) {
+  if (B == 0) return LB_OK;
+  if (max_iter == 0) {
+    // no iteration: the variable phase on zero messages, app = ch (the uncoded
+    // hard decision), 0 iterations; k_bp would leave app unwritten
+    HIP_TRY(hipMemcpyAsync(d_app, d_ch, (size_t)B * c->Nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_it, 0, (size_t)B * sizeof(int), c->stream));
+    return LB_OK;
+  }
+  if (t.base >= LB_LAYERED_SUMPROD2) return launch_layered(c, B, d_ch, d_app, d_it, t, corr, max_iter);
+  return launch_flooding(c, B, d_ch, d_app, d_it, t.base, corr, max_iter, sized_on_host);
 }
 
 }  // namespace lb
@@ -1731,12 +1651,14 @@ int lb_decode(lb_ctx* c, int B, const double* ch, double* app, int* iters, int a
   if (!c) return fail(LB_ERR_ARG, "null context");
   if (B < 0 || (B > 0 && (!ch || !app || !iters))) return fail(LB_ERR_ARG, "bad batch arguments");
   if (B == 0) return LB_OK;
-  HIP_TRY(hipSetDevice(c->dev));
+  DecType t;
   int rc;
+  if ((rc = resolve(c, algo, corr_factor, max_iter, false, &t))) return rc;
+  HIP_TRY(hipSetDevice(c->dev));
   if ((rc = ensure_io(c, B))) return rc;
   const size_t bytes = (size_t)B * c->Nv * sizeof(double);
   HIP_TRY(hipMemcpyAsync(c->d_ch, ch, bytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr_factor, max_iter, true))) return rc;
+  if ((rc = launch(c, B, c->d_ch, c->d_app, c->d_it, t, corr_factor, max_iter, true))) return rc;
   HIP_TRY(hipMemcpyAsync(app, c->d_app, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(iters, c->d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1747,8 +1669,11 @@ int lb_decode_device(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d
                      double corr_factor, int max_iter) {
   if (!c) return fail(LB_ERR_ARG, "null context");
   if (B < 0 || (B > 0 && (!d_ch || !d_app || !d_iters))) return fail(LB_ERR_ARG, "bad batch arguments");
+  DecType t;
+  int rc;
+  if ((rc = resolve(c, algo, corr_factor, max_iter, false, &t))) return rc;
   HIP_TRY(hipSetDevice(c->dev));
-  return launch(c, B, d_ch, d_app, d_iters, algo, corr_factor, max_iter, false);
+  return launch(c, B, d_ch, d_app, d_iters, t, corr_factor, max_iter, false);
 }
 
 int lb_buffers(lb_ctx* c, int B, double** d_ch, double** d_app, int** d_iters) {
@@ -1774,10 +1699,12 @@ int lb_stage(lb_ctx* c, int B, const double* ch) {
 
 int lb_run(lb_ctx* c, int B, int algo, double corr_factor, int max_iter) {
   if (!c || B <= 0 || B > c->capB) return fail(LB_ERR_ARG, "run before stage, or B larger than staged");
+  DecType t;
+  int rc;
+  if ((rc = resolve(c, algo, corr_factor, max_iter, false, &t))) return rc;
   HIP_TRY(hipSetDevice(c->dev));
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  int rc = launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr_factor, max_iter, false);
-  if (rc) return rc;
+  if ((rc = launch(c, B, c->d_ch, c->d_app, c->d_it, t, corr_factor, max_iter, false))) return rc;
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   return LB_OK;
 }
@@ -1866,7 +1793,7 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   c->maxlayer = maxlayer;
   const size_t app_bytes = (size_t)c->Nv * sizeof(double), r_bytes = (size_t)c->Nmsg * sizeof(double);
   c->lmode = app_bytes + r_bytes <= kLdsBytes - 64 ? 2 : (app_bytes <= kLdsBytes - 64 ? 1 : 0);
-  // binary32 (LB_F32): the same choice at the element size 4
+  // binary32: the same choice at the element size 4
   const size_t app32 = (size_t)c->Nv * sizeof(float), r32 = (size_t)c->Nmsg * sizeof(float);
   c->lmode32 = app32 + r32 <= kLdsBytes - 64 ? 2 : (app32 <= kLdsBytes - 64 ? 1 : 0);
   // measurement and test switches: LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app out of LDS
@@ -1888,7 +1815,7 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   // against the two that share a CU at 802.16 5/6 z=192
   if (const char* e = getenv("LDPC_BP_LAYERED_F32_RESIDENT"); e && *e) c->lone32 = atoi(e) == 1;
   else c->lone32 = false;
-  c->lattrs = 0;
+  c->raised.clear();
   plan_fixed(c);
   return LB_OK;
 }
@@ -1917,10 +1844,11 @@ int lb_fixed_info(lb_ctx* c, long long* out) {
   out[7] = c->qfit ? 1 : 0;
   if (!c->qfit) return LB_OK;
   HIP_TRY(hipSetDevice(c->dev));
-  const FixedFn fn = pick_fixed(c->qlanes, c->maxdc);
+  DecType t;
+  t.base = LB_LAYERED_MINSUM;
+  t.fixed = true;
   int rc, n = 0;
-  if ((rc = raise_lds((const void*)fn, &c->qattrs, fixed_index(c->qlanes, c->maxdc)))) return rc;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->qnt, (size_t)c->qlds));
+  if ((rc = residency(c, t, false, &n))) return rc;
   out[6] = n;
   return LB_OK;
 }
@@ -1946,11 +1874,12 @@ int lb_layer_info_ex(lb_ctx* c, int precision, long long* out) {
   if (!c->nlayers) return LB_OK;
   HIP_TRY(hipSetDevice(c->dev));
   for (int k = 0; k < 2; ++k) {  // the sumprod2 and the minsum instance
-    LayeredFn fn;
+    DecType t;
+    t.base = LB_LAYERED_SUMPROD2 + k;
+    t.f32 = f32;
     size_t shm;
     int rc, n = 0;
-    if ((rc = layered_instance(c, LB_LAYERED_SUMPROD2 + k, f32, &fn, &shm))) return rc;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, c->lnt, shm));
+    if ((rc = residency(c, t, false, &n, &shm))) return rc;
     out[4] = (long long)shm;
     out[5 + k] = n;
   }

@@ -38,7 +38,6 @@ struct lb_ctx {
   int capB = 0, capMsgB = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool attrs_set = false;
   // layered schedule (k_bpl), set by lb_set_layers: the layers' first checks on
   // the device, where the messages live (2: r + app in LDS, 1: app in LDS,
   // 0: HBM), threads per workgroup; host copies of the edge tables for its checks
@@ -48,14 +47,12 @@ struct lb_ctx {
   int lmode32 = 0;            // lmode of the binary32 instances (LB_F32): the same choice at 4 bytes a message
   bool lfixed = false;
   bool lone32 = false;        // LDPC_BP_LAYERED_F32_RESIDENT = 1: binary32 workgroups padded to one per CU
-  unsigned lattrs = 0;        // layered instances whose dynamic LDS size has been raised (bit per algorithm
-                              // and precision)
+  std::vector<const void*> raised;  // kernel instances whose dynamic LDS limit this context has raised
   // fixed-point layered min-sum (k_bplq), lb_set_fixed: the widths; the plan made by lb_set_layers /
   // lb_set_fixed: threads per workgroup, lanes per check, dynamic LDS bytes, whether the image fits
   int qfrac = 2, qmsg = 6, qapp = 8;
   int qnt = 0, qlanes = 0, qlds = 0;
   bool qfit = false;
-  unsigned long long qattrs = 0;  // fixed-point instances whose dynamic LDS size has been raised
   lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
 };
 
@@ -67,8 +64,24 @@ int fail(int code, const std::string& msg);
 int dev_alloc(void** p, size_t bytes);
 // the context's ch / app / iters buffers sized for B words
 int ensure_io(lb_ctx* c, int B);
+// the fixed-point kernels' parameters: fraction bits, the clips of r and app, 16 corr_factor
+struct FixedPar {
+  int frac, rmax, amax, alpha;
+};
+// A decoder type (`algo` of the C ABI: one of the five LB_* numbers, with LB_F32 or LB_FIXED) as
+// lb::resolve found it on a context; what launch, stream_plan and launch_stream take.
+struct DecType {
+  int base = 0;   // LB_SUMPROD2 .. LB_LAYERED_MINSUM
+  bool f32 = false, fixed = false;
+  bool hbm = false;  // a layered type that keeps each word's messages in a slice of HBM (lmode < 2)
+  FixedPar par{};    // fixed
+};
+// Fill `t`, or refuse algo / corr / max_iter on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED): every
+// refusal of a decoder type is here.  for_stream: the block stream, which has the layered types only
+// and refuses up front what the batch path refuses once it has work (lb::launch).
+int resolve(lb_ctx* c, int algo, double corr, int max_iter, bool for_stream, DecType* t);
 // queue a decode of B words on the context's stream; sized_on_host = false never waits
-int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, int algo, double corr,
+int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const DecType& t, double corr,
            int max_iter, bool sized_on_host);
 // One chunk of lb_mc_stream_seeds for the persistent layered kernels (k_bpls,
 // k_bpls32, k_bplsq in ldpc_bp.hip): a grid of `slots` workgroups takes the chunk's
@@ -86,11 +99,11 @@ struct StreamChunk {
   int* ecur;          // zeroed: block errors of this chunk
   int chunk, base, min_errors;
 };
-// Whether algo / corr / max_iter can stream on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED; nothing is
-// changed then); resident (may be null): workgroups of the instance a CU holds at once
-int stream_plan(lb_ctx* c, int algo, double corr, int max_iter, int* resident);
+// resident: workgroups of the type's persistent instance a CU holds at once (t resolved for_stream)
+int stream_plan(lb_ctx* c, const DecType& t, int* resident);
 // queue one chunk on `st`; never waits
-int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, int algo, double corr, int max_iter);
+int launch_stream(lb_ctx* c, hipStream_t st, int slots, const StreamChunk& k, const DecType& t, double corr,
+                  int max_iter);
 // free the Monte-Carlo state of a context (ldpc_mc.hip)
 void mc_release(lb_ctx* c);
 

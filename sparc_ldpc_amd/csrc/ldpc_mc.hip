@@ -516,9 +516,11 @@ int lb_mc_run(lb_ctx* c, int nblk, const uint8_t* u, const double* w, double a, 
   if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_run: the BSC sends the all-zero word (u must be null)");
   if (enc && (!c->mc || c->mc->Mp == 0)) return fail(LB_ERR_ARG, "lb_mc_run: no encoder set (lb_mc_set_code)");
   if (nblk == 0) return LB_OK;
+  lb::DecType t;
+  int rc;
+  if ((rc = lb::resolve(c, algo, corr, max_iter, false, &t))) return rc;
   batch = std::min(batch, nblk);
   HIP_TRY(hipSetDevice(c->dev));
-  int rc;
   if ((rc = ensure_state(c))) return rc;
   if ((rc = lb::ensure_io(c, batch))) return rc;
   if ((rc = ensure_staging(c, batch))) return rc;
@@ -559,7 +561,7 @@ int lb_mc_run(lb_ctx* c, int nblk, const uint8_t* u, const double* w, double a, 
     hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), c->stream, p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(m->ev_prep[i], c->stream));
-    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr, max_iter, false))) return rc;
+    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, t, corr, max_iter, false))) return rc;
     hipLaunchKernelGGL(k_mc_count, dim3(B), dim3(kCountThreads), 0, c->stream, c->d_app, m->d_x, c->d_it, (int)N,
                        m->d_res + b0, m->d_res + nblk + b0);
     HIP_TRY(hipGetLastError());
@@ -573,22 +575,30 @@ int lb_mc_run(lb_ctx* c, int nblk, const uint8_t* u, const double* w, double a, 
   return LB_OK;
 }
 
+// the argument checks of the seeded entries (`who`), in their order; per: the batch or the chunk,
+// ptrs: the entry's own pointers are there
+static int check_seeded(const std::string& who, lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a, int kind,
+                        int per, const int* errs, const int* iters, bool ptrs = true) {
+  if (!c) return fail(LB_ERR_ARG, who + ": null context");
+  if (nblk < 0 || per <= 0 || (kind != 0 && kind != 1) || !ptrs || (nblk > 0 && (!seeds || !errs || !iters)))
+    return fail(LB_ERR_ARG, who + ": bad arguments");
+  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0)) return fail(LB_ERR_ARG, who + ": sigma must be > 0, p in (0, 1)");
+  if (K != 0 && K != c->Nv - c->Nc) return fail(LB_ERR_ARG, who + ": K must be Nv - Nc, or 0 for no bits");
+  if (K > 0 && kind == 1) return fail(LB_ERR_ARG, who + ": the BSC sends the all-zero word (K must be 0)");
+  if (K > 0 && (!c->mc || c->mc->Mp == 0)) return fail(LB_ERR_ARG, who + ": no encoder set (lb_mc_set_code)");
+  return LB_OK;
+}
+
 int lb_mc_run_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a, int kind, int batch, int algo,
                     double corr, int max_iter, int* errs, int* iters) {
-  if (!c) return fail(LB_ERR_ARG, "lb_mc_run_seeds: null context");
-  if (nblk < 0 || batch <= 0 || (kind != 0 && kind != 1) || (nblk > 0 && (!seeds || !errs || !iters)))
-    return fail(LB_ERR_ARG, "lb_mc_run_seeds: bad arguments");
-  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0))
-    return fail(LB_ERR_ARG, "lb_mc_run_seeds: sigma must be > 0, p in (0, 1)");
-  if (K != 0 && K != c->Nv - c->Nc) return fail(LB_ERR_ARG, "lb_mc_run_seeds: K must be Nv - Nc, or 0 for no bits");
+  int rc;
+  if ((rc = check_seeded("lb_mc_run_seeds", c, nblk, seeds, K, a, kind, batch, errs, iters))) return rc;
   const bool enc = K > 0;
-  if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_run_seeds: the BSC sends the all-zero word (K must be 0)");
-  if (enc && (!c->mc || c->mc->Mp == 0))
-    return fail(LB_ERR_ARG, "lb_mc_run_seeds: no encoder set (lb_mc_set_code)");
   if (nblk == 0) return LB_OK;
+  lb::DecType t;
+  if ((rc = lb::resolve(c, algo, corr, max_iter, false, &t))) return rc;
   batch = std::min(batch, nblk);
   HIP_TRY(hipSetDevice(c->dev));
-  int rc;
   if ((rc = ensure_state(c))) return rc;
   if ((rc = lb::ensure_io(c, batch))) return rc;
   if ((rc = ensure_staging(c, batch, false))) return rc;
@@ -617,7 +627,7 @@ int lb_mc_run_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a,
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_mc_prep, dim3(B), dim3(kPrepThreads), prep_lds(p), c->stream, p);
     HIP_TRY(hipGetLastError());
-    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, algo, corr, max_iter, false))) return rc;
+    if ((rc = lb::launch(c, B, c->d_ch, c->d_app, c->d_it, t, corr, max_iter, false))) return rc;
     hipLaunchKernelGGL(k_mc_count, dim3(B), dim3(kCountThreads), 0, c->stream, c->d_app, m->d_x, c->d_it, N,
                        m->d_res + b0, m->d_res + nblk + b0);
     HIP_TRY(hipGetLastError());
@@ -635,31 +645,22 @@ int lb_mc_run_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a,
 
 int lb_mc_stream_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double a, int kind, int chunk, int slots,
                        int min_errors, int algo, double corr, int max_iter, int* errs, int* iters, long long* out) {
-  if (!c) return fail(LB_ERR_ARG, "lb_mc_stream_seeds: null context");
-  if (nblk < 0 || chunk <= 0 || (kind != 0 && kind != 1) || !out || (nblk > 0 && (!seeds || !errs || !iters)))
-    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: bad arguments");
-  if (kind == 0 ? !(a > 0.0) : !(a > 0.0 && a < 1.0))
-    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: sigma must be > 0, p in (0, 1)");
-  if (K != 0 && K != c->Nv - c->Nc)
-    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: K must be Nv - Nc, or 0 for no bits");
-  const bool enc = K > 0;
-  if (enc && kind == 1) return fail(LB_ERR_ARG, "lb_mc_stream_seeds: the BSC sends the all-zero word (K must be 0)");
-  if (enc && (!c->mc || c->mc->Mp == 0))
-    return fail(LB_ERR_ARG, "lb_mc_stream_seeds: no encoder set (lb_mc_set_code)");
   int rc, resident = 1;
-  if ((rc = lb::stream_plan(c, algo, corr, max_iter, nullptr))) return rc;
+  if ((rc = check_seeded("lb_mc_stream_seeds", c, nblk, seeds, K, a, kind, chunk, errs, iters, out != nullptr)))
+    return rc;
+  const bool enc = K > 0;
+  lb::DecType t;
+  if ((rc = lb::resolve(c, algo, corr, max_iter, true, &t))) return rc;
   out[0] = out[1] = out[2] = out[3] = 0;
   if (nblk == 0) return LB_OK;
-  HIP_TRY(hipSetDevice(c->dev));
-  if ((rc = lb::stream_plan(c, algo, corr, max_iter, &resident))) return rc;
+  if ((rc = lb::stream_plan(c, t, &resident))) return rc;
   chunk = std::min(chunk, nblk);
   // a slot beyond the chunk's blocks would find no ticket
   slots = std::min(slots > 0 ? slots : resident * c->ncu, chunk);
   const int nchunks = (nblk + chunk - 1) / chunk;
   if ((rc = ensure_state(c))) return rc;
   if ((rc = ensure_staging(c, chunk, false))) return rc;
-  const bool f32 = (algo & LB_F32) != 0, fixed = (algo & LB_FIXED) != 0;  // (fixed point: no HBM messages)
-  if ((rc = ensure_stream(c, chunk, slots, nchunks, !fixed && (f32 ? c->lmode32 : c->lmode) < 2))) return rc;
+  if ((rc = ensure_stream(c, chunk, slots, nchunks, t.hbm))) return rc;
   lb_mc* m = c->mc;
   if ((rc = ensure_results(m, nblk))) return rc;
   if ((rc = ensure_seeds(m, nblk))) return rc;
@@ -724,7 +725,7 @@ int lb_mc_stream_seeds(lb_ctx* c, int nblk, const uint32_t* seeds, int K, double
     s.chunk = B;
     s.base = nerr;  // the block errors of chunks <= k - 2, all consumed above
     s.min_errors = min_errors;
-    if ((rc = lb::launch_stream(c, st[i], std::min(slots, B), s, algo, corr, max_iter))) return rc;
+    if ((rc = lb::launch_stream(c, st[i], std::min(slots, B), s, t, corr, max_iter))) return rc;
     HIP_TRY(hipMemcpyAsync(m->h_res + b0, m->d_res + b0, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st[i]));
     HIP_TRY(hipMemcpyAsync(m->h_res + nblk + b0, m->d_res + nblk + b0, (size_t)B * sizeof(int), hipMemcpyDeviceToHost,
                            st[i]));

@@ -451,6 +451,20 @@ class code:
                                             int(max_iter), errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
 
+    def _seeded(self, seeds, channel, dectype, quant):
+        """What mc_blocks_seeds and mc_stream_seeds start from: the decoder's
+        number, the seeds as uint32, K (ldpc_mc.info_bits; the encoder set where
+        bits are drawn) and the two result arrays."""
+        from .ldpc_mc import _seed_array, info_bits
+        algo = self._algo(dectype, quant)
+        if channel not in _CHANNELS:
+            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
+        seeds = _seed_array(seeds)
+        K = info_bits(self, channel)
+        if K:
+            self._set_encoder()
+        return algo, seeds, K, np.empty(len(seeds), dtype=np.intc), np.empty(len(seeds), dtype=np.intc)
+
     def mc_blocks_seeds(self, seeds, a, channel="awgn", batch=1024, dectype="sumprod2", corr_factor=0.7,
                         max_iter=MAX_ITCOUNT, quant=None):
         """mc_blocks on blocks drawn on the device from their seeds
@@ -458,21 +472,11 @@ class code:
         seeds go up.  The information bits are drawn where ldpc_mc.info_bits
         says the reference encodes, else the all-zero word is sent.  Returns
         int64 (bit_errors, iters) in seed order."""
-        from .ldpc_mc import _seed_array, info_bits
-        algo = self._algo(dectype, quant)
-        if channel not in _CHANNELS:
-            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
-        seeds = _seed_array(seeds)
-        B = len(seeds)
-        K = info_bits(self, channel)
-        if K:
-            self._set_encoder()
-        errs = np.empty(B, dtype=np.intc)
-        it = np.empty(B, dtype=np.intc)
-        _check(load_bp_library().lb_mc_run_seeds(self._context(), B, seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)),
-                                                  K, float(a), _CHANNELS[channel], int(batch), algo,
-                                                  float(corr_factor), int(max_iter), errs.ctypes.data_as(_IP),
-                                                  it.ctypes.data_as(_IP)))
+        algo, seeds, K, errs, it = self._seeded(seeds, channel, dectype, quant)
+        _check(load_bp_library().lb_mc_run_seeds(self._context(), len(seeds),
+                                                  seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), K, float(a),
+                                                  _CHANNELS[channel], int(batch), algo, float(corr_factor),
+                                                  int(max_iter), errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP)))
         return errs.astype(np.int64), it.astype(np.int64)
 
     def mc_stream_seeds(self, seeds, a, channel="awgn", chunk=STREAM_CHUNK, dectype="layered_sumprod2",
@@ -488,21 +492,12 @@ class code:
         = 0).  Returns int64 (bit_errors, iters) in seed order and info =
         dict(used: the blocks the rule consumes (all of them without a rule),
         decoded, slots, chunks)."""
-        from .ldpc_mc import _seed_array, info_bits
-        algo = self._algo(dectype, quant)  # (a flooding type: LdpcBpError -5 from the library)
-        if channel not in _CHANNELS:
-            raise ValueError(f"channel must be one of {sorted(_CHANNELS)}")
-        seeds = _seed_array(seeds)
-        B = len(seeds)
-        K = info_bits(self, channel)
-        if K:
-            self._set_encoder()
-        errs = np.empty(B, dtype=np.intc)
-        it = np.empty(B, dtype=np.intc)
+        # (a flooding type: LdpcBpError -5 from the library)
+        algo, seeds, K, errs, it = self._seeded(seeds, channel, dectype, quant)
         out = (ct.c_int64 * 4)()
         _check(_layered_entry("lb_mc_stream_seeds")(
-            self._context(), B, seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), K, float(a), _CHANNELS[channel],
-            int(chunk), int(slots), int(min_errors), algo, float(corr_factor), int(max_iter),
+            self._context(), len(seeds), seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), K, float(a),
+            _CHANNELS[channel], int(chunk), int(slots), int(min_errors), algo, float(corr_factor), int(max_iter),
             errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP), out))
         return errs.astype(np.int64), it.astype(np.int64), dict(zip(("used", "decoded", "slots", "chunks"), list(out)))
 

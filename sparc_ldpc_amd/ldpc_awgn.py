@@ -45,11 +45,7 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     decoder slots (ldpc_mc._mc_point); the same tuples.  quant (None, True or
     (frac_bits, msg_bits, app_bits), with dectype "layered_minsum"): the
     fixed-point decoder (ldpc.code)."""
-    ldpc_mc._check_draws(draws)
-    ldpc_mc._check_stream(stream, draws, dectype)
-    if dectype not in _ldpc._ALGOS:
-        raise NameError("Decoder type unknonwn")
-    _ldpc._quant_widths(quant, dectype)
+    ldpc_mc._check_request(draws, stream, dectype, quant)
     if rate not in _RATES:
         raise NameError("Rate unsupported")
     R = _RATES[rate]
@@ -60,10 +56,8 @@ def sim(standard, rate, z, ptype='A', N_MEASUREMENTS=24, C_AWGN_OFFSET=1.0, P_ST
     for datapoint in range(N_MEASUREMENTS):
         sigma2 = 1 / np.power(10, SNR / 10.0)
         r = ldpc_mc._mc_point(code, float(np.sqrt(sigma2)), "awgn", MIN_ERRORS, MAX_BLOCKS,
-                              seed0 + datapoint * 10_000_000, batch, draws=draws,
-                              **({} if dectype == "sumprod2" else {"dectype": dectype}),
-                              **({"stream": True} if stream else {}),
-                              **({} if quant is None else {"quant": quant}))
+                              seed0 + datapoint * 10_000_000, batch, dectype=dectype, draws=draws, stream=stream,
+                              quant=quant)
         nblocks = r["blocks"]
         output = (standard, rate, z, SNR, nblocks, r["block_errors"], nblocks * K, r["bit_errors"], r["iters_total"])
         res.append(output)

@@ -29,11 +29,7 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
     dectype): the blocks through refilled decoder slots (ldpc_mc.mc_ldpc); the
     same results.  quant (None, True or (frac_bits, msg_bits, app_bits), with
     dectype "layered_minsum"): the fixed-point decoder (ldpc.code)."""
-    ldpc_mc._check_draws(draws)
-    ldpc_mc._check_stream(stream, draws, dectype)
-    if dectype not in _ldpc._ALGOS:
-        raise NameError("Decoder type unknonwn")
-    _ldpc._quant_widths(quant, dectype)
+    ldpc_mc._check_request(draws, stream, dectype, quant)
     if rate not in _P0:
         raise NameError("Rate unsupported")
     p = _P0[rate]
@@ -43,11 +39,8 @@ def sim(standard, rate, z, ptype='A', *, repeats=100, seed0=0, draws="host", dec
     parray = np.linspace(p, 0.001, 10)
     for i, q in enumerate(parray):
         base = seed0 + i * 10_000_000
-        be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc",
-                                **({} if draws == "host" else {"draws": draws}),
-                                **({} if dectype == "sumprod2" else {"dectype": dectype}),
-                                **({"stream": True} if stream else {}),
-                                **({} if quant is None else {"quant": quant}))
+        be, _ = ldpc_mc.mc_ldpc(code, float(q), range(base, base + repeats), channel="bsc", dectype=dectype, draws=draws,
+                                stream=stream, quant=quant)
         errors = [int(b) / N for b in be]
         res.append(np.sum(errors) / repeats)
     return res, parray

@@ -53,25 +53,24 @@ _STANDARD = ("802.11n", "802.16")  # the codes the reference encodes (sparc_ldpc
 _RATES = {"1/2": .5, "2/3": 0.6667, "3/4": 0.75, "5/6": 0.83333, "0.45": 0.45}  # sparc_ldpc.py:1075-1086
 
 
-def _check_draws(draws) -> str:
+def _check_request(draws, stream, dectype, quant, world=1) -> bool:
+    """What every entry here checks of its keywords before any library call:
+    draws; stream=True (the blocks through refilled decoder slots,
+    code.mc_stream_seeds) goes with device draws, a layered decoder and one
+    rank; the decoder's name; quant (ldpc._quant_widths).  Returns ``stream``."""
     if draws not in ("host", "device"):
         raise ValueError('draws must be "host" or "device"')
-    return draws
-
-
-def _check_stream(stream, draws, dectype, world=1) -> bool:
-    """stream=True (the blocks through refilled decoder slots,
-    code.mc_stream_seeds) goes with device draws, a layered decoder and one
-    rank; checked before any library call."""
-    if not stream:
-        return False
-    if draws != "device":
-        raise ValueError('stream=True needs draws="device"')
-    if not str(dectype).startswith("layered_"):
-        raise ValueError("stream=True needs a layered dectype")
-    if world != 1:
-        raise ValueError("stream=True runs on one rank (world == 1)")
-    return True
+    if stream:
+        if draws != "device":
+            raise ValueError('stream=True needs draws="device"')
+        if not str(dectype).startswith("layered_"):
+            raise ValueError("stream=True needs a layered dectype")
+        if world != 1:
+            raise ValueError("stream=True runs on one rank (world == 1)")
+    if dectype not in _ldpc._ALGOS:
+        raise NameError("Decoder type unknonwn")
+    _ldpc._quant_widths(quant, dectype)
+    return bool(stream)
 
 
 def info_bits(code, channel="awgn") -> int:
@@ -80,15 +79,21 @@ def info_bits(code, channel="awgn") -> int:
     return code.K if channel == "awgn" and code.standard in _STANDARD else 0
 
 
+def _draw_arrays(seeds, K, N, channel):
+    """What the three draw functions start from: the channel checked, the seeds
+    as uint32, and u (B, K) uint8 (None when K == 0) and w (B, N) float64 to fill."""
+    if channel not in _ldpc._CHANNELS:
+        raise ValueError(f"channel must be one of {sorted(_ldpc._CHANNELS)}")
+    seeds = _seed_array(seeds)
+    K, N = int(K), int(N)
+    return seeds, K, N, (np.empty((len(seeds), K), dtype=np.uint8) if K else None), np.empty((len(seeds), N))
+
+
 def _draw_blocks(seeds, K, N, channel="awgn"):
     """The seed contract in NumPy: (u (B, K) uint8 or None when K == 0,
     w (B, N) float64) — randint(0, 2, K) then randn(N) ("awgn") or
     random_sample(N) ("bsc") of RandomState(s) per block."""
-    if channel not in _ldpc._CHANNELS:
-        raise ValueError(f"channel must be one of {sorted(_ldpc._CHANNELS)}")
-    seeds = _seed_array(seeds)
-    u = np.empty((len(seeds), K), dtype=np.uint8) if K else None
-    w = np.empty((len(seeds), N))
+    seeds, K, N, u, w = _draw_arrays(seeds, K, N, channel)
     for i, s in enumerate(seeds):
         rs = np.random.RandomState(int(s))
         if K:
@@ -101,12 +106,7 @@ def draw_blocks(seeds, K, N, channel="awgn", threads=None):
     """_draw_blocks, bit for bit, by libldpc_bp's native restatement of NumPy's
     legacy generator over at most draw_threads() host threads
     (lb_draw_blocks).  Needs no device; releases the GIL."""
-    if channel not in _ldpc._CHANNELS:
-        raise ValueError(f"channel must be one of {sorted(_ldpc._CHANNELS)}")
-    seeds = _seed_array(seeds)
-    K, N = int(K), int(N)
-    u = np.empty((len(seeds), K), dtype=np.uint8) if K else None
-    w = np.empty((len(seeds), N))
+    seeds, K, N, u, w = _draw_arrays(seeds, K, N, channel)
     lib = _ldpc.load_bp_library()
     _ldpc._check(lib.lb_draw_blocks(seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), len(seeds), K, N,
                                     _ldpc._CHANNELS[channel], None if u is None else u.ctypes.data_as(_ldpc._U8),
@@ -118,12 +118,7 @@ def draw_blocks_device(code, seeds, channel="awgn"):
     """The blocks mc_ldpc(draws="device") decodes: _draw_blocks' (u, w) for
     ``code`` (K = info_bits, N = code.N) drawn on the GPU from their seeds
     (lb_draw_blocks_device) and copied back."""
-    if channel not in _ldpc._CHANNELS:
-        raise ValueError(f"channel must be one of {sorted(_ldpc._CHANNELS)}")
-    seeds = _seed_array(seeds)
-    K, N = info_bits(code, channel), int(code.N)
-    u = np.empty((len(seeds), K), dtype=np.uint8) if K else None
-    w = np.empty((len(seeds), N))
+    seeds, K, N, u, w = _draw_arrays(seeds, info_bits(code, channel), code.N, channel)
     lib = _ldpc.load_bp_library()
     _ldpc._check(lib.lb_draw_blocks_device(code._context(), seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), len(seeds),
                                            K, N, _ldpc._CHANNELS[channel],
@@ -141,10 +136,7 @@ def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", draw
     stream=True (device draws, a layered dectype): the same results through
     code.mc_stream_seeds, ``batch`` being its chunk.  quant (with dectype
     "layered_minsum"): the fixed-point decoder, see ldpc.code."""
-    _check_draws(draws)
-    _check_stream(stream, draws, dectype)
-    _ldpc._quant_widths(quant, dectype)
-    q = {} if quant is None else {"quant": quant}
+    _check_request(draws, stream, dectype, quant)
     seeds = list(seeds)
     if draws == "device":
         if drawn is not None:
@@ -153,11 +145,11 @@ def mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", draw
     if not len(seeds):
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     if stream:
-        return code.mc_stream_seeds(seeds, a, channel, batch, dectype, **q)[:2]
+        return code.mc_stream_seeds(seeds, a, channel, batch, dectype, quant=quant)[:2]
     if draws == "device":
-        return code.mc_blocks_seeds(seeds, a, channel, batch, dectype, **q)
+        return code.mc_blocks_seeds(seeds, a, channel, batch, dectype, quant=quant)
     u, w = draw_blocks(seeds, info_bits(code, channel), code.N, channel) if drawn is None else drawn
-    return code.mc_blocks(u, w, a, channel, batch, dectype, **q)
+    return code.mc_blocks(u, w, a, channel, batch, dectype, quant=quant)
 
 
 def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectype="sumprod2", rank=0, world=1,
@@ -174,12 +166,10 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
     by the same sequential arithmetic (harness.consume_in_seed_order): the
     same dict as stream=False.  ``timings["stream"]`` receives the call's
     info (used, decoded, slots, chunks).  quant: as mc_ldpc."""
-    _check_draws(draws)
-    q = {} if quant is None else {"quant": quant}
-    if _check_stream(stream, draws, dectype, world):
+    if _check_request(draws, stream, dectype, quant, world):
         nblk = max(1, int(max_blocks))
         be, it, info = code.mc_stream_seeds(int(seed_base) + np.arange(nblk, dtype=np.int64), a, channel, batch,
-                                            dectype, min_errors=int(min_errors), **q)
+                                            dectype, min_errors=int(min_errors), quant=quant)
         if timings is not None:
             timings["draw_s"] = timings.get("draw_s", 0.0)  # (inside device_ms)
             timings["device_ms"] = timings.get("device_ms", 0.0) + code.mc_event_ms()
@@ -190,7 +180,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
         ms = [0.0]
 
         def decode_seeds(seeds):
-            out = mc_ldpc(code, a, seeds, channel, batch, dectype, draws="device", **q)
+            out = mc_ldpc(code, a, seeds, channel, batch, dectype, draws="device", quant=quant)
             ms[0] += code.mc_event_ms()
             return out
 
@@ -219,7 +209,7 @@ def _mc_point(code, a, channel, min_errors, max_blocks, seed_base, batch, dectyp
             drawn = fut.result() if fut is not None else draw(seeds)
             if r + 1 < max_rounds:
                 pending[r + 1] = pool.submit(draw, shard_seeds(seed_base, r + 1, batch, rank, world))
-            out = mc_ldpc(code, a, seeds, channel, batch, dectype, drawn=drawn, **q)
+            out = mc_ldpc(code, a, seeds, channel, batch, dectype, drawn=drawn, quant=quant)
             if timings is not None:
                 state["device_ms"] += code.mc_event_ms()
             return out
@@ -246,15 +236,11 @@ def sim_ldpc_mc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000
     one stream of refilled decoder slots (_mc_point); the same dict.
     quant (None, True or (frac_bits, msg_bits, app_bits), with dectype
     "layered_minsum"): the fixed-point decoder (ldpc.code)."""
-    _check_draws(draws)
-    _check_stream(stream, draws, dectype, world)
-    if dectype not in _ldpc._ALGOS:
-        raise NameError("Decoder type unknonwn")
-    _ldpc._quant_widths(quant, dectype)
+    _check_request(draws, stream, dectype, quant, world)
     if ldpcparams.r_ldpc not in _RATES:
         raise NameError("Rate unsupported")
     code = _ldpc.code(ldpcparams.standard, ldpcparams.r_ldpc, ldpcparams.z, ldpcparams.ptype)
     r = _mc_point(code, float(sigma), "awgn", MIN_ERRORS, MAX_BLOCKS, seed0, batch, dectype, rank, world,
-                  allreduce, timings, draws, stream, **({} if quant is None else {"quant": quant}))
+                  allreduce, timings, draws, stream, quant)
     return dict(ber=r["bit_errors"] / (r["blocks"] * code.N), blocks=r["blocks"], block_errors=r["block_errors"],
                 bit_errors=r["bit_errors"], nit_total=r["iters_total"])

@@ -430,6 +430,24 @@ def test_stream_equals_batch_per_block(bp, name):
                 np.testing.assert_array_equal(it, it0, err_msg=f"{widths} max_iter {max_iter} chunk {chunk}")
 
 
+@pytest.mark.parametrize("std,rate,z,sigma,degrees", [("802.16", "3/4", 24, 0.62, [14, 15]),
+                                                      ("802.11n", "5/6", 27, 0.54, [22])])
+def test_stream_equals_batch_in_degree_classes_16_and_32(bp, std, rate, z, sigma, degrees):
+    """The batch / stream pairs of the two check-degree classes that no case of MC reaches: 16 (802.16 3/4,
+    checks of 14 and 15 edges) and 32 (802.11n 5/6, 22 edges)."""
+    c = bp.code(std, rate, z)
+    assert sorted(set(np.asarray(c.cdeg).tolist())) == degrees
+    be0, it0 = c.mc_blocks_seeds(SEEDS, sigma, "awgn", 64, DT, 0.75, quant=True)
+    failed, clean = int((be0 > 0).sum()), int((be0 == 0).sum())
+    print(f"{std} {rate} z={z} sigma={sigma} fixed point: failed={failed} clean={clean} mean sweeps={it0.mean():.2f}")
+    assert failed and clean, "the case must hold both clean and failed blocks"
+    for chunk, slots in [(64, 3), (300, 0)]:
+        be, it, info = c.mc_stream_seeds(SEEDS, sigma, "awgn", chunk, DT, 0.75, slots=slots, quant=True)
+        np.testing.assert_array_equal(be, be0, err_msg=f"chunk {chunk} slots {slots}")
+        np.testing.assert_array_equal(it, it0, err_msg=f"chunk {chunk} slots {slots}")
+        assert info["used"] == info["decoded"] == 300 and info["chunks"] == -(-300 // chunk), info
+
+
 def test_stream_stop_rule_and_python_layers(bp):
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import ldpc_awgn, ldpc_bsc

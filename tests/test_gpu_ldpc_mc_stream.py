@@ -20,6 +20,9 @@ CASES = {
     "11n-1/2-z27": ("802.11n", "1/2", 27, "awgn", 0.85),
     "16-5/6-z8": ("802.16", "5/6", 8, "awgn", 0.56),
     "16-5/6-z24-dcfix20": ("802.16", "5/6", 24, "awgn", None),
+    # the degree classes 16 (checks of 14 and 15 edges) and 32 (22 edges: regular, but not the straight-line 20)
+    "16-3/4-z24-dc16": ("802.16", "3/4", 24, "awgn", 0.62),
+    "11n-5/6-z27-dc32": ("802.11n", "5/6", 27, "awgn", 0.54),
     "2_7_12_good-K0": ("2_7_12_good", "1/2", 16, "awgn", None),
     "bsc-p0.03": ("802.11n", "1/2", 27, "bsc", 0.03),
 }

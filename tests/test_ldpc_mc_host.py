@@ -84,7 +84,7 @@ def test_sim_param_grids():
         assert mod.sim_param[24] == ("802.11n", "1/2", 27, "A") and mod.sim_param[35] == ("802.11n", "5/6", 81, "A")
 
 
-def _fake_mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None):
+def _fake_mc_ldpc(code, a, seeds, channel="awgn", batch=1024, dectype="sumprod2", drawn=None, **kw):
     """Deterministic stand-in for ldpc_mc.mc_ldpc: a block fails more often at a
     larger sigma / p, as a function of its seed alone."""
     s = np.asarray(list(seeds), dtype=np.int64)
