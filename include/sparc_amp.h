@@ -406,6 +406,45 @@ int sa_mc_fetch_draws(sa_ctx* ctx, int nreps, int32_t* idx_out, double* noise_ou
  * the first n of each kept, w = 2^ceil(log2(max(M+1, n+1))); out [L][n]. */
 int sa_make_ordering(int L, int M, int n, uint32_t seed, uint32_t* out);
 
+/* State evolution (SE) of the AMP decoder: the scalar recursion that predicts
+ * a decode's effective noise variance tau_t^2 and its section error rate,
+ * iteration by iteration, without a codeword.  Context-free like sa_draw_reps;
+ * binary64 on the device.  For B allocations Pl [B][L] (P_b = sum_l Pl_{b,l}),
+ * section size M, code length n and noise sigma [B]:
+ *   tau_0^2 = sigma^2 + P,  c_l = sqrt(n Pl_l),  a = c_l / tau_t,
+ *   E_l = E[ e^(a^2 + a U_1) / (e^(a^2 + a U_1) + sum_{j >= 2} e^(a U_j)) ],  U_j i.i.d. N(0, 1),
+ *   x_{t+1} = sum_l (Pl_l / P) E_l,  tau_{t+1}^2 = sigma^2 + P (1 - x_{t+1}),
+ * the decoder's section softmax (sparc_ldpc.py:213-219) applied to
+ * s = c e_true + tau U; a (section, sample) pair is missed when
+ * a^2 + a U_1 < max_{j >= 2} a U_j.  The expectation is the mean over S rows
+ * of M Gaussians: row s = RandomState(seeds[s]).randn(M) drawn on the device
+ * (NumPy's legacy generator, as sa_mc_draw), or the caller's U [S][M]; exactly
+ * one of seeds and U is given.  The same S rows serve every section, every
+ * iteration and every allocation of the call (common random numbers), so a
+ * call is deterministic (the same inputs give the same bits, and an
+ * allocation's results do not depend on the rest of the batch) and
+ * allocations are compared on the same noise.  Sections of an allocation whose
+ * powers are equal bit for bit are computed once.  All T iterations are queued
+ * on one stream; the call waits once and copies back once.
+ *   tau2_out [B][T+1], x_out [B][T], miss_out [B][T]: the missed (section,
+ *   sample) pairs of iteration t, out of L * S; sec_out [B][L] or NULL: E_l of
+ *   the last iteration; ms_out or NULL: device time of the draw and the
+ *   iterations (events).
+ * SA_ERR_ARG (sa_last_error names the argument; nothing is written): B < 1,
+ * L < 1, M < 2, n < 1, T < 1, S < 1, a sigma that is not finite and > 0, a Pl
+ * that is negative or not finite, P = 0, both or neither of seeds and U.
+ * SA_ERR_UNSUPPORTED: M > SA_SE_MAX_M, the largest row a workgroup holds (M
+ * need not be a power of two); S > 2^24.  SA_ERR_NO_DEVICE as elsewhere.
+ *
+ * sa_se_draws: the rows the seeded path uses, U_out [S][M]: NumPy's up to the
+ * device library's log against the C library's (about one value in a
+ * hundred differs, by under 2^-49 relative). */
+enum { SA_SE_MAX_M = 4096 };
+int sa_se(int device, int B, int L, int M, int n, const double* Pl, const double* sigma, int T, int S,
+          const uint32_t* seeds, const double* U, double* tau2_out, double* x_out, int64_t* miss_out,
+          double* sec_out, double* ms_out);
+int sa_se_draws(int device, int S, int M, const uint32_t* seeds, double* U_out);
+
 /* Introspection. */
 /* The kernels a decode of B codewords runs: out8 = {section path (sa_sec_path),
  * Ab partials per codeword, row splits, codewords per batched workgroup,

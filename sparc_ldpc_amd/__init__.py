@@ -11,7 +11,7 @@ from .operators import (SparcOperator, AbOp, AzOp, make_ordering, sub_fht, block
                         gaussian_transforms,
                         sparc_transforms, sparc_transforms_shorter, default_device)
 from .amp import amp, amp_test, amp_batch, operator_of
-from .harness import (SPARCParams, LDPCParams, pa_parameterised, bits2indices, ber_of,
+from .harness import (SPARCParams, LDPCParams, pa_parameterised, pa_iterative, bits2indices, ber_of,
                       amp_ldpc_sim, mc_decode, mc_decode_batched, mc_stream, mc_stream_seeds, draw_reps, ebno_to_sigma, ber_point, waterfall_plain,
                       amp_test_reps, amp_init_test)
 from . import ldpc
@@ -24,5 +24,7 @@ from . import threshold
 from .threshold import (hard_initialisation, prep_y, calc_E, hist_E, calc_I_e, J, J_inverse,
                         soft_amp_ldpc_hardinit, ber_from_LLRs, soft_hardinit_plot, calc_E_batch, amp_exit_curve)
 from . import dist
+from . import se
+from .se import state_evolution, se_draws, pa_search, SEResult, PASearch
 
 __version__ = "0.1.0"

@@ -33,6 +33,7 @@ SA_PREC_F64 = 1
 SA_FLAG_NO_EARLY_STOP = 1
 SA_FLAG_BETA0 = 0x100
 SA_PTR_DEVICE = 0x200
+SA_SE_MAX_M = 4096  # the largest section size sa_se holds (include/sparc_amp.h)
 SA_LLR_MODES = {"reference": 0, "two_sided": 1}  # sa_llr_ex: SA_LLR_REFERENCE, SA_LLR_TWO_SIDED
 
 # sa_create_ex plan options (include/sparc_amp.h): overrides of the built-in
@@ -71,6 +72,7 @@ EXPORTS = (
     "sa_threshold", "sa_cancel", "sa_plan", "sa_plan_batched", "sa_stage_onehot_scaled", "sa_cancel_scaled",
     "sa_host_init", "sa_host_tau", "sa_host_eta", "sa_host_residual",
     "sa_draw_reps", "sa_mc_stage", "sa_mc_run", "sa_make_ordering", "sa_mc_draw", "sa_mc_fetch_draws",
+    "sa_se", "sa_se_draws",
 )
 
 _P = ct.c_void_p
@@ -129,6 +131,8 @@ _SIG = {
     "sa_make_ordering": (_I, [_I, _I, _I, ct.c_uint32, ct.POINTER(ct.c_uint32)]),
     "sa_mc_draw": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _D, _D]),
     "sa_mc_fetch_draws": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D]),
+    "sa_se": (_I, [_I, _I, _I, _I, _I, _D, _D, _I, _I, ct.POINTER(ct.c_uint32), _D, _D, _D, ct.POINTER(ct.c_int64), _D, _D]),
+    "sa_se_draws": (_I, [_I, _I, _I, ct.POINTER(ct.c_uint32), _D]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@ from .amp import amp, amp_test
 from .operators import SparcOperator, make_ordering, sparc_transforms, sparc_transforms_shorter
 
 __all__ = [
-    "SPARCParams", "LDPCParams", "pa_parameterised", "bits2indices", "ber_of",
+    "SPARCParams", "LDPCParams", "pa_parameterised", "pa_iterative", "bits2indices", "ber_of",
     "amp_ldpc_sim", "mc_decode", "mc_decode_batched", "mc_stream", "mc_stream_seeds", "draw_reps", "ebno_to_sigma", "ber_point", "waterfall_plain", "amp_test_reps", "amp_init_test",
 ]
 
@@ -59,6 +59,36 @@ def pa_parameterised(L, C, P, a, f):
     pa[int(f * L):] = pa[int(f * L)]
     pa /= pa.sum() / P
     return pa
+
+
+def pa_iterative(L, B, sigma, P, R_PA):
+    """The iterative power allocation of the reference's tutorial notebook
+    (sparc_amp.ipynb, "Power Allocation / Iterative"), the allocation state
+    evolution (se.py) is used to check.  The L sections form B blocks of
+    L // B sections.  Block by block, with ``left`` the power not yet given
+    out, a block's sections get the least power SE lets decode at the noise
+    level they will meet, ``2 ln2 (R_PA / L) (sigma^2 + left)`` each, as long
+    as that is more than ``left`` spread evenly over the sections still
+    without power; at the first block where it is not, those sections all get
+    the even share and the allocation is complete (the flat tail).  The tail
+    also starts at the last block, and at a block whose rule asks for all that
+    is left or more (an R_PA above what P can serve), so the allocation is
+    positive, non-increasing and sums to P whatever R_PA is; the notebook
+    gives such a block the rule's power all the same and then exceeds P, and
+    the two agree wherever the notebook's result sums to P.  R_PA is a design
+    rate of its own: it need not be the code's rate."""
+    per = L // B
+    out = np.zeros(L)
+    for blk in range(B):
+        first = per * blk
+        left = P - out.sum()
+        need = 2.0 * np.log(2.0) * (R_PA / L) * (sigma ** 2 + left)
+        even = left / (L - first)
+        if need <= even or blk == B - 1 or per * need >= left:
+            out[first:] = even
+            return out
+        out[first:first + per] = need
+    return out
 
 
 def bits2indices(bits, m):
