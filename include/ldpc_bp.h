@@ -303,6 +303,29 @@ int lb_mc_stream_seeds(lb_ctx* ctx, int nblk, const unsigned int* seeds, int K, 
                        int slots, int min_errors, int algo, double corr_factor, int max_iter, int* errs,
                        int* iters, long long* out);
 
+/* The reps of the joint SPARC + LDPC simulators (sparc_ldpc.py:419-446 /
+ * :606-634) drawn and encoded on the device, one workgroup per seed.  For
+ * RandomState(seeds[i]): randint(0, 2, K) are the protected bits (output word
+ * k & 1), randint(0, 2, U) the unprotected bits (word (K + j) & 1; U = 0 draws
+ * nothing), randn(n) * sigma the noise (from word K + U on, no cached value).
+ * The protected bits are then encoded (the encoder of lb_encode).  Two buffers
+ * of the context receive the reps and stay valid until its next lb_joint_draw:
+ *   *d_bits   [nrep][U + Nv] bytes: the U unprotected bits, then the codeword
+ *   *d_noise  [nrep][n] binary64
+ * device pointers for sa_encode_bits (include/sparc_amp.h).  The bits are bit
+ * for bit NumPy's and ldpc.encode_batch's; the noise is NumPy's up to the
+ * device library's log, as in lb_mc_run_seeds.  Blocking (a consumer on another
+ * stream needs no event); ms_out (or NULL): the device time of the draw and the
+ * encoder (events).  LB_ERR_ARG, and nothing is touched: K != Nv - Nc, no
+ * encoder set (lb_mc_set_code), U < 0, n <= 0, sigma not finite, nrep <= 0.
+ * A rep whose randn runs into the chunk cap: LB_ERR_HIP, as in lb_mc_run_seeds.
+ *
+ * lb_joint_fetch copies the first nrep reps of the last lb_joint_draw back:
+ * bits_out [nrep][U + Nv], noise_out [nrep][n], host arrays; either may be NULL. */
+int lb_joint_draw(lb_ctx* ctx, int nrep, const unsigned int* seeds, int K, int U, int n, double sigma,
+                  unsigned char** d_bits, double** d_noise, double* ms_out);
+int lb_joint_fetch(lb_ctx* ctx, int nrep, unsigned char* bits_out, double* noise_out);
+
 int lb_device_count(void);
 const char* lb_last_error(void);
 const char* lb_version(void);

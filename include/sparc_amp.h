@@ -282,6 +282,17 @@ int sa_decide_collect(sa_ctx* ctx, int B, int slot, int32_t* idx_out);
  * (sa_stage(ctx, B, NULL, Pl, NULL)). */
 int sa_encode(sa_ctx* ctx, int B, const int32_t* idx, const double* noise);
 
+/* The encoder from message bits that are on the device already (the reps
+ * lb_joint_draw of libldpc_bp.so draws): d_bits [B][L log2 M] bytes, section l
+ * taking bits [l log2 M, (l + 1) log2 M) MSB first (bits2indices,
+ * sparc_ldpc.py:317), d_noise [B][n] binary64 or NULL; both device pointers on
+ * the context's device, their producer finished.  Forms idx on the device and
+ * stages y exactly as sa_encode stages it from the same idx and noise (the
+ * same kernel), bit for bit.  idx_out: B x L on the host, or NULL.  M not a
+ * power of two: SA_ERR_UNSUPPORTED; d_bits NULL or B <= 0: SA_ERR_ARG.  Needs
+ * Pl staged.  Blocking. */
+int sa_encode_bits(sa_ctx* ctx, int B, const uint8_t* d_bits, const double* d_noise, int32_t* idx_out);
+
 /* Hard re-initialisation (sparc_ldpc.py:831-838): stage the one-hot beta0
  * with c_l at idx[b][l] (B x L) for the next sa_run(..., SA_FLAG_BETA0). */
 int sa_stage_onehot(sa_ctx* ctx, int B, const int32_t* idx);

@@ -49,7 +49,8 @@ def main():
     ap.add_argument("--no-stream", dest="stream", action="store_false",
                     help="l768: decode batch by batch instead of one refilled stream")
     ap.add_argument("--draws", default="host", choices=["host", "device"],
-                    help="l768 stream: draw the reps on the host cores (default) or on the device from their seeds")
+                    help="l768 stream and the joint sweeps: draw the reps on the host (default) or on the device "
+                         "from their seeds")
     ap.add_argument("--out", default="gpurun_out/waterfall")
     ap.add_argument("--precision", default=None, help="fp32 | fp64 (default: fp32 plain sweeps, fp64 joint)")
     ap.add_argument("--min-errors", type=int, default=None, help="joint sweeps: MIN_ERRORS (default: the published run's)")
@@ -62,6 +63,8 @@ def main():
     chosen = opts != decoder_options(argparse.Namespace())
     if chosen and args.sweep in ("plain", "l768"):
         ap.error("--llr / --llr-clip / --bp-dectype / --bp-quant go with the joint sweeps")
+    if args.draws == "device" and (args.sweep == "plain" or (args.sweep == "threshold" and args.unit_cancel)):
+        ap.error("--draws device goes with l768 and the joint sweeps (without --unit-cancel)")
     import sparc_ldpc_amd as sp
     from sparc_ldpc_amd import dist
     rank, world, _ = dist.init()
@@ -92,7 +95,8 @@ def main():
                             MIN_ERRORS=args.min_errors or cfg["MIN_ERRORS"],
                             MAX_BLOCKS=args.max_blocks or cfg["MAX_BLOCKS"], sections=sections,
                             batch=args.batch, precision=args.precision, rank=rank, world=world,
-                            allreduce=dist.allreduce_sum, ebno_dbs=ebno, bpsk=not args.no_bpsk, **opts)
+                            allreduce=dist.allreduce_sum, ebno_dbs=ebno, bpsk=not args.no_bpsk, draws=args.draws,
+                            **opts)
         ref = pub["waterfall_joint"]["runs"][args.sweep]
         for i, r in enumerate(rows):
             r["reference"] = {k: ref[k][i] for k in ref if k not in ("file", "EbN0_dB")}
@@ -104,7 +108,8 @@ def main():
         rows = sp.soft_hard_plot(True, True, cfg["sec"], cfg["soft_iter"], spp, lp,
                                  args.out + ".csv" if rank == 0 else None, None, MIN_ERRORS=cfg["MIN_ERRORS"],
                                  MAX_BLOCKS=cfg["MAX_BLOCKS"], batch=args.batch, precision=args.precision,
-                                 rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig, **opts)
+                                 rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig, draws=args.draws,
+                                 **opts)
         ps, ph = pub["soft_hard"]["soft"], pub["soft_hard"]["hard"]
         for i, r in enumerate(rows):
             r["reference"] = dict(BER_sparc=ps["BER_sparc"][i], BER_ldpc_soft=ps["BER_ldpc"][i],
@@ -119,7 +124,7 @@ def main():
                                      MIN_ERRORS=200, MAX_BLOCKS=200, soft_iter=cfg["soft_iter"],
                                      threshold=args.threshold, batch=args.batch, precision=args.precision or "fp64",
                                      rank=rank, world=world, allreduce=dist.allreduce_sum, sigmas=sig,
-                                     unit_cancel=args.unit_cancel, **opts)
+                                     unit_cancel=args.unit_cancel, draws=args.draws, **opts)
         refs = [r for r in pub["threshold_init"]["runs"] if r["threshold"] == args.threshold]
         for i, r in enumerate(rows):
             r["reference_runs"] = [{k: ref[k][i] for k in ("BER_amp", "BER_ldpc", "BER_plain")} for ref in refs]

@@ -17,7 +17,7 @@ from .harness import (SPARCParams, LDPCParams, pa_parameterised, pa_iterative, b
 from . import ldpc
 from .ldpc import code, LdpcBpError
 from .joint import (JointDecoder, joint_decoder, joint_options, soft_amp_ldpc_sim, hardinitbeta_amp_ldpc_sim, sim_ldpc, soft_hard_plot,
-                    waterfall, sp2bp, bp2sp, mc_joint)
+                    waterfall, sp2bp, bp2sp, mc_joint, draw_reps_device)
 from . import ldpc_mc, ldpc_awgn, ldpc_bsc
 from .ldpc_mc import draw_blocks, draw_blocks_device, mc_ldpc, sim_ldpc_mc
 from . import threshold

@@ -72,7 +72,7 @@ EXPORTS = (
     "sa_threshold", "sa_cancel", "sa_plan", "sa_plan_batched", "sa_stage_onehot_scaled", "sa_cancel_scaled",
     "sa_host_init", "sa_host_tau", "sa_host_eta", "sa_host_residual",
     "sa_draw_reps", "sa_mc_stage", "sa_mc_run", "sa_make_ordering", "sa_mc_draw", "sa_mc_fetch_draws",
-    "sa_se", "sa_se_draws",
+    "sa_se", "sa_se_draws", "sa_encode_bits",
 )
 
 _P = ct.c_void_p
@@ -110,6 +110,7 @@ _SIG = {
     "sa_last_error": (ct.c_char_p, []),
     "sa_version": (ct.c_char_p, []),
     "sa_encode": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D]),
+    "sa_encode_bits": (_I, [_P, _I, _P, _P, ct.POINTER(ct.c_int32)]),
     "sa_threshold": (_I, [_P, _I, _I, _I, _P, _I, ct.c_double, ct.POINTER(ct.c_int32)]),
     "sa_cancel": (_I, [_P, _I, ct.POINTER(ct.c_int32), _P]),
     "sa_plan": (_I, [_P, _I, ct.POINTER(ct.c_int64)]),

@@ -35,6 +35,12 @@
 //    chunks in flight) and stops queuing once min_errors block errors are
 //    reached; the kernel skips blocks that are provably behind the stopping
 //    block.  Decoder memory grows with the slots, not with the chunk.
+//  * lb_joint_draw: the reps of the joint SPARC + LDPC simulators drawn on the
+//    device from their seeds (k_joint_draw: protected bits, unprotected bits,
+//    scaled noise, in the reference's order) and their protected bits encoded
+//    by k_mc_prep (encode only) behind the unprotected bits of the message.
+//    The message bits and the noise stay on the device for libsparc_amp.so
+//    (sa_encode_bits); lb_joint_fetch copies them back.
 
 #include <algorithm>
 #include <cmath>
@@ -83,6 +89,12 @@ struct lb_mc {
                               // stays 0); room for capCtr chunks
   int capCtr = 0;
   hipEvent_t ev_go = nullptr, ev_join = nullptr;  // the seeds and counters are up; lane 1 is through
+  // lb_joint_draw: the reps' protected bits [jrep][K], message bits [jrep][jU + Nv] (unprotected bits, then the
+  // codeword) and noise [jrep][jn]; capacities in elements, jrep == 0: nothing drawn
+  uint8_t *j_u = nullptr, *j_bits = nullptr;
+  double* j_noise = nullptr;
+  size_t capJu = 0, capJbits = 0, capJnoise = 0;
+  int jrep = 0, jU = 0, jn = 0;
 };
 
 namespace {
@@ -96,9 +108,9 @@ struct PrepArgs {
   const uint8_t* u;  // [B][K] information bits (encoder only)
   const double* w;   // [B][N] randn (kind 0) or random_sample (kind 1) values
   double* ch;        // [B][N]
-  uint8_t* x;        // [B][N] codeword bits
+  uint8_t* x;        // codeword bits, word b at x + b * ldx (ldx = N: [B][N])
   const int* proto;  // [Mp][Np]
-  int Mp, Np, z, off, N, K;
+  int Mp, Np, z, off, N, K, ldx;
   int kind;          // 0: AWGN, 1: BSC, -1: encode only
   double c0, a;      // AWGN: 2 / sigma^2, sigma; BSC: log((1 - p) / p), p
 };
@@ -145,7 +157,7 @@ __global__ void __launch_bounds__(kPrepThreads) k_mc_prep(PrepArgs a) {
       __syncthreads();
     }
   }
-  uint8_t* xo = a.x + (size_t)b * N;
+  uint8_t* xo = a.x + (size_t)b * a.ldx;
   if (a.kind < 0) {
     for (int n = tid; n < N; n += nt) xo[n] = xs[n];
     return;
@@ -208,6 +220,28 @@ __global__ void __launch_bounds__(legacy_rng_dev::kThreads) k_mc_draw_blocks(con
   } else {
     legacy_rng_dev::draw_samples(st, have, K, N, wb);
   }
+}
+
+// A rep of the joint SPARC + LDPC simulators (sparc_ldpc.py:419-446 / :606-634), one workgroup per seed:
+// RandomState(seeds[b]).randint(0, 2, K) into u[b] (the protected bits, word k & 1), randint(0, 2, U) into
+// bits[b][0 .. U) (the unprotected bits, word (K + j) & 1; bits[b] is ldb bytes, the encoder fills the rest),
+// then randn(n) * sigma from word K + U on into noise[b].  A rep whose randn runs into the chunk cap sets *err.
+__global__ void __launch_bounds__(legacy_rng_dev::kThreads) k_joint_draw(const uint32_t* __restrict__ seeds, int K,
+                                                                         int U, int n, double sigma,
+                                                                         uint8_t* __restrict__ u,
+                                                                         uint8_t* __restrict__ bits, int ldb,
+                                                                         double* __restrict__ noise, int max_chunks,
+                                                                         int* err) {
+  __shared__ legacy_rng_dev::State st;
+  const int b = blockIdx.x;
+  legacy_rng_dev::seed_state(st, seeds[b]);
+  int have = 0;
+  uint8_t* ub = u + (size_t)b * K;
+  legacy_rng_dev::draw_masked(st, have, K, 1u, [&](int k, uint32_t v) { ub[k] = (uint8_t)v; });
+  uint8_t* mb = bits + (size_t)b * ldb;
+  legacy_rng_dev::draw_masked_from(st, have, K, U, 1u, [&](int j, uint32_t v) { mb[j] = (uint8_t)v; });
+  const bool ok = legacy_rng_dev::draw_randn(st, have, K + U, n, true, sigma, noise + (size_t)b * n, max_chunks);
+  if (!ok && threadIdx.x == 0) *err = 1;
 }
 
 void free_pinned(lb_mc* m) {
@@ -290,6 +324,46 @@ int ensure_seeds(lb_mc* m, int nblk) {
   m->capSeeds = 0;
   if ((rc = lb::dev_alloc((void**)&m->d_seeds, (size_t)nblk * sizeof(uint32_t)))) return rc;
   m->capSeeds = nblk;
+  return LB_OK;
+}
+
+void free_joint(lb_mc* m) {
+  (void)hipFree(m->j_u);
+  (void)hipFree(m->j_bits);
+  (void)hipFree(m->j_noise);
+  m->j_u = m->j_bits = nullptr;
+  m->j_noise = nullptr;
+  m->capJu = m->capJbits = m->capJnoise = 0;
+  m->jrep = 0;
+}
+
+// lb_joint_draw's buffers for nrep reps of U unprotected bits and n noise values; each grows on its own
+int ensure_joint(lb_ctx* c, int nrep, int U, int n) {
+  lb_mc* m = c->mc;
+  const size_t nu = (size_t)nrep * (c->Nv - c->Nc), nb = (size_t)nrep * ((size_t)U + c->Nv), nn = (size_t)nrep * n;
+  int rc;
+  m->jrep = 0;  // until the draw has succeeded
+  if (nu > m->capJu) {
+    (void)hipFree(m->j_u);
+    m->j_u = nullptr;
+    m->capJu = 0;
+    if ((rc = lb::dev_alloc((void**)&m->j_u, nu))) return rc;
+    m->capJu = nu;
+  }
+  if (nb > m->capJbits) {
+    (void)hipFree(m->j_bits);
+    m->j_bits = nullptr;
+    m->capJbits = 0;
+    if ((rc = lb::dev_alloc((void**)&m->j_bits, nb))) return rc;
+    m->capJbits = nb;
+  }
+  if (nn > m->capJnoise) {
+    (void)hipFree(m->j_noise);
+    m->j_noise = nullptr;
+    m->capJnoise = 0;
+    if ((rc = lb::dev_alloc((void**)&m->j_noise, nn * sizeof(double)))) return rc;
+    m->capJnoise = nn;
+  }
   return LB_OK;
 }
 
@@ -385,6 +459,7 @@ void fill_prep(PrepArgs& p, const lb_ctx* c, bool enc) {
   p.off = m->off;
   p.N = c->Nv;
   p.K = c->Nv - c->Nc;
+  p.ldx = c->Nv;
 }
 
 size_t prep_lds(const PrepArgs& p) { return p.Mp > 0 ? (size_t)(p.Np + p.Mp) * p.z : 0; }
@@ -399,6 +474,7 @@ void mc_release(lb_ctx* c) {
   (void)hipSetDevice(c->dev);
   free_staging(m);
   free_stream(m);
+  free_joint(m);
   (void)hipFree(m->d_ctr);
   for (hipEvent_t e : {m->lane[0].done, m->lane[1].done, m->ev_go, m->ev_join})
     if (e) (void)hipEventDestroy(e);
@@ -792,6 +868,69 @@ int lb_draw_blocks_device(lb_ctx* c, const uint32_t* seeds, int nblk, int K, int
   if (N > 0) HIP_TRY(hipMemcpyAsync(w, d.w, (size_t)nblk * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (err) return fail(LB_ERR_HIP, "lb_draw_blocks_device: a block's randn ran into the chunk cap");
+  return LB_OK;
+}
+
+int lb_joint_draw(lb_ctx* c, int nrep, const uint32_t* seeds, int K, int U, int n, double sigma, uint8_t** d_bits,
+                  double** d_noise, double* ms_out) {
+  if (!c) return fail(LB_ERR_ARG, "lb_joint_draw: null context");
+  if (nrep <= 0 || !seeds || !d_bits || !d_noise) return fail(LB_ERR_ARG, "lb_joint_draw: bad arguments");
+  if (U < 0 || n <= 0 || U > (1 << 27) || n > (1 << 27))
+    return fail(LB_ERR_ARG, "lb_joint_draw: U must be in [0, 2^27], n in [1, 2^27]");
+  if (!std::isfinite(sigma)) return fail(LB_ERR_ARG, "lb_joint_draw: sigma must be finite");
+  if (!c->mc || c->mc->Mp == 0) return fail(LB_ERR_ARG, "lb_joint_draw: no encoder set (lb_mc_set_code)");
+  if (K != c->Nv - c->Nc) return fail(LB_ERR_ARG, "lb_joint_draw: K must be Nv - Nc");
+  HIP_TRY(hipSetDevice(c->dev));
+  int rc;
+  lb_mc* m = c->mc;
+  if ((rc = ensure_joint(c, nrep, U, n))) return rc;
+  if ((rc = ensure_seeds(m, nrep))) return rc;
+  const int N = c->Nv, ldb = U + N;
+  PrepArgs p{};
+  fill_prep(p, c, true);
+  p.u = m->j_u;
+  p.x = m->j_bits + U;  // the codeword behind the rep's unprotected bits
+  p.ldx = ldb;
+  p.kind = -1;
+  HIP_TRY(hipMemcpyAsync(m->d_seeds, seeds, (size_t)nrep * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(m->d_err, 0, sizeof(int), c->stream));
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(k_joint_draw, dim3(nrep), dim3(legacy_rng_dev::kThreads), 0, c->stream, m->d_seeds, K, U, n,
+                     sigma, m->j_u, m->j_bits, ldb, m->j_noise, legacy_rng_dev::randn_chunk_cap(n), m->d_err);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_mc_prep, dim3(nrep), dim3(kPrepThreads), prep_lds(p), c->stream, p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  int err = 0;
+  HIP_TRY(hipMemcpyAsync(&err, m->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (err) return fail(LB_ERR_HIP, "lb_joint_draw: a rep's randn ran into the chunk cap");
+  if (ms_out) {
+    float ms = -1.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *ms_out = ms;
+  }
+  m->jrep = nrep;
+  m->jU = U;
+  m->jn = n;
+  *d_bits = m->j_bits;
+  *d_noise = m->j_noise;
+  return LB_OK;
+}
+
+int lb_joint_fetch(lb_ctx* c, int nrep, uint8_t* bits_out, double* noise_out) {
+  if (!c) return fail(LB_ERR_ARG, "lb_joint_fetch: null context");
+  if (nrep <= 0 || !c->mc || nrep > c->mc->jrep)
+    return fail(LB_ERR_ARG, "lb_joint_fetch: nrep outside the drawn reps (lb_joint_draw)");
+  HIP_TRY(hipSetDevice(c->dev));
+  const lb_mc* m = c->mc;
+  if (bits_out)
+    HIP_TRY(hipMemcpyAsync(bits_out, m->j_bits, (size_t)nrep * ((size_t)m->jU + c->Nv), hipMemcpyDeviceToHost,
+                           c->stream));
+  if (noise_out)
+    HIP_TRY(hipMemcpyAsync(noise_out, m->j_noise, (size_t)nrep * m->jn * sizeof(double), hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return LB_OK;
 }
 

@@ -130,14 +130,23 @@ __device__ __forceinline__ double polar_r2(const State& s, int g, double& x1, do
 }
 
 // `count` draws next32() & mask (mask + 1 a power of two: none rejected) from
-// word 0 on, each handed to put(l, value)
+// word `base` on, draw l (word base + l) handed to put(l, value).  The block
+// of word `base` must be one of the two newest, or not drawn yet.
+template <typename Put>
+__device__ __forceinline__ void draw_masked_from(State& s, int& have, int base, int count, uint32_t mask, Put put) {
+  const int last = base + count;
+  for (int b = base / kWords; b * kWords < last; ++b) {
+    ensure_block(s, have, b);
+    const int beg = base > b * kWords ? base : b * kWords;
+    const int end = last < (b + 1) * kWords ? last : (b + 1) * kWords;
+    for (int g = beg + (int)threadIdx.x; g < end; g += kThreads) put(g - base, s.w[b & 1][g - b * kWords] & mask);
+  }
+}
+
+// the same from word 0 on
 template <typename Put>
 __device__ __forceinline__ void draw_masked(State& s, int& have, int count, uint32_t mask, Put put) {
-  for (int b = 0; b * kWords < count; ++b) {
-    ensure_block(s, have, b);
-    const int end = count < (b + 1) * kWords ? count : (b + 1) * kWords;
-    for (int l = b * kWords + (int)threadIdx.x; l < end; l += kThreads) put(l, s.w[b & 1][l - b * kWords] & mask);
-  }
+  draw_masked_from(s, have, 0, count, mask, put);
 }
 
 // randn(n) from word `base` on into out[0 .. n) (times sigma when scaled, a

@@ -193,6 +193,17 @@ __global__ void k_app_idx(const double* __restrict__ app, int lgM, int ns, int B
   idx[i] = v;
 }
 
+// Message bits to section indices (bits2indices, sparc_ldpc.py:317): section l of codeword b takes bits
+// [l lgM, (l + 1) lgM) of the codeword's L lgM bytes, MSB first; a byte counts as 1 unless it is 0.
+__global__ void k_bits_idx(const uint8_t* __restrict__ bits, int lgM, int L, int B, int32_t* __restrict__ idx) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * L) return;
+  const uint8_t* a = bits + i * lgM;
+  int32_t v = 0;
+  for (int t = 0; t < lgM; ++t) v = (v << 1) | (a[t] != 0 ? 1 : 0);
+  idx[i] = v;
+}
+
 // One-hot beta0 (sparc_ldpc.py:832-835): beta[b][l*M + idx[b][l]] = c_l, 0 elsewhere.
 template <typename real>
 __global__ void k_onehot(const int32_t* __restrict__ idx, const double* __restrict__ cd, int L, int M, int B,
@@ -281,6 +292,34 @@ int launch_colsum(sa_ctx* c, const int32_t* d_idx, int ldi, int l0, int ns, cons
   return SA_OK;
 }
 
+// What sa_encode and sa_encode_bits check before anything else (`who`), and the workspace for B codewords.
+int encode_begin(sa_ctx* c, int B, bool args_ok, const std::string& who) {
+  if (check_ctx(c)) return SA_ERR_ARG;
+  if (B <= 0 || !args_ok) return fail(SA_ERR_ARG, who + ": bad arguments");
+  if (!c->power_set) return fail(SA_ERR_ARG, who + ": power allocation not staged");
+  if (int rc0 = check_tables(c, who.c_str())) return rc0;
+  if (!c->pow2) return fail(SA_ERR_UNSUPPORTED, who + ": the row-parallel encoder needs M a power of two");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
+}
+
+// The encoder on the device: y = A beta(d_idx) + d_noise (NULL: none) of B codewords becomes the current lane's
+// staged y, from the section indices queued into c->d_idx on that lane's stream; idx_out (host, or NULL) receives
+// them.  Blocking.
+int encode_staged(sa_ctx* c, int B, const double* d_noise, int32_t* idx_out) {
+  sa_lane& ln = c->at();
+  int rc;
+  if ((rc = y_begin_write(c, ln.stream, B))) return rc;  // the current lane's y becomes the staged one
+  rc = c->prec == SA_PREC_F64
+           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (double*)ln.d_y, B)
+           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (float*)ln.d_y, B);
+  if (rc) return rc;
+  if (idx_out)
+    HIP_TRY(hipMemcpyAsync(idx_out, c->d_idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+  HIP_TRY(hipStreamSynchronize(ln.stream));
+  return y_mark(c);
+}
+
 }  // namespace sa
 
 using namespace sa;
@@ -288,13 +327,7 @@ using namespace sa;
 extern "C" {
 
 int sa_encode(sa_ctx* c, int B, const int32_t* idx, const double* noise) {
-  if (check_ctx(c)) return SA_ERR_ARG;
-  if (B <= 0 || !idx) return fail(SA_ERR_ARG, "sa_encode: bad arguments");
-  if (!c->power_set) return fail(SA_ERR_ARG, "sa_encode: power allocation not staged");
-  if (int rc0 = check_tables(c, "sa_encode")) return rc0;
-  if (!c->pow2) return fail(SA_ERR_UNSUPPORTED, "sa_encode: the row-parallel encoder needs M a power of two");
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = ensure_workspace(c, B, c->Tcap > 0 ? c->Tcap : 1);
+  int rc = encode_begin(c, B, idx != nullptr, "sa_encode");
   if (rc) return rc;
   sa_lane& ln = c->at();
   for (size_t i = 0; i < (size_t)B * c->L; ++i)
@@ -302,13 +335,17 @@ int sa_encode(sa_ctx* c, int B, const int32_t* idx, const double* noise) {
   HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
   const double* d_noise = nullptr;
   if (noise && (rc = dev_in(c, noise, (size_t)B * c->n, 0, &d_noise))) return rc;
-  if ((rc = y_begin_write(c, ln.stream, B))) return rc;  // the current lane's y becomes the staged one
-  rc = c->prec == SA_PREC_F64
-           ? launch_colsum<double>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (double*)ln.d_y, B)
-           : launch_colsum<float>(c, c->d_idx, c->L, 0, c->L, nullptr, d_noise, (float*)ln.d_y, B);
+  return encode_staged(c, B, d_noise, nullptr);
+}
+
+int sa_encode_bits(sa_ctx* c, int B, const uint8_t* d_bits, const double* d_noise, int32_t* idx_out) {
+  int rc = encode_begin(c, B, d_bits != nullptr, "sa_encode_bits");
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(ln.stream));
-  return y_mark(c);
+  if (c->M < 2) return fail(SA_ERR_UNSUPPORTED, "sa_encode_bits: M < 2 carries no bits");
+  const size_t tot = (size_t)B * c->L;
+  k_bits_idx<<<(unsigned)((tot + 255) / 256), 256, 0, c->at().stream>>>(d_bits, ilog2(c->M), c->L, B, c->d_idx);
+  HIP_TRY(hipGetLastError());
+  return encode_staged(c, B, d_noise, idx_out);
 }
 
 namespace {

@@ -24,7 +24,10 @@ Every step of a round runs on the device: encoding (``sa_encode``), AMP
 ``sa_hard_cancel``, ``sa_stage_onehot``); LLRs and a-posteriori values move
 between the two libraries as device pointers.  The host draws the message
 bits and the noise and LDPC-encodes the protected bits (numpy), exactly in
-the reference's draw order, and counts bit errors.
+the reference's draw order, and counts bit errors.  With ``draws="device"``
+(opt-in: mc_joint and the sweeps on it) the draws, the LDPC encoder and the
+bit -> section packing run on the device too (``lb_joint_draw``,
+``sa_encode_bits``): only the seeds go up.
 
 Opt-in (``joint_options``; nothing of it is a default): the two-sided form of
 the section->bit LLR and a bound on its magnitude (``sa_llr_ex``), with which
@@ -43,9 +46,9 @@ from . import ldpc as _ldpc
 from .harness import SPARCParams, LDPCParams, pa_parameterised, ebno_to_sigma
 from .operators import SparcOperator, llr_mode, make_ordering
 
-__all__ = ["JointDecoder", "JointPipeline", "joint_decoder", "joint_options", "draw_reps", "amp_ldpc_sim_ldpc",
-           "soft_amp_ldpc_sim", "hardinitbeta_amp_ldpc_sim", "sim_ldpc", "waterfall", "soft_hard_plot", "sp2bp",
-           "bp2sp", "mc_joint"]
+__all__ = ["JointDecoder", "JointPipeline", "joint_decoder", "joint_options", "draw_reps", "draw_reps_device",
+           "amp_ldpc_sim_ldpc", "soft_amp_ldpc_sim", "hardinitbeta_amp_ldpc_sim", "sim_ldpc", "waterfall",
+           "soft_hard_plot", "sp2bp", "bp2sp", "mc_joint"]
 
 MODES = ("originalHard", "soft", "hard", "threshold")
 
@@ -131,6 +134,28 @@ def draw_reps(code, L, M, n, rs, B, sigma):
     return (bits * w).sum(axis=2).astype(np.int32), noise
 
 
+def _check_draws(draws, unit_cancel=False):
+    """The draws keyword of the joint simulators, before any library call."""
+    if draws not in ("host", "device"):
+        raise ValueError('draws must be "host" or "device"')
+    if draws == "device" and unit_cancel:
+        raise ValueError('unit_cancel=True reads the host noise of the batch: it goes with draws="host"')
+
+
+def draw_reps_device(jd, seeds, sigma):
+    """draw_reps for the reps RandomState(s), s in seeds, drawn, LDPC-encoded on
+    the device of jd's code (ldpc.code.joint_draw) and copied back: what
+    mc_joint(draws="device") decodes.  Seeds are ints in [0, 2**32); anything
+    else raises ValueError (no masking).  The indices are draw_reps' bit for bit,
+    the noise is its noise up to the device library's log (under 2**-49 relative).
+    Returns (section indices (B, L) int32, noise (B, n))."""
+    jd.draw_device(seeds, sigma)
+    bits, noise = jd.code.joint_fetch()
+    w = 1 << np.arange(jd.logm - 1, -1, -1)
+    idx = (bits.reshape(len(bits), jd.L, jd.logm).astype(np.int64) * w).sum(axis=2).astype(np.int32)
+    return idx, noise
+
+
 class JointDecoder:
     """AMP operator + LDPC code + the shortened operator of the unprotected
     sections, for B-codeword batches of the joint schemes."""
@@ -167,10 +192,20 @@ class JointDecoder:
         self.R = (self.L * self.logm - (code.N - code.K)) / n  # sparc_ldpc.py:541
         self._masked = None  # full-size operator for the per-codeword masked decodes (threshold mode)
         self._after_first_amp = None  # JointPipeline's stagger signal
+        self._noise = None  # the staged batch's host noise (stage; unit_cancel reads it)
+        self.last_draw_ms = 0.0  # device milliseconds of the last draw_device
 
     # -- message / channel draws (the reference's order) --------------------------
     def draw(self, rs, B, sigma):
         return draw_reps(self.code, self.L, self.M, self.n, rs, B, sigma)
+
+    def draw_device(self, seeds, sigma):
+        """draw's reps of RandomState(s), s in seeds, drawn and LDPC-encoded on
+        the device (ldpc.code.joint_draw): the device pointers of the message
+        bits (B, L log2 M) uint8 and of the noise (B, n), and the device
+        milliseconds (kept in last_draw_ms)."""
+        d_bits, d_noise, self.last_draw_ms = self.code.joint_draw(seeds, self.total_bits - self.code.N, self.n, sigma)
+        return d_bits, d_noise, self.last_draw_ms
 
     # -- one batch ------------------------------------------------------------------
     def _bp(self, B):
@@ -201,6 +236,24 @@ class JointDecoder:
         self.op.encode(idx, noise)
         self.code.device_buffers(B)
         self._noise = np.asarray(noise, dtype=np.float64).reshape(B, self.n)
+
+    def stage_seeds(self, seeds, sigma, Pl):
+        """stage for the reps of RandomState(s), s in seeds, made on the device:
+        drawn and LDPC-encoded (draw_device), packed into section indices and
+        encoded (SparcOperator.encode_bits); only the seeds go up.  No host
+        noise is kept (unit_cancel needs stage).  Returns the section indices
+        (B, L) int32 that score the decode."""
+        seeds = list(seeds)
+        B = len(seeds)
+        self.op.reserve(B, self.T)
+        if self.sub is not None:
+            self.sub.reserve(B, self.T)
+        self.op.stage_power(B, np.asarray(Pl, dtype=np.float64))
+        d_bits, d_noise, _ = self.draw_device(seeds, sigma)
+        idx = self.op.encode_bits(B, d_bits, d_noise)
+        self.code.device_buffers(B)
+        self._noise = None
+        return idx
 
     def decode_staged(self, idx, Pl, mode="soft", soft_iter=2, threshold=0.5, unit_cancel=False):
         """The joint decode of the staged batch (see run); idx only scores the
@@ -304,6 +357,8 @@ class JointDecoder:
     def _stage_unit_cancel(self, B, idx, full, Pl, mk):
         """Stage y - A beta_1(decided) into mk, beta_1 one-hot with amplitude 1."""
         L, M = self.L, self.M
+        if self._noise is None:
+            raise ValueError("unit_cancel reads the host noise of the batch: stage it with stage, not stage_seeds")
         c = np.sqrt(self.n * np.asarray(Pl, dtype=np.float64))
         rows = np.arange(B)[:, None]
         b0 = np.zeros((B, L * M))
@@ -369,6 +424,14 @@ class JointPipeline:
         noise = np.asarray(noise, dtype=np.float64).reshape(idx.shape[0], -1)
         self._slices = self._cut(idx.shape[0])
         self._map(lambda part, sl: part.stage(idx[sl], noise[sl], Pl))
+
+    def stage_seeds(self, seeds, sigma, Pl):
+        """JointDecoder.stage_seeds with the seeds cut as stage cuts the batch:
+        every slice draws its own seeds on its own contexts.  Returns the
+        section indices of the whole batch."""
+        seeds = list(seeds)
+        self._slices = self._cut(len(seeds))
+        return np.concatenate(self._map(lambda part, sl: part.stage_seeds(seeds[sl], sigma, Pl)), axis=0)
 
     def decode_staged(self, idx, Pl, mode="soft", soft_iter=2, threshold=0.5, unit_cancel=False):
         """The slices start staggered: slice i + 1 starts when slice i's first
@@ -511,21 +574,38 @@ def hardinitbeta_amp_ldpc_sim(sparcparams: SPARCParams, ldpcparams: LDPCParams, 
 
 
 def mc_joint(jd: JointDecoder, Pl, sigma, seeds, mode, soft_iter=2, batch=256, threshold=0.5, unit_cancel=False,
-             pipeline=None):
+             pipeline=None, draws="host"):
     """Seeded batched reps: rep s draws from RandomState(s) in the reference's
     order.  Returns the per-rep error-count dict of JointDecoder.run, in seed
     order.  pipeline (default: batches of PIPELINE_MIN_BATCH or more in the
     soft / hard / originalHard modes on the Hadamard backend, whose slices
     share one copy of the tables): decode each batch as two concurrent halves
-    (JointPipeline), with the same per-rep results."""
+    (JointPipeline), with the same per-rep results.
+    draws="device" (opt-in): every batch is drawn, LDPC-encoded, packed and
+    encoded on the device from its seeds (stage_seeds; the reps of
+    draw_reps_device): only the seeds go up and the section indices come back.
+    The messages are the host's bit for bit; the noise is the host's up to the
+    device library's log, so a rep's counts may differ from its host-drawn
+    ones.  Seeds outside [0, 2**32) raise ValueError, and so does
+    unit_cancel=True, which reads the host noise."""
+    _check_draws(draws, unit_cancel)
     seeds = list(seeds)
+    if draws == "device":
+        from .operators import seed_array
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}")
+        seeds = [int(s) for s in seed_array(seeds)]
     parts = []
     for s0 in range(0, len(seeds), batch):
         chunk = seeds[s0:s0 + batch]
-        idx, noise = jd.draw([np.random.RandomState(s) for s in chunk], len(chunk), sigma)
         pipe = pipeline if pipeline is not None else (len(chunk) >= PIPELINE_MIN_BATCH and mode != "threshold"
                                                       and jd.op.backend == "hadamard")
         runner = joint_pipeline(jd) if pipe else jd
+        if draws == "device":
+            idx = runner.stage_seeds(chunk, sigma, Pl)
+            parts.append(runner.decode_staged(idx, Pl, mode, soft_iter, threshold))
+            continue
+        idx, noise = jd.draw([np.random.RandomState(s) for s in chunk], len(chunk), sigma)
         parts.append(runner.run(idx, noise, Pl, mode, soft_iter, threshold, unit_cancel))
     return {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
 
@@ -566,17 +646,19 @@ def sim_ldpc(ldpcparams: LDPCParams, sigma, MIN_ERRORS=100, MAX_BLOCKS=400000, b
 def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None, png_filename=None,
               init="soft", pa_param=False, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, bpsk=True,
               sections=512, batch=64, seed0=0, backend=None, precision=None, rank=0, world=1, allreduce=None,
-              ebno_dbs=None, bpsk_mc=False, **options):
+              ebno_dbs=None, bpsk_mc=False, draws="host", **options):
     """The reference's waterfall sweep on the GPU.  Per Eb/N0 point (20 log10
     convention): blocks of the joint scheme ``init`` and of plain SPARC at the
     same overall rate, consumed in seed order until MIN_ERRORS plain block
     errors or MAX_BLOCKS blocks (:1217-1245 counts the PLAIN block errors);
     BER_bpsk from sim_ldpc, or with ``bpsk_mc`` from the device-side
     ldpc_mc.sim_ldpc_mc (its own seeded blocks, sharded over ranks).  Reps are
-    sharded over ranks like ber_point.  options: the joint decoder's LLR / BP
+    sharded over ranks like ber_point.  draws: mc_joint's, for the joint blocks
+    only (the plain-SPARC and BPSK columns draw as ever).  options: the joint decoder's LLR / BP
     options (joint_options); the BER_bpsk column keeps the reference's sumprod2.
     Returns the rows; writes the reference CSV schema (:1257-1264) on rank 0."""
     from .harness import mc_decode
+    _check_draws(draws)
     precision = precision or "fp64"  # see joint_decoder
     L, M = sparcparams.L, sparcparams.M
     logm = int(np.log2(M))
@@ -606,7 +688,7 @@ def waterfall(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=Non
         base = seed0 + pi * 10_000_000
 
         def round_fn(seeds, sigma=sigma, Pl=Pl, Pl_plain=Pl_plain):
-            rj = mc_joint(jd, Pl, sigma, seeds, init, 2, batch)
+            rj = mc_joint(jd, Pl, sigma, seeds, init, 2, batch, draws=draws)
             be_plain, _ = mc_decode(plain, Pl_plain, sigma, T, [s + 5_000_000 for s in seeds], batch=batch)
             cols = [rj["amp"][:, 0], rj["ldpc"][:, 0] if rj["ldpc"].shape[1] else 0 * be_plain]
             if init == "originalHard":
@@ -682,7 +764,8 @@ def _ber_point_multi(round_fn, total_bits, min_errors, max_blocks, batch, rank, 
 
 def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None,
                    png_filename=None, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, batch=64, seed0=0,
-                   backend=None, precision=None, rank=0, world=1, allreduce=None, sigmas=None, **options):
+                   backend=None, precision=None, rank=0, world=1, allreduce=None, sigmas=None, draws="host",
+                   **options):
     """Soft exchange vs the original hard exchange on the GPU.
 
     The LDPC code covers nl = log2(M) * sec bits with z = int(nl / 24)
@@ -696,9 +779,11 @@ def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcpar
     sharded over ranks like waterfall.  Returns rows (EbN0_dB, BER_sparc,
     BER_ldpc_soft [soft_iter], BER_amp_soft [soft_iter + 1], BER_ldpc_hard,
     BER_amp_hard [2], blocks); rank 0 appends the reference's two CSV blocks
-    (:1397-1413).  No plots.  options: the joint decoder's LLR / BP options."""
+    (:1397-1413).  No plots.  draws: mc_joint's, for the joint blocks only.
+    options: the joint decoder's LLR / BP options."""
     from .harness import mc_decode
     from .dist import shard_seeds
+    _check_draws(draws)
     precision = precision or "fp64"
     L, M, p, r_sparc, T = sparcparams.L, sparcparams.M, sparcparams.p, sparcparams.r, sparcparams.t
     logm = int(np.log2(M))
@@ -730,7 +815,7 @@ def soft_hard_plot(soft, hard, sec, soft_iter, sparcparams: SPARCParams, ldpcpar
                 continue
 
             def round_fn(sds, mode=mode, sigma=sigma):
-                rj = mc_joint(jd, Pl, sigma, sds, mode, soft_iter, batch)
+                rj = mc_joint(jd, Pl, sigma, sds, mode, soft_iter, batch, draws=draws)
                 if mode == "soft":
                     return rj["ldpc"][:, 0], np.concatenate([rj["ldpc"], rj["amp"]], axis=1)
                 cols = [rj["ldpc"][:, 0], rj["amp"][:, 0], rj.get("ldpc_amp", 0 * rj["amp"][:, 0])]

@@ -42,7 +42,7 @@ EXPORTS = (
     "lb_fetch", "lb_run_event_ms", "lb_info", "lb_device_count", "lb_last_error", "lb_version",
     "lb_buffers", "lb_set_tail", "lb_set_layers", "lb_layer_info", "lb_layer_info_ex",
     "lb_draw_blocks", "lb_mc_set_code", "lb_encode", "lb_mc_run", "lb_mc_run_seeds", "lb_draw_blocks_device",
-    "lb_mc_stream_seeds", "lb_set_fixed", "lb_fixed_info",
+    "lb_mc_stream_seeds", "lb_set_fixed", "lb_fixed_info", "lb_joint_draw", "lb_joint_fetch",
 )
 
 _P, _I, _D = ct.c_void_p, ct.c_int, ct.POINTER(ct.c_double)
@@ -83,6 +83,9 @@ _SIG = {
     "lb_draw_blocks_device": (_I, [_P, ct.POINTER(ct.c_uint32), _I, _I, _I, _I, _U8, _D]),
     "lb_mc_stream_seeds": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _I, ct.c_double, _I, _I, _I, _I, _I, ct.c_double,
                                 _I, _IP, _IP, ct.POINTER(ct.c_int64)]),
+    "lb_joint_draw": (_I, [_P, _I, ct.POINTER(ct.c_uint32), _I, _I, _I, ct.c_double, ct.POINTER(_P), ct.POINTER(_P),
+                           _D]),
+    "lb_joint_fetch": (_I, [_P, _I, _U8, _D]),
 }
 
 _lib = None
@@ -279,6 +282,7 @@ class code:
         self._ctx = None
         self._encoder_set = False
         self._layers_set = False
+        self._joint_shape = (0, 0, 0)  # reps, message bits and noise values a rep of the last joint_draw
 
     # -- construction ---------------------------------------------------------
     def assign_proto(self):
@@ -500,6 +504,35 @@ class code:
             _CHANNELS[channel], int(chunk), int(slots), int(min_errors), algo, float(corr_factor), int(max_iter),
             errs.ctypes.data_as(_IP), it.ctypes.data_as(_IP), out))
         return errs.astype(np.int64), it.astype(np.int64), dict(zip(("used", "decoded", "slots", "chunks"), list(out)))
+
+    def joint_draw(self, seeds, U, n, sigma):
+        """The reps of the joint SPARC + LDPC simulators drawn and encoded on the
+        device from their seeds (lb_joint_draw): per seed randint(0, 2, K)
+        protected bits, randint(0, 2, U) unprotected bits, randn(n) * sigma, the
+        protected bits encoded.  Seeds outside [0, 2**32) raise ValueError (no
+        masking).  Returns the device pointers (message bits (B, U + N) uint8:
+        unprotected bits then codeword; noise (B, n) float64), valid until the
+        next joint_draw of this code, and the device milliseconds."""
+        from .operators import seed_array
+        seeds = seed_array(seeds)
+        self._set_encoder()
+        bits, noise = ct.c_void_p(), ct.c_void_p()
+        ms = ct.c_double(0.0)
+        _check(load_bp_library().lb_joint_draw(self._context(), len(seeds),
+                                               seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), self.K, int(U), int(n),
+                                               float(sigma), ct.byref(bits), ct.byref(noise), ct.byref(ms)))
+        self._joint_shape = (len(seeds), int(U) + self.N, int(n))
+        return bits.value, noise.value, float(ms.value)
+
+    def joint_fetch(self, bits=True, noise=True):
+        """The reps of the last joint_draw copied back (lb_joint_fetch):
+        (message bits (B, U + N) uint8 or None, noise (B, n) float64 or None)."""
+        B, nb, n = self._joint_shape
+        b = np.empty((B, nb), dtype=np.uint8) if bits else None
+        w = np.empty((B, n)) if noise else None
+        _check(load_bp_library().lb_joint_fetch(self._context(), B, None if b is None else b.ctypes.data_as(_U8),
+                                                None if w is None else w.ctypes.data_as(_D)))
+        return b, w
 
     def mc_event_ms(self):
         """Device milliseconds of the last mc_blocks / run_buffers (events on the context's stream)."""

@@ -456,6 +456,18 @@ class SparcOperator:
         check(self._lib.sa_encode(self._ctx, B, idx.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int32)), nz))
         return B
 
+    def encode_bits(self, B, d_bits, d_noise=None, fetch_idx=True):
+        """encode from message bits on the device (sa_encode_bits): d_bits, an int
+        device pointer to (B, L log2 M) uint8 bits, MSB first per section, and
+        d_noise, one to (B, n) float64 or None (ldpc.code.joint_draw's
+        buffers).  The staged y is encode's of the same indices and noise, bit
+        for bit.  Returns the section indices (B, L) int32 (None without
+        fetch_idx)."""
+        idx = np.empty((int(B), self.L), dtype=np.int32) if fetch_idx else None
+        check(self._lib.sa_encode_bits(self._ctx, int(B), _lib.ct.c_void_p(d_bits), _lib.ct.c_void_p(d_noise),
+                                       None if idx is None else idx.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int32))))
+        return idx
+
     def stage_onehot(self, idx, scale=None):
         """Stage the one-hot β₀ of section indices idx (B, L) for run(..., beta0=True):
         c_l at idx[b, l]; with ``scale``, scale * c_l and idx -1 = an all-zero section."""

@@ -277,7 +277,7 @@ def soft_amp_ldpc_hardinit(sparcparams: SPARCParams, ldpcparams: LDPCParams, sof
 def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_filename=None, png_filename=None,
                        sections=None, datapoints=10, MIN_ERRORS=100, MAX_BLOCKS=500, soft_iter=3, threshold=0.6,
                        batch=64, seed0=0, precision="fp64", rank=0, world=1, allreduce=None, sigmas=None,
-                       unit_cancel=False, **options):
+                       unit_cancel=False, draws="host", **options):
     """The threshold-initialised exchange sweep of sparc_ldpc.py:1435-1590 on the GPU.
 
     Per sigma of linspace(0.9, 1.4, datapoints) (:1488): blocks of
@@ -296,10 +296,13 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
     unit_cancel=True cancels decided sections with amplitude 1 (the
     reference's behaviour before the fix noted at amp_exit.py:97-98, which its
     published threshold-init CSVs reflect; batched path only).
+    draws: joint.mc_joint's, for the batched joint blocks only ("device" does
+    not go with unit_cancel, nor with the per-block designed protographs).
     options: the joint decoder's LLR / BP options (joint.joint_options).
     No plots (figure code is out of scope)."""
     from .harness import mc_decode, amp_ldpc_sim
-    from .joint import joint_decoder, mc_joint, _ber_point_multi
+    from .joint import joint_decoder, mc_joint, _ber_point_multi, _check_draws
+    _check_draws(draws, unit_cancel)
     L, M = sparcparams.L, sparcparams.M
     logm = int(np.log2(M))
     p, r_sparc, T = sparcparams.p, sparcparams.r, sparcparams.t
@@ -311,6 +314,8 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
     nl = logm * sections
     z = ldpcparams.z
     std = ldpcparams.standard in ("802.11n", "802.16")
+    if draws == "device" and not std:
+        raise ValueError('draws="device" draws the batched blocks of the 802.11n / 802.16 codes only')
     if z is None:
         z = int(nl / 24) if std else int(nl / 40)
     ldp = LDPCParams(ldpcparams.standard, ldpcparams.r_ldpc, z, ldpcparams.ptype)
@@ -330,7 +335,8 @@ def soft_hardinit_plot(sparcparams: SPARCParams, ldpcparams: LDPCParams, csv_fil
         sigma = float(sigma)
         if std:
             def round_fn(seeds, sigma=sigma):
-                rj = mc_joint(jd, Pl, sigma, seeds, "threshold", soft_iter, batch, threshold, unit_cancel)
+                rj = mc_joint(jd, Pl, sigma, seeds, "threshold", soft_iter, batch, threshold, unit_cancel,
+                              draws=draws)
                 be_plain, _ = mc_decode(plain, Pl, sigma, T, [s + 5_000_000 for s in seeds], batch=batch)
                 return be_plain, np.concatenate([rj["amp"], rj["ldpc"]], axis=1)
 
