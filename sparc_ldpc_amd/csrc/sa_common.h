@@ -1,7 +1,7 @@
 // sa_common.h — device-side building blocks shared by the AMP kernel units
 // (sa_sec.hip, sa_secb.hip, sa_row.hip, sa_dense.hip, sa_glue.hip): cross-lane
 // moves, the M-point FWHT, the section denoiser, loads / stores, the kernel
-// argument blocks and the operator constants.  See sparc_amp.hip for the
+// argument blocks (the operator constants: sa_shape.h).  See sparc_amp.hip for the
 // operator's factorisation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "sparc_amp.h"
+#include "sa_shape.h"
 
 namespace sa {
 
@@ -871,20 +872,18 @@ __device__ __forceinline__ void store_section_any(real* p, const real (&x)[E], i
 enum { SEC_AMP = 0, SEC_AZ = 1, SEC_AB = 2 };
 enum { ROW_INIT0 = 0, ROW_INIT = 1, ROW_AMP = 2, ROW_ABOUT = 3 };
 
-constexpr int kSpw = 4;      // sections (wavefronts) per section-kernel workgroup
-constexpr int kRowsPerBlk = 64;  // rows per row-kernel workgroup (one per lane)
 
 template <typename real>
 struct SecArgs {
   const uint16_t* __restrict__ inv;  // [L][w]  row of ordering value o, or n (zero slot)
-  // k_secb: the bucket table in bank-aware step order (build_invb), or null
+  // k_secb: the bucket table in bank-aware step order (banked_section), or null
   const uint16_t* __restrict__ invb;
   // the codeword-interleaved k_secb: invb (or inv) lane-major [L][nhi][64][E]
   const uint16_t* __restrict__ invl;
   // [L] steps of invb's two halves that hold occupied slots (s0 | s1 << 16), or null
   const uint32_t* __restrict__ hs;
   const ushort4* __restrict__ fwd;   // [G][n]  4 sections: (o & (M-1)) | parity(o >> log2 M) << 15
-  // k_secb's Ab table (build_fwdb): [Gb * W / 4][npad][4] with npad = n rounded
+  // k_secb's Ab table (fwdb_group): [Gb * W / 4][npad][4] with npad = n rounded
   // up to 64; entry (s * M + t_pos(k)) | sign << 15 for the workgroup's local
   // section s (t_pos: the staged image's position of column k), each row's W
   // entries in a bank-aware step order
@@ -920,7 +919,7 @@ struct SecArgs {
   // Monte-Carlo stream (sa_mc_run): per-codeword iteration index t_b (slot_t),
   // -1 for an empty slot; null: every codeword is at iteration t
   const int* tb;
-  int dead;  // leading dead columns of a padded section (sa_ctx::dead; k_sec only)
+  int dead;  // leading dead columns of a padded section (Shape::dead; k_sec only)
   // k_sec4 / k_sec43: the previous estimate is zero whatever `beta` holds (the
   // first iteration of a decode without beta0: no zero fill of the buffer)
   int bzero;
@@ -1182,26 +1181,6 @@ static __device__ unsigned long long g_stamps[16 * 16];
 #define STAMP(i) do {} while (0)
 #endif
 
-constexpr int kSG = 16;  // fwd table padding (sections)
-// table bytes of the section groups one XCD works on at a time (SecArgs::gpx).
-// C4 binary32 k_secb HBM bytes per launch (PMC, round 4; the 1.7 / 0.9 MB
-// points on an intermediate build with an L2-budget switch since removed):
-// one pass (6 groups, 4.7 MB) 1.715 GB; 2.5 MB -> 2 x 3 groups 1.495 GB;
-// 1.7 MB -> 3 x 2 groups 1.514 GB; 0.9 MB -> 6 x 1 group 1.711 GB (every
-// pass re-reads z)
-constexpr size_t kSecbL2 = (size_t)5 << 19;  // 2.5 MB of the 4 MB L2
-// sections (waves) per batched workgroup: 8 (two workgroups per CU), or 16
-// (one per CU) where the wider workgroup's LDS holds a larger codeword chunk
-// (sa_ctx::WB, chosen at context creation)
-constexpr int kWB = 8, kWB16 = 16;
-// zero rows after z in the batched kernel's LDS image (empty bucket slots read
-// them; 16, one per 16-byte bank group: build_invb)
-constexpr int kInvbZeroRows = 16;
-// k_secb's bucket h-steps with table loads in flight per block (binary32 at
-// CB = 4 or E = 16 / binary64); the bank-aware table (ensure_invb) pads each
-// half's occupied steps to a multiple of it
-constexpr int kSecbKH32 = 2, kSecbKH64 = 2;
-
 template <int N>
 constexpr int ilog2c() { return N <= 1 ? 0 : 1 + ilog2c<N / 2>(); }
 
@@ -1226,14 +1205,6 @@ __device__ __forceinline__ int section_argmax(const real* bl, int lane, int M, i
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
   return bi == 0x7fffffff ? 0 : bi - dead;  // the caller's column (a padded section's dead columns first)
-}
-
-constexpr int kRow2Rows = 32;  // k_row2: one 128-B line of a partial per row block
-
-inline int ilog2(int x) {
-  int r = 0;
-  while ((1 << r) < x) ++r;
-  return r;
 }
 
 }  // namespace sa

@@ -339,7 +339,7 @@ int i8_set_bfix(sa_ctx* c) {
 
 // Builds A8 / AT8 on first use and sizes the digit planes for B codewords.
 int ensure_i8(sa_ctx* c, int B) {
-  if (!use_i8(c, B)) return SA_OK;
+  if (!use_i8(*c, B)) return SA_OK;
   int rc;
   if (!c->d_A8) {
     c->np8 = ((long long)c->n + kI8TY - 1) / kI8TY * kI8TY;
@@ -522,7 +522,7 @@ int fgemm_splits(const sa_ctx* c, int B) {
 
 // The transposed matrix (first batched use) and the padded GEMM vectors for B codewords.
 int ensure_fgemm(sa_ctx* c, int B) {
-  if (!use_fgemm(c, B)) return SA_OK;
+  if (!use_fgemm(*c, B)) return SA_OK;
   const size_t s = rsz(c);
   int rc;
   if (!c->d_AT) {
@@ -617,7 +617,7 @@ int build_dense(sa_ctx* c) {
 
 // Ab partials of A beta: the GEMM's K splits (B >= 4) or the GEMV's KS splits
 int dense_parts(const sa_ctx* c, int B) {
-  return use_i8(c, B) ? i8_splits(c, B) : (use_fgemm(c, B) ? fgemm_splits(c, B) : c->KS);
+  return use_i8(*c, B) ? i8_splits(c, B) : (use_fgemm(*c, B) ? fgemm_splits(c, B) : c->KS);
 }
 
 // A beta of the beta in d_beta on the plan's path: p.G partials in d_abp

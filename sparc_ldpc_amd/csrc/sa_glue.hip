@@ -287,7 +287,7 @@ int launch_colsum(sa_ctx* c, const int32_t* d_idx, int ldi, int l0, int ns, cons
                   real* out, int B, double amp = 1.0) {
   dim3 grid((c->n + 255) / 256, B);
   k_colsum<real><<<grid, 256, (size_t)ns * sizeof(int32_t), c->at().stream>>>(
-      (const ushort4*)c->d_fwd, c->d_cd, d_idx, ldi, l0, ns, base, add, out, c->n, std::sqrt((double)c->n), amp);
+      (const ushort4*)c->tab.fwd, c->d_cd, d_idx, ldi, l0, ns, base, add, out, c->n, std::sqrt((double)c->n), amp);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }

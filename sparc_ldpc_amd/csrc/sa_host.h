@@ -2,6 +2,7 @@
 // helpers shared by the kernel units and the C ABI (sparc_amp.hip).
 #pragma once
 #include "sa_common.h"
+#include "sa_tables.h"
 
 namespace sa {
 
@@ -84,7 +85,9 @@ struct sa_lane {
   int row_B = 0, row_T = 0;
 };
 
-struct sa_ctx {
+// The operator context.  Its shape numbers are the base (sa_shape.h: Shape,
+// filled by shape_for alone), its tables are `tab` (sa_tables.h: Tables).
+struct sa_ctx : sa::Shape {
   sa::Prof* prof = nullptr;
   // decode lanes (compile-time 2: the ring and bench protocols keep at most two steps in flight)
   enum { kLanes = 2 };
@@ -97,55 +100,14 @@ struct sa_ctx {
   int y_lane = 0;                // the lane that holds it
   std::vector<double> h_Pl;      // the Pl behind d_c / d_cd / d_P1 (set_power skips an unchanged one)
   std::vector<double> h_Plb;     // the Pl behind d_cb / d_Pb (set_power_batch)
-  int L = 0, M = 0, n = 0, w = 0, nhi = 0, backend = 0, prec = 0, device = 0;
-  int plan = 0;       // SA_PLAN_* options of sa_create_ex (0: every choice by the built-in rules)
-  bool pow2 = true;  // M a power of two (the Hadamard kernels, bit-level glue)
-  // the caller's section size Mu; the Hadamard backend pads a section of any
-  // Mu to M = 2^ceil(log2 Mu) columns, the first dead = M - Mu of them never
-  // used (column c of the reference is column dead + c: sparc_ldpc.py:54, 68)
-  int Mu = 0, dead = 0;
-  int G = 0, NZ = 0, E = 1;
-  int n_cus = 256;
-  int Gb = 0, CB = 0;  // batched kernel: groups of WB sections, codewords per workgroup (0 = off)
-  int WB = 8;          // batched kernel: sections per workgroup (kWB or kWB16)
-  int gpx = 1 << 20;   // batched kernel: section groups per XCD per pass (SecArgs::gpx)
-  size_t secb_lds = 0;
-  int RS = 1, KS = 1, Gd = 0;  // dense splits; Gd = dense denoiser groups
+  int device = 0;
+  int RS = 1, KS = 1;  // dense splits
   size_t lda = 0;
-  size_t sec_lds = 0;
-  int G2 = 0;          // k_sec2 pairs of sections (0: k_sec2 unavailable)
-  int G3 = 0;          // k_sec43 triples of sections (used when sec3)
-  bool sec3 = false;   // k_sec43 (three sections x 4 waves per workgroup) chosen over k_sec4
-  size_t sec3_lds = 0;
-  int G4 = 0;          // k_sec44 quads of sections (used when sec4q)
-  bool sec4q = false;  // k_sec44 (four sections x 4 waves per workgroup, the pair table) chosen over k_sec4
-  size_t sec4q_lds = 0;
-  uint32_t* d_fwd3 = nullptr;
-  bool pt_on = false;  // row-block-major Ab partials between k_sec4 / k_sec43 and k_row2 (SecArgs::pt)
-  bool sec4 = false;   // k_sec4 (4 waves per section) fits and is chosen
-  size_t sec4_lds = 0;
-  int NZ16 = 0;        // k_row2 32-row blocks
-  int NZh = 0;         // k_row2 16-row blocks (row16)
-  bool row16 = false;  // k_row2<16> after k_sec4 (row-block-major partials, NZh <= 320)
-  int NZ4 = 0, NZ2 = 0;  // k_rowv<4> 256-row / k_rowv<2> 128-row blocks
   // (describes one lane's d_z, yet stays here: in the lane, sa_fetch_z after sa_mc_stage would answer differently)
   bool zil_last = false;  // the last decode left z codeword-interleaved ([NC][n][CB], zil_for)
-  size_t sec2_lds = 0;
   std::vector<uint32_t> ordering;
-  uint16_t* d_inv = nullptr;
-  // operators whose z does not fit the section kernels' LDS (n >= 65535, or
-  // the z image past 160 KB): k_secg with 32-bit bucket entries, no batched /
-  // multi-wave kernels
-  bool big = false;
-  uint32_t* d_inv32 = nullptr;
-  uint16_t* d_invb = nullptr;  // k_secb's bank-aware bucket table (build_invb), built on first batched use
-  uint16_t* d_fwdb = nullptr;  // k_secb's Ab table, bank-aware step order per row (build_fwdb), the same
-  uint16_t* d_invl = nullptr;  // the codeword-interleaved k_secb's bucket table, lane-major (k_lane_major)
-  uint32_t* d_hs = nullptr;    // [L] occupied steps of d_invb's halves (build_banked)
-  bool borrowed = false;       // the operator tables are another context's (sa_create_twin): not freed here
-  bool invb_done = false;
-  uint16_t* d_fwd = nullptr;
-  uint32_t* d_fwd2 = nullptr;
+  sa::Tables tab;         // the operator tables (sa_tables.h)
+  bool borrowed = false;  // ... are another context's (sa_create_twin): not freed here
   void* d_A = nullptr;  // dense [np][lda] design matrix (binary32; SA_BACKEND_MATRIX: the context precision)
   // int8 matrix-core dense path (B >= 4; dense_i8.hip): A8 [np8][LMp8], AT8 [LMp8][np8],
   // digit planes of z [3][Bp8][np8] and beta [3][Bp8][LMp8], per-codeword scales
@@ -204,7 +166,7 @@ struct sa_ctx {
   hipEvent_t mc_ev[4] = {};
   std::map<std::tuple<int, int, int, int>, hipGraphExec_t> mc_graphs;
   // host copies of the bucket table inv [L][w] and the Ab table fwd [G][n][4]
-  // (build_tables), kept until the batched tables are built from them (ensure_invb)
+  // (build_tables, sa_tables.hip), kept until the batched tables are built from them (ensure_invb)
   std::vector<uint16_t> h_inv, h_fwd;
 };
 
@@ -243,113 +205,11 @@ int capture_graph(hipStream_t s, F seq, hipGraphExec_t* out) {
   return SA_OK;
 }
 
-// ---- backend / kernel choice rules (shared by the units) --------------------
-constexpr int kI8MinB = 4;   // dense backend: batches at least this large take the int8 GEMM path
-constexpr int kI8MaxS = 16;  // K splits of the int8 A beta GEMM (its Ab partials)
-constexpr int kFMinB = 4;    // matrix backend: batches at least this large take the f32 / f64 GEMM path
-constexpr int kFMaxS = 16;   // K splits of its A beta GEMM
-
-inline size_t rsz(const sa_ctx* c) { return c->prec == SA_PREC_F64 ? 8 : 4; }
-
-// the dense backends: a materialised n x (L*M) matrix streamed by GEMVs
-// (the Hadamard design's, or a caller's own: SA_BACKEND_MATRIX)
-inline bool is_dense(const sa_ctx* c) { return c->backend == SA_BACKEND_DENSE || c->backend == SA_BACKEND_MATRIX; }
-inline bool use_i8(const sa_ctx* c, int B) { return c->backend == SA_BACKEND_DENSE && B >= kI8MinB; }
-inline bool use_fgemm(const sa_ctx* c, int B) { return c->backend == SA_BACKEND_MATRIX && B >= kFMinB; }
-inline bool use_batched(const sa_ctx* c, int B) { return c->CB > 0 && B >= 4; }
-
-// The batched decode with z and the Ab partials interleaved by codeword chunk
-// (SecArgs::zil, 16-byte rows of CB codewords: binary32 CB = 4, binary64
-// CB = 2), row kernel k_rowc.  The default in binary32 (C3 +1.7 %, C4
-// +4.7 %) and, since the binary64 k_secb no longer spills (round 4: one
-// bucket h-step in flight, 16-byte non-temporal beta), in binary64 too (C3
-// 6.30 k -> 6.44 k, C4 3.09-3.12 k -> 3.19 k cw/s; round 3's spilling kernel
-// lost 1.6 %); SA_PLAN_NO_ZIL keeps [B][n]
-inline bool zil_for(const sa_ctx* c, int B) {
-  const bool on = (c->plan & SA_PLAN_NO_ZIL) ? false : true;
-  return on && c->backend == SA_BACKEND_HADAMARD && use_batched(c, B) && c->CB * (int)rsz(c) == 16;
-}
-
+// ---- the kernel choice of a context (sa_shape.h: plan_for, fused_tail) --------
 int dense_parts(const sa_ctx* c, int B);  // sa_dense.hip: Ab partials of the dense A beta (GEMM K splits or GEMV splits)
-
-// Which kernels a decode of B codewords runs, and the counts that follow from
-// the choice: everything (context, B) decides, filled by plan_for alone.  An
-// entry point that launches decode kernels computes it once and hands it to
-// the launchers; nothing of it is kept in the context.
-struct Plan {
-  sa_sec_path sec = SA_SEC_K_SEC;    // the section path of the iterations
-  sa_row_kernel row = SA_ROW_K_ROW;  // the row kernel of the decode (ROW_ABOUT: always k_row)
-  int nz = 0;          // z^2 partials per codeword: the row kernel's blocks per codeword
-  int G = 0, Gb = 0;   // partials per codeword of the loop's producer of abp (A beta) and bbp (beta^2)
-  int pt = 0;          // Ab partials of the loop row-block major (SecArgs::pt): rows per block, 0 for [G][n]
-  int rs = 1;          // row splits of a k_sec / k_secg launch (the loop's, the beta0 start's, sa_Ab / sa_Az)
-  int CB = 1;          // codewords per k_secb workgroup
-  bool zil = false;    // z and the Ab partials codeword-interleaved (zil_for)
-  bool dense() const { return sec == SA_SEC_DENSE || sec == SA_SEC_DENSE_I8 || sec == SA_SEC_MATRIX; }
-  bool batched() const { return sec == SA_SEC_K_SECB; }
-  bool multiwave() const {
-    return sec == SA_SEC_K_SEC2 || sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43 || sec == SA_SEC_K_SEC44;
-  }
-  // k_row2 launches can carry the iters writes (RowArgs::itset); the small-batch Hadamard decode uses them
-  bool row_sets_iters() const { return row == SA_ROW_K_ROW2 || row == SA_ROW_K_ROW2_16; }
-  bool it_row() const { return !dense() && !batched() && row_sets_iters(); }
-  // k_sec4 / k_sec43 / k_sec44 can take the previous estimate as zero (SecArgs::bzero)
-  bool bzero() const { return sec == SA_SEC_K_SEC4 || sec == SA_SEC_K_SEC43 || sec == SA_SEC_K_SEC44; }
-};
-
-// Row kernel for B codewords: k_row2 (32-row blocks, 16-row for one codeword
-// where row16) while B * ceil(n/64) < 4 CUs, else in binary32 k_rowv<4>
-// (n % 4 == 0) or k_rowv<2> (n even) when their blocks cover the CUs twice,
-// else k_row (64 rows); k_rowc behind the codeword-interleaved k_secb.
-// Section path: the GEMMs / GEMVs of a dense backend; k_secb from 4 codewords;
-// a multi-wave kernel (k_sec43 over k_sec44 over k_sec4 over k_sec2) when its workgroups
-// fill at least half of the CUs; else k_sec's (k_secg's) row splits.
-inline Plan plan_for(const sa_ctx* c, int B) {
-  Plan p;
-  const bool f32 = c->prec == SA_PREC_F32;
-  p.zil = zil_for(c, B);
-  if (p.zil) {
-    p.row = SA_ROW_K_ROWC; p.nz = c->NZ2;  // 128-row blocks
-  } else if ((long long)B * c->NZ < 4LL * c->n_cus) {
-    if (c->row16 && B == 1) { p.row = SA_ROW_K_ROW2_16; p.nz = c->NZh; }
-    else { p.row = SA_ROW_K_ROW2; p.nz = c->NZ16; }
-  } else if (c->n % (f32 ? 4 : 2) == 0 && (long long)B * (f32 ? c->NZ4 : c->NZ2) >= 2LL * c->n_cus) {
-    // 16-byte rows: binary32 n % 4 == 0 (256-row blocks) or binary64 n even (128)
-    p.row = SA_ROW_K_ROWV16; p.nz = f32 ? c->NZ4 : c->NZ2;
-  } else if (f32 && c->n % 2 == 0 && (long long)B * c->NZ2 >= 2LL * c->n_cus) {
-    p.row = SA_ROW_K_ROWV8; p.nz = c->NZ2;
-  } else {
-    p.row = SA_ROW_K_ROW; p.nz = c->NZ;
-  }
-  const int wgs = c->G * B;  // k_sec / k_secg: enough row splits to cover every CU
-  p.rs = std::min(4, std::max(1, (c->n_cus + wgs - 1) / wgs));
-  if (is_dense(c)) {
-    p.sec = use_i8(c, B) ? SA_SEC_DENSE_I8 : (use_fgemm(c, B) ? SA_SEC_MATRIX : SA_SEC_DENSE);
-    p.G = dense_parts(c, B);
-    p.Gb = c->Gd;
-  } else if (use_batched(c, B)) {
-    p.sec = SA_SEC_K_SECB;
-    p.G = p.Gb = c->Gb;
-    p.CB = c->CB;
-  } else if (c->backend == SA_BACKEND_HADAMARD && c->G2 > 0 && c->G2 * B * 2 >= c->n_cus) {
-    p.sec = c->sec3 ? SA_SEC_K_SEC43 : (c->sec4q ? SA_SEC_K_SEC44 : (c->sec4 ? SA_SEC_K_SEC4 : SA_SEC_K_SEC2));
-    p.G = p.Gb = c->sec3 ? c->G3 : (c->sec4q ? c->G4 : c->G2);  // triples / quads / pairs of sections
-    if (p.sec != SA_SEC_K_SEC2 && p.row_sets_iters() && c->pt_on) p.pt = p.row == SA_ROW_K_ROW2_16 ? 16 : kRow2Rows;
-  } else {
-    p.sec = c->big ? SA_SEC_K_SECG : SA_SEC_K_SEC;
-    p.G = p.Gb = c->G;
-  }
-  return p;
-}
-
-// Fused tail of a decode: with the early stop off the last launch is known at
-// capture time, so the last section launch of the pair / triple / quad kernels
-// also writes the section decisions and iters (SecArgs::dec, itset), k_decide
-// is never launched, and the last k_row2 step, whose z_T only sa_fetch_z
-// reads, is deferred (sa_lane::row_B).  Depends on (context, B, T, flags) alone.
+inline Plan plan_for(const sa_ctx* c, int B) { return plan_for(*c, B, is_dense(*c) ? dense_parts(c, B) : 0); }
 inline bool fused_tail(const sa_ctx* c, const Plan& p, int T, int flags) {
-  return p.bzero() && p.it_row() && (flags & SA_FLAG_NO_EARLY_STOP) && T > 0 && c->dead == 0 && !c->prof &&
-         !(c->plan & SA_PLAN_NO_FUSED_TAIL);
+  return fused_tail(*c, p, T, flags, c->prof != nullptr);
 }
 
 // t_b: the Monte-Carlo stream's per-slot iteration indices (SecArgs::tb), else null
@@ -357,9 +217,10 @@ template <typename real>
 SecArgs<real> sec_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop, const int* tb = nullptr) {
   SecArgs<real> a;
   const sa_lane& ln = c->at();
-  a.inv = c->d_inv; a.inv32 = c->d_inv32; a.invb = c->d_invb; a.invl = c->d_invl; a.hs = c->d_hs;
-  a.fwd = (const ushort4*)c->d_fwd;
-  a.fwdb = (const ushort4*)c->d_fwdb; a.fwd2 = c->d_fwd2; a.fwd3 = c->d_fwd3; a.c = (const real*)c->d_c;
+  const Tables& tab = c->tab;
+  a.inv = tab.inv; a.inv32 = tab.inv32; a.invb = tab.invb; a.invl = tab.invl; a.hs = tab.hs;
+  a.fwd = (const ushort4*)tab.fwd; a.fwdb = (const ushort4*)tab.fwdb; a.fwd2 = tab.fwd2; a.fwd3 = tab.fwd3;
+  a.c = (const real*)c->d_c;
   a.z = (const real*)ln.d_z; a.beta = (real*)ln.d_beta; a.beta_out = (real*)ln.d_beta; a.out = (real*)c->d_out;
   a.abp = (real*)ln.d_abp; a.bbp = (real*)ln.d_bbp; a.zzp = (const real*)ln.d_zzp;
   a.tau = (real*)ln.d_tau; a.iters = ln.d_iters;
@@ -461,10 +322,14 @@ inline int ensure_stage(sa_ctx* c, size_t count) { return ensure_stage(c, c->at(
 inline int upload(sa_ctx* c, void* dst, const double* src, size_t count) { return upload(c, c->at(), dst, src, count); }
 inline int download(sa_ctx* c, double* dst, const void* src, size_t count) { return download(c, c->at(), dst, src, count); }
 int set_power(sa_ctx* c, const double* Pl);
-int ensure_invb(sa_ctx* c);
 int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int backend, int prec, int device,
                 int plan, const sa_ctx* share = nullptr);
 extern __global__ void k_fill32(uint32_t* p, uint32_t v, size_t nw);
+
+// ---- sa_tables.hip: the operator tables ------------------------------------------
+int build_tables(sa_ctx* c);   // inv / fwd / fwd2 / fwd3 from the ordering, which it validates
+int ensure_invb(sa_ctx* c);    // k_secb's tables (fwdb, invb, hs, invl), built at its first use
+void tables_free(Tables& t);
 
 // ---- sa_sec.hip: the single-codeword section kernels ---------------------------
 template <typename real>

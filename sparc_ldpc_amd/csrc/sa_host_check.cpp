@@ -1,0 +1,253 @@
+// sa_host_check — the operator's host rules from the command line, on a
+// machine without a GPU (sa_shape.h and sa_tables.h only; no HIP).
+//
+//   sa_host_check shape L M n backend prec plan n_cus B
+//     one JSON object: the Shape of the operator, the plan of a decode of B
+//     codewords in sa_plan's field order and, where B runs k_secb,
+//     sa_plan_batched's four numbers; {"error", "message"} for a shape that
+//     sa_create refuses as unsupported.
+//   sa_host_check tables L M n prec plan
+//     draws a valid ordering (per section a seeded shuffle of 1 .. w-1, its
+//     first n), builds every table of the Hadamard operator with the pure
+//     builders and checks what the kernels rely on; exit status 1 with the
+//     first violation on stderr.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+
+#include "sa_shape.h"
+#include "sa_tables.h"
+
+using namespace sa;
+
+static int usage() {
+  std::fprintf(stderr, "usage: sa_host_check shape L M n backend prec plan n_cus B\n"
+                       "       sa_host_check tables L M n prec plan\n");
+  return 2;
+}
+
+static int shape_of(Shape& s, int L, int M, int n, int backend, int prec, int plan, int n_cus) {
+  std::string err;
+  int rc = SA_OK;
+  if (L <= 0 || M <= 0 || n <= 0 || n_cus <= 0 || backend < SA_BACKEND_HADAMARD || backend > SA_BACKEND_MATRIX ||
+      (prec != SA_PREC_F32 && prec != SA_PREC_F64) || (plan & ~SA_PLAN_ALL)) {
+    rc = SA_ERR_ARG;
+    err = "bad arguments";
+  }
+  if (!rc) rc = shape_limits(M, n, backend, err);
+  if (!rc) rc = shape_for(s, L, M, n, backend, prec, plan, n_cus, err);
+  if (rc) std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+  return rc;
+}
+
+static int cmd_shape(int L, int M, int n, int backend, int prec, int plan, int n_cus, int B) {
+  Shape s;
+  if (shape_of(s, L, M, n, backend, prec, plan, n_cus)) return 0;  // reported
+  if (B <= 0) return usage();
+#define F(x) std::printf("\"" #x "\": %lld, ", (long long)s.x);
+  std::printf("{");
+  F(L) F(M) F(Mu) F(dead) F(n) F(w) F(nhi) F(E) F(pow2) F(big)
+  F(G) F(Gb) F(Gd) F(G2) F(G3) F(G4)
+  F(NZ) F(NZ16) F(NZh) F(NZ4) F(NZ2)
+  F(sec_lds) F(sec2_lds) F(sec4_lds) F(sec3_lds) F(sec4q_lds) F(secb_lds)
+  F(sec3) F(sec4) F(sec4q) F(pt_on) F(row16)
+  F(WB) F(CB) F(gpx)
+  F(backend) F(prec) F(plan) F(n_cus)
+#undef F
+  const Plan p = plan_for(s, B);  // (a dense backend's Ab partial count is device state: 0 here)
+  std::printf("\"B\": %d, \"zil\": %d, \"plan_of_B\": [%d, %d, %d, %d, %d, %d, %d, %d]", B, p.zil ? 1 : 0, (int)p.sec, p.G,
+              (p.sec == SA_SEC_K_SEC || p.sec == SA_SEC_K_SECG) ? p.rs : 1, p.CB, p.nz, s.w, (int)p.row, s.n_cus);
+  if (p.batched()) {
+    const SecbOrder so = secb_order(s, B);
+    std::printf(", \"plan_batched\": [%d, %d, %d, %d]", s.Gb, s.WB, so.gp, so.passes);
+  }
+  std::printf("}\n");
+  return 0;
+}
+
+// ---- tables ------------------------------------------------------------------
+#define CHECK(cond, ...)                       \
+  do {                                         \
+    if (!(cond)) {                             \
+      std::fprintf(stderr, "FAILED: " __VA_ARGS__); \
+      std::fprintf(stderr, "\n");              \
+      return 1;                                \
+    }                                          \
+  } while (0)
+
+template <typename T>
+static int check_inv(const Shape& s, const std::vector<uint32_t>& ord, std::vector<T>& inv) {
+  const int L = s.L, n = s.n, w = s.w;
+  inv.assign((size_t)L * w, (T)n);
+  for (int l = 0; l < L; ++l) {
+    std::string bad;
+    CHECK(inv_row(ord.data() + (size_t)l * n, l, n, w, inv.data() + (size_t)l * w, bad), "inv_row: %s", bad.c_str());
+    std::vector<int> where(w, n);  // the inverse, by its definition
+    for (int r = 0; r < n; ++r) where[ord[(size_t)l * n + r]] = r;
+    for (int v = 0; v < w; ++v)
+      CHECK((int)inv[(size_t)l * w + v] == where[v], "inv[%d][%d] = %d, expected %d", l, v, (int)inv[(size_t)l * w + v],
+            where[v]);
+  }
+  // a repeated and an out-of-range value are refused with their messages
+  std::vector<uint32_t> o2(ord.begin(), ord.begin() + n);
+  std::vector<T> il(w, (T)n);
+  std::string bad;
+  if (n > 1) {
+    o2[n - 1] = o2[0];
+    CHECK(!inv_row(o2.data(), 0, n, w, il.data(), bad) && bad.find("repeats value") != std::string::npos,
+          "a repeated value passed inv_row");
+  }
+  o2[0] = (uint32_t)w;
+  std::fill(il.begin(), il.end(), (T)n);
+  CHECK(!inv_row(o2.data(), 0, n, w, il.data(), bad) && bad.find("outside [1, w=") != std::string::npos,
+        "an out-of-range value passed inv_row");
+  return 0;
+}
+
+static int check_fwd(const Shape& s, const std::vector<uint32_t>& ord, std::vector<uint16_t>& fwd) {
+  const int L = s.L, n = s.n, M = s.M, lgM = ilog2(M);
+  fwd.assign((size_t)fwd_groups(L) * n * kSpw, 0);
+  std::vector<uint32_t> fwd2(s.big ? 0 : (size_t)((L + 1) / 2) * n, 0), fwd3(s.sec3 ? (size_t)s.G3 * n : 0, 0);
+  for (int l = 0; l < L; ++l)
+    fwd_section(ord.data() + (size_t)l * n, l, n, M, fwd.data(), s.big ? nullptr : fwd2.data(),
+                s.sec3 ? fwd3.data() : nullptr);
+  CHECK(!s.sec3 || M <= 512, "k_sec43's 10-bit fields with M = %d", M);
+  const int Lp = fwd_groups(L) * kSpw;
+  for (int l = 0; l < Lp; ++l)
+    for (int r = 0; r < n; ++r) {
+      const uint32_t v = l < L ? ord[(size_t)l * n + r] : 0;
+      const unsigned k = l < L ? (v & (uint32_t)(M - 1)) : 0, sg = l < L ? (__builtin_popcount(v >> lgM) & 1) : 0;
+      const uint16_t e = fwd[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)];
+      CHECK((e & 0x7fffu) == k && (unsigned)(e >> 15) == sg, "fwd[%d][%d] = %#x, expected k %u sign %u", l, r, e, k, sg);
+      if (!s.big && l < (L + 1) / 2 * 2) {
+        const uint32_t e2 = (fwd2[(size_t)(l / 2) * n + r] >> (16 * (l & 1))) & 0xffffu;
+        CHECK((e2 & 0x7fffu) == k && (e2 >> 15) == sg, "fwd2[%d][%d] = %#x, expected k %u sign %u", l, r, e2, k, sg);
+      }
+      if (s.sec3 && l < s.G3 * 3) {
+        const uint32_t e3 = (fwd3[(size_t)(l / 3) * n + r] >> (10 * (l % 3))) & 0x3ffu;
+        CHECK((e3 & 0x1ffu) == k && (e3 >> 9) == sg, "fwd3[%d][%d] = %#x, expected k %u sign %u", l, r, e3, k, sg);
+      }
+    }
+  return 0;
+}
+
+static int check_banked(const Shape& s, const std::vector<uint16_t>& inv) {
+  const int L = s.L, n = s.n, w = s.w, M = s.M, nhi = s.nhi, Sh = nhi / 2, kh = invb_kh(s);
+  const std::vector<int> sets = invb_sets(s.E, s.prec == SA_PREC_F32);
+  {  // the sets cover every column once
+    std::vector<int> seen(M, 0);
+    for (int col : sets) {
+      CHECK(col >= 0 && col < M, "invb_sets: column %d outside the section", col);
+      ++seen[col];
+    }
+    for (int col = 0; col < M; ++col) CHECK(seen[col] == 1, "invb_sets: column %d in %d sets", col, seen[col]);
+  }
+  std::vector<uint16_t> out((size_t)L * w, 0xffff);
+  std::vector<uint32_t> hs(L, 0);
+  for (int l = 0; l < L; ++l)
+    banked_section(M, n, nhi, l, inv.data() + (size_t)l * w, out.data() + (size_t)l * w, sets, 16, 16, hs.data(), kh);
+  for (int l = 0; l < L; ++l) {
+    const uint16_t *il = inv.data() + (size_t)l * w, *ob = out.data() + (size_t)l * w;
+    for (int cls = 0; cls < 2; ++cls) {
+      const int S = (int)((hs[l] >> (16 * cls)) & 0xffffu);
+      // whole blocks of kh steps within the half (a half shorter than kh: all of it)
+      CHECK((S % kh == 0 && S >= kh && S <= Sh) || (Sh < kh && S == Sh), "hs[%d] class %d = %d (kh %d, nhi/2 %d)", l, cls, S,
+            kh, Sh);
+      for (int col = 0; col < M; ++col) {
+        std::vector<int> want, got;
+        for (int h = 0; h < nhi; ++h)
+          if ((__builtin_popcount(h) & 1) == cls && il[(size_t)h * M + col] != (uint16_t)n) want.push_back(il[(size_t)h * M + col]);
+        for (int st = 0; st < Sh; ++st) {
+          const int v = ob[(size_t)(cls * Sh + st) * M + col];
+          if (st >= S) CHECK(v == n, "invb[%d] class %d step %d column %d = %d past hs = %d, expected n", l, cls, st, col, v, S);
+          else if (v < n) got.push_back(v);
+          else CHECK(v < n + kInvbZeroRows, "invb[%d] class %d step %d column %d = %d: no zero row", l, cls, st, col, v);
+        }
+        std::sort(want.begin(), want.end());
+        std::sort(got.begin(), got.end());
+        CHECK(want == got, "invb[%d] class %d column %d: its rows are not those of inv", l, cls, col);
+      }
+    }
+  }
+  return 0;
+}
+
+static int check_fwdb(const Shape& s, const std::vector<uint16_t>& fwd) {
+  const int W = s.WB, M = s.M, n = s.n, L = s.L, E = s.E, npad = (n + 63) & ~63;
+  const int rowb = s.CB * (int)rsz(&s);
+  const bool search = !(s.plan & SA_PLAN_NO_BANKS), b128 = rowb == 16;
+  CHECK(W * M < 32768, "k_secb: W * M >= 2^15");
+  std::vector<uint16_t> out((size_t)s.Gb * W * npad, 0xffff);
+  for (int g = 0; g < s.Gb; ++g) fwdb_group(W, M, n, L, E, rowb, search, g, fwd.data(), npad, out.data());
+  auto at = [&](int g, int r, int st) { return out[((size_t)(g * (W / 4) + st / 4) * npad + r) * 4 + (st % 4)]; };
+  const int gsize = b128 ? 16 : 32;
+  for (int g = 0; g < s.Gb; ++g) {
+    for (int r = 0; r < n; ++r) {
+      std::vector<int> want(W), got(W);
+      for (int sl = 0; sl < W; ++sl) {
+        const int l = g * W + sl;
+        const uint16_t e = l < L ? fwd[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)] : 0;  // past L: column 0, +
+        want[sl] = (int)(((unsigned)sl * M + t_pos(E, e & 0x7fffu)) | (e & 0x8000u));
+        got[sl] = at(g, r, sl);
+      }
+      if (search) {  // a re-ordering of the same terms
+        std::sort(want.begin(), want.end());
+        std::sort(got.begin(), got.end());
+      }
+      CHECK(want == got, "fwdb group %d row %d: its entries are not the row's sections%s", g, r,
+            search ? "" : " in section order");
+    }
+    for (int b0 = 0; b0 < npad; b0 += 64)
+      for (int G = 0; G < 64 / gsize; ++G) {
+        int lanes[32], real = -1;
+        for (int j = 0; j < gsize; ++j) {
+          lanes[j] = b128 ? kLdsGroups16[G][j] : G * 32 + j;
+          if (real < 0 && b0 + lanes[j] < n) real = b0 + lanes[j];
+        }
+        for (int j = 0; j < gsize; ++j) {
+          const int r = b0 + lanes[j];
+          if (r < n) continue;
+          for (int st = 0; st < W; ++st)  // an idle row: a real row of its lane group, else column 0 of section st
+            CHECK(at(g, r, st) == (real >= 0 ? at(g, real, st) : (uint16_t)((unsigned)st * M)),
+                  "fwdb group %d idle row %d step %d = %#x", g, r, st, at(g, r, st));
+        }
+      }
+  }
+  return 0;
+}
+
+static int cmd_tables(int L, int M, int n, int prec, int plan) {
+  Shape s;
+  if (shape_of(s, L, M, n, SA_BACKEND_HADAMARD, prec, plan, Shape().n_cus)) return 1;
+  std::vector<uint32_t> ord((size_t)L * n), all(s.w - 1);
+  for (int l = 0; l < L; ++l) {
+    std::mt19937 rng(0x0d0000u + (uint32_t)l);
+    std::iota(all.begin(), all.end(), 1u);
+    std::shuffle(all.begin(), all.end(), rng);
+    std::copy(all.begin(), all.begin() + n, ord.begin() + (size_t)l * n);
+  }
+  std::vector<uint16_t> inv, fwd;
+  std::vector<uint32_t> inv32;
+  if (s.big ? check_inv(s, ord, inv32) : check_inv(s, ord, inv)) return 1;
+  if (check_fwd(s, ord, fwd)) return 1;
+  const bool secb = s.CB > 0 && !s.big, banked = invb_banked(s);
+  if (secb && check_fwdb(s, fwd)) return 1;
+  if (banked && check_banked(s, inv)) return 1;
+  std::printf("{\"ok\": 1, \"M\": %d, \"dead\": %d, \"w\": %d, \"E\": %d, \"big\": %d, \"sec3\": %d, \"CB\": %d, \"WB\": %d, "
+              "\"fwdb\": %d, \"fwdb_lanes\": %d, \"banked\": %d, \"kh\": %d, \"search\": %d}\n",
+              s.M, s.dead, s.w, s.E, s.big ? 1 : 0, s.sec3 ? 1 : 0, s.CB, s.WB, secb ? 1 : 0,
+              secb ? (s.CB * (int)rsz(&s) == 16 ? 16 : 32) : 0, banked ? 1 : 0, banked ? invb_kh(s) : 0,
+              (plan & SA_PLAN_NO_BANKS) ? 0 : 1);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) return usage();
+  std::vector<int> a;
+  for (int i = 2; i < argc; ++i) a.push_back(std::atoi(argv[i]));
+  if (!std::strcmp(argv[1], "shape") && a.size() == 8) return cmd_shape(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
+  if (!std::strcmp(argv[1], "tables") && a.size() == 5) return cmd_tables(a[0], a[1], a[2], a[3], a[4]);
+  return usage();
+}

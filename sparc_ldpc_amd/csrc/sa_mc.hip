@@ -350,7 +350,7 @@ int mc_turnover(sa_ctx* c, const McArgs& a) {
 template <typename real>
 int mc_encode_all(sa_ctx* c, const McArgs& a, int nreps) {
   k_mc_encode<real><<<dim3(c->NZ2, (nreps + kFillSlots - 1) / kFillSlots), 128, 0, c->at().stream>>>(
-      a, nreps, (const ushort4*)c->d_fwd, c->d_cd, std::sqrt((double)c->n), (real*)c->d_mc_y, (real*)c->d_mc_zzp);
+      a, nreps, (const ushort4*)c->tab.fwd, c->d_cd, std::sqrt((double)c->n), (real*)c->d_mc_y, (real*)c->d_mc_zzp);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -573,7 +573,7 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   if (B < 4 || B > kMcStepThreads || T <= 0) return fail(SA_ERR_ARG, "sa_mc_run: B in [4, 1024], T > 0");
   if (c->mc_nreps <= 0) return fail(SA_ERR_ARG, "sa_mc_run: no reps staged (sa_mc_stage)");
   if (!c->shared_power || c->pb_on) return fail(SA_ERR_ARG, "sa_mc_run: one power allocation must be staged");
-  if (c->backend != SA_BACKEND_HADAMARD || !c->pow2 || c->big || !zil_for(c, B))
+  if (c->backend != SA_BACKEND_HADAMARD || !c->pow2 || c->big || !zil_for(*c, B))
     return fail(SA_ERR_UNSUPPORTED, "sa_mc_run: needs the batched codeword-interleaved Hadamard decode "
                                     "(k_secb + k_rowc)");
   HIP_TRY(hipSetDevice(c->device));

@@ -261,7 +261,7 @@ static bool pipelining(const sa_ctx* c) {
 
 // Whether a run of B codewords may rotate lanes at all (the plan, the backend, the batch).
 static bool lane_shape(const sa_ctx* c, int B) {
-  return c->backend == SA_BACKEND_HADAMARD && !use_batched(c, B) && !(c->plan & (SA_PLAN_EAGER | SA_PLAN_NO_LANES));
+  return c->backend == SA_BACKEND_HADAMARD && !use_batched(*c, B) && !(c->plan & (SA_PLAN_EAGER | SA_PLAN_NO_LANES));
 }
 
 void graphs_clear(GraphMap& m) {
@@ -344,7 +344,7 @@ int ensure_workspace(sa_ctx* c, int B, int T) {
   if ((rc = dev_alloc(c, (void**)&c->d_idx, nB * c->L * sizeof(int32_t)))) return rc;
   if ((rc = dev_alloc(c, &c->d_cb, nB * c->L * s))) return rc;
   if ((rc = dev_alloc(c, &c->d_Pb, nB * s))) return rc;
-  if (is_dense(c))
+  if (is_dense(*c))
     if ((rc = dev_alloc(c, &c->d_azp, nB * c->RS * c->lda * s))) return rc;
   if (c->backend == SA_BACKEND_HOST)  // the caller's A^T z, one partial per codeword
     if ((rc = dev_alloc(c, &c->d_azp, nB * c->lda * s))) return rc;
@@ -363,6 +363,9 @@ int ensure_stage(sa_ctx* c, sa_lane& l, size_t count) {
   return SA_OK;
 }
 
+// k_convert's grid for count values: 256 per block, at least one block, at most 4096
+static int convert_blocks(size_t count) { return (int)std::min<size_t>(std::max<size_t>((count + 255) / 256, 1), 4096); }
+
 // Host fp64 -> device `real` buffer (through the fp64 staging buffer).
 int upload(sa_ctx* c, sa_lane& l, void* dst, const double* src, size_t count) {
   if (c->prec == SA_PREC_F64) {
@@ -372,8 +375,7 @@ int upload(sa_ctx* c, sa_lane& l, void* dst, const double* src, size_t count) {
   int rc = ensure_stage(c, l, count);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(l.d_stage, src, count * 8, hipMemcpyHostToDevice, l.stream));
-  const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-  k_convert<double, float><<<blocks > 0 ? blocks : 1, 256, 0, l.stream>>>(l.d_stage, (float*)dst, count);
+  k_convert<double, float><<<convert_blocks(count), 256, 0, l.stream>>>(l.d_stage, (float*)dst, count);
   HIP_TRY(hipGetLastError());
   return SA_OK;
 }
@@ -385,8 +387,7 @@ int download(sa_ctx* c, sa_lane& l, double* dst, const void* src, size_t count) 
   }
   int rc = ensure_stage(c, l, count);
   if (rc) return rc;
-  const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-  k_convert<float, double><<<blocks > 0 ? blocks : 1, 256, 0, l.stream>>>((const float*)src, l.d_stage, count);
+  k_convert<float, double><<<convert_blocks(count), 256, 0, l.stream>>>((const float*)src, l.d_stage, count);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(dst, l.d_stage, count * 8, hipMemcpyDeviceToHost, l.stream));
   return SA_OK;
@@ -509,7 +510,7 @@ static void tail_mark(sa_ctx* c, int B, int T, int flags) {
 }
 
 int ensure_beta2(sa_ctx* c, int B) {
-  if (is_dense(c) || use_batched(c, B) || c->at().beta2_cap >= c->Bcap) return SA_OK;
+  if (is_dense(*c) || use_batched(*c, B) || c->at().beta2_cap >= c->Bcap) return SA_OK;
   if (int rcl = lanes_release(c)) return rcl;
   // lane 0 has none yet (lane 1 is created with its own; a grown workspace drops lane 0's)
   if (int rc = beta2_alloc(c, c->lane[0], c->Bcap)) return rc;
@@ -517,12 +518,10 @@ int ensure_beta2(sa_ctx* c, int B) {
   return SA_OK;
 }
 
-int ensure_invb(sa_ctx* c);
-
 template <typename real>
 int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   int rc0 = ensure_beta2(c, B);
-  if (!rc0 && use_batched(c, B)) rc0 = ensure_invb(c);  // before any capture: it uploads
+  if (!rc0 && use_batched(*c, B)) rc0 = ensure_invb(c);  // before any capture: it uploads
   if (rc0) return rc0;
   // Decode lanes: a small-batch graph decode without beta0, issued while the
   // previous step is outstanding, takes the lane the previous run did not, so
@@ -532,7 +531,7 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
     if (!c->lanes_on)
       if (int rcl = lane_create(c)) return rcl;
     lane_switch(c, 1 - c->cur);
-  } else if (use_batched(c, B)) {
+  } else if (use_batched(*c, B)) {
     lane_switch(c, 0);  // lane 1's buffers hold no batched layout (no chunk padding, no k_secb partials)
   }
   {
@@ -543,32 +542,29 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   }
   if (int rcy = y_sync(c)) return rcy;  // a lane whose y is older than the latest staged one
   sa_lane& ln = c->at();
-  if (c->plan & SA_PLAN_EAGER) {  // eager launches instead of the captured graph
-    HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
-    int rc = seq_amp<real>(c, B, T, flags, has_b0);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
-    tail_mark(c, B, T, flags);
-    c->last_B = B;
-    c->last_T = T;
-    c->zil_last = zil_for(c, B);
-    return SA_OK;
-  }
-  // the power-allocation mode selects the captured kernel arguments (c, P arrays)
-  const auto key = std::make_tuple(B, T, flags | (c->pb_on ? 0x10000 : 0), has_b0);
-  auto it = ln.graphs.find(key);
-  if (it == ln.graphs.end()) {
-    hipGraphExec_t ex = nullptr;
-    if (int rc = capture_graph(ln.stream, [&] { return seq_amp<real>(c, B, T, flags, has_b0); }, &ex)) return rc;
-    it = ln.graphs.emplace(key, ex).first;
+  hipGraphExec_t graph = nullptr;  // stays null: eager launches instead of the captured graph
+  if (!(c->plan & SA_PLAN_EAGER)) {
+    // the power-allocation mode selects the captured kernel arguments (c, P arrays)
+    const auto key = std::make_tuple(B, T, flags | (c->pb_on ? 0x10000 : 0), has_b0);
+    auto it = ln.graphs.find(key);
+    if (it == ln.graphs.end()) {
+      hipGraphExec_t ex = nullptr;
+      if (int rc = capture_graph(ln.stream, [&] { return seq_amp<real>(c, B, T, flags, has_b0); }, &ex)) return rc;
+      it = ln.graphs.emplace(key, ex).first;
+    }
+    graph = it->second;
   }
   HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
-  HIP_TRY(hipGraphLaunch(it->second, ln.stream));
+  if (graph) {
+    HIP_TRY(hipGraphLaunch(graph, ln.stream));
+  } else if (int rc = seq_amp<real>(c, B, T, flags, has_b0)) {
+    return rc;
+  }
   HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
   tail_mark(c, B, T, flags);
   c->last_B = B;
   c->last_T = T;
-  c->zil_last = zil_for(c, B);  // the layout d_z is left in by THIS run (a cached graph does not run seq_amp)
+  c->zil_last = zil_for(*c, B);  // the layout d_z is left in by THIS run (a cached graph does not run seq_amp)
   return SA_OK;
 }
 
@@ -671,7 +667,7 @@ int set_power(sa_ctx* c, const double* Pl) {
 // (amp_exit.py:113-116) as a mask, per codeword, in one batch.
 int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   if (!Pl) return fail(SA_ERR_ARG, "Pl is NULL");
-  if (is_dense(c)) return fail(SA_ERR_UNSUPPORTED, "per-codeword power: Hadamard backend only");
+  if (is_dense(*c)) return fail(SA_ERR_UNSUPPORTED, "per-codeword power: Hadamard backend only");
   const size_t L = (size_t)c->L;
   for (int k = 0; k < sa_ctx::kLanes; ++k)
     if (int rcf = row_flush(c, k)) return rcf;
@@ -704,447 +700,6 @@ int set_power_batch(sa_ctx* c, int B, const double* Pl) {
   return SA_OK;
 }
 
-// Tables of a k_secg operator: the bucket table with 32-bit row entries and
-// the 4-section Ab table (k | sign << 15 per row, any n).
-int build_tables_big(sa_ctx* c) {
-  const int L = c->L, n = c->n, w = c->w, M = c->M;
-  const int lgM = ilog2(M);
-  std::vector<uint32_t> inv((size_t)L * w, (uint32_t)n);
-  const int G = (L + kSG - 1) / kSG * (kSG / kSpw);
-  std::vector<uint16_t> fwd((size_t)G * n * kSpw, 0);
-  for (int l = 0; l < L; ++l) {
-    const uint32_t* o = c->ordering.data() + (size_t)l * n;
-    uint32_t* il = inv.data() + (size_t)l * w;
-    for (int r = 0; r < n; ++r) {
-      const uint32_t v = o[r];
-      if (v == 0 || v >= (uint32_t)w)
-        return fail(SA_ERR_ORDERING, "ordering[" + std::to_string(l) + "," + std::to_string(r) +
-                                         "] = " + std::to_string(v) + " outside [1, w=" + std::to_string(w) + ")");
-      if (il[v] != (uint32_t)n)
-        return fail(SA_ERR_ORDERING, "ordering row " + std::to_string(l) + " repeats value " + std::to_string(v));
-      il[v] = (uint32_t)r;
-      const uint32_t hi = v >> lgM;
-      fwd[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)] =
-          (uint16_t)((v & (uint32_t)(M - 1)) | ((__builtin_popcount(hi) & 1u) << 15));
-    }
-  }
-  int rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_inv32, inv.size() * 4))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_fwd, fwd.size() * 2))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_inv32, inv.data(), inv.size() * 4, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipStreamSynchronize(c->at().stream));
-  return SA_OK;
-}
-
-int build_tables(sa_ctx* c) {
-  const int L = c->L, n = c->n, w = c->w, M = c->M;
-  const int lgM = ilog2(M);
-  if (c->big) return build_tables_big(c);
-  std::vector<uint16_t> inv((size_t)L * w, (uint16_t)n);
-  const int G = (L + kSG - 1) / kSG * (kSG / kSpw);  // padded to whole batched groups
-  std::vector<uint16_t> fwd((size_t)G * n * kSpw, 0);  // [G][n][4]; missing sections -> (k 0, +)
-  std::vector<uint32_t> fwd2((size_t)((L + 1) / 2) * n, 0);  // [L/2][n] section pairs
-  std::vector<uint32_t> fwd3(c->sec3 ? (size_t)c->G3 * n : 0, 0);  // [L/3][n] section triples
-  // sections in blocks of 12 over the host's cores (a pair / triple word is
-  // filled by one block); the first bad entry of each section is reported
-  std::vector<std::string> bad((size_t)L);
-  parallel_for(L, 12, [&](int l) {
-    const uint32_t* o = c->ordering.data() + (size_t)l * n;
-    uint16_t* il = inv.data() + (size_t)l * w;
-    for (int r = 0; r < n; ++r) {
-      const uint32_t v = o[r];
-      if (v == 0 || v >= (uint32_t)w) {
-        bad[l] = "ordering[" + std::to_string(l) + "," + std::to_string(r) + "] = " + std::to_string(v) +
-                 " outside [1, w=" + std::to_string(w) + ")";
-        return;
-      }
-      if (il[v] != (uint16_t)n) {
-        bad[l] = "ordering row " + std::to_string(l) + " repeats value " + std::to_string(v);
-        return;
-      }
-      il[v] = (uint16_t)r;
-      const uint32_t hi = v >> lgM;
-      const uint16_t e = (uint16_t)((v & (uint32_t)(M - 1)) | ((__builtin_popcount(hi) & 1u) << 15));
-      fwd[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)] = e;
-      fwd2[(size_t)(l / 2) * n + r] |= (uint32_t)e << (16 * (l & 1));
-      if (c->sec3)  // M <= 512: k in 9 bits, the sign in bit 9 of a 10-bit field
-        fwd3[(size_t)(l / 3) * n + r] |= (uint32_t)((e & 0x1ffu) | ((e >> 15) << 9)) << (10 * (l % 3));
-    }
-  });
-  for (int l = 0; l < L; ++l)
-    if (!bad[l].empty()) return fail(SA_ERR_ORDERING, bad[l]);
-  int rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_inv, inv.size() * 2))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_fwd, fwd.size() * 2))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->d_fwd2, fwd2.size() * 4))) return rc;
-  if (c->sec3 && (rc = dev_alloc(c, (void**)&c->d_fwd3, fwd3.size() * 4))) return rc;
-  // On the context's (non-blocking) stream and waited for: a pageable
-  // hipMemcpy may return once the data is staged, before the DMA lands, and
-  // the null stream does not order the kernels of a non-blocking stream.
-  HIP_TRY(hipMemcpyAsync(c->d_inv, inv.data(), inv.size() * 2, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd, fwd.data(), fwd.size() * 2, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipMemcpyAsync(c->d_fwd2, fwd2.data(), fwd2.size() * 4, hipMemcpyHostToDevice, c->at().stream));
-  if (c->sec3)
-    HIP_TRY(hipMemcpyAsync(c->d_fwd3, fwd3.data(), fwd3.size() * 4, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipStreamSynchronize(c->at().stream));
-  if (c->backend == SA_BACKEND_HADAMARD && c->CB > 0) {  // kept for the batched tables (ensure_invb)
-    c->h_inv = std::move(inv);
-    c->h_fwd = std::move(fwd);
-  }
-  return SA_OK;
-}
-
-// ---- bank-aware bucket order --------------------------------------------
-// The batched section kernel gathers z from LDS, one read per (bucket step,
-// element) for a whole wave: 64 random row addresses, served in fixed lane
-// groups (MI355X_MICROARCH.md §LDS) where each extra distinct address on a
-// busy bank adds one LDS cycle.  k_secb reads 16-byte rows of CB codewords
-// (ds_read_b128: four 16-lane groups, 16 bank groups = row % 16).  Visited in
-// h order the c3 gather took 2.30 LDS cycles per lane group.  (The same
-// order for the single-codeword kernels' 4-byte reads — two 32-lane groups,
-// 32 banks — measured neutral: those kernels are latency-bound)  The sum of a
-// bucket column k over its slots h does not depend on the order of the
-// slots, so these tables re-order them: the slots of sign +1 (popcount(h)
-// even) fill steps 0 .. nhi/2 - 1, those of sign -1 steps nhi/2 .. nhi - 1
-// (the sign stays uniform per step), and within each half a local search
-// swaps a column's slots between steps to minimise, per lane group, the
-// largest number of distinct rows on one bank (c3: 1.1 cycles per group
-// instead of 2.3).  Empty slots read one of `nbank` zero rows n .. n+nbank-1,
-// the one on the step's least loaded bank (all empty lanes of a group read the
-// same row: a broadcast).  Seeded per section: the table, and every decode,
-// is reproducible.
-constexpr int kLdsGroups16[4][16] = {  // ds_read_b128
-    {0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-    {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
-    {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
-    {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
-
-// sets: nsets x gsize columns read by one lane group of one read
-// instruction; writes out[h * M + k] (h < nhi) for every column of the sets
-void banked_section(const sa_ctx* c, int l, const uint16_t* inv_l, uint16_t* out, const std::vector<int>& sets,
-                    int gsize, int nbank, uint32_t* hs, int kh) {
-  const int M = c->M, n = c->n, Sh = c->nhi / 2;
-  const int nsets = (int)sets.size() / gsize;
-  std::mt19937 rng(0x5eed0000u + (uint32_t)l);
-  // per sign class, the section's largest number of occupied slots in one
-  // column (rounded up to whole blocks of kh steps): the steps used
-  int Sc[2] = {0, 0};
-  for (int cls = 0; cls < 2; ++cls) {
-    for (int col = 0; col < M; ++col) {
-      int m = 0;
-      for (int h = 0; h < c->nhi; ++h)
-        if ((__builtin_popcount(h) & 1) == cls && inv_l[(size_t)h * M + col] != (uint16_t)n) ++m;
-      Sc[cls] = std::max(Sc[cls], m);
-    }
-    Sc[cls] = std::min(Sh, std::max(kh, (Sc[cls] + kh - 1) / kh * kh));
-  }
-  if (hs) hs[l] = (uint32_t)Sc[0] | ((uint32_t)Sc[1] << 16);
-  std::vector<int> A((size_t)gsize * Sh), cnt((size_t)Sh * nbank), emp(Sh), cost(Sh);
-  auto step_cost = [&](int st) {
-    const int* ct = &cnt[(size_t)st * nbank];
-    int mx = 0, mn = 1 << 30;
-    for (int g = 0; g < nbank; ++g) { mx = std::max(mx, ct[g]); mn = std::min(mn, ct[g]); }
-    return emp[st] ? std::max(mx, mn + 1) : mx;
-  };
-  auto take = [&](int st, int v, int d) {
-    if (v < 0) emp[st] += d;
-    else cnt[(size_t)st * nbank + (v % nbank)] += d;
-  };
-  for (int si = 0; si < nsets; ++si) {
-    const int* cols = &sets[(size_t)si * gsize];
-    for (int cls = 0; cls < 2; ++cls) {
-      const int S = Sc[cls];
-      std::fill(cnt.begin(), cnt.end(), 0);
-      std::fill(emp.begin(), emp.end(), 0);
-      for (int j = 0; j < gsize; ++j) {
-        int m = 0;
-        int* a = &A[(size_t)j * S];
-        for (int h = 0; h < c->nhi; ++h)
-          if ((__builtin_popcount(h) & 1) == cls && inv_l[(size_t)h * M + cols[j]] != (uint16_t)n)
-            a[m++] = inv_l[(size_t)h * M + cols[j]];
-        for (; m < S; ++m) a[m] = -1;
-        std::shuffle(a, a + S, rng);
-        for (int st = 0; st < S; ++st) take(st, a[st], +1);
-      }
-      for (int st = 0; st < S; ++st) cost[st] = step_cost(st);
-      // moves target the conflict: a column of the worst step that sits on
-      // that step's most loaded bank (random columns: the same tables after
-      // 4000 moves that these reach after 256, c3 1.10 / c4 1.005 LDS cycles
-      // per lane group, ~1 / 16 of the host time)
-      for (int it = 0; it < 256; ++it) {
-        int s1 = 0;
-        for (int st = 1; st < S; ++st)
-          if (cost[st] > cost[s1]) s1 = st;
-        if (cost[s1] <= 1) break;  // conflict-free
-        int j;
-        {
-          const int* ct = &cnt[(size_t)s1 * nbank];
-          int bm = 0;
-          for (int g = 1; g < nbank; ++g)
-            if (ct[g] > ct[bm]) bm = g;
-          int cand[64], nc = 0;
-          for (int jj = 0; jj < gsize && nc < 64; ++jj) {
-            const int v = A[(size_t)jj * S + s1];
-            if (v >= 0 && v % nbank == bm) cand[nc++] = jj;
-          }
-          j = nc > 0 ? cand[rng() % (unsigned)nc] : (int)(rng() % (unsigned)gsize);
-        }
-        const int s2 = (int)(rng() % (unsigned)S);
-        if (s2 == s1) continue;
-        int& x = A[(size_t)j * S + s1];
-        int& y = A[(size_t)j * S + s2];
-        if (x == y) continue;
-        take(s1, x, -1); take(s2, y, -1); take(s1, y, +1); take(s2, x, +1);
-        const int n1 = step_cost(s1), n2 = step_cost(s2);
-        if (n1 + n2 <= cost[s1] + cost[s2]) {
-          std::swap(x, y);
-          cost[s1] = n1;
-          cost[s2] = n2;
-        } else {
-          take(s1, y, -1); take(s2, x, -1); take(s1, x, +1); take(s2, y, +1);
-        }
-      }
-      for (int st = 0; st < S; ++st) {
-        int zg = 0;
-        for (int g = 1; g < nbank; ++g)
-          if (cnt[(size_t)st * nbank + g] < cnt[(size_t)st * nbank + zg]) zg = g;
-        const int zrow = n + ((zg - n % nbank + nbank) % nbank);  // the zero row on bank zg
-        for (int j = 0; j < gsize; ++j) {
-          const int v = A[(size_t)j * S + st];
-          out[(size_t)(cls * Sh + st) * M + cols[j]] = (uint16_t)(v >= 0 ? v : zrow);
-        }
-      }
-      for (int st = S; st < Sh; ++st)  // never gathered (every column's slots sit in the first S steps)
-        for (int j = 0; j < gsize; ++j) out[(size_t)(cls * Sh + st) * M + cols[j]] = (uint16_t)n;
-    }
-  }
-}
-
-// All sections in parallel on the host; uploaded into *dst.
-int build_banked(sa_ctx* c, const std::vector<int>& sets, int gsize, int nbank, uint16_t** dst, int kh) {
-  const int L = c->L, n = c->n, w = c->w;
-  std::vector<uint16_t> inv_own, out((size_t)L * w, 0);
-  std::vector<uint32_t> hs((size_t)L, 0);
-  if (c->h_inv.size() != (size_t)L * w) {  // the host copy went (or never was): rebuild it
-    inv_own.assign((size_t)L * w, (uint16_t)n);
-    parallel_for(L, 1, [&](int l) {
-      for (int r = 0; r < n; ++r) inv_own[(size_t)l * w + c->ordering[(size_t)l * n + r]] = (uint16_t)r;
-    });
-  }
-  const uint16_t* inv = inv_own.empty() ? c->h_inv.data() : inv_own.data();
-  parallel_for(L, 1, [&](int l) {
-    banked_section(c, l, inv + (size_t)l * w, out.data() + (size_t)l * w, sets, gsize, nbank, hs.data(), kh);
-  });
-  int rc = dev_alloc(c, (void**)dst, out.size() * 2);
-  if (!rc) rc = dev_alloc(c, (void**)&c->d_hs, hs.size() * 4);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(*dst, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipMemcpyAsync(c->d_hs, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipStreamSynchronize(c->at().stream));
-  return SA_OK;
-}
-
-bool banks_enabled(const sa_ctx* c) { return !(c->plan & SA_PLAN_NO_BANKS); }
-
-// [L][w] bucket table (slot h * M + column) -> [L][nhi][64][E]: lane L's E
-// entries of step h contiguous, in register order (columns elem_index<E >= 4>
-// of lane L ^ 3 in binary32 (sgn), of L in binary64)
-__global__ void k_lane_major(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int L, int nhi, int M,
-                             int w, int E, int sgn) {
-  const size_t tot = (size_t)L * nhi * 64 * E;
-  for (size_t x = blockIdx.x * (size_t)blockDim.x + threadIdx.x; x < tot; x += (size_t)gridDim.x * blockDim.x) {
-    const int i = (int)(x % E);
-    size_t t = x / E;
-    const int lane = (int)(t % 64);
-    t /= 64;
-    const int h = (int)(t % nhi), l = (int)(t / nhi);
-    const int lp = sgn ? (lane ^ 3) : lane;
-    const int e = (i / 4) * 256 + lp * 4 + (i % 4);
-    dst[x] = src[(size_t)l * w + (size_t)h * M + e];
-  }
-}
-
-// ---- bank-aware Ab row order ----------------------------------------------
-// k_secb's Ab pass gives lane L of a wave row r0 + L and reads, per step, one
-// staged T element (section s, column k(r, s)) per lane: for 16-byte T rows a
-// ds_read_b128 whose four 16-lane groups each take one LDS cycle per distinct
-// row on their busiest 16-byte bank group (MI355X_MICROARCH.md §LDS).  In
-// section order the columns k(r, s) of 16 rows are random: ~3 cycles per
-// group.  A row's partial sum does not care in which order its W sections
-// are added, so each row gets its own step order: a local search over swaps
-// of two steps of one row that lowers, per lane group, the largest number of
-// rows on one bank in a step (the addition order changes, the terms do not).
-// Rows n .. npad-1 (the last block's idle lanes) repeat a real row of their
-// lane group (a broadcast); sections past L read column 0 (a broadcast).
-// LDS position of T column e in k_secb's staged image: the element index of
-// (lane, register i) is (i / Q) 64 Q + lane Q + i % Q (elem_index), staged at
-// (i / Q) 64 Q + (i % Q) 64 + lane
-unsigned t_pos(int E, unsigned e) {
-  const unsigned Q = E < 4 ? (unsigned)E : 4u;
-  const unsigned blk = e / (64 * Q), rem = e % (64 * Q);
-  return blk * 64 * Q + (rem % Q) * 64 + rem / Q;
-}
-
-void fwdb_group(const sa_ctx* c, int g, const uint16_t* fwd, int npad, uint16_t* out) {
-  const int W = c->WB, M = c->M, n = c->n, L = c->L;
-  const int rowb = c->CB * (int)rsz(c);  // bytes per staged T element
-  const bool b128 = rowb == 16;
-  const int gsize = b128 ? 16 : 32, nbank = b128 ? 16 : 32, ngroups = 64 / gsize;
-  const bool search = banks_enabled(c);
-  std::mt19937 rng(0xab0000u + (uint32_t)g);
-  std::vector<int> cnt((size_t)W * nbank), perm((size_t)gsize * W), bank((size_t)gsize * W), cost(W);
-  std::vector<uint16_t> ent((size_t)gsize * W);
-  auto step_cost = [&](int st) {
-    int mx = 0;
-    for (int b = 0; b < nbank; ++b) mx = std::max(mx, cnt[(size_t)st * nbank + b]);
-    return mx;
-  };
-  for (int b0 = 0; b0 < npad; b0 += 64) {
-    for (int G = 0; G < ngroups; ++G) {
-      int rows[32], nreal = 0;
-      for (int j = 0; j < gsize; ++j) {
-        const int lane = b128 ? kLdsGroups16[G][j] : G * 32 + j;
-        rows[j] = b0 + lane;
-      }
-      // entries (s * M + k | sign) and banks of the real rows, identity order
-      std::fill(cnt.begin(), cnt.end(), 0);
-      for (int j = 0; j < gsize; ++j) {
-        const int r = rows[j];
-        if (r >= n) continue;
-        ++nreal;
-        for (int sl = 0; sl < W; ++sl) {
-          const int l = g * W + sl;
-          uint16_t e = 0;
-          if (l < L) e = fwd[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)];
-          const unsigned k = t_pos(c->E, e & 0x7fffu);
-          ent[(size_t)j * W + sl] = (uint16_t)(((unsigned)sl * M + k) | (e & 0x8000u));
-          bank[(size_t)j * W + sl] = l < L ? (int)(((unsigned)sl * M + k) % (unsigned)nbank) : -1;
-          perm[(size_t)j * W + sl] = sl;
-          if (l < L) ++cnt[(size_t)sl * nbank + bank[(size_t)j * W + sl]];
-        }
-      }
-      if (search && nreal > 1) {
-        for (int st = 0; st < W; ++st) cost[st] = step_cost(st);
-        // 16 W moves: the searched tables reach a sum of step costs 1.17x that
-        // of 64 W moves (C4), with the same C3 / C4 throughput, in a quarter
-        // of the host time (0.11 -> 0.05 s at C4)
-        for (int it = 0; it < 16 * W; ++it) {
-          int s1 = 0;
-          for (int st = 1; st < W; ++st)
-            if (cost[st] > cost[s1]) s1 = st;
-          if (cost[s1] <= 1) break;
-          int bm = 0;
-          for (int b = 1; b < nbank; ++b)
-            if (cnt[(size_t)s1 * nbank + b] > cnt[(size_t)s1 * nbank + bm]) bm = b;
-          int cand[32], nc = 0;
-          for (int j = 0; j < gsize; ++j)
-            if (rows[j] < n && bank[(size_t)j * W + perm[(size_t)j * W + s1]] == bm) cand[nc++] = j;
-          if (nc == 0) break;
-          const int j = cand[rng() % (unsigned)nc];
-          const int s2 = (int)(rng() % (unsigned)W);
-          if (s2 == s1) continue;
-          int& x = perm[(size_t)j * W + s1];
-          int& y = perm[(size_t)j * W + s2];
-          const int bx = bank[(size_t)j * W + x], by = bank[(size_t)j * W + y];
-          auto mv = [&](int st, int b, int d) {
-            if (b >= 0) cnt[(size_t)st * nbank + b] += d;
-          };
-          mv(s1, bx, -1); mv(s2, by, -1); mv(s1, by, +1); mv(s2, bx, +1);
-          const int n1 = step_cost(s1), n2 = step_cost(s2);
-          if (n1 + n2 <= cost[s1] + cost[s2]) {
-            std::swap(x, y);
-            cost[s1] = n1;
-            cost[s2] = n2;
-          } else {
-            mv(s1, by, -1); mv(s2, bx, -1); mv(s1, bx, +1); mv(s2, by, +1);
-          }
-        }
-      }
-      // out [g * W/4 + q][npad][4]: step st = 4 q + slot; idle rows copy the
-      // group's first real row (or, with none, row 0 of the block's order)
-      int jr = -1;
-      for (int j = 0; j < gsize && jr < 0; ++j)
-        if (rows[j] < n) jr = j;
-      for (int j = 0; j < gsize; ++j) {
-        const int src = rows[j] < n ? j : jr;
-        for (int st = 0; st < W; ++st) {
-          const uint16_t e = src >= 0 ? ent[(size_t)src * W + perm[(size_t)src * W + st]] : (uint16_t)((unsigned)st * M);
-          out[((size_t)(g * (W / 4) + st / 4) * npad + rows[j]) * 4 + (st % 4)] = e;
-        }
-      }
-    }
-  }
-}
-
-int build_fwdb(sa_ctx* c) {
-  const int n = c->n, npad = (n + 63) & ~63, Gb = c->Gb, W = c->WB;
-  // the host copy of d_fwd, [G][n][4] (built again from the ordering: the
-  // same entries build_tables uploads)
-  const int lgM = ilog2(c->M);
-  const int G = (c->L + kSG - 1) / kSG * (kSG / kSpw);
-  std::vector<uint16_t> fwd_own;
-  if (c->h_fwd.size() != (size_t)G * n * kSpw) {  // the host copy went (or never was): rebuild it
-    fwd_own.assign((size_t)G * n * kSpw, 0);
-    parallel_for(c->L, 4, [&](int l) {
-      for (int r = 0; r < n; ++r) {
-        const uint32_t v = c->ordering[(size_t)l * n + r];
-        fwd_own[((size_t)(l / kSpw) * n + r) * kSpw + (l % kSpw)] =
-            (uint16_t)((v & (uint32_t)(c->M - 1)) | ((__builtin_popcount(v >> lgM) & 1u) << 15));
-      }
-    });
-  }
-  const uint16_t* fwd = fwd_own.empty() ? c->h_fwd.data() : fwd_own.data();
-  std::vector<uint16_t> out((size_t)Gb * W * npad, 0);
-  parallel_for(Gb, 1, [&](int g) { fwdb_group(c, g, fwd, npad, out.data()); });
-  int rc = dev_alloc(c, (void**)&c->d_fwdb, out.size() * 2);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_fwdb, out.data(), out.size() * 2, hipMemcpyHostToDevice, c->at().stream));
-  HIP_TRY(hipStreamSynchronize(c->at().stream));
-  return SA_OK;
-}
-
-// k_secb (16-byte rows: binary32 CB = 4, binary64 CB = 2; E >= 4): lane L of a
-// wave holds columns elem_index<E>(L ^ 3 in binary32, i) (quad-mirrored positions)
-int ensure_invb(sa_ctx* c) {
-  // the Ab table first (every k_secb configuration reads it)
-  if (c->backend == SA_BACKEND_HADAMARD && c->CB > 0 && !c->big && !c->d_fwdb) {
-    if (c->WB * c->M >= 32768) return fail(SA_ERR_UNSUPPORTED, "k_secb: W * M >= 2^15");
-    if (int rc = build_fwdb(c)) return rc;
-  }
-  if (c->invb_done) return SA_OK;
-  c->invb_done = true;
-  const bool sgn = c->prec == SA_PREC_F32;  // k_secb's SGN (E >= 2)
-  const bool rows16 = c->backend == SA_BACKEND_HADAMARD && c->CB > 0 && c->CB * (int)rsz(c) == 16 && !c->big;
-  if (rows16 && banks_enabled(c) && c->E >= 4 && c->nhi >= 2 && c->n + kInvbZeroRows <= 65535) {
-    std::vector<int> sets;
-    for (int i = 0; i < c->E; ++i)
-      for (int G = 0; G < 4; ++G)
-        for (int j = 0; j < 16; ++j) {
-          const int lane = kLdsGroups16[G][j], lp = sgn ? (lane ^ 3) : lane;
-          sets.push_back((i / 4) * 256 + lp * 4 + (i % 4));  // elem_index<E >= 4>
-        }
-    // (the kernel's h-steps per table block: kSecbKH64 in binary64, kSecbKH32 at CB = 4)
-    const int kh = sgn ? kSecbKH32 : kSecbKH64;
-    if (int rc = build_banked(c, sets, 16, 16, &c->d_invb, kh)) return rc;
-  }
-  // the codeword-interleaved k_secb's copy of its bucket table with each
-  // lane's E entries of a step contiguous (one 16-byte load per lane and
-  // step at E = 8 instead of two 8-byte loads 512 B apart)
-  if (rows16 && c->E >= 4 && c->E % 4 == 0) {
-    const size_t cnt = (size_t)c->L * c->nhi * 64 * c->E;
-    if (int rc = dev_alloc(c, (void**)&c->d_invl, cnt * 2)) return rc;
-    k_lane_major<<<(int)std::min<size_t>((cnt + 255) / 256, 16384), 256, 0, c->at().stream>>>(
-        c->d_invb ? c->d_invb : c->d_inv, c->d_invl, c->L, c->nhi, c->M, c->w, c->E, sgn ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->at().stream));
-  }
-  std::vector<uint16_t>().swap(c->h_inv);  // the host copies have served
-  std::vector<uint16_t>().swap(c->h_fwd);
-  return SA_OK;
-}
-
-
 // Every section-kernel instantiation may use the full 160 KB LDS, the MFMA
 // GEMMs their staging buffers (once per process).
 int set_lds_limits() {
@@ -1175,184 +730,27 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
   if (plan & ~SA_PLAN_ALL) return fail(SA_ERR_ARG, "unknown plan option bits");
   if (backend == SA_BACKEND_DENSE && prec != SA_PREC_F32)
     return fail(SA_ERR_UNSUPPORTED, "dense backend streams an fp32 matrix (precision must be F32)");
-  const bool pow2 = (M & (M - 1)) == 0;
-  if (M > 4096) return fail(SA_ERR_UNSUPPORTED, "M must be <= 4096");
-  // the Hadamard operator takes n past 16-bit row indices (k_secg); the
-  // materialised designs and the host-operator loop keep the 16-bit limit
-  if (n >= (backend == SA_BACKEND_HADAMARD ? (1 << 24) : 65535))
-    return fail(SA_ERR_UNSUPPORTED, backend == SA_BACKEND_HADAMARD ? "n must be < 2^24" : "n must be < 65535");
+  std::string err;
+  if (int rcl = shape_limits(M, n, backend, err)) return fail(rcl, err);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SA_ERR_NO_DEVICE, "no HIP device visible");
   if (device < 0 || device >= ndev) return fail(SA_ERR_ARG, "device index out of range");
   HIP_TRY(hipSetDevice(device));
-
-  sa_ctx* c = new sa_ctx();
-  c->L = L; c->M = M; c->n = n; c->backend = backend; c->prec = prec; c->device = device; c->plan = plan;
-  c->Mu = M;
-  const int mx = (M + 1) > (n + 1) ? (M + 1) : (n + 1);
-  c->w = 1 << ilog2(mx);  // 2^ceil(log2(max(M+1, n+1))), sparc_ldpc.py:52/:110
-  if (!pow2 && backend == SA_BACKEND_HADAMARD) {
-    // any M on the matrix-free operator: the reference keeps the last M of the
-    // w columns (sparc_ldpc.py:68/:77), which are the last M of the last
-    // Mp = 2^ceil(log2 M) <= w, whose high index bits are all ones: a section
-    // is a padded section of Mp columns whose first Mp - M never carry an
-    // estimate (the denoiser excludes them, beta stays 0 there); the caller's
-    // beta / A^T z move in and out of the padded layout at the boundary
-    c->M = 1 << ilog2(M);
-    c->dead = c->M - M;
-    M = c->M;
-  }
-  c->nhi = c->w / M;
-  c->E = 1;  // elements per lane of a one-wave section: the power of two covering M
-  while (c->E * 64 < M) c->E *= 2;
-  c->pow2 = pow2;
-  if (ordering) c->ordering.assign(ordering, ordering + (size_t)L * n);
-  c->NZ = (n + kRowsPerBlk - 1) / kRowsPerBlk;
-  c->NZ16 = (n + kRow2Rows - 1) / kRow2Rows;
-  c->NZh = (n + 15) / 16;
-  c->NZ4 = (n + 255) / 256;
-  c->NZ2 = (n + 127) / 128;
-  // section kernel LDS: z slots + 4 sections x M + 4 beta^2 partials
-  const size_t s = rsz(c);
-  const size_t zbytes = ((size_t)(n + 1) * s + 15) / 16 * 16;
-  c->sec_lds = zbytes + (size_t)kSpw * M * s + (size_t)kSpw * s;
-  if (backend == SA_BACKEND_HADAMARD && (n >= 65535 || c->sec_lds > 160 * 1024)) {
-    // z from global memory, 32-bit bucket entries (k_secg); the multi-wave and
-    // batched kernels' LDS images need z too: they stay off (G2, CB below)
-    c->big = true;
-    c->sec_lds = (size_t)kSpw * M * s + (size_t)kSpw * s;
-  }
-  if (c->dead > 0 && c->big) {
-    delete c;
-    return fail(SA_ERR_UNSUPPORTED, "M not a power of two: the Hadamard operator keeps z in LDS (n < 65535 and "
-                                    "the z image within 160 KB)");
-  }
-  if (c->sec_lds > 160 * 1024) {
-    delete c;
-    return fail(SA_ERR_UNSUPPORTED, "section kernel does not fit in LDS (n and M too large for this precision)");
-  }
-  c->G = (L + kSpw - 1) / kSpw;
-  c->Gb = (L + kWB - 1) / kWB;  // (re-set after the batched width is chosen)
-  // (a padded section runs on k_sec alone, the one section kernel that masks dead columns)
-  if (M >= 128 && M <= 4096 && !c->big && c->dead == 0) {  // k_sec2: z + 2 sections' T + top-bit exchange + reductions
-    const size_t need = zbytes + 2 * (size_t)M * s + 4 * (size_t)(M / 2) * s + 16 * s;
-    if (need <= 160 * 1024) {
-      c->G2 = (L + 1) / 2;
-      c->sec2_lds = need;
-    }
-    // k_sec4: z + 2 sections' T + one exchange image per section + reductions
-    const size_t need4 = zbytes + 4 * (size_t)M * s + 32 * s;
-    if (c->G2 > 0 && M >= 256 && need4 <= 160 * 1024) {
-      c->sec4 = true;
-      c->sec4_lds = need4;
-    }
-    // row-block-major Ab partials for k_row2 (SA_PLAN_NO_PT: the [G][n] layout):
-    // each k_row2 workgroup reads one contiguous G x 128-B block instead of G
-    // lines n rows apart.  C4 single codeword 880 -> 950 cw/s (k_row2 4.1 ->
-    // 3.4 us, two interleaved A/B rounds); c2 within noise
-    c->pt_on = !(plan & SA_PLAN_NO_PT);
-    // 16-row k_row2 blocks for one codeword where the z^2 partials still fit
-    // the section kernels' registers (ceil(n / 16) <= 320; C2: 288 workgroups
-    // instead of 144, every CU pulls partials): c2 1362-1374 -> 1396 cw/s
-    // (two interleaved A/B rounds).  Binary32 only: in binary64 the 32-row
-    // blocks are faster (c2 fp64 984-988 -> 990-1013 cw/s, two interleaved
-    // rounds, round 3).  SA_PLAN_NO_ROW16 / SA_PLAN_ROW16 force 32- / 16-row blocks
-    const bool r16 = (plan & SA_PLAN_ROW16) ? true : (plan & SA_PLAN_NO_ROW16) ? false : s == 4;
-    c->row16 = r16 && c->pt_on && c->sec4 && c->NZh <= 320;
-  }
-
-  // batched kernel: the most codewords per workgroup (CB in {4, 2, 1}; 4 for
-  // fp32 only) whose LDS image (z and T share one region) still lets two
-  // 8-section workgroups share a CU (CB = 1 takes the whole LDS if it must);
-  // one 16-section workgroup per CU instead where its whole-LDS image holds a
-  // larger chunk (L = 768, n = 8294: CB 4 instead of 2; binary64 2 instead of
-  // 1), and also at equal CB (half the Ab partials: the row kernel's HBM read
-  // halves, the section kernel pays a 16-wave barrier): C4 batch 256 4.45 k
-  // -> 5.51 k cw/s (binary64 2.17 k -> 2.41 k), C3 11.10 k -> 11.26 k; in
-  // binary64 at equal CB since round 4 (C3 fp64 with ZIL 6.44 k -> 7.02 k,
-  // the joint configs[4] step 1.65 k -> 1.75 k).  SA_PLAN_WB8 / WB16 force it.
-  {
-    auto cb_for = [&](int W) -> std::pair<int, size_t> {
-      for (int cb = (s == 4 ? 4 : 2); cb >= 1 && M <= 1024; cb >>= 1) {
-        const size_t zb = (((size_t)(n + kInvbZeroRows) * cb * s) + 15) / 16 * 16;
-        const size_t tb = (size_t)W * M * cb * s;
-        const size_t need = (zb > tb ? zb : tb) + (size_t)W * cb * s + (s == 8 ? 64 * 8 : 0);
-        if (need <= (cb == 1 || W > kWB ? 160 : 80) * 1024) return {cb, need};
-      }
-      return {0, 0};
-    };
-    const bool nob = c->big || c->dead > 0;
-    const auto c8 = nob ? std::pair<int, size_t>{0, 0} : cb_for(kWB);
-    const auto c16 = nob ? std::pair<int, size_t>{0, 0} : cb_for(kWB16);
-    const bool w16 = (plan & SA_PLAN_WB16) ? true
-                     : (plan & SA_PLAN_WB8) ? false
-                                            : c16.first >= c8.first;
-    c->WB = w16 && c16.first > 0 ? kWB16 : kWB;
-    c->CB = c->WB == kWB16 ? c16.first : c8.first;
-    c->secb_lds = c->WB == kWB16 ? c16.second : c8.second;
-    c->Gb = (L + c->WB - 1) / c->WB;
-    // passes over each XCD's section groups so one pass's bucket and Ab
-    // tables (W sections x (w + n) x 2 B per group) stay within kSecbL2
-    // bytes of the XCD's 4 MB L2 (the rest: z chunks, streamed beta)
-    const size_t per_group = (size_t)c->WB * ((size_t)c->w + (size_t)n) * 2;
-    const int gx = c->Gb / 8 > 0 ? c->Gb / 8 : 1;
-    const int fit = (int)std::max<size_t>(1, kSecbL2 / per_group);
-    int npass = (gx + fit - 1) / fit;
-    c->gpx = (gx + npass - 1) / npass;  // balanced passes
-    if (plan & SA_PLAN_ONE_PASS) c->gpx = 1 << 20;
-  }
+  int n_cus = Shape().n_cus;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-      c->n_cus = prop.multiProcessorCount;
+      n_cus = prop.multiProcessorCount;
   }
-  c->Gd = (L + 3) / 4;
-  {
-    // k_sec43: three sections per workgroup where pairs overfill the chip
-    // (ceil(L/2) > CUs >= ceil(L/3), e.g. L = 768) — one workgroup per CU
-    // instead of two on half of them; in binary64 also where pairs fill the
-    // chip exactly (L = 2 x CUs, c2): a third fewer 8-byte Ab partials for
-    // k_row2 outweigh the longer section step (c2 fp64 989-997 -> 1026-1027
-    // cw/s, two interleaved A/B rounds, round 3; binary32 at c2: neutral, pairs
-    // kept).  SA_PLAN_NO_SEC3 / SA_PLAN_SEC3 force it off / on
-    const size_t need3 = (((size_t)(n + 1) * s + 15) / 16 * 16) + 6 * (size_t)M * s + 48 * s;
-    const int G3 = (L + 2) / 3;
-    const bool fits = c->sec4 && backend == SA_BACKEND_HADAMARD && M <= 512 && need3 <= 160 * 1024;
-    const bool over = c->G2 > c->n_cus || (s == 8 && c->G2 == c->n_cus);
-    const bool want = (plan & SA_PLAN_SEC3) ? true : (plan & SA_PLAN_NO_SEC3) ? false : (over && G3 <= c->n_cus);
-    if (fits && want) {
-      c->sec3 = true;
-      c->G3 = G3;
-      c->sec3_lds = need3;
-    }
-    // k_sec44: four sections per workgroup on the pair table.  z + 4 sections'
-    // T + one exchange image per section + reductions.  SA_PLAN_SEC4Q runs it
-    // wherever pairs would run (SA_PLAN_SEC3 beside it keeps triples) and is
-    // never chosen otherwise.  At c2 (L = 2 x CUs) one launch takes half the
-    // CUs, so the section kernels of two decodes in flight (decode lanes) stop
-    // sharing CUs, and the Ab partials and z fills halve: +4.2 % to +4.8 % over
-    // pairs with lanes (as much as triples), but a lone decode, which leaves
-    // the other half of the chip idle, takes 0.74 ms against 0.68 ms (DESIGN.md
-    // section 8, "lane shapes"), so it stays an option for throughput callers
-    const size_t need4q = zbytes + 8 * (size_t)M * s + 64 * s;
-    // (M <= 512: the larger sections' instances spill at 128 VGPRs)
-    const bool fits4q = c->sec4 && backend == SA_BACKEND_HADAMARD && M <= 512 && need4q <= 160 * 1024;
-    if (fits4q && (plan & SA_PLAN_SEC4Q) && !(plan & (SA_PLAN_SEC3 | SA_PLAN_NO_SEC4Q))) {
-      c->sec4q = true;
-      c->sec3 = false;
-      c->G4 = (L + 3) / 4;
-      c->sec4q_lds = need4q;
-    }
-    // 32-row k_row2 blocks where pairs fill the chip exactly (L = 2 x CUs,
-    // c2): with two decodes in flight every CU already holds a section
-    // workgroup of each lane, and the 144 32-row workgroups of a row step
-    // disturb them less than 288 16-row ones: c2 +3 % with lanes, every run
-    // above every 16-row run, the lone decode inside its run-to-run range
-    // ("lane shapes").  SA_PLAN_ROW16
-    // keeps 16-row blocks, and so does SA_PLAN_NO_SEC3, which asks for the
-    // pair shape as it was (k_sec4 in front of 16-row blocks)
-    if (c->G2 == c->n_cus && !(plan & (SA_PLAN_ROW16 | SA_PLAN_NO_SEC3))) c->row16 = false;
+
+  sa_ctx* c = new sa_ctx();
+  if (int rcs = shape_for(*c, L, M, n, backend, prec, plan, n_cus, err)) {  // every shape number (sa_shape.h)
+    delete c;
+    return fail(rcs, err);
   }
+  c->device = device;
+  if (ordering) c->ordering.assign(ordering, ordering + (size_t)L * n);
+  const size_t s = rsz(c);
   if (lane_open(c->lane[0]) != SA_OK) {
     delete c;
     return fail(SA_ERR_HIP, "stream/event creation failed");
@@ -1371,10 +769,7 @@ int create_impl(sa_ctx** out, int L, int M, int n, const uint32_t* ordering, int
     c->KS = 8;
     rc = matrix_init(c);
   } else if (share) {  // sa_create_twin: the same tables, read-only, borrowed
-    c->d_inv = share->d_inv; c->d_inv32 = share->d_inv32; c->d_invb = share->d_invb;
-    c->d_fwdb = share->d_fwdb; c->d_fwd = share->d_fwd; c->d_fwd2 = share->d_fwd2; c->d_fwd3 = share->d_fwd3;
-    c->d_invl = share->d_invl; c->d_hs = share->d_hs;
-    c->invb_done = share->invb_done;
+    c->tab = share->tab;
     c->borrowed = true;
   } else {
     rc = build_tables(c);
@@ -1446,17 +841,7 @@ void sa_destroy(sa_ctx* c) {
   drop_graphs(c);
   free_workspace(c);
   mc_release(c);
-  if (!c->borrowed) {
-    dev_free(c->d_inv);
-    dev_free(c->d_inv32);
-    dev_free(c->d_invb);
-    dev_free(c->d_fwdb);
-    dev_free(c->d_invl);
-    dev_free(c->d_hs);
-    dev_free(c->d_fwd);
-    dev_free(c->d_fwd2);
-    dev_free(c->d_fwd3);
-  }
+  if (!c->borrowed) tables_free(c->tab);
   dev_free(c->d_A);
   dev_free(c->d_AT); dev_free(c->d_xz); dev_free(c->d_xb);
   dev_free(c->d_A8); dev_free(c->d_AT8); dev_free(c->d_zq); dev_free(c->d_bq);
@@ -1518,7 +903,7 @@ int sa_reserve(sa_ctx* c, int B, int T) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_workspace(c, B, T > 0 ? T : 1);
   // the batched kernel's tables (built once per operator) now, not at the first decode
-  if (!rc && c->backend == SA_BACKEND_HADAMARD && use_batched(c, B)) rc = ensure_invb(c);
+  if (!rc && c->backend == SA_BACKEND_HADAMARD && use_batched(*c, B)) rc = ensure_invb(c);
   return rc;
 }
 
@@ -1661,11 +1046,11 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   HIP_TRY(hipSetDevice(c->device));
   if (int rcs = sync_all(c)) return rcs;  // the profiled decode has the chip to itself (it stays on the current lane)
   if (int rcb = ensure_beta2(c, B)) return rcb;
-  if (use_batched(c, B)) lane_switch(c, 0);  // as sa_run
+  if (use_batched(*c, B)) lane_switch(c, 0);  // as sa_run
   c->at().row_B = c->at().row_T = 0;  // as sa_run: a new decode of the lane (never a fused tail: fused_tail)
   c->at().fused_B = 0;
   if (int rcy = y_sync(c)) return rcy;
-  if (use_batched(c, B))
+  if (use_batched(*c, B))
     if (int rci = ensure_invb(c)) return rci;
   Prof prof;
   prof.rep = rep;
@@ -1809,17 +1194,12 @@ int sa_plan(sa_ctx* c, int B, int64_t* o) {
 
 int sa_plan_batched(sa_ctx* c, int B, int64_t* o) {
   if (check_ctx(c) || !o || B <= 0) return fail(SA_ERR_ARG, "sa_plan_batched: bad arguments");
-  if (is_dense(c) || !use_batched(c, B)) return fail(SA_ERR_ARG, "sa_plan_batched: this batch does not run k_secb");
-  // k_secb's XCD-grouped work order (sa_secb.hip): used when the groups and the
-  // workgroups split evenly over the 8 XCDs, else one plain pass
-  const int NC = (B + c->CB - 1) / c->CB;
-  const bool xcd = (c->Gb % 8) == 0 && ((long long)c->Gb * NC) % 8 == 0;
-  const int gx = xcd ? c->Gb / 8 : c->Gb;
-  const int gp = xcd ? std::min(c->gpx, gx) : gx;
+  if (is_dense(*c) || !use_batched(*c, B)) return fail(SA_ERR_ARG, "sa_plan_batched: this batch does not run k_secb");
+  const SecbOrder so = secb_order(*c, B);
   o[0] = c->Gb;
   o[1] = c->WB;
-  o[2] = gp;
-  o[3] = (gx + gp - 1) / gp;
+  o[2] = so.gp;
+  o[3] = so.passes;
   return SA_OK;
 }
 

@@ -4,7 +4,7 @@ tests/test_secb_cases_host.py).  No GPU import.
 
 k_secb<real, E, CB, W, ZIL> (csrc/sa_secb.hip) is registered in 70 instances
 (secb_lds_attrs_t).  `expected_instance` restates the host rules that pick
-one: cb_for and the WB8 / WB16 override of create_impl, zil_for, the bank
+one: cb_for and the WB8 / WB16 override of shape_for (csrc/sa_shape.h), zil_for, the bank
 conditions of ensure_invb, and the kernel's own condition for its sign-split
 gather loop.  62 instances can be selected; the eight with E = 16 and 16-byte
 rows (binary32 CB = 4, binary64 CB = 2; both W, both ZIL) cannot: their T tile
@@ -53,7 +53,7 @@ def _r16(x):
 
 
 def cb_for(prec, M, n, W):
-    """create_impl's cb_for: (CB, LDS bytes), (0, 0) where nothing fits."""
+    """shape_for's cb_for: (CB, LDS bytes), (0, 0) where nothing fits."""
     s = SIZE[prec]
     cb = 4 if s == 4 else 2
     while cb >= 1 and M <= 1024:
@@ -67,7 +67,7 @@ def cb_for(prec, M, n, W):
 
 
 def _big(prec, M, n):
-    """create_impl's `big`: z past the one-codeword kernel's LDS image (no batched kernel)."""
+    """shape_for's `big`: z past the one-codeword kernel's LDS image (no batched kernel)."""
     s = SIZE[prec]
     return n >= 65535 or _r16((n + 1) * s) + K_SPW * M * s + K_SPW * s > LDS_FULL
 
