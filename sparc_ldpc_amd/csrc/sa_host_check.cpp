@@ -6,6 +6,11 @@
 //     codewords in sa_plan's field order and, where B runs k_secb,
 //     sa_plan_batched's four numbers; {"error", "message"} for a shape that
 //     sa_create refuses as unsupported.
+//   sa_host_check sweep L M backend prec plan n_cus B n0 n1
+//     the section path of a decode of B codewords at every n of [n0, n1], as
+//     one JSON list of runs [first n, last n, sec, big]: consecutive n with
+//     the same section path (sa_plan's number; -1: sa_create refuses the
+//     shape) and the same `big`.
 //   sa_host_check tables L M n prec plan
 //     draws a valid ordering (per section a seeded shuffle of 1 .. w-1, its
 //     first n), builds every table of the Hadamard operator with the pure
@@ -24,6 +29,7 @@ using namespace sa;
 
 static int usage() {
   std::fprintf(stderr, "usage: sa_host_check shape L M n backend prec plan n_cus B\n"
+                       "       sa_host_check sweep L M backend prec plan n_cus B n0 n1\n"
                        "       sa_host_check tables L M n prec plan\n");
   return 2;
 }
@@ -64,6 +70,33 @@ static int cmd_shape(int L, int M, int n, int backend, int prec, int plan, int n
     std::printf(", \"plan_batched\": [%d, %d, %d, %d]", s.Gb, s.WB, so.gp, so.passes);
   }
   std::printf("}\n");
+  return 0;
+}
+
+static int cmd_sweep(int L, int M, int backend, int prec, int plan, int n_cus, int B, int n0, int n1) {
+  if (L <= 0 || M <= 0 || n_cus <= 0 || B <= 0 || n0 <= 0 || n1 < n0 || backend < SA_BACKEND_HADAMARD ||
+      backend > SA_BACKEND_MATRIX || (prec != SA_PREC_F32 && prec != SA_PREC_F64) || (plan & ~SA_PLAN_ALL))
+    return usage();
+  int first = n0, sec = 0, big = 0, runs = 0;
+  std::printf("[");
+  for (int n = n0; n <= n1 + 1; ++n) {
+    int s1 = -1, b1 = 0;
+    if (n <= n1) {
+      Shape s;
+      std::string err;
+      if (!shape_limits(M, n, backend, err) && !shape_for(s, L, M, n, backend, prec, plan, n_cus, err)) {
+        s1 = (int)plan_for(s, B).sec;
+        b1 = s.big ? 1 : 0;
+      }
+    }
+    if (n > n0 && (n > n1 || s1 != sec || b1 != big)) {
+      std::printf("%s[%d, %d, %d, %d]", runs++ ? ", " : "", first, n - 1, sec, big);
+      first = n;
+    }
+    sec = s1;
+    big = b1;
+  }
+  std::printf("]\n");
   return 0;
 }
 
@@ -248,6 +281,8 @@ int main(int argc, char** argv) {
   std::vector<int> a;
   for (int i = 2; i < argc; ++i) a.push_back(std::atoi(argv[i]));
   if (!std::strcmp(argv[1], "shape") && a.size() == 8) return cmd_shape(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
+  if (!std::strcmp(argv[1], "sweep") && a.size() == 9)
+    return cmd_sweep(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
   if (!std::strcmp(argv[1], "tables") && a.size() == 5) return cmd_tables(a[0], a[1], a[2], a[3], a[4]);
   return usage();
 }
