@@ -73,7 +73,7 @@ int sa_create(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
  * (sa_plan reports the choice); these bits override a rule, e.g. to test a
  * kernel on shapes where the rule would not pick it.  Every option keeps the
  * results within the same parity bounds; SA_PLAN_NO_PT, SA_PLAN_EAGER,
- * SA_PLAN_ONE_PASS, SA_PLAN_NO_LANES and SA_PLAN_NO_FUSED_TAIL are bit-identical to the default plan.  `sa_subset` contexts
+ * SA_PLAN_ONE_PASS, SA_PLAN_NO_LANES, SA_PLAN_NO_FUSED_TAIL and SA_PLAN_NO_PACK are bit-identical to the default plan.  `sa_subset` contexts
  * inherit their parent's options. */
 enum {
   SA_PLAN_DEFAULT = 0,
@@ -95,7 +95,10 @@ enum {
   SA_PLAN_NO_SEC4Q = 1 << 14, /* one codeword: never k_sec44 (the default; overrides SA_PLAN_SEC4Q) */
   SA_PLAN_NO_FUSED_TAIL = 1 << 15, /* one codeword, early stop off: keep the decode's last k_row2 launch and decide
                                       with k_decide (no decisions out of the last section launch; bit-identical) */
-  SA_PLAN_ALL = (1 << 16) - 1
+  SA_PLAN_NO_PACK = 1 << 16,  /* one codeword, pairs / quads: the 16-bit bucket table and the 32-bit pair Ab table
+                                 instead of their packed forms (13-bit bucket records; pairs: three rows per
+                                 64-bit word), which are then not built (bit-identical) */
+  SA_PLAN_ALL = (1 << 17) - 1
 };
 int sa_create_ex(sa_ctx** out, int L, int M, int n, const uint32_t* ordering,
                  int backend, int precision, int device, int plan);

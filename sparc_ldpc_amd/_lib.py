@@ -42,7 +42,7 @@ SA_PLAN = {
     "SEC3": 1 << 0, "NO_SEC3": 1 << 1, "ROW16": 1 << 2, "NO_ROW16": 1 << 3, "NO_PT": 1 << 4,
     "ZIL": 1 << 5, "NO_ZIL": 1 << 6, "WB8": 1 << 7, "WB16": 1 << 8, "NO_BANKS": 1 << 9, "EAGER": 1 << 10,
     "ONE_PASS": 1 << 11, "NO_LANES": 1 << 12, "SEC4Q": 1 << 13, "NO_SEC4Q": 1 << 14,
-    "NO_FUSED_TAIL": 1 << 15,
+    "NO_FUSED_TAIL": 1 << 15, "NO_PACK": 1 << 16,
 }
 
 

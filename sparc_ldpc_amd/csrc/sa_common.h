@@ -891,7 +891,14 @@ struct SecArgs {
   const uint32_t* __restrict__ fwd2; // [ceil(L/2)][n] the same entries of one section pair (k_sec2)
   const uint32_t* __restrict__ fwd3; // [ceil(L/3)][n] a section triple, 10-bit fields k | sign<<9 (M <= 512)
   const uint32_t* __restrict__ inv32;  // [L][w] k_secg: inv with 32-bit rows (n >= 65535 or z past the LDS)
-  const real* __restrict__ c;        // [L] sqrt(n * Pl), or [B][L] per codeword (cst = L)
+  // k_sec4 / k_sec44: the packed tables (sa_shape.h), read instead of inv /
+  // fwd2 where set (uniform: the kernels branch once, at their top, between a
+  // packed and an unpacked body).  Here, in the cache lines of the arguments a
+  // launch reads first: behind the last field the branch waited for one more
+  // line of the argument segment in front of the kernel's first loads
+  const uint32_t* __restrict__ invp;   // 13-bit bucket records
+  const uint64_t* __restrict__ fwd2p;  // [G][pj][512] three rows of a pair per word
+  const real* __restrict__ c;       // [L] sqrt(n * Pl), or [B][L] per codeword (cst = L)
   const real* __restrict__ z;        // [B][n]
   real* __restrict__ beta;           // [B][L*M] previous estimate (read)
   real* __restrict__ beta_out;       // [B][L*M] new estimate (k_sec: the other ping-pong buffer)
@@ -929,6 +936,7 @@ struct SecArgs {
   // device-visible buffer, and iters[b] = itset; null / 0 on every other launch
   int32_t* dec;
   int itset;
+  int pj;  // fwd2p words per thread and pair (pack_fwd_words)
 };
 
 template <typename real>
@@ -1085,6 +1093,56 @@ __device__ __forceinline__ void load_buckets_off(const uint16_t* __restrict__ ba
       }
     }
   }
+}
+
+// ---- packed bucket records (sa_shape.h: pack_rd, pack_dword_pos) -----------
+using u4v = unsigned __attribute__((ext_vector_type(4)));
+
+// The lane's record of block blk of its wave's bucket steps: rd / 4 16-byte
+// loads and rd % 4 4-byte loads, unconditional, from a workgroup-uniform base
+// and the wave's 32-bit byte offset woff (its section's and quarter's blocks)
+template <int E, int KH>
+__device__ __forceinline__ void load_packed(const uint32_t* __restrict__ base, unsigned woff, int blk, int lane,
+                                            uint32_t (&pw)[pack_rd(E, KH)]) {
+  constexpr int RD = pack_rd(E, KH), NV = RD / 4;
+  const unsigned b0 = woff + (unsigned)blk * (64u * RD * 4u);
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const u4v t = ld_off(reinterpret_cast<const u4v*>(base), b0 + (unsigned)(v * 256 + lane * 4) * 4u);
+    pw[4 * v] = t.x; pw[4 * v + 1] = t.y; pw[4 * v + 2] = t.z; pw[4 * v + 3] = t.w;
+  }
+#pragma unroll
+  for (int j = 4 * NV; j < RD; ++j) pw[j] = ld_off(base, b0 + (unsigned)(NV * 256 + (j - 4 * NV) * 64 + lane) * 4u);
+}
+
+// A record's entries as the dwords load_buckets_off loads (step hh: element 0
+// | element 1 << 16): constant shifts only (every loop unrolled).  Called in
+// front of the z barrier, where the VALU idles under tau's dependent chain;
+// behind the barrier the gather then starts from the registers it starts from
+// with the 16-bit table (unpacked there, the extra ~30 VALU ops per wave sat on
+// the lone decode's critical path).  The empty asm keeps each dword formed here.
+template <int E, int KH>
+__device__ __forceinline__ void unpack_pairs(const uint32_t (&pw)[pack_rd(E, KH)], uint32_t (&tw)[KH]) {
+  static_assert(E <= 2, "packed records: one dword per step");
+#pragma unroll
+  for (int hh = 0; hh < KH; ++hh) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+      const int bit = (hh * E + i) * kPackBits, dw = bit / 32, sh = bit % 32;
+      uint32_t x = pw[dw] >> sh;
+      if (sh + kPackBits > 32) x |= pw[dw + 1] << (32 - sh);
+      w |= (x & ((1u << kPackBits) - 1u)) << (16 * i);
+    }
+    asm("" : "+v"(w));
+    tw[hh] = w;
+  }
+}
+template <int KH>
+__device__ __forceinline__ void pairs_to_buckets(const uint32_t (&tw)[KH], ushort4 (&tb)[KH][1]) {
+#pragma unroll
+  for (int hh = 0; hh < KH; ++hh)
+    tb[hh][0] = make_ushort4((unsigned short)(tw[hh] & 0xffffu), (unsigned short)(tw[hh] >> 16), 0, 0);
 }
 
 template <typename real, int E, int KH>

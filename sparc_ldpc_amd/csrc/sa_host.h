@@ -237,6 +237,7 @@ SecArgs<real> sec_args(sa_ctx* c, const Plan& p, int mode, int t, int early_stop
   a.bzero = 0;
   a.dec = nullptr;
   a.itset = 0;
+  a.invp = nullptr; a.fwd2p = nullptr; a.pj = 0;  // set by launch_sec2 for the kernels that read them
   return a;
 }
 

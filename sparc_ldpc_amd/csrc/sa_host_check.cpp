@@ -16,6 +16,11 @@
 //     first n), builds every table of the Hadamard operator with the pure
 //     builders and checks what the kernels rely on; exit status 1 with the
 //     first violation on stderr.
+//   sa_host_check packed L M n prec plan
+//     the same ordering; builds the packed bucket and pair Ab tables of
+//     k_sec4 / k_sec44 where the shape rules ask for them, unpacks them and
+//     compares every entry with inv and fwd2; one JSON object with the rule's
+//     answer and the byte counts, exit status 1 at the first difference.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -30,7 +35,8 @@ using namespace sa;
 static int usage() {
   std::fprintf(stderr, "usage: sa_host_check shape L M n backend prec plan n_cus B\n"
                        "       sa_host_check sweep L M backend prec plan n_cus B n0 n1\n"
-                       "       sa_host_check tables L M n prec plan\n");
+                       "       sa_host_check tables L M n prec plan\n"
+                       "       sa_host_check packed L M n prec plan\n");
   return 2;
 }
 
@@ -276,6 +282,79 @@ static int cmd_tables(int L, int M, int n, int prec, int plan) {
   return 0;
 }
 
+// The packed tables of k_sec4 / k_sec44 (Shape::pack_inv, pack_fwd): built from
+// inv and fwd2 as build_tables does, unpacked again, compared entry for entry
+static int cmd_packed(int L, int M, int n, int prec, int plan) {
+  Shape s;
+  if (shape_of(s, L, M, n, SA_BACKEND_HADAMARD, prec, plan, Shape().n_cus)) return 1;
+  size_t invp_bytes = 0, fwd2p_bytes = 0;
+  if (s.pack_inv || s.pack_fwd) {
+    std::vector<uint32_t> ord((size_t)L * n), all(s.w - 1);
+    for (int l = 0; l < L; ++l) {
+      std::mt19937 rng(0x0d0000u + (uint32_t)l);
+      std::iota(all.begin(), all.end(), 1u);
+      std::shuffle(all.begin(), all.end(), rng);
+      std::copy(all.begin(), all.begin() + n, ord.begin() + (size_t)l * n);
+    }
+    std::vector<uint16_t> inv((size_t)L * s.w, (uint16_t)n), fwd((size_t)fwd_groups(L) * n * kSpw, 0);
+    std::vector<uint32_t> fwd2((size_t)s.G2 * n, 0);
+    for (int l = 0; l < L; ++l) {
+      std::string bad;
+      CHECK(inv_row(ord.data() + (size_t)l * n, l, n, s.w, inv.data() + (size_t)l * s.w, bad), "inv_row: %s", bad.c_str());
+      fwd_section(ord.data() + (size_t)l * n, l, n, s.M, fwd.data(), fwd2.data(), nullptr);
+    }
+    if (s.pack_inv) {
+      const int kh = s.pack_kh, EQ = s.M / 256, rd = pack_rd(EQ, kh);
+      CHECK(EQ >= 1 && EQ <= 2 && n <= kPackMaxN, "packed bucket records at M = %d, n = %d", s.M, n);
+      const size_t per = pack_inv_section_dwords(s.M, s.nhi, kh);
+      CHECK(per == (size_t)4 * ((s.nhi + kh - 1) / kh) * 64 * rd, "section size");
+      // a wave's block: every dword of every record has a place of its own
+      std::vector<int> seen((size_t)64 * rd, 0);
+      for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < rd; ++j) {
+          const unsigned pos = pack_dword_pos(rd, lane, j);
+          CHECK(pos < (unsigned)(64 * rd) && !seen[pos]++, "pack_dword_pos(%d, %d, %d) = %u", rd, lane, j, pos);
+        }
+      std::vector<uint32_t> invp((size_t)L * per, 0);
+      for (int l = 0; l < L; ++l) pack_inv_section(s.M, n, s.nhi, kh, inv.data() + (size_t)l * s.w, invp.data() + (size_t)l * per);
+      for (int l = 0; l < L; ++l)
+        for (int h = 0; h < s.nhi; ++h)
+          for (int col = 0; col < s.M; ++col) {
+            const uint32_t got = pack_inv_get(s.M, s.nhi, kh, invp.data() + (size_t)l * per, h, col);
+            CHECK(got == inv[(size_t)l * s.w + (size_t)h * s.M + col], "invp[%d] step %d column %d = %u, inv has %u", l, h, col,
+                  got, (unsigned)inv[(size_t)l * s.w + (size_t)h * s.M + col]);
+          }
+      // steps past nhi in the last block hold the zero slot
+      for (int l = 0; l < L; ++l)
+        for (int h = s.nhi; h < (s.nhi + kh - 1) / kh * kh; ++h)
+          for (int col = 0; col < s.M; ++col)
+            CHECK(pack_inv_get(s.M, s.nhi, kh, invp.data() + (size_t)l * per, h, col) == (uint32_t)n,
+                  "invp[%d] step %d (past nhi) column %d is not the zero slot", l, h, col);
+      invp_bytes = invp.size() * 4;
+    }
+    if (s.pack_fwd) {
+      CHECK(s.M <= 512 && !s.sec4q, "packed pair table at M = %d, quads %d", s.M, s.sec4q ? 1 : 0);
+      const int words = pack_fwd_words(n);
+      const size_t per = (size_t)words * kPackNT;
+      std::vector<uint64_t> fwd2p((size_t)s.G2 * per, 0);
+      for (int g = 0; g < s.G2; ++g) pack_fwd_pair(n, fwd2.data() + (size_t)g * n, fwd2p.data() + (size_t)g * per);
+      for (int g = 0; g < s.G2; ++g)
+        for (int r = 0; r < words * 3 * kPackNT; ++r) {  // rows past n: row 0's entry
+          const uint32_t want = fwd2[(size_t)g * n + (r < n ? r : 0)], got = pack_fwd_get(fwd2p.data() + (size_t)g * per, r);
+          CHECK(got == want, "fwd2p[%d] row %d = %#x, fwd2 has %#x", g, r, got, want);
+        }
+      for (uint64_t wv : fwd2p) CHECK((wv >> 60) == 0, "fwd2p: bits past the three fields");
+      fwd2p_bytes = fwd2p.size() * 8;
+    }
+  }
+  std::printf("{\"ok\": 1, \"M\": %d, \"n\": %d, \"nhi\": %d, \"pack_inv\": %d, \"pack_fwd\": %d, \"kh\": %d, \"rd\": %d, "
+              "\"blocks\": %d, \"words\": %d, \"inv_bytes\": %zu, \"invp_bytes\": %zu, \"fwd2_bytes\": %zu, \"fwd2p_bytes\": %zu}\n",
+              s.M, n, s.nhi, s.pack_inv ? 1 : 0, s.pack_fwd ? 1 : 0, s.pack_kh,
+              s.pack_inv ? pack_rd(s.M / 256, s.pack_kh) : 0, s.pack_inv ? (s.nhi + s.pack_kh - 1) / s.pack_kh : 0,
+              s.pack_fwd ? pack_fwd_words(n) : 0, (size_t)L * s.w * 2, invp_bytes, (size_t)s.G2 * n * 4, fwd2p_bytes);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage();
   std::vector<int> a;
@@ -284,5 +363,6 @@ int main(int argc, char** argv) {
   if (!std::strcmp(argv[1], "sweep") && a.size() == 9)
     return cmd_sweep(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
   if (!std::strcmp(argv[1], "tables") && a.size() == 5) return cmd_tables(a[0], a[1], a[2], a[3], a[4]);
+  if (!std::strcmp(argv[1], "packed") && a.size() == 5) return cmd_packed(a[0], a[1], a[2], a[3], a[4]);
   return usage();
 }

@@ -573,9 +573,14 @@ __device__ __forceinline__ real combine_q(const real* red, int w0, int f) {
 // Quads (SPW = 4) have no table of their own: workgroup g reads the pair
 // table's rows 2g and 2g + 1, and a row's partial is the sum of its two pair
 // sums, (+-v0 +- v1) + (+-v2 +- v3).
-template <typename real, int EQ, int QW, int SPW = 2>
+// PKI: the bucket entries come from the 13-bit packed records (SecArgs::invp),
+// PKF: the pair table's rows three to a 64-bit word (SecArgs::fwd2p); the
+// values they unpack to, and every sum and its order, are those of inv / fwd2.
+template <typename real, int EQ, int QW, int SPW = 2, bool PKI = false, bool PKF = false>
 __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   static_assert(SPW == 2 || SPW == 3 || SPW == 4, "sections per workgroup");
+  static_assert(!PKI || (EQ <= 2 && QW == 4 && SPW != 3), "packed bucket records: pairs and quads, M <= 512");
+  static_assert(!PKF || (EQ <= 2 && QW == 4 && SPW == 2), "packed pair table: pairs, M <= 512");
   STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = SPW * QW * 64;
@@ -620,6 +625,17 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   const uint32_t* fw1 = a.fwd2 + (size_t)(2 * g + 1 < (a.L + 1) / 2 ? 2 * g + 1 : 2 * g) * n;
   ushort4 tb[KH][NQ];
   uint32_t f[KR][FW];  // Ab-table entries of this thread's rows
+  // the packed tables: this wave's records (section, quarter; blocks of KH
+  // steps) at a 32-bit byte offset from the workgroup's first section, the
+  // pair's words [pj][NT]
+  constexpr int RD = pack_rd(EQ <= 2 ? EQ : 1, KH);
+  static_assert(!PKF || (NT == kPackNT && KR == kPackKR), "the packed pair table's thread and row counts");
+  const int pnb = (a.nhi + KH - 1) / KH;
+  const uint32_t* pkbase = a.invp + (size_t)g * SPW * 4 * pnb * (64 * RD);
+  const unsigned pkoff = (unsigned)(((lc - g * SPW) * 4 + q) * pnb) * (64u * RD * 4u);
+  const uint64_t* fwp = a.fwd2p + (size_t)g * a.pj * NT;
+  uint32_t pw[RD];          // PKI: the record of the block in hand
+  uint64_t fq[KR / 3 + 1];  // PKF: three rows per word
 
   // Load order: z's LDS-DMA first, then the z^2 partials and tau_{t-1}, then
   // the tables, all unconditional (straight-line).  While an LDS-DMA is in
@@ -639,9 +655,12 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   if (!dma) zst.issue(zb, n, tid);
   zz.issue(zzb, a.NZ, lane);
   const real last = a.t > 0 ? ld_vmem(a.tau + (size_t)b * a.T1 + a.t - 1) : (real)0;
-  load_buckets_off<EQ, KH>(ibase, ioff, 0, a.nhi, M, lane, tb);  // bucket stride M; lane elements < Mq
+  if constexpr (PKI) load_packed<EQ, KH>(pkbase, pkoff, 0, lane, pw);
+  else load_buckets_off<EQ, KH>(ibase, ioff, 0, a.nhi, M, lane, tb);  // bucket stride M; lane elements < Mq
   load_section<real, EQ>(bl, bprev, lane, Mq);
   const real cl = ld_vmem(a.c + (size_t)b * a.cst + lc);
+  uint32_t tw[KH];  // PKI: the block's entries as the dwords of the 16-bit table, formed beside tau's chain
+  if constexpr (PKI) unpack_pairs<EQ, KH>(pw, tw);
   const real tau = zz.tau(zzb, a.NZ, n);
   // a decode without beta0: its first launch takes the previous estimate as
   // zero, selected after the (unconditional) load: the buffer is not filled
@@ -681,15 +700,23 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #pragma unroll
   for (int i = 0; i < EQ; ++i) v[i] = 0;
   for (int h0 = 0; h0 < a.nhi; h0 += KH) {
-    ushort4 tn[KH][NQ];
     const bool more = h0 + KH < a.nhi;
-    if (more) load_buckets_off<EQ, KH>(ibase, ioff, h0 + KH, a.nhi, M, lane, tn);
-    gather_buckets<real, EQ, KH>(zs, h0, a.nhi, tb, v);
-    if (more) {
+    if constexpr (PKI) {
+      uint32_t pn[RD];
+      if (more) load_packed<EQ, KH>(pkbase, pkoff, h0 / KH + 1, lane, pn);
+      pairs_to_buckets<KH>(tw, tb);
+      gather_buckets<real, EQ, KH>(zs, h0, a.nhi, tb, v);
+      if (more) unpack_pairs<EQ, KH>(pn, tw);
+    } else {
+      ushort4 tn[KH][NQ];
+      if (more) load_buckets_off<EQ, KH>(ibase, ioff, h0 + KH, a.nhi, M, lane, tn);
+      gather_buckets<real, EQ, KH>(zs, h0, a.nhi, tb, v);
+      if (more) {
 #pragma unroll
-      for (int hh = 0; hh < KH; ++hh)
+        for (int hh = 0; hh < KH; ++hh)
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) tb[hh][j] = tn[hh][j];
+          for (int j = 0; j < NQ; ++j) tb[hh][j] = tn[hh][j];
+      }
     }
   }
   real* xs = xb + sidx * M;
@@ -698,11 +725,16 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   // flight, instead of adding their bytes (C2 18 KB, C4 33 KB per workgroup)
   // to the first memory round trip, which every wave waits for (C4 single
   // codeword 860 -> 894 cw/s, c2 1378 -> 1394; `k_sec43` 11.0 -> 10.7 us)
+  if constexpr (PKF) {  // three 8-byte loads for the pass's nine rows (rows past n: row 0's entry, in the table)
 #pragma unroll
-  for (int u = 0; u < KR; ++u) {  // unconditional (clamped): see load_section
-    const int r = u * NT + tid;
-    f[u][0] = ld_off(fw, (unsigned)(r < n ? r : 0) * 4u);  // uniform base + 32-bit offset
-    if constexpr (SPW == 4) f[u][1] = ld_off(fw1, (unsigned)(r < n ? r : 0) * 4u);
+    for (int j = 0; j < KR / 3; ++j) fq[j] = ld_off(fwp, (unsigned)(j * NT + tid) * 8u);
+  } else {
+#pragma unroll
+    for (int u = 0; u < KR; ++u) {  // unconditional (clamped): see load_section
+      const int r = u * NT + tid;
+      f[u][0] = ld_off(fw, (unsigned)(r < n ? r : 0) * 4u);  // uniform base + 32-bit offset
+      if constexpr (SPW == 4) f[u][1] = ld_off(fw1, (unsigned)(r < n ? r : 0) * 4u);
+    }
   }
   STAMP(3);
   fwht_wave<real, EQ>(v, lane, 64);
@@ -773,6 +805,14 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #pragma unroll
     for (int i = 0; i < EQ; ++i) tl[elem_index<EQ>(lane, i)] = v[i];
   }
+  if constexpr (PKF) {  // the pass's nine 20-bit fields, each in a register of its own, in front of the barrier
+#pragma unroll
+    for (int u = 0; u < KR; ++u) {
+      uint32_t e = (uint32_t)(fq[u / 3] >> (20 * (u % 3))) & 0xfffffu;
+      asm("" : "+v"(e));
+      f[u][0] = e;
+    }
+  }
   if (lane == 0) {
     red[wv * 4 + 3] = bb;
     // slots 0 (max) and 1 (S) were last read in front of the barriers of the transform above
@@ -813,18 +853,35 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
   const size_t ustep = sh < 31 ? (size_t)(NT >> sh) * gstride : (size_t)NT;
   for (int r0 = 0; r0 < n; r0 += NT * KR) {
     if (r0 > 0) {  // n > NT * KR only
+      if constexpr (PKF) {
 #pragma unroll
-      for (int u = 0; u < KR; ++u) {
-        const int r = r0 + u * NT + tid;
-        f[u][0] = fw[r < n ? r : 0];
-        if constexpr (SPW == 4) f[u][1] = fw1[r < n ? r : 0];
+        for (int j = 0; j < KR / 3; ++j) fq[j] = fwp[(size_t)(r0 / (NT * KR) * (KR / 3) + j) * NT + tid];
+#pragma unroll
+        for (int u = 0; u < KR; ++u) {
+          uint32_t e = (uint32_t)(fq[u / 3] >> (20 * (u % 3))) & 0xfffffu;
+          asm("" : "+v"(e));
+          f[u][0] = e;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < KR; ++u) {
+          const int r = r0 + u * NT + tid;
+          f[u][0] = fw[r < n ? r : 0];
+          if constexpr (SPW == 4) f[u][1] = fw1[r < n ? r : 0];
+        }
       }
     }
     real* const pbase = sbase + (size_t)((r0 + tid) >> sh) * gstride + ((r0 + tid) & smask);
     // row r's term of the pair (triple) and its store
     auto row = [&](int u, int r) {
       real t;
-      if constexpr (SPW == 2) {
+      if constexpr (PKF) {  // field u % 3 of word u / 3: fwd2's k0, s0, k1, s1
+        const uint32_t e = f[u][0];
+        const real v0 = ts[e & 0x1ffu];
+        const real v1 = ts[M + ((e >> 10) & 0x1ffu)];
+        t = (e & 0x200u) ? -v0 : v0;
+        t += (e & 0x80000u) ? -v1 : v1;
+      } else if constexpr (SPW == 2) {
         const uint32_t e = f[u][0];
         const real v0 = ts[e & 0x7fffu];
         const real v1 = ts[M + ((e >> 16) & 0x7fffu)];
@@ -882,8 +939,20 @@ __device__ __forceinline__ void secq_body(const SecArgs<real>& a) {
 #endif
 }
 
+// The packed tables (M <= 512): one uniform branch at the top between a body
+// compiled for them and the body for inv / fwd2, so neither path carries the
+// other's registers.  The pointers tested lie among the first arguments a
+// launch loads (SecArgs).
 template <typename real, int E4>
-__global__ void __launch_bounds__(512) k_sec4(SecArgs<real> a) { secq_body<real, E4, 4, 2>(a); }
+__global__ void __launch_bounds__(512) k_sec4(SecArgs<real> a) {
+  if constexpr (E4 <= 2) {
+    // the packed body falls through from the kernel's entry (the unpacked one is
+    // a jump into code no instruction fetch has run ahead to)
+    if (__builtin_expect(!(a.invp && a.fwd2p), 0)) return secq_body<real, E4, 4, 2>(a);
+    return secq_body<real, E4, 4, 2, true, true>(a);
+  }
+  secq_body<real, E4, 4, 2>(a);
+}
 // Three sections per workgroup (12 waves): L = 3 x CUs (L = 768 on 256 CUs)
 // puts one workgroup on every CU where pairs leave half the CUs with two.
 template <typename real, int E4>
@@ -892,7 +961,10 @@ __global__ void __launch_bounds__(768) k_sec43(SecArgs<real> a) { secq_body<real
 // one launch half the chip, so the section kernels of two decodes in flight
 // (the decode lanes) share no CU, and half the pairs' Ab partials and z fills.
 template <typename real, int E4>
-__global__ void __launch_bounds__(1024) k_sec44(SecArgs<real> a) { secq_body<real, E4, 4, 4>(a); }
+__global__ void __launch_bounds__(1024) k_sec44(SecArgs<real> a) {
+  if (__builtin_expect(!a.invp, 0)) return secq_body<real, E4, 4, 4>(a);
+  secq_body<real, E4, 4, 4, true>(a);  // quads keep the pair table as it is
+}
 
 // ---- launchers ------------------------------------------------------------
 template <typename real, int E>
@@ -922,6 +994,15 @@ int launch_sec2(sa_ctx* c, const Plan& p, int B, int t, int es, void* bin, void*
   a.beta = (real*)bin;
   a.beta_out = (real*)bout;
   a.G = p.G;
+  // the packed tables, where the operator has them (Shape::pack_inv / pack_fwd:
+  // M <= 512, so the instances below that read them)
+  if (p.sec == SA_SEC_K_SEC4 || p.sec == SA_SEC_K_SEC44) {
+    if (c->pack_inv) a.invp = c->tab.invp;
+    if (c->pack_fwd && p.sec == SA_SEC_K_SEC4) {
+      a.fwd2p = c->tab.fwd2p;
+      a.pj = pack_fwd_words(c->n);
+    }
+  }
   dim3 grid(a.G, B);
   if (c->prof) c->prof->begin(c->at().stream, K_SEC);
   switch (p.sec) {

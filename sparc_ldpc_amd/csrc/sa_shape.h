@@ -38,6 +38,31 @@ constexpr int kSecbKH32 = 2, kSecbKH64 = 2;
 // the LDS of a CU: what a section kernel's image may take
 constexpr size_t kLdsBytes = 160 * 1024;
 
+// ---- packed tables of the pair / quad section kernels (k_sec4, k_sec44) -----
+// Bucket table: an entry is a row index 0 .. n (n: the zero slot), 13 bits
+// while n + 1 < 8192.  One record per (section, quarter q, lane, block of KH
+// bucket steps) holds the lane's EQ * KH entries (element-major inside a step,
+// steps in h order; steps past nhi hold n) as one little-endian bit string,
+// padded to whole dwords.  The 64 records of a wave's block are contiguous and
+// laid out for the wave's loads: dwords 0 .. 4 nv - 1 of a record as nv 16-byte
+// pieces [piece][lane], the rest dword-interleaved [dword][lane], so that every
+// load instruction reads one contiguous run (pack_dword_pos).
+constexpr int kPackBits = 13;
+constexpr int kPackMaxN = (1 << kPackBits) - 2;                                      // n + 1 < 8192
+constexpr int pack_rd(int EQ, int KH) { return (EQ * KH * kPackBits + 31) / 32; }   // dwords of a record
+// dword of a wave's block (64 records of rd dwords) that holds dword j of lane's record
+constexpr unsigned pack_dword_pos(int rd, int lane, int j) {
+  return j < rd / 4 * 4 ? (unsigned)((j / 4) * 256 + lane * 4 + j % 4)
+                        : (unsigned)(rd / 4 * 256 + (j - rd / 4 * 4) * 64 + lane);
+}
+// Pair Ab table: one 64-bit word per three rows of a thread of the pair
+// kernel's row phase (512 threads, passes of kPackRows rows): word
+// [pair][j][tid] holds rows (3 j + f) 512 + tid, f = 0, 1, 2, as 20-bit
+// fields k0 | s0 << 9 | k1 << 10 | s1 << 19 (M <= 512); a row past n holds
+// row 0's entry
+constexpr int kPackNT = 512, kPackKR = 9, kPackRows = kPackNT * kPackKR;
+constexpr int pack_fwd_words(int n) { return (n + kPackRows - 1) / kPackRows * (kPackKR / 3); }  // per thread and pair
+
 inline int ilog2(int x) {
   int r = 0;
   while ((1 << r) < x) ++r;
@@ -81,6 +106,10 @@ struct Shape {
   int G4 = 0;          // k_sec44 quads of sections (used when sec4q)
   bool sec4q = false;  // k_sec44 (four sections x 4 waves per workgroup, the pair table) chosen over k_sec4
   size_t sec4q_lds = 0;
+  // packed tables of k_sec4 / k_sec44 (n <= kPackMaxN, M <= 512; SA_PLAN_NO_PACK)
+  bool pack_inv = false;  // 13-bit bucket records (Tables::invp) in blocks of pack_kh steps
+  bool pack_fwd = false;  // three rows per 64-bit word of the pair Ab table (Tables::fwd2p); pairs only
+  int pack_kh = 0;        // the kernel's bucket steps per block (secq_body's KH)
   // batched kernel k_secb
   int WB = 8;          // sections per workgroup (kWB or kWB16)
   int CB = 0;          // codewords per workgroup (0 = off)
@@ -284,6 +313,15 @@ inline int shape_for(Shape& c, int L, int M, int n, int backend, int prec, int p
     // keeps 16-row blocks, and so does SA_PLAN_NO_SEC3, which asks for the
     // pair shape as it was (k_sec4 in front of 16-row blocks)
     if (c.G2 == c.n_cus && !(plan & (SA_PLAN_ROW16 | SA_PLAN_NO_SEC3))) c.row16 = false;
+    // packed tables where pairs or quads run (triples pack their own Ab table
+    // and C4's n needs 14 bits): the tables are over half of the bytes a c2
+    // iteration moves, and with two decodes in flight the headline follows
+    // the bytes ("packed tables").  Either precision;
+    // M <= 512 (EQ <= 2: the 9-bit columns of a field, 13 dwords of a record)
+    const bool packable = c.sec4 && !c.sec3 && backend == SA_BACKEND_HADAMARD && M <= 512 && n <= kPackMaxN;
+    c.pack_inv = packable && !(plan & SA_PLAN_NO_PACK);
+    c.pack_fwd = packable && !c.sec4q && !(plan & SA_PLAN_NO_PACK);
+    c.pack_kh = c.sec4q && s == 8 ? 8 : 16;
   }
   return SA_OK;
 }

@@ -26,6 +26,8 @@ struct Tables {
   uint16_t* fwdb = nullptr;   // k_secb's Ab table, bank-aware step order per row (fwdb_group)
   uint32_t* fwd2 = nullptr;   // [ceil(L/2)][n] section pairs
   uint32_t* fwd3 = nullptr;   // [ceil(L/3)][n] section triples (Shape::sec3)
+  uint32_t* invp = nullptr;   // [L][4][blocks][64 records] 13-bit bucket records (Shape::pack_inv; pack_inv_section)
+  uint64_t* fwd2p = nullptr;  // [ceil(L/2)][words][512] three rows of a section pair per word (Shape::pack_fwd)
   bool invb_done = false;     // ensure_invb has run
 };
 
@@ -72,6 +74,80 @@ inline void fwd_section(const uint32_t* o, int l, int n, int M, uint16_t* fwd, u
     if (fwd3)  // M <= 512: k in 9 bits, the sign in bit 9 of a 10-bit field
       fwd3[(size_t)(l / 3) * n + r] |= (uint32_t)((e & 0x1ffu) | ((e >> 15) << 9)) << (10 * (l % 3));
   }
+}
+
+// ---- packed tables of the pair / quad kernels (sa_shape.h: pack_rd, pack_dword_pos) ----
+// column of a section held by (lane, register i) of a wave with E elements per lane (sa_common.h: elem_index)
+inline int elem_index_host(int E, int lane, int i) {
+  const int Q = E < 4 ? E : 4;
+  return (i / Q) * (64 * Q) + lane * Q + (i % Q);
+}
+// dwords of one section of the packed bucket table: 4 quarters x blocks of kh steps x 64 records
+inline size_t pack_inv_section_dwords(int M, int nhi, int kh) {
+  return (size_t)4 * ((nhi + kh - 1) / kh) * 64 * pack_rd(M / 256, kh);
+}
+// dword and bit of entry (step hh of its block, element i) of a record
+inline void pack_entry_at(int EQ, int hh, int i, int& dw, int& sh) {
+  const int bit = (hh * EQ + i) * kPackBits;
+  dw = bit / 32;
+  sh = bit % 32;
+}
+// Section l of the packed bucket table from its row inv_l [w] of inv: out
+// [4][blocks][64 x rd] (zeroed by the caller)
+inline void pack_inv_section(int M, int n, int nhi, int kh, const uint16_t* inv_l, uint32_t* out) {
+  const int EQ = M / 256, Mq = M / 4, rd = pack_rd(EQ, kh), nb = (nhi + kh - 1) / kh;
+  for (int q = 0; q < 4; ++q)
+    for (int blk = 0; blk < nb; ++blk) {
+      uint32_t* wb = out + ((size_t)q * nb + blk) * 64 * rd;
+      for (int lane = 0; lane < 64; ++lane)
+        for (int hh = 0; hh < kh; ++hh)
+          for (int i = 0; i < EQ; ++i) {
+            const int h = blk * kh + hh;
+            const uint32_t v = h < nhi ? inv_l[(size_t)h * M + q * Mq + elem_index_host(EQ, lane, i)] : (uint32_t)n;
+            int dw, sh;
+            pack_entry_at(EQ, hh, i, dw, sh);
+            wb[pack_dword_pos(rd, lane, dw)] |= v << sh;
+            if (sh + kPackBits > 32) wb[pack_dword_pos(rd, lane, dw + 1)] |= v >> (32 - sh);
+          }
+    }
+}
+// ... and its entry of bucket step h, column col, read back
+inline uint32_t pack_inv_get(int M, int nhi, int kh, const uint32_t* sec, int h, int col) {
+  const int EQ = M / 256, Mq = M / 4, rd = pack_rd(EQ, kh), nb = (nhi + kh - 1) / kh;
+  const int q = col / Mq, e = col % Mq, Q = EQ < 4 ? EQ : 4;
+  const int lane = (e % (64 * Q)) / Q, i = (e / (64 * Q)) * Q + e % Q;  // elem_index inverted
+  const uint32_t* wb = sec + ((size_t)q * nb + h / kh) * 64 * rd;
+  int dw, sh;
+  pack_entry_at(EQ, h % kh, i, dw, sh);
+  uint64_t x = wb[pack_dword_pos(rd, lane, dw)];
+  if (sh + kPackBits > 32) x |= (uint64_t)wb[pack_dword_pos(rd, lane, dw + 1)] << 32;
+  return (uint32_t)(x >> sh) & ((1u << kPackBits) - 1u);
+}
+
+// 20-bit field of a pair-table entry (k0 | s0 << 15 | k1 << 16 | s1 << 31, M <= 512), and back
+inline uint32_t pack_fwd_field(uint32_t e) {
+  return (e & 0x1ffu) | (((e >> 15) & 1u) << 9) | (((e >> 16) & 0x1ffu) << 10) | ((e >> 31) << 19);
+}
+inline uint32_t pack_fwd_entry(uint32_t f) {
+  return (f & 0x1ffu) | (((f >> 9) & 1u) << 15) | (((f >> 10) & 0x1ffu) << 16) | (((f >> 19) & 1u) << 31);
+}
+// Pair g of the packed pair Ab table from its row fwd2_g [n]: out [words][512]
+inline void pack_fwd_pair(int n, const uint32_t* fwd2_g, uint64_t* out) {
+  const int words = pack_fwd_words(n);
+  for (int j = 0; j < words; ++j)
+    for (int tid = 0; tid < kPackNT; ++tid) {
+      uint64_t wv = 0;
+      for (int f = 0; f < 3; ++f) {
+        const int r = (3 * j + f) * kPackNT + tid;
+        wv |= (uint64_t)pack_fwd_field(fwd2_g[r < n ? r : 0]) << (20 * f);
+      }
+      out[(size_t)j * kPackNT + tid] = wv;
+    }
+}
+// ... and row r's entry, in fwd2's form, read back
+inline uint32_t pack_fwd_get(const uint64_t* pair, int r) {
+  const int u = r / kPackNT, tid = r % kPackNT;
+  return pack_fwd_entry((uint32_t)(pair[(size_t)(u / 3) * kPackNT + tid] >> (20 * (u % 3))) & 0xfffffu);
 }
 
 // ---- bank-aware bucket order --------------------------------------------

@@ -7,7 +7,7 @@
 namespace sa {
 
 void tables_free(Tables& t) {
-  void* all[] = {t.inv, t.inv32, t.invb, t.invl, t.hs, t.fwd, t.fwdb, t.fwd2, t.fwd3};
+  void* all[] = {t.inv, t.inv32, t.invb, t.invl, t.hs, t.fwd, t.fwdb, t.fwd2, t.fwd3, t.invp, t.fwd2p};
   for (void* p : all) dev_free(p);
   t = Tables();
 }
@@ -81,6 +81,25 @@ int build_tables(sa_ctx* c) {
   if (!rc) rc = table_upload(c, &t.fwd, c->h_fwd);
   if (!rc && !c->big) rc = table_upload(c, &t.fwd2, fwd2);
   if (!rc && c->sec3) rc = table_upload(c, &t.fwd3, fwd3);
+  // the packed forms of inv and fwd2 for k_sec4 / k_sec44, from the same host copies
+  std::vector<uint32_t> invp;
+  std::vector<uint64_t> fwd2p;
+  if (!rc && c->pack_inv) {
+    const size_t per = pack_inv_section_dwords(c->M, c->nhi, c->pack_kh);
+    invp.assign((size_t)c->L * per, 0);
+    parallel_for(c->L, 1, [&](int l) {
+      pack_inv_section(c->M, c->n, c->nhi, c->pack_kh, c->h_inv.data() + (size_t)l * c->w, invp.data() + (size_t)l * per);
+    });
+    rc = table_upload(c, &t.invp, invp);
+  }
+  if (!rc && c->pack_fwd) {
+    const size_t per = (size_t)pack_fwd_words(c->n) * kPackNT;
+    fwd2p.assign((size_t)c->G2 * per, 0);
+    parallel_for(c->G2, 1, [&](int g) {
+      pack_fwd_pair(c->n, fwd2.data() + (size_t)g * c->n, fwd2p.data() + (size_t)g * per);
+    });
+    rc = table_upload(c, &t.fwd2p, fwd2p);
+  }
   HIP_TRY(hipStreamSynchronize(c->at().stream));  // (also after a failed allocation: the vectors go)
   if (rc) return rc;
   // the host copies stay for the batched tables (ensure_invb)
