@@ -971,6 +971,18 @@ struct RowArgs {
   const int* tb;  // k_rowc: per-codeword iteration index (SecArgs::tb), or null
 };
 
+// k_row2's arguments: a head of plain parameters (sa_row2.hip) and this tail;
+// the flag bits of the head's flt word (above its 24 bits of T1)
+enum : unsigned { kRow2Mode = 3u, kRow2Pt = 4u, kRow2Es = 8u, kRow2Tpos = 16u, kRow2Pbst = 32u };
+template <typename real>
+struct Row2Tail {
+  real* zzp;    // [B][ceil(n / R)]
+  real* out;    // [B][n] (ROW_ABOUT)
+  int* iters;   // [B] (itset)
+  real sqrt_n;
+  int itset;    // RowArgs::itset
+};
+
 // One workgroup = 4 wavefronts = 4 consecutive sections of one codeword
 // (blockIdx.y).  Per wave: v = bucket gather of z (LDS), FWHT, denoise,
 // FWHT of the new beta (for Ab), staged to LDS.  Then the workgroup gathers

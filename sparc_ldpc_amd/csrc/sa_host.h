@@ -63,7 +63,7 @@ struct sa_lane {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_abp = nullptr;
-  void *d_bbp = nullptr, *d_zzp = nullptr, *d_tau = nullptr;
+  void *d_bbp = nullptr, *d_zzp = nullptr, *d_tau = nullptr;  // d_bbp lies in d_tau's allocation (lane_alloc)
   void* d_beta2 = nullptr;  // ping-pong partner of d_beta for k_sec (B x L*M), sized beta2_cap
   int* d_iters = nullptr;
   double* d_stage = nullptr;  // a lane's uploads go through its own staging buffer
@@ -354,6 +354,9 @@ template <typename real>
 int launch_row(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, int G, int Gb, int itset = 0,
                const int* tb = nullptr);
 int launch_decide(sa_ctx* c, int B, int32_t* idx);  // idx: device-visible [B][L]
+// ---- sa_row2.hip: k_row2 (R rows per workgroup) out of launch_row's RowArgs ------
+template <typename real, int R>
+int launch_row2(sa_ctx* c, const Plan& p, int B, const RowArgs<real>& a);
 
 // ---- sa_dense.hip: the materialised-matrix backends ----------------------------
 int dense_den_groups(const sa_ctx* c);

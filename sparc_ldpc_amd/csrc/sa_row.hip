@@ -1,6 +1,6 @@
 // sa_row.hip — the row kernels (Ab partial sums + Onsager residual + z^2
-// partials: k_row, k_rowv, k_rowc, k_row2), the section decision k_decide
-// and their launchers.
+// partials: k_row, k_rowv, k_rowc; k_row2 is sa_row2.hip), the section
+// decision k_decide and their launchers.
 #include "sa_host.h"
 
 namespace sa {
@@ -306,156 +306,6 @@ __global__ void __launch_bounds__(256) k_rowc(RowArgs<real> a, int pil) {
   }
 }
 
-// Row kernel for small batches: 32 rows per 512-thread workgroup, so the
-// ceil(n/32) workgroups of a codeword spread over twice as many CUs as
-// k_row's 64-row workgroups.  Thread (row rl, group pg) sums the Ab
-// partials g = pg, pg+16, ... of its row in order
-// (all loads of a thread in flight together); the 16 group sums are added in
-// group order; wave 0 finishes the rows (Onsager residual, z^2 partial).
-// R = 16 (row-block-major partials only, where the line holds two partials of
-// the same block): twice the workgroups, NG = 32 partial groups of G / 32.
-//
-// One scalar and one vector memory trip per launch: every argument the kernel
-// uses is read into registers at the top (sgpr_now: one batch of scalar
-// loads, none left to trickle in along the control flow), the row-block count
-// is RowArgs::NZ (no hidden grid-size argument), and everything wave 0 needs
-// behind the barrier (y, z, the beta^2 partials, the codeword's power) is
-// loaded with the Ab partials in front of it.
-template <typename real, int R = kRow2Rows, int NT = 512>
-__global__ void __launch_bounds__(NT) k_row2(RowArgs<real> a) {
-  constexpr int NG = NT / R;  // partial groups
-  __shared__ real red[NG][R + 1];
-  const real* tau_p = a.tau;
-  const real* y_p = a.y;
-  const real* zin_p = a.z_in;
-  const real* bbp_p = a.bbp;
-  const real* Pb_p = a.Pb;
-  const real* abp_p = a.abp;
-  int n = a.n, G = a.G, Gb = a.Gb, NZ = a.NZ, T1 = a.T1, t = a.t, mode = a.mode, es = a.early_stop;
-  int Pbst = a.Pbst, pt = a.pt, itset = a.itset;
-  real* z_p = a.z;
-  real* zzp_p = a.zzp;
-  real* out_p = a.out;
-  int* iters_p = a.iters;
-  real sqrt_n = a.sqrt_n;
-  sgpr_now(tau_p, y_p, zin_p, bbp_p, Pb_p, abp_p);
-  sgpr_now(n, G, Gb, NZ, T1, t, mode, es, Pbst, pt, itset);
-  sgpr_now(z_p, zzp_p, out_p, iters_p, sqrt_n);
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int rl = tid & (R - 1), pg = tid / R;
-  const int r = blockIdx.x * R + rl;
-  // tau_t and tau_{t-1} are loaded with everything else; the early-stop
-  // test waits for them only after the Ab-partial loads are in flight
-  // (testing first cost a whole memory round trip per launch)
-  real tau = 1, last = 0;
-  if (mode == ROW_AMP) {
-    tau = ld_vmem(tau_p + (size_t)b * T1 + t);
-    last = t > 0 ? ld_vmem(tau_p + (size_t)b * T1 + t - 1) : (real)0;
-  }
-  const size_t o = (size_t)b * n + (r < n ? r : 0);
-  real yv = 0, zv = 0, Pv = 0, bbv[4] = {0, 0, 0, 0};
-  if (tid < 64) {
-    yv = y_p[o];
-    if (mode == ROW_AMP) {
-      zv = zin_p[o];
-      // the codeword's power: constant over the decode, but behind the barrier
-      // its load was a second memory round trip of every launch
-      Pv = ld_vmem(Pb_p + (size_t)b * Pbst);
-      const real* bp = bbp_p + (size_t)b * Gb;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bbv[q] = tid + 64 * q < Gb ? bp[tid + 64 * q] : (real)0;
-    }
-  }
-  if (mode != ROW_INIT0) {
-    // pt: partial g of row r at [b][r / R][g][r % R] (n padded to R rows)
-    const size_t gs = pt ? (size_t)R : (size_t)n;
-    const real* p = pt ? abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R + rl
-                       : abp_p + (size_t)b * G * n + (r < n ? r : 0);
-    real acc = 0;
-    constexpr int U = 256 / NG;  // G = 256 (C2, C4): every load of a thread in one pass
-    if (pt && (R == 16 || sizeof(real) == 4) && G == NG * U) {
-      // row-block-major partials with exactly NG x U partials (32-row blocks:
-      // binary32 only, C4 single codeword +1 %; the binary64 32-row blocks
-      // measured 1.4 % slower in this form).  The [G][n] partials of k_sec
-      // (sa_Ab, the beta0 start) take the general loop even in 16-row blocks:
-      // constant strides from the block base, no bounds, 32-bit offsets (the
-      // general form spent ~40 VALU ops of 64-bit address math before the
-      // first load); the same loads and sums in the same order
-      const real* pb = abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R;
-      real tt[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        tt[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc += tt[u];
-    } else if (pt && (R == 16 || sizeof(real) == 4) && G == NG * (U / 2)) {
-      // the same with G = 128 (c2 on k_sec44): half the loads per thread
-      constexpr int UH = U / 2;
-      const real* pb = abp_p + (size_t)b * G * ((size_t)NZ * R) + (size_t)blockIdx.x * G * R;
-      real tt[UH];
-#pragma unroll
-      for (int u = 0; u < UH; ++u)
-        tt[u] = ld_off(pb, (unsigned)(((pg + NG * u) * R + rl) * (int)sizeof(real)));
-#pragma unroll
-      for (int u = 0; u < UH; ++u) acc += tt[u];
-    } else
-    for (int g0 = pg; g0 < G; g0 += NG * U) {
-      real tt[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int g = g0 + NG * u;
-        tt[u] = p[(size_t)(g < G ? g : pg) * gs];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (g0 + NG * u < G) acc += tt[u];
-    }
-    red[pg][rl] = acc;
-  }
-  if (mode == ROW_AMP && es && tau == last) return;  // uniform over the workgroup
-  const real tau2 = tau * tau;
-  __syncthreads();
-  if (tid >= 64) return;
-  // the decode's iters[b]: -1 with the residual's initialisation; T with the
-  // last iteration, which runs to here only when no stop has fired (a stopped
-  // codeword stops every later launch too, and keeps the index it stopped at)
-  if (itset != 0 && blockIdx.x == 0 && tid == 0) iters_p[b] = itset;
-  real ons = 0;
-  if (mode == ROW_AMP) {
-    real bb;
-    if (Gb <= 256) {
-      real sacc = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) sacc += bbv[q];
-      bb = wave_sum(sacc);
-    } else {
-      bb = wave_sum_parts(bbp_p + (size_t)b * Gb, Gb);
-    }
-    ons = Pv - bb / (real)n;
-  }
-  real zn = 0;
-  if (tid < R && r < n) {
-    if (mode == ROW_INIT0) {
-      zn = yv;
-    } else {
-      real acc = 0;
-#pragma unroll
-      for (int q = 0; q < NG; ++q) acc += red[q][rl];
-      const real ab = acc / sqrt_n;
-      if (mode == ROW_ABOUT) {
-        out_p[o] = ab;
-        return;
-      }
-      zn = yv - ab;
-      if (mode == ROW_AMP) zn += (zv / tau2) * ons;
-    }
-    z_p[o] = zn;
-  }
-  if (mode == ROW_ABOUT) return;
-  const real sz = wave_sum(zn * zn);
-  if (tid == 0) zzp_p[(size_t)b * NZ + blockIdx.x] = sz;
-}
-
 // Per-section decision (sparc_ldpc.py:452-455): argmax, first index on ties.
 template <typename real, int E>
 __global__ void __launch_bounds__(256) k_decide(const real* beta, int32_t* idx, int L, int M, int dead) {
@@ -489,9 +339,13 @@ int launch_row(sa_ctx* c, const Plan& p, int B, int mode, int t, int es, int G, 
         plaunch(c, k_rowc<real, CBz>, dim3(p.nz, (B + CBz - 1) / CBz), 256, 0, a, mode == ROW_AMP ? 1 : 0);
       break;
     }
-    // k_row2 takes its row-block count from RowArgs::NZ (no hidden grid argument)
-    case SA_ROW_K_ROW2: plaunch(c, k_row2<real>, dim3(p.nz, B), 512, 0, a); break;
-    case SA_ROW_K_ROW2_16: plaunch(c, k_row2<real, 16>, dim3(p.nz, B), 512, 0, a); break;
+    // k_row2 takes its row-block count from n (no hidden grid argument)
+    case SA_ROW_K_ROW2:
+      if (int rc = launch_row2<real, kRow2Rows>(c, p, B, a)) return rc;
+      break;
+    case SA_ROW_K_ROW2_16:
+      if (int rc = launch_row2<real, 16>(c, p, B, a)) return rc;
+      break;
     case SA_ROW_K_ROWV16: {
       constexpr int V = 16 / (int)sizeof(real);  // 16-byte rows
       plaunch(c, k_rowv<real, V>, dim3(p.nz, B), 256, 0, a);

@@ -174,9 +174,12 @@ static int lane_alloc(sa_ctx* c, sa_lane& l, size_t nB, size_t nBp, int T, int G
   if ((rc = dev_alloc(c, &l.d_beta, nB * LM * s))) return rc;
   // rows padded to 32: the row-block-major layout of the pair / triple kernels (SecArgs::pt)
   if ((rc = dev_alloc(c, &l.d_abp, nBp * Gmax * ((size_t)c->NZ16 * kRow2Rows) * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_bbp, nB * Gmax * s))) return rc;
   if ((rc = dev_alloc(c, &l.d_zzp, nB * c->NZh * s))) return rc;
-  if ((rc = dev_alloc(c, &l.d_tau, nB * (T + 1) * s))) return rc;
+  // tau and, behind it (256-byte aligned), the beta^2 partials in one allocation:
+  // k_row2 reaches the partials at a 32-bit offset from the tau it is handed
+  const size_t tau_bytes = (nB * (T + 1) * s + 255) / 256 * 256;
+  if ((rc = dev_alloc(c, &l.d_tau, tau_bytes + nB * Gmax * s))) return rc;
+  l.d_bbp = static_cast<char*>(l.d_tau) + tau_bytes;
   if ((rc = dev_alloc(c, (void**)&l.d_iters, nB * sizeof(int)))) return rc;
   // the fused tail's decisions: written by the last section launch, read by the host behind ev1
   if (hipHostMalloc((void**)&l.h_dec, nB * c->L * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
@@ -189,11 +192,12 @@ static int lane_alloc(sa_ctx* c, sa_lane& l, size_t nB, size_t nBp, int T, int G
 }
 
 static void lane_free(sa_lane& l) {
-  void** bufs[] = {&l.d_y, &l.d_z, &l.d_beta, &l.d_beta2, &l.d_abp, &l.d_bbp, &l.d_zzp, &l.d_tau, (void**)&l.d_iters};
+  void** bufs[] = {&l.d_y, &l.d_z, &l.d_beta, &l.d_beta2, &l.d_abp, &l.d_zzp, &l.d_tau, (void**)&l.d_iters};
   for (void** p : bufs) {
     dev_free(*p);
     *p = nullptr;
   }
+  l.d_bbp = nullptr;  // inside d_tau's allocation
   l.beta2_cap = 0;
   if (l.h_dec) (void)hipHostFree(l.h_dec);
   l.h_dec = l.d_dec = nullptr;
