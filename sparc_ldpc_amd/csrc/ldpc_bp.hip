@@ -59,9 +59,6 @@ using namespace lb;
 
 namespace {
 
-constexpr int kMaxThreads = 1024;
-constexpr size_t kLdsBytes = 160 * 1024;
-
 // ---------------------------------------------------------------------------
 // Node rules
 // ---------------------------------------------------------------------------
@@ -258,7 +255,6 @@ struct BpArgs {
 // DCFIX > 0: every check node has exactly DCFIX edges (lxfb_fixed; launched
 // with at most kFixThreads threads, so a thread may hold the two chains in
 // registers: 3 waves per SIMD)
-constexpr int kFixThreads = 768;
 template <int ALGO, int DCMAX, bool LDSM, int DCFIX = 0>
 __global__ void __launch_bounds__(DCFIX > 0 ? kFixThreads : kMaxThreads) k_bp(BpArgs a) {
   extern __shared__ double lds_msg[];
@@ -801,7 +797,6 @@ __device__ __forceinline__ double swap_pair(double x) {
   return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
 
-constexpr int kTailFixThreads = 256, kTailThreads = 128;
 template <int ALGO, int DCMAX, int DCFIX>
 __global__ void __launch_bounds__(DCFIX > 0 ? kTailFixThreads : kTailThreads) k_bp_tail_chk(TailArgs a) {
   constexpr int ROW = DCMAX + 1;
@@ -898,24 +893,25 @@ __global__ void k_lxfb(double* L, int dc, int corr, double* out) {
 
 using KernelFn = void (*)(BpArgs);
 
+// The pick_* functions take the check-degree class as ldpc_plan.h computed it (GraphPlan::dcmax,
+// LayeredLaunch): 8 / 16 / 32, and 20 beside them for the fixed-point kernels.
 template <int ALGO, bool LDSM>
-KernelFn pick_dc(int maxdc) {
-  if (maxdc <= 8) return k_bp<ALGO, 8, LDSM>;
-  if (maxdc <= 16) return k_bp<ALGO, 16, LDSM>;
-  return k_bp<ALGO, 32, LDSM>;
+KernelFn pick_dc(int dcmax) {
+  switch (dcmax) {
+    case 8: return k_bp<ALGO, 8, LDSM>;
+    case 16: return k_bp<ALGO, 16, LDSM>;
+    default: return k_bp<ALGO, 32, LDSM>;
+  }
 }
 
-// check-regular codes whose degree has a straight-line instance (lxfb_fixed)
-bool fixed_dc(int mindc, int maxdc, int nt) { return mindc == maxdc && maxdc == 20 && nt <= kFixThreads; }
-
-KernelFn pick_kernel(int algo, int maxdc, bool lds, bool fixed = false) {
+KernelFn pick_kernel(int algo, int dcmax, bool lds, bool fixed = false) {
   if (fixed && algo == LB_SUMPROD2) return lds ? k_bp<LB_SUMPROD2, 32, true, 20> : k_bp<LB_SUMPROD2, 32, false, 20>;
   if (fixed && algo == LB_MINSUM) return lds ? k_bp<LB_MINSUM, 32, true, 20> : k_bp<LB_MINSUM, 32, false, 20>;
   // sumprod does not use the register-resident forward values: one instance suffices
   switch (algo) {
-    case LB_SUMPROD2: return lds ? pick_dc<LB_SUMPROD2, true>(maxdc) : pick_dc<LB_SUMPROD2, false>(maxdc);
+    case LB_SUMPROD2: return lds ? pick_dc<LB_SUMPROD2, true>(dcmax) : pick_dc<LB_SUMPROD2, false>(dcmax);
     case LB_SUMPROD: return lds ? k_bp<LB_SUMPROD, 8, true> : k_bp<LB_SUMPROD, 8, false>;
-    default: return lds ? pick_dc<LB_MINSUM, true>(maxdc) : pick_dc<LB_MINSUM, false>(maxdc);
+    default: return lds ? pick_dc<LB_MINSUM, true>(dcmax) : pick_dc<LB_MINSUM, false>(dcmax);
   }
 }
 
@@ -933,32 +929,32 @@ LayeredInst layered_row(bool f32) {
 }
 
 template <int ALGO, int MODE>
-LayeredInst pick_layered_dc(int maxdc, bool fixed, bool f32) {
-  if (fixed) return layered_row<ALGO, 32, 20, MODE>(f32);
-  if (maxdc <= 8) return layered_row<ALGO, 8, 0, MODE>(f32);
-  if (maxdc <= 16) return layered_row<ALGO, 16, 0, MODE>(f32);
-  return layered_row<ALGO, 32, 0, MODE>(f32);
+LayeredInst pick_layered_dc(int dcmax, int dcfix, bool f32) {
+  if (dcfix) return layered_row<ALGO, 32, 20, MODE>(f32);
+  switch (dcmax) {
+    case 8: return layered_row<ALGO, 8, 0, MODE>(f32);
+    case 16: return layered_row<ALGO, 16, 0, MODE>(f32);
+    default: return layered_row<ALGO, 32, 0, MODE>(f32);
+  }
 }
 
 // algo: LB_LAYERED_SUMPROD2 or LB_LAYERED_MINSUM; the check rules are the flooding decoders'
-LayeredInst pick_layered(int algo, int maxdc, bool fixed, int mode, bool f32) {
+LayeredInst pick_layered(int algo, int dcmax, int dcfix, int mode, bool f32) {
   if (algo == LB_LAYERED_SUMPROD2)
-    return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(maxdc, fixed, f32)
-           : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(maxdc, fixed, f32)
-                       : pick_layered_dc<LB_SUMPROD2, 0>(maxdc, fixed, f32);
-  return mode == 2   ? pick_layered_dc<LB_MINSUM, 2>(maxdc, fixed, f32)
-         : mode == 1 ? pick_layered_dc<LB_MINSUM, 1>(maxdc, fixed, f32)
-                     : pick_layered_dc<LB_MINSUM, 0>(maxdc, fixed, f32);
+    return mode == 2   ? pick_layered_dc<LB_SUMPROD2, 2>(dcmax, dcfix, f32)
+           : mode == 1 ? pick_layered_dc<LB_SUMPROD2, 1>(dcmax, dcfix, f32)
+                       : pick_layered_dc<LB_SUMPROD2, 0>(dcmax, dcfix, f32);
+  return mode == 2   ? pick_layered_dc<LB_MINSUM, 2>(dcmax, dcfix, f32)
+         : mode == 1 ? pick_layered_dc<LB_MINSUM, 1>(dcmax, dcfix, f32)
+                     : pick_layered_dc<LB_MINSUM, 0>(dcmax, dcfix, f32);
 }
 
 // The fixed-point instances: lanes per check G x the check-degree class (8 / 16 / 20 / 32 edges over
-// the group's lanes; 20 is the 802.16 5/6 codes' degree and keeps their lanes at 10 edges, not 16).
+// the group's lanes, dc_class_fixed).
 struct FixedInst {
   void (*batch)(BplqArgs);
   void (*stream)(BplqStreamArgs);
 };
-
-constexpr int edges_per_lane(int dcmax, int g) { return (dcmax + g - 1) / g; }
 
 template <int G, int DCMAX>
 FixedInst fixed_row() {
@@ -966,49 +962,49 @@ FixedInst fixed_row() {
 }
 
 template <int G>
-FixedInst pick_fixed_g(int maxdc) {
-  if (maxdc <= 8) return fixed_row<G, 8>();
-  if (maxdc <= 16) return fixed_row<G, 16>();
-  if (maxdc <= 20) return fixed_row<G, 20>();
-  return fixed_row<G, 32>();
+FixedInst pick_fixed_g(int dcmax) {
+  switch (dcmax) {
+    case 8: return fixed_row<G, 8>();
+    case 16: return fixed_row<G, 16>();
+    case 20: return fixed_row<G, 20>();
+    default: return fixed_row<G, 32>();
+  }
 }
 
-FixedInst pick_fixed(int lanes, int maxdc) {
+FixedInst pick_fixed(int lanes, int dcmax) {
   switch (lanes) {
-    case 1: return pick_fixed_g<1>(maxdc);
-    case 2: return pick_fixed_g<2>(maxdc);
-    case 4: return pick_fixed_g<4>(maxdc);
-    case 8: return pick_fixed_g<8>(maxdc);
-    default: return pick_fixed_g<16>(maxdc);
+    case 1: return pick_fixed_g<1>(dcmax);
+    case 2: return pick_fixed_g<2>(dcmax);
+    case 4: return pick_fixed_g<4>(dcmax);
+    case 8: return pick_fixed_g<8>(dcmax);
+    default: return pick_fixed_g<16>(dcmax);
   }
 }
 
 using TailFn = void (*)(TailArgs);
 
 template <int ALGO>
-TailFn pick_tail_dc(int maxdc) {
-  if (maxdc <= 8) return k_bp_tail_chk<ALGO, 8, 0>;
-  if (maxdc <= 16) return k_bp_tail_chk<ALGO, 16, 0>;
-  return k_bp_tail_chk<ALGO, 32, 0>;
+TailFn pick_tail_dc(int dcmax) {
+  switch (dcmax) {
+    case 8: return k_bp_tail_chk<ALGO, 8, 0>;
+    case 16: return k_bp_tail_chk<ALGO, 16, 0>;
+    default: return k_bp_tail_chk<ALGO, 32, 0>;
+  }
 }
 
-TailFn pick_tail(int algo, int maxdc, bool fixed) {
+TailFn pick_tail(int algo, int dcmax, bool fixed) {
   if (fixed && algo == LB_SUMPROD2) return k_bp_tail_chk<LB_SUMPROD2, 32, 20>;
   if (fixed && algo == LB_MINSUM) return k_bp_tail_chk<LB_MINSUM, 32, 20>;
   switch (algo) {
-    case LB_SUMPROD2: return pick_tail_dc<LB_SUMPROD2>(maxdc);
-    case LB_SUMPROD: return pick_tail_dc<LB_SUMPROD>(maxdc);
-    default: return pick_tail_dc<LB_MINSUM>(maxdc);
+    case LB_SUMPROD2: return pick_tail_dc<LB_SUMPROD2>(dcmax);
+    case LB_SUMPROD: return pick_tail_dc<LB_SUMPROD>(dcmax);
+    default: return pick_tail_dc<LB_MINSUM>(dcmax);
   }
 }
 
 TailFn pick_tail_var(int nq) {
   return nq == 1 ? k_bp_tail_var<4> : (nq == 2 ? k_bp_tail_var<8> : k_bp_tail_var<12>);
 }
-
-// first iteration of the tail launches (0: off); LDPC_BP_TAIL overrides
-constexpr int kTailAt = 8;
-constexpr int kTailChunk = 8;  // tail iterations per stop test
 
 int device_count() {
   int n = 0;
@@ -1092,46 +1088,11 @@ int ensure_slices(lb_ctx* c, int need) {
 
 int ensure_msg(lb_ctx* c, int B, bool tail) { return ensure_slices(c, tail ? 2 * B : (c->lds ? 0 : B)); }
 
-// binary32 with app in HBM keeps it behind r in the word's slice of d_msg (Nmsg doubles)
-int f32_slice_fits(const lb_ctx* c, const DecType& t) {
-  if (t.f32 && c->lmode32 == 0 && c->Nv > c->Nmsg)
-    return fail(LB_ERR_UNSUPPORTED, "binary32 layered decoder without LDS needs Nv <= Nmsg");
-  return LB_OK;
-}
-
 // (lb::resolve, declared in ldpc_bp_int.h)
 int resolve(lb_ctx* c, int algo, double corr, int max_iter, bool for_stream, DecType* t) {
-  DecType d;
-  d.f32 = algo >= 0 && (algo & LB_F32);
-  d.fixed = algo >= 0 && (algo & LB_FIXED);
-  d.base = algo >= 0 ? algo & ~(LB_F32 | LB_FIXED) : algo;
-  if (d.base < LB_SUMPROD2 || d.base > LB_LAYERED_MINSUM) return fail(LB_ERR_ARG, "unknown decoder type");
-  const bool layered = d.base >= LB_LAYERED_SUMPROD2;
-  // LB_FIXED goes with layered min-sum alone
-  if (d.fixed && d.f32) return fail(LB_ERR_ARG, "LB_FIXED | LB_F32: the fixed-point decoder has no binary32 form");
-  if (d.fixed && d.base != LB_LAYERED_MINSUM)
-    return fail(LB_ERR_UNSUPPORTED, "fixed-point (LB_FIXED) exists for layered min-sum (LB_LAYERED_MINSUM) only");
-  if (d.f32 && !layered)
-    return fail(LB_ERR_UNSUPPORTED, "binary32 (LB_F32) exists for the layered decoder types only");
-  if (for_stream && !layered)
-    return fail(LB_ERR_UNSUPPORTED, "the block stream exists for the layered decoder types only");
-  if (max_iter < 0) return fail(LB_ERR_ARG, "max_iter < 0");
-  if (layered && !c->nlayers)
-    return fail(LB_ERR_ARG, "layered decoder on a context without layers (lb_set_layers)");
-  if (d.fixed) {  // the kernel's parameters from the context's widths and corr_factor
-    const double alpha = nearbyint(16.0 * corr);  // half to even, as rint in the statement
-    if (!(alpha >= 1.0 && alpha <= 16.0))
-      return fail(LB_ERR_ARG, "fixed-point min-sum needs rint(16 corr_factor) in 1..16");
-    if (!c->qfit)
-      return fail(LB_ERR_UNSUPPORTED, "fixed-point decoder: the image (" + std::to_string(c->qlds) +
-                                          " bytes) does not fit a workgroup's LDS, and there is no HBM layout");
-    d.par = {c->qfrac, (1 << (c->qmsg - 1)) - 1, (1 << (c->qapp - 1)) - 1, (int)alpha};
-  }
-  int rc;
-  if (for_stream && (rc = f32_slice_fits(c, d))) return rc;  // (lb::launch: once it has work)
-  d.hbm = layered && !d.fixed && (d.f32 ? c->lmode32 : c->lmode) < 2;
-  *t = d;
-  return LB_OK;
+  std::string err;
+  const int rc = resolve(*c, *c, *c, algo, corr, max_iter, for_stream, t, err);
+  return rc ? fail(rc, err) : LB_OK;
 }
 
 // Raise a kernel's dynamic LDS limit, once per context.  The layered instances ask for the whole
@@ -1144,7 +1105,7 @@ int raise_lds(lb_ctx* c, const void* fn, size_t bytes = kLdsBytes - 64) {
 }
 
 // How a resolved layered type launches on this context: its batch / stream instance pair
-// (floating or fixed point), threads per workgroup and dynamic LDS bytes.
+// (floating or fixed point), threads per workgroup and dynamic LDS bytes (layered_launch).
 struct LayeredShape {
   LayeredInst fn{};
   FixedInst qfn{};               // DecType::fixed
@@ -1155,20 +1116,15 @@ struct LayeredShape {
 
 // stream: the persistent kernel of the pair.  Raises that kernel's LDS limit on first use.
 int layered_shape(lb_ctx* c, const DecType& t, bool stream, LayeredShape* s) {
+  const LayeredLaunch ll = layered_launch(*c, *c, *c, t);
+  s->nt = ll.nt;
+  s->shm = ll.shm;
   if (t.fixed) {
-    s->qfn = pick_fixed(c->qlanes, c->maxdc);
+    s->qfn = pick_fixed(ll.lanes, ll.dcmax);
     s->kernel = stream ? (const void*)s->qfn.stream : (const void*)s->qfn.batch;
-    s->nt = c->qnt;
-    s->shm = (size_t)c->qlds;
   } else {
-    const int mode = t.f32 ? c->lmode32 : c->lmode;
-    const size_t el = t.f32 ? sizeof(float) : sizeof(double);
-    s->fn = pick_layered(t.base, c->maxdc, c->lfixed, mode, t.f32);
+    s->fn = pick_layered(t.base, ll.dcmax, ll.dcfix, ll.mode, t.f32);
     s->kernel = stream ? (const void*)s->fn.stream : (const void*)s->fn.batch;
-    s->nt = c->lnt;
-    s->shm = mode == 2 ? (size_t)(c->Nv + c->Nmsg) * el : mode == 1 ? (size_t)c->Nv * el : 0;
-    // measurement switch: more than half a CU's LDS, so that a binary32 workgroup has its CU alone
-    if (t.f32 && c->lone32) s->shm = std::max(s->shm, kLdsBytes / 2 + 64);
   }
   return s->shm ? raise_lds(c, s->kernel) : LB_OK;
 }
@@ -1205,7 +1161,8 @@ BplArgs bpl_args(const lb_ctx* c, const double* ch, double* app, int* iters, dou
 int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const DecType& t, double corr,
                    int max_iter) {
   int rc;
-  if ((rc = f32_slice_fits(c, t))) return rc;
+  std::string err;
+  if ((rc = f32_slice_fits(*c, *c, t, err))) return fail(rc, err);
   if ((rc = ensure_slices(c, t.hbm ? B : 0))) return rc;
   LayeredShape s;
   if ((rc = layered_shape(c, t, false, &s))) return rc;
@@ -1218,33 +1175,6 @@ int launch_layered(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_i
   }
   HIP_TRY(hipGetLastError());
   return LB_OK;
-}
-
-// ---- fixed point ----
-
-// threads per workgroup, lanes per check and LDS bytes of the fixed-point decoder (lb_set_layers,
-// lb_set_fixed).  Lanes: the largest power of two, at most the largest check degree and 16, at which
-// the largest layer's groups still fit 768 threads (measured at 802.16 5/6 z=192, DESIGN.md section
-// 10b: 4 lanes against 2 and 8); threads: a lane for every group of the largest layer, and all 1024
-// where that is more than a third of a CU's 2048 (two workgroups share a CU either way, and the
-// loops over all checks and variables take fewer passes).
-void plan_fixed(lb_ctx* c) {
-  int cap = 1;
-  while (cap * 2 <= c->maxdc && cap < 16) cap *= 2;
-  int g = 1;
-  while (g * 2 <= cap && (long long)c->maxlayer * g * 2 <= 768) g *= 2;
-  if (const char* e = getenv("LDPC_BP_FIXED_LANES"); e && *e) {
-    const int v = atoi(e);
-    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) g = v;
-  }
-  long long nt = std::min<long long>(kMaxThreads, ((long long)c->maxlayer * g + 63) / 64 * 64);
-  if (nt * 3 > 2048) nt = kMaxThreads;
-  if (const char* e = getenv("LDPC_BP_FIXED_THREADS"); e && *e) nt = std::min(kMaxThreads, atoi(e) / 64 * 64);
-  c->qlanes = g;
-  c->qnt = (int)std::max<long long>(64, nt);
-  const long long bytes = (2LL * c->Nv + c->Nmsg + 15) / 16 * 16;
-  c->qfit = bytes <= (long long)kLdsBytes - 64;
-  c->qlds = (int)std::min<long long>(bytes, INT32_MAX);
 }
 
 // (lb::stream_plan, declared in ldpc_bp_int.h)
@@ -1313,7 +1243,7 @@ int set_attrs(lb_ctx* c) {
   const size_t bytes = (size_t)c->Nmsg * sizeof(double);
   int rc;
   for (int algo = 0; algo < 3; ++algo)
-    if ((rc = raise_lds(c, (const void*)pick_kernel(algo, c->maxdc, true, c->fixed), bytes))) return rc;
+    if ((rc = raise_lds(c, (const void*)pick_kernel(algo, c->dcmax, true, c->fixed), bytes))) return rc;
   return LB_OK;
 }
 
@@ -1357,7 +1287,7 @@ int launch_flooding(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_
   }
   if (tail) HIP_TRY(hipMemsetAsync(c->d_nact, 0, 2 * sizeof(int), c->stream));  // nactive, ndone
   const size_t shm = c->lds ? (size_t)c->Nmsg * sizeof(double) : 0;
-  hipLaunchKernelGGL(pick_kernel(algo, c->maxdc, c->lds, c->fixed), dim3(B), dim3(c->nt), shm, c->stream, a);
+  hipLaunchKernelGGL(pick_kernel(algo, c->dcmax, c->lds, c->fixed), dim3(B), dim3(c->nt), shm, c->stream, a);
   HIP_TRY(hipGetLastError());
   return tail ? launch_tail(c, B, d_ch, d_app, d_it, algo, corr, max_iter, sized_on_host) : LB_OK;
 }
@@ -1376,23 +1306,10 @@ int launch_tail(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, 
     if (n < 0 || n > B) return fail(LB_ERR_HIP, "tail word count out of range");
     if (n == 0) return LB_OK;
   }
-  // the words the grids are sized for: exact, or the last device-sized tail's
-  // share of its batch applied to this one (a quarter before any), with slack
-  int nsz = n;
-  if (!sized_on_host) {
-    const double share = c->est_B > 0 ? (double)c->est_n / c->est_B : 0.25;
-    nsz = std::min(B, std::max(8, (int)std::ceil(share * B * 1.25)));
-  }
-  // m waves per workgroup so that the words' waves (one thread per check)
-  // cover the SIMDs once: S = ceil(Nc / 64m) workgroups per word
-  // the straight-line check rule runs on lane pairs (32 checks per wave)
+  // the straight-line check rule runs on lane pairs
   const bool split = c->fixed && algo != LB_SUMPROD;
-  const int cpt = split ? 32 : 64;  // checks per wave
-  const long waves = (long)nsz * ((c->Nc + cpt - 1) / cpt);
-  const int mmax = (split ? kTailFixThreads : kTailThreads) / 64;
-  int m = (int)((waves + 4L * c->ncu - 1) / (4L * c->ncu));
-  m = m < 1 ? 1 : (m > mmax ? mmax : m);
-  const int S = (c->Nc + cpt * m - 1) / (cpt * m);
+  const TailShape ts = tail_shape(B, n, sized_on_host, c->est_n, c->est_B, c->Nc, c->ncu, split);
+  const int nsz = ts.nsz, m = ts.m, S = ts.S;
   TailArgs t;
   t.ch = d_ch;
   t.app = d_app;
@@ -1415,7 +1332,7 @@ int launch_tail(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, 
   t.dyn = sized_on_host ? 0 : 1;
   t.corr = corr;
   double* slot[2] = {c->d_msg, c->d_msg + (size_t)B * c->Nmsg};
-  const TailFn chk = pick_tail(algo, c->maxdc, split);
+  const TailFn chk = pick_tail(algo, c->dcmax, split);
   const TailFn var = pick_tail_var(c->nq);
   const dim3 vgrid((c->Nv + 255) / 256, nsz);
   const dim3 cgrid((unsigned)nsz * S);
@@ -1546,82 +1463,27 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
               int Nmsg, int device) {
   if (!out) return fail(LB_ERR_ARG, "out is null");
   *out = nullptr;
-  if (!vdeg || !cdeg || !intrlv || Nv <= 0 || Nc <= 0 || Nmsg <= 0)
-    return fail(LB_ERR_ARG, "empty or null graph");
-  // host-side validation (the reference trusts its own prepare_decoder)
-  long sv = 0, sc = 0;
-  int maxdv = 0, maxdc = 0, mindc = 1 << 30;
-  for (int j = 0; j < Nv; ++j) {
-    if (vdeg[j] < 0) return fail(LB_ERR_GRAPH, "negative variable degree");
-    sv += vdeg[j];
-    maxdv = vdeg[j] > maxdv ? (int)vdeg[j] : maxdv;
-  }
-  for (int j = 0; j < Nc; ++j) {
-    if (cdeg[j] < 1) return fail(LB_ERR_GRAPH, "check node of degree < 1");
-    sc += cdeg[j];
-    maxdc = cdeg[j] > maxdc ? (int)cdeg[j] : maxdc;
-    mindc = cdeg[j] < mindc ? (int)cdeg[j] : mindc;
-  }
-  if (sv != Nmsg || sc != Nmsg) return fail(LB_ERR_GRAPH, "sum(vdeg) and sum(cdeg) must equal Nmsg");
-  if (maxdc > 32) return fail(LB_ERR_UNSUPPORTED, "check degree > 32");
-  if (maxdv > 255) return fail(LB_ERR_UNSUPPORTED, "variable degree > 255");
-  std::vector<char> seen(Nmsg, 0);
-  for (int i = 0; i < Nmsg; ++i) {
-    if (intrlv[i] < 0 || intrlv[i] >= Nmsg || seen[intrlv[i]]) return fail(LB_ERR_GRAPH, "intrlv is not a permutation");
-    seen[intrlv[i]] = 1;
-  }
+  // a bad graph is refused on the host, before the device is looked at
+  GraphPlan g;
+  std::string err;
+  int rc = check_graph(vdeg, cdeg, intrlv, Nv, Nc, Nmsg, g, err);
+  if (rc) return fail(rc, err);
   const int ndev = device_count();
   if (ndev == 0) return fail(LB_ERR_NO_DEVICE, "no HIP device visible (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(LB_ERR_ARG, "device index out of range");
-
-  std::vector<int> vedge((size_t)std::max(maxdv, 1) * Nv, 0);
-  std::vector<uint8_t> vd(Nv);
-  std::vector<int> cs(Nc + 1);
-  long p = 0;
-  for (int j = 0; j < Nv; ++j) {
-    vd[j] = (uint8_t)vdeg[j];
-    for (int k = 0; k < vdeg[j]; ++k) vedge[(size_t)k * Nv + j] = (int)intrlv[p++];
-  }
-  cs[0] = 0;
-  for (int j = 0; j < Nc; ++j) cs[j + 1] = cs[j] + (int)cdeg[j];
-  // edge table of the tail and the layered kernels: the variable node of each edge
-  // (kept on the host as well: lb_set_layers checks its layers against it)
-  const int nq = maxdv <= 12 ? std::max(1, (maxdv + 3) / 4) : 0;
-  std::vector<int> evar(Nmsg);
-  {
-    long q = 0;
-    for (int j = 0; j < Nv; ++j)
-      for (int k = 0; k < vdeg[j]; ++k) evar[intrlv[q++]] = j;
-  }
+  const GraphTables t = graph_tables(vdeg, cdeg, intrlv, g);
 
   lb_ctx* c = new lb_ctx;
+  static_cast<GraphPlan&>(*c) = plan_graph(g, read_switches());
   c->dev = device;
-  c->Nv = Nv;
-  c->Nc = Nc;
-  c->Nmsg = Nmsg;
-  c->maxdv = maxdv;
-  c->maxdc = maxdc;
-  c->h_evar = evar;
-  c->h_cstart = cs;
-  c->lds = (size_t)Nmsg * sizeof(double) <= kLdsBytes - 64;
-  // one thread per check node when possible (the check phase dominates)
-  c->nt = std::min(kMaxThreads, std::max(256, (Nc + 63) / 64 * 64));
-  c->mindc = mindc;
-  c->fixed = fixed_dc(mindc, maxdc, c->nt);
-  c->nq = nq;
-  c->tail_at = 0;
-  if (c->nq) {
-    const char* e = getenv("LDPC_BP_TAIL");
-    c->tail_at = (e && *e) ? std::max(0, atoi(e)) : kTailAt;
-  }
-  c->tail_default = c->tail_at;
-  int rc = LB_OK;
+  c->h_evar = t.evar;
+  c->h_cstart = t.cstart;
   auto bail = [&](int r) { release(c); return r; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(LB_ERR_HIP, "hipSetDevice failed"));
-  if ((rc = dev_alloc((void**)&c->d_vedge, vedge.size() * sizeof(int)))) return bail(rc);
+  if ((rc = dev_alloc((void**)&c->d_vedge, t.vedge.size() * sizeof(int)))) return bail(rc);
   if ((rc = dev_alloc((void**)&c->d_vdeg, (size_t)Nv))) return bail(rc);
   if ((rc = dev_alloc((void**)&c->d_cstart, (size_t)(Nc + 1) * sizeof(int)))) return bail(rc);
-  if ((rc = dev_alloc((void**)&c->d_evar, evar.size() * sizeof(int)))) return bail(rc);
+  if ((rc = dev_alloc((void**)&c->d_evar, t.evar.size() * sizeof(int)))) return bail(rc);
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
@@ -1634,10 +1496,10 @@ int lb_create(lb_ctx** out, const long* vdeg, const long* cdeg, const long* intr
     return bail(fail(LB_ERR_HIP, "stream/event creation failed"));
   // uploads on the context's non-blocking stream, waited for (a pageable
   // hipMemcpy may return before its DMA lands, unordered with this stream)
-  if (hipMemcpyAsync(c->d_vedge, vedge.data(), vedge.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_vdeg, vd.data(), (size_t)Nv, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_cstart, cs.data(), (size_t)(Nc + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_evar, evar.data(), evar.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+  if (hipMemcpyAsync(c->d_vedge, t.vedge.data(), t.vedge.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_vdeg, t.vdeg.data(), (size_t)Nv, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_cstart, t.cstart.data(), (size_t)(Nc + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_evar, t.evar.data(), t.evar.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return bail(fail(LB_ERR_HIP, "graph upload failed"));
   *out = c;
@@ -1754,33 +1616,18 @@ int lb_set_tail(lb_ctx* c, int tail_at) {
 }
 
 int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
-  if (!c || nlayers < 1 || !first_check) return fail(LB_ERR_ARG, "bad layer arguments");
-  // on the host, before anything is uploaded or changed
-  if (first_check[0] != 0) return fail(LB_ERR_GRAPH, "first_check[0] must be 0");
-  int maxlayer = 0;
-  for (int l = 0; l < nlayers; ++l) {
-    if (first_check[l + 1] <= first_check[l] || first_check[l + 1] > c->Nc)
-      return fail(LB_ERR_GRAPH, "first_check must increase strictly from 0 to Nc (layer " + std::to_string(l) + ")");
-    maxlayer = std::max(maxlayer, first_check[l + 1] - first_check[l]);
-  }
-  int maxedges = 0;
-  for (int l = 0; l < nlayers; ++l)
-    maxedges = std::max(maxedges, c->h_cstart[first_check[l + 1]] - c->h_cstart[first_check[l]]);
-  if (first_check[nlayers] != c->Nc)
-    return fail(LB_ERR_GRAPH, "first_check[nlayers] = " + std::to_string(first_check[nlayers]) + " is not Nc = " +
-                                  std::to_string(c->Nc));
-  std::vector<int> owner(c->Nv, -1);
-  for (int l = 0; l < nlayers; ++l)
-    for (int e = c->h_cstart[first_check[l]]; e < c->h_cstart[first_check[l + 1]]; ++e) {
-      const int v = c->h_evar[e];
-      if (owner[v] == l)
-        return fail(LB_ERR_GRAPH, "layer " + std::to_string(l) + ": variable " + std::to_string(v) + " occurs twice");
-      owner[v] = l;
-    }
+  if (!c) return fail(LB_ERR_ARG, "bad layer arguments");
+  // on the host, before anything is uploaded or changed: the layers checked, the plans made
+  LayerPlan lp;
+  std::string err;
+  int rc = check_layers(*c, c->h_cstart.data(), c->h_evar.data(), nlayers, first_check, lp, err);
+  if (rc) return fail(rc, err);
+  const Switches sw = read_switches();
+  lp = plan_layers(*c, lp, sw);
+  const FixedPlan qp = plan_fixed(c->qfrac, c->qmsg, c->qapp, c->maxdc, lp.maxlayer, c->Nv, c->Nmsg, sw);
   HIP_TRY(hipSetDevice(c->dev));
   HIP_TRY(hipStreamSynchronize(c->stream));  // a decode may still read the old table
   int* d = nullptr;
-  int rc;
   if ((rc = dev_alloc((void**)&d, (size_t)(nlayers + 1) * sizeof(int)))) return rc;
   if (hipMemcpyAsync(d, first_check, (size_t)(nlayers + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess) {
@@ -1789,45 +1636,20 @@ int lb_set_layers(lb_ctx* c, int nlayers, const int* first_check) {
   }
   (void)hipFree(c->d_lfirst);
   c->d_lfirst = d;
-  c->nlayers = nlayers;
-  c->maxlayer = maxlayer;
-  const size_t app_bytes = (size_t)c->Nv * sizeof(double), r_bytes = (size_t)c->Nmsg * sizeof(double);
-  c->lmode = app_bytes + r_bytes <= kLdsBytes - 64 ? 2 : (app_bytes <= kLdsBytes - 64 ? 1 : 0);
-  // binary32: the same choice at the element size 4
-  const size_t app32 = (size_t)c->Nv * sizeof(float), r32 = (size_t)c->Nmsg * sizeof(float);
-  c->lmode32 = app32 + r32 <= kLdsBytes - 64 ? 2 : (app32 <= kLdsBytes - 64 ? 1 : 0);
-  // measurement and test switches: LDPC_BP_LAYERED_LDS = 1 / 0 keeps r / r and app out of LDS
-  // although they would fit; LDPC_BP_LAYERED_THREADS = the workgroup's threads (a multiple of 64
-  // within the instance's bound)
-  if (const char* e = getenv("LDPC_BP_LAYERED_LDS"); e && *e) {
-    c->lmode = std::min(c->lmode, std::max(0, atoi(e)));
-    c->lmode32 = std::min(c->lmode32, std::max(0, atoi(e)));
-  }
-  c->lfixed = c->mindc == c->maxdc && c->maxdc == 20;
-  // a thread per edge of the largest layer: gather and scatter take one pass where the bound
-  // allows, the check chains run on the first waves (measured against a thread per check at
-  // 802.16 5/6 z=192)
-  const int ntmax = c->lfixed ? kFixThreads : kMaxThreads;
-  c->lnt = std::min(ntmax, std::max(128, (maxedges + 63) / 64 * 64));
-  if (const char* e = getenv("LDPC_BP_LAYERED_THREADS"); e && *e)
-    c->lnt = std::min(ntmax, std::max(64, atoi(e) / 64 * 64));
-  // LDPC_BP_LAYERED_F32_RESIDENT = 1: one binary32 workgroup per CU (padded dynamic LDS), to time
-  // against the two that share a CU at 802.16 5/6 z=192
-  if (const char* e = getenv("LDPC_BP_LAYERED_F32_RESIDENT"); e && *e) c->lone32 = atoi(e) == 1;
-  else c->lone32 = false;
+  static_cast<LayerPlan&>(*c) = lp;
+  static_cast<FixedPlan&>(*c) = qp;
   c->raised.clear();
-  plan_fixed(c);
   return LB_OK;
 }
 
 int lb_set_fixed(lb_ctx* c, int frac_bits, int msg_bits, int app_bits) {
   if (!c) return fail(LB_ERR_ARG, "null context");
-  if (frac_bits < 0 || frac_bits > 8 || msg_bits < 2 || msg_bits > 8 || app_bits < msg_bits || app_bits > 16)
-    return fail(LB_ERR_ARG, "fixed-point widths: frac_bits in 0..8, msg_bits in 2..8, app_bits in msg_bits..16");
-  c->qfrac = frac_bits;
-  c->qmsg = msg_bits;
-  c->qapp = app_bits;
-  if (c->nlayers) plan_fixed(c);  // (the switches of the environment, read again)
+  std::string err;
+  if (const int rc = check_widths(frac_bits, msg_bits, app_bits, err)) return fail(rc, err);
+  FixedPlan& q = *c;
+  q = FixedPlan{frac_bits, msg_bits, app_bits};
+  // (the switches of the environment, read again)
+  if (c->nlayers) q = plan_fixed(frac_bits, msg_bits, app_bits, c->maxdc, c->maxlayer, c->Nv, c->Nmsg, read_switches());
   return LB_OK;
 }
 

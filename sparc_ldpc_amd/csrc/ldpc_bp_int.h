@@ -11,15 +11,15 @@
 #include <vector>
 
 #include "ldpc_bp.h"
+#include "ldpc_plan.h"
 
 struct lb_mc;  // the Monte-Carlo pipeline's state (ldpc_mc.hip)
 
-struct lb_ctx {
-  int dev = 0, Nv = 0, Nc = 0, Nmsg = 0, maxdv = 0, maxdc = 0, mindc = 0, nt = 0;
-  bool fixed = false;  // check-regular with a straight-line check kernel (lxfb_fixed)
-  bool lds = false;
-  // tail launches (k_bp_tail): edge tables, per-word state, first tail iteration
-  int tail_at = 0, nq = 0, ncu = 256;
+// The plans are lb_ctx's bases: lb_create sets the GraphPlan, lb_set_layers the LayerPlan and the
+// FixedPlan, lb_set_tail and lb_set_fixed change tail_at and the FixedPlan (ldpc_plan.h has the fields).
+struct lb_ctx : lb::GraphPlan, lb::LayerPlan, lb::FixedPlan {
+  int dev = 0, ncu = 256;
+  // tail launches (k_bp_tail): edge tables, per-word state
   int* d_evar = nullptr;
   int *d_active = nullptr, *d_nact = nullptr, *d_done = nullptr, *d_lastbad = nullptr;
   int* h_nact = nullptr;  // pinned: [0] words entering the tail, [1..2] done counts of the last chunks,
@@ -29,7 +29,6 @@ struct lb_ctx {
   bool est_pending = false;   // a device-sized tail's word count is in flight
   int est_n = 0, est_B = 0, est_Bq = 0;  // the last landed count and its batch; the batch in flight
   int capTailB = 0;
-  int tail_default = 0;       // tail_at chosen at lb_create (kTailAt or LDPC_BP_TAIL)
   int* d_vedge = nullptr;
   uint8_t* d_vdeg = nullptr;
   int* d_cstart = nullptr;
@@ -38,21 +37,11 @@ struct lb_ctx {
   int capB = 0, capMsgB = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // layered schedule (k_bpl), set by lb_set_layers: the layers' first checks on
-  // the device, where the messages live (2: r + app in LDS, 1: app in LDS,
-  // 0: HBM), threads per workgroup; host copies of the edge tables for its checks
+  // layered schedule (k_bpl), set by lb_set_layers: the layers' first checks on the device; host
+  // copies of the edge tables for its checks
   std::vector<int> h_evar, h_cstart;
   int* d_lfirst = nullptr;
-  int nlayers = 0, maxlayer = 0, lmode = 0, lnt = 0;
-  int lmode32 = 0;            // lmode of the binary32 instances (LB_F32): the same choice at 4 bytes a message
-  bool lfixed = false;
-  bool lone32 = false;        // LDPC_BP_LAYERED_F32_RESIDENT = 1: binary32 workgroups padded to one per CU
   std::vector<const void*> raised;  // kernel instances whose dynamic LDS limit this context has raised
-  // fixed-point layered min-sum (k_bplq), lb_set_fixed: the widths; the plan made by lb_set_layers /
-  // lb_set_fixed: threads per workgroup, lanes per check, dynamic LDS bytes, whether the image fits
-  int qfrac = 2, qmsg = 6, qapp = 8;
-  int qnt = 0, qlanes = 0, qlds = 0;
-  bool qfit = false;
   lb_mc* mc = nullptr;        // encoder tables, staging and counters of lb_mc_run (ldpc_mc.hip)
 };
 
@@ -64,21 +53,7 @@ int fail(int code, const std::string& msg);
 int dev_alloc(void** p, size_t bytes);
 // the context's ch / app / iters buffers sized for B words
 int ensure_io(lb_ctx* c, int B);
-// the fixed-point kernels' parameters: fraction bits, the clips of r and app, 16 corr_factor
-struct FixedPar {
-  int frac, rmax, amax, alpha;
-};
-// A decoder type (`algo` of the C ABI: one of the five LB_* numbers, with LB_F32 or LB_FIXED) as
-// lb::resolve found it on a context; what launch, stream_plan and launch_stream take.
-struct DecType {
-  int base = 0;   // LB_SUMPROD2 .. LB_LAYERED_MINSUM
-  bool f32 = false, fixed = false;
-  bool hbm = false;  // a layered type that keeps each word's messages in a slice of HBM (lmode < 2)
-  FixedPar par{};    // fixed
-};
-// Fill `t`, or refuse algo / corr / max_iter on this context (LB_ERR_ARG, LB_ERR_UNSUPPORTED): every
-// refusal of a decoder type is here.  for_stream: the block stream, which has the layered types only
-// and refuses up front what the batch path refuses once it has work (lb::launch).
+// ldpc_plan.h's resolve on the context's plans, the refusal recorded by fail (DecType: there)
 int resolve(lb_ctx* c, int algo, double corr, int max_iter, bool for_stream, DecType* t);
 // queue a decode of B words on the context's stream; sized_on_host = false never waits
 int launch(lb_ctx* c, int B, const double* d_ch, double* d_app, int* d_it, const DecType& t, double corr,
