@@ -24,6 +24,7 @@
 
 #include "sparc_amp.h"
 #include "sa_shape.h"
+#include "sa_seq.h"
 
 namespace sa {
 
@@ -869,9 +870,6 @@ __device__ __forceinline__ void store_section_any(real* p, const real (&x)[E], i
 // Matrix-free Hadamard backend
 // ---------------------------------------------------------------------------
 
-enum { SEC_AMP = 0, SEC_AZ = 1, SEC_AB = 2 };
-enum { ROW_INIT0 = 0, ROW_INIT = 1, ROW_AMP = 2, ROW_ABOUT = 3 };
-
 
 template <typename real>
 struct SecArgs {
@@ -931,7 +929,7 @@ struct SecArgs {
   // first iteration of a decode without beta0: no zero fill of the buffer)
   int bzero;
   // k_sec4 / k_sec43 / k_sec44, the last launch of a decode with the early
-  // stop off (fused tail, sa_host.h: fused_tail): the section decisions
+  // stop off (fused tail, sa_seq.h: DecodeSeq::fused): the section decisions
   // [B][L] (argmax of the new estimate, section_argmax's rule) go to `dec`, a
   // device-visible buffer, and iters[b] = itset; null / 0 on every other launch
   int32_t* dec;

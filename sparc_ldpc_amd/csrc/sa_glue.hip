@@ -360,7 +360,7 @@ int stage_onehot_impl(sa_ctx* c, int B, const int32_t* idx, double scale, bool a
       return fail(SA_ERR_ARG, "sa_stage_onehot: index outside [0, M)");
   HIP_TRY(hipSetDevice(c->device));
   sa_lane& ln = c->at();
-  ln.fused_B = 0;  // d_beta changes: decisions come from k_decide again
+  tail_beta_rewritten(ln);
   HIP_TRY(hipMemcpyAsync(c->d_idx, idx, (size_t)B * c->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
   const size_t tot = (size_t)B * c->L * c->M;
   if (c->prec == SA_PREC_F64)
@@ -426,7 +426,7 @@ int sa_soft_beta0(sa_ctx* c, int B, int l0, int ns, const double* app, int flags
   if (!app) return fail(SA_ERR_ARG, "sa_soft_beta0: app is NULL");
   HIP_TRY(hipSetDevice(c->device));
   sa_lane& ln = c->at();
-  ln.fused_B = 0;  // d_beta changes: decisions come from k_decide again
+  tail_beta_rewritten(ln);
   const int lgM = ilog2(c->M);
   const size_t na = (size_t)B * ns * lgM;
   const double* d_app = app;

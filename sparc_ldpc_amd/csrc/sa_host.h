@@ -73,13 +73,14 @@ struct sa_lane {
   hipEvent_t y_ev = nullptr;      // behind the last write of this lane's d_y (staging, or the copy from the other lane)
   unsigned long long y_ver = 0;   // version of the y this lane holds (sa_ctx::y_ver: the latest staged)
   bool y_read = false;            // this lane's last y copy read the other lane's d_y (that lane's next y write waits for y_ev)
-  // Fused tail (fused_tail below): the lane's last run ended with its last
-  // section launch, which wrote the decisions of fused_B codewords into h_dec
-  // (pinned, device-mapped at d_dec, Bcap x L; marked by ev1), and left the
-  // row step of iteration row_T - 1 of row_B codewords undone: nothing of the
-  // decode, its decisions or its estimate reads z_T.  row_flush launches that
-  // step for whoever reads d_z / d_zzp, or is about to change what it reads
-  // (y, the power, the partials); the lane's next run drops it.
+  // Fused tail (sa_seq.h: DecodeSeq::fused): the lane's last run ended with its
+  // last section launch, which wrote the decisions of fused_B codewords into
+  // h_dec (pinned, device-mapped at d_dec, Bcap x L; marked by ev1), and left
+  // the row step of iteration row_T - 1 of row_B codewords undone: nothing of
+  // the decode, its decisions or its estimate reads z_T.  row_flush launches
+  // that step for whoever reads d_z / d_zzp, or is about to change what it
+  // reads (y, the power, the partials); the lane's next run drops it.
+  // Assigned by the tail_* transitions below and nowhere else.
   int32_t *h_dec = nullptr, *d_dec = nullptr;
   int fused_B = 0;
   int row_B = 0, row_T = 0;
@@ -205,12 +206,9 @@ int capture_graph(hipStream_t s, F seq, hipGraphExec_t* out) {
   return SA_OK;
 }
 
-// ---- the kernel choice of a context (sa_shape.h: plan_for, fused_tail) --------
+// ---- the kernel choice of a context (sa_shape.h: plan_for) ---------------------
 int dense_parts(const sa_ctx* c, int B);  // sa_dense.hip: Ab partials of the dense A beta (GEMM K splits or GEMV splits)
 inline Plan plan_for(const sa_ctx* c, int B) { return plan_for(*c, B, is_dense(*c) ? dense_parts(c, B) : 0); }
-inline bool fused_tail(const sa_ctx* c, const Plan& p, int T, int flags) {
-  return fused_tail(*c, p, T, flags, c->prof != nullptr);
-}
 
 // t_b: the Monte-Carlo stream's per-slot iteration indices (SecArgs::tb), else null
 template <typename real>
@@ -294,12 +292,38 @@ void drop_graphs(sa_ctx* c);  // every lane's, and sa_mc_run's
 int sync_all(sa_ctx* c);
 inline void lane_switch(sa_ctx* c, int k) { c->cur = k; }
 int lanes_release(sa_ctx* c);
-// fused tail: launch lane k's deferred row step, if one is pending, on its
-// stream; tail_settle: that, and the lane's fused decisions no longer stand
-// for its d_beta (entry points that change the current lane's buffers)
+// ---- a lane's tail state (sa_lane: fused_B, row_B, row_T) and its transitions ----
+// A new decode begins on the lane (sa_run, sa_profile, sa_mc_run; its buffers
+// go): a deferred row step of the lane's previous run is dropped (z starts
+// from y again) and that run's fused decisions no longer stand.
+inline void tail_begin(sa_lane& l) { l.fused_B = l.row_B = l.row_T = 0; }
+// The decode q of B codewords finished issuing on the current lane: what it
+// leaves there beside the results, and the layout it leaves d_z in.  Set by
+// every run (a replayed graph walks no steps).
+inline void tail_issued(sa_ctx* c, int B, const DecodeSeq& q) {
+  sa_lane& l = c->at();
+  l.fused_B = l.row_B = q.fused ? B : 0;
+  l.row_T = q.fused ? q.T : 0;
+  c->zil_last = q.zil;
+}
+// d_beta was rewritten outside a run: it no longer holds the estimate the
+// fused decisions were taken from, decisions come from k_decide again.
+inline void tail_beta_rewritten(sa_lane& l) { l.fused_B = 0; }
+// Take the lane's pending row step: false if there is none, else its decode's
+// (B, T), and the lane holds none any more.
+inline bool tail_take_row(sa_lane& l, int* B, int* T) {
+  if (!l.row_B) return false;
+  *B = l.row_B;
+  *T = l.row_T;
+  l.row_B = l.row_T = 0;
+  return true;
+}
+// row_flush launches lane k's pending row step, if there is one, on its
+// stream; tail_settle: that, and beta is about to be rewritten (entry points
+// that change the current lane's d_beta and partials)
 int row_flush(sa_ctx* c, int k);
 inline int tail_settle(sa_ctx* c) {
-  c->at().fused_B = 0;
+  tail_beta_rewritten(c->at());
   return row_flush(c, c->cur);
 }
 // the staged y across lanes: y_sync brings lane k's d_y up to the latest

@@ -1,5 +1,5 @@
 // sa_host_check — the operator's host rules from the command line, on a
-// machine without a GPU (sa_shape.h and sa_tables.h only; no HIP).
+// machine without a GPU (sa_shape.h, sa_seq.h and sa_tables.h only; no HIP).
 //
 //   sa_host_check shape L M n backend prec plan n_cus B
 //     one JSON object: the Shape of the operator, the plan of a decode of B
@@ -11,6 +11,11 @@
 //     one JSON list of runs [first n, last n, sec, big]: consecutive n with
 //     the same section path (sa_plan's number; -1: sa_create refuses the
 //     shape) and the same `big`.
+//   sa_host_check seq L M n backend prec plan n_cus B T flags has_b0 profiled
+//     the launch sequence of a decode (sa_seq.h: decode_seq) as one JSON
+//     object: the DecodeSeq summary (fused, the deferred row step or null,
+//     zil, beta_final, nsteps) and "steps", every Step in launch order.  (A
+//     dense backend's Ab partial count is device state: 0 here.)
 //   sa_host_check tables L M n prec plan
 //     draws a valid ordering (per section a seeded shuffle of 1 .. w-1, its
 //     first n), builds every table of the Hadamard operator with the pure
@@ -27,6 +32,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "sa_seq.h"
 #include "sa_shape.h"
 #include "sa_tables.h"
 
@@ -35,6 +41,7 @@ using namespace sa;
 static int usage() {
   std::fprintf(stderr, "usage: sa_host_check shape L M n backend prec plan n_cus B\n"
                        "       sa_host_check sweep L M backend prec plan n_cus B n0 n1\n"
+                       "       sa_host_check seq L M n backend prec plan n_cus B T flags has_b0 profiled\n"
                        "       sa_host_check tables L M n prec plan\n"
                        "       sa_host_check packed L M n prec plan\n");
   return 2;
@@ -103,6 +110,34 @@ static int cmd_sweep(int L, int M, int backend, int prec, int plan, int n_cus, i
     big = b1;
   }
   std::printf("]\n");
+  return 0;
+}
+
+static int print_step(const Step& s) {
+  static const char* const kinds[] = {"fill_iters", "zero_beta", "dense_start", "sec_ab",      "row",       "sec",
+                                      "sec_mw",     "sec_b",     "dense_iter",  "iters_final", "beta_final"};
+  std::printf("{\"kind\": \"%s\", \"t\": %d, \"mode\": %d, \"rd\": %d, \"wr\": %d, \"bzero\": %d, \"decide\": %d, "
+              "\"itset\": %d, \"G\": %d, \"Gb\": %d, \"es\": %d}",
+              kinds[s.kind], s.t, s.mode, s.rd, s.wr, s.bzero ? 1 : 0, s.decide ? 1 : 0, s.itset, s.G, s.Gb, s.es);
+  return 0;
+}
+
+static int cmd_seq(const std::vector<int>& a) {
+  Shape s;
+  if (shape_of(s, a[0], a[1], a[2], a[3], a[4], a[5], a[6])) return 0;  // reported
+  const int B = a[7], T = a[8], flags = a[9];
+  if (B <= 0 || T < 0) return usage();
+  const DecodeSeq q = decode_seq(s, plan_for(s, B), T, flags, a[10] != 0, a[11] != 0);
+  std::printf("{\"fused\": %d, \"row\": ", q.fused ? 1 : 0);
+  if (q.fused) print_step(q.row);
+  else std::printf("null");
+  std::printf(", \"zil\": %d, \"beta_final\": %d, \"nsteps\": %d, \"steps\": [", q.zil ? 1 : 0, q.beta_final ? 1 : 0, q.nsteps);
+  int k = 0;
+  for_each_step(q, [&](const Step& st) {
+    if (k++) std::printf(", ");
+    return print_step(st);
+  });
+  std::printf("]}\n");
   return 0;
 }
 
@@ -362,6 +397,7 @@ int main(int argc, char** argv) {
   if (!std::strcmp(argv[1], "shape") && a.size() == 8) return cmd_shape(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
   if (!std::strcmp(argv[1], "sweep") && a.size() == 9)
     return cmd_sweep(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
+  if (!std::strcmp(argv[1], "seq") && a.size() == 12) return cmd_seq(a);
   if (!std::strcmp(argv[1], "tables") && a.size() == 5) return cmd_tables(a[0], a[1], a[2], a[3], a[4]);
   if (!std::strcmp(argv[1], "packed") && a.size() == 5) return cmd_packed(a[0], a[1], a[2], a[3], a[4]);
   return usage();

@@ -583,8 +583,7 @@ int sa_mc_run(sa_ctx* c, int B, int T, int flags, int32_t* dec_out, int32_t* ite
   if ((rc = ensure_invb(c))) return rc;
   if ((rc = mc_ensure_slots(c, B))) return rc;
   sa_lane& ln = c->at();  // lane 0, for the rest of the run
-  ln.row_B = ln.row_T = 0;  // as sa_run: a new decode of the lane drops a deferred row step
-  ln.fused_B = 0;
+  tail_begin(ln);
   if (!c->h_mc_live) {
     HIP_TRY(hipHostMalloc((void**)&c->h_mc_live, 4 * sizeof(int), hipHostMallocDefault));
     for (auto& e : c->mc_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));

@@ -423,17 +423,6 @@ inline Plan plan_for(const Shape& c, int B, int dense_G = 0) {
   return p;
 }
 
-// Fused tail of a decode: with the early stop off the last launch is known at
-// capture time, so the last section launch of the pair / triple / quad kernels
-// also writes the section decisions and iters (SecArgs::dec, itset), k_decide
-// is never launched, and the last k_row2 step, whose z_T only sa_fetch_z
-// reads, is deferred (sa_lane::row_B).  Depends on (shape, B, T, flags) and on
-// whether the decode is being profiled (sa_profile times every launch).
-inline bool fused_tail(const Shape& c, const Plan& p, int T, int flags, bool profiled) {
-  return p.bzero() && p.it_row() && (flags & SA_FLAG_NO_EARLY_STOP) && T > 0 && c.dead == 0 && !profiled &&
-         !(c.plan & SA_PLAN_NO_FUSED_TAIL);
-}
-
 // k_secb's XCD-grouped work order (sa_secb.hip computes it per workgroup):
 // used when the section groups and the workgroups split evenly over the 8
 // XCDs, else one plain pass.  gp: groups per pass; passes: per XCD.

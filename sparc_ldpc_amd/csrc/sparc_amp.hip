@@ -201,7 +201,7 @@ static void lane_free(sa_lane& l) {
   l.beta2_cap = 0;
   if (l.h_dec) (void)hipHostFree(l.h_dec);
   l.h_dec = l.d_dec = nullptr;
-  l.fused_B = l.row_B = l.row_T = 0;
+  tail_begin(l);
 }
 
 // Lane k's buffers are about to go (every lane waited for): decisions that a
@@ -418,99 +418,60 @@ int seq_az(sa_ctx* c, int B) {
   return launch_sec<real>(c, p, B, SEC_AZ, 0, 0);
 }
 
-// Whole AMP decode of the staged batch: y in d_y, beta0 in d_beta if has_b0.
+// One launch of a decode (sa_seq.h: Step) on the current lane: side 0 / 1 of
+// the estimate is d_beta / d_beta2, the decisions go to the lane's d_dec.
 template <typename real>
-int seq_amp(sa_ctx* c, int B, int T, int flags, int has_b0) {
-  const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
-  sa_lane& ln = c->at();  // (nothing below changes lanes)
-  const Plan p = plan_for(c, B);  // the kernels of this decode and their partial counts
-  const bool dense = p.dense(), batched = p.batched();
-  c->zil_last = p.zil;
-  int rc;
-  // The fixed launches around the T iterations.  Behind k_row2 (the small-batch
-  // path) the iters writes ride on row launches the decode makes anyway: -1
-  // with the residual's initialisation, T with the last iteration.  Behind
-  // k_sec4 / k_sec43 a decode without beta0 fills no zero estimate: its first
-  // section launch takes the previous estimate as zero.  With the early stop
-  // off the final estimate's buffer is known here: without beta0 the ping-pong
-  // starts on the side that ends in d_beta, and k_beta_final is launched only
-  // where the estimate ends in d_beta2.
-  const bool it_row = p.it_row() && T > 0;
-  const bool bzero = !has_b0 && p.bzero() && T > 0;
-  const int flip = (bzero && !es) ? (T & 1) : 0;  // beta0 lies in d_beta: no choice of side
-  // Fused tail: the last section launch also decides and sets iters = T, and
-  // the sequence ends with it: the row step behind it (z_T) is deferred
-  // (run_graph records it in the lane; row_flush launches it on demand)
-  const bool ft = fused_tail(c, p, T, flags);
-  if (!it_row) k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
-  if (has_b0) {
-    if (dense) {
-      if ((rc = dense_start<real>(c, p, B))) return rc;
-    } else {  // A beta0 by k_sec: its c->G partials, whatever the loop's producer
-      if ((rc = launch_sec<real>(c, p, B, SEC_AB, 0, 0))) return rc;
-      if ((rc = launch_row<real>(c, p, B, ROW_INIT, 0, 0, c->G, c->G, it_row ? -1 : 0))) return rc;
-    }
-  } else {
-    if (!bzero) {
+int launch_step(sa_ctx* c, const Plan& p, int B, const Step& s) {
+  sa_lane& ln = c->at();
+  void* const side[2] = {ln.d_beta, ln.d_beta2};
+  switch (s.kind) {
+    case ST_FILL_ITERS:
+      k_fill32<<<(B + 255) / 256, 256, 0, ln.stream>>>((uint32_t*)ln.d_iters, 0xffffffffu, (size_t)B);
+      break;
+    case ST_ZERO_BETA: {
       const size_t nw = (size_t)B * c->L * c->M * rsz(c) / 4;
       k_fill32<<<(int)std::min<size_t>((nw + 255) / 256, 8192), 256, 0, ln.stream>>>((uint32_t*)ln.d_beta, 0u, nw);
+      break;
     }
-    if ((rc = launch_row<real>(c, p, B, ROW_INIT0, 0, 0, p.G, p.Gb, it_row ? -1 : 0))) return rc;
-  }
-  for (int t = 0; t < T; ++t) {
-    if (dense) {
-      if ((rc = dense_iter<real>(c, p, B, t, es))) return rc;
-    } else if (batched) {
-      if ((rc = launch_secb<real>(c, p, B, t, es))) return rc;
-    } else {
-      void* pin = ((t ^ flip) & 1) ? ln.d_beta2 : ln.d_beta;
-      void* pout = ((t ^ flip) & 1) ? ln.d_beta : ln.d_beta2;
-      if (p.multiwave()) {
-        const bool tail = ft && t == T - 1;
-        if ((rc = launch_sec2<real>(c, p, B, t, es, pin, pout, bzero && t == 0, tail ? ln.d_dec : nullptr, tail ? T : 0)))
-          return rc;
-      } else if ((rc = launch_sec<real>(c, p, B, SEC_AMP, t, es, pin, pout))) {
-        return rc;
-      }
+    case ST_DENSE_START: return dense_start<real>(c, p, B);
+    case ST_SEC_AB: return launch_sec<real>(c, p, B, SEC_AB, 0, 0);
+    case ST_ROW: return launch_row<real>(c, p, B, s.mode, s.t, s.es, s.G, s.Gb, s.itset);
+    case ST_SEC: return launch_sec<real>(c, p, B, SEC_AMP, s.t, s.es, side[s.rd], side[s.wr]);
+    case ST_SEC_MW:
+      return launch_sec2<real>(c, p, B, s.t, s.es, side[s.rd], side[s.wr], s.bzero, s.decide ? ln.d_dec : nullptr, s.itset);
+    case ST_SEC_B: return launch_secb<real>(c, p, B, s.t, s.es);
+    case ST_DENSE_ITER: return dense_iter<real>(c, p, B, s.t, s.es);
+    case ST_ITERS_FINAL:
+      k_iters_final<<<(B + 255) / 256, 256, 0, ln.stream>>>(ln.d_iters, B, s.itset);
+      break;
+    case ST_BETA_FINAL: {
+      const size_t LM = (size_t)c->L * c->M;
+      k_beta_final<real><<<dim3((unsigned)std::min<size_t>((LM + 255) / 256, 4096), B), 256, 0, ln.stream>>>(
+          (real*)ln.d_beta, (const real*)ln.d_beta2, ln.d_iters, LM);
+      break;
     }
-    if (ft && t == T - 1) break;
-    if ((rc = launch_row<real>(c, p, B, ROW_AMP, t, es, p.G, p.Gb, it_row && t == T - 1 ? T : 0))) return rc;
   }
-  if (!it_row) k_iters_final<<<(B + 255) / 256, 256, 0, ln.stream>>>(ln.d_iters, B, T);
   HIP_TRY(hipGetLastError());
-  // early stop off: every codeword runs T iterations, the last one into pout(T - 1)
-  const bool home = !es && (((T - 1) ^ flip) & 1);
-  if (!dense && !batched && T > 0 && !home) {
-    // the estimate of codeword b is in the buffer of parity iters[b]
-    const size_t LM = (size_t)c->L * c->M;
-    k_beta_final<real><<<dim3((unsigned)std::min<size_t>((LM + 255) / 256, 4096), B), 256, 0, ln.stream>>>(
-        (real*)ln.d_beta, (const real*)ln.d_beta2, ln.d_iters, LM);
-    HIP_TRY(hipGetLastError());
-  }
   return SA_OK;
 }
 
-int row_flush(sa_ctx* c, int k) {
-  sa_lane& l = c->lane[k];
-  if (!l.row_B) return SA_OK;
-  const int B = l.row_B, T = l.row_T, keep = c->cur;
-  l.row_B = l.row_T = 0;
-  const Plan p = plan_for(c, B);  // the run's own: (context, B) decide it
-  lane_switch(c, k);  // the launchers address the current lane
-  const int rc = c->prec == SA_PREC_F64 ? launch_row<double>(c, p, B, ROW_AMP, T - 1, 0, p.G, p.Gb, 0)
-                                        : launch_row<float>(c, p, B, ROW_AMP, T - 1, 0, p.G, p.Gb, 0);
-  lane_switch(c, keep);
-  return rc;
+// Whole AMP decode q (sa_seq.h: decode_seq) of the staged batch on the current
+// lane: y in d_y, beta0 in d_beta.
+template <typename real>
+int seq_amp(sa_ctx* c, const Plan& p, int B, const DecodeSeq& q) {
+  return for_each_step(q, [&](const Step& s) { return launch_step<real>(c, p, B, s); });
 }
 
-// What a run of (B, T, flags) leaves in its lane beside the results (the
-// captured graph does not run seq_amp again: set by every run)
-static void tail_mark(sa_ctx* c, int B, int T, int flags) {
-  sa_lane& ln = c->at();
-  const bool ft = fused_tail(c, plan_for(c, B), T, flags);
-  ln.fused_B = ft ? B : 0;
-  ln.row_B = ft ? B : 0;
-  ln.row_T = ft ? T : 0;
+int row_flush(sa_ctx* c, int k) {
+  int B, T;
+  if (!tail_take_row(c->lane[k], &B, &T)) return SA_OK;
+  const int keep = c->cur;
+  const Plan p = plan_for(c, B);  // the run's own: (context, B) decide it
+  const Step row = deferred_row(p, T);
+  lane_switch(c, k);  // the launchers address the current lane
+  const int rc = c->prec == SA_PREC_F64 ? launch_step<double>(c, p, B, row) : launch_step<float>(c, p, B, row);
+  lane_switch(c, keep);
+  return rc;
 }
 
 int ensure_beta2(sa_ctx* c, int B) {
@@ -540,12 +501,15 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   }
   {
     sa_lane& l = c->at();  // the run's lane: cur is settled
-    l.row_B = l.row_T = 0;  // a deferred row step of the lane's previous run: dropped (z starts from y again)
+    int rb, rt;
+    (void)tail_take_row(l, &rb, &rt);  // dropped, before y_sync would flush it
     if (int rcd = dec_spill(c, c->cur)) return rcd;
-    l.fused_B = 0;
+    tail_begin(l);
   }
   if (int rcy = y_sync(c)) return rcy;  // a lane whose y is older than the latest staged one
   sa_lane& ln = c->at();
+  const Plan p = plan_for(c, B);  // the kernels of this decode and their partial counts
+  const DecodeSeq q = decode_seq(*c, p, T, flags, has_b0 != 0, c->prof != nullptr);
   hipGraphExec_t graph = nullptr;  // stays null: eager launches instead of the captured graph
   if (!(c->plan & SA_PLAN_EAGER)) {
     // the power-allocation mode selects the captured kernel arguments (c, P arrays)
@@ -553,7 +517,7 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
     auto it = ln.graphs.find(key);
     if (it == ln.graphs.end()) {
       hipGraphExec_t ex = nullptr;
-      if (int rc = capture_graph(ln.stream, [&] { return seq_amp<real>(c, B, T, flags, has_b0); }, &ex)) return rc;
+      if (int rc = capture_graph(ln.stream, [&] { return seq_amp<real>(c, p, B, q); }, &ex)) return rc;
       it = ln.graphs.emplace(key, ex).first;
     }
     graph = it->second;
@@ -561,14 +525,13 @@ int run_graph(sa_ctx* c, int B, int T, int flags, int has_b0) {
   HIP_TRY(hipEventRecord(ln.ev0, ln.stream));
   if (graph) {
     HIP_TRY(hipGraphLaunch(graph, ln.stream));
-  } else if (int rc = seq_amp<real>(c, B, T, flags, has_b0)) {
+  } else if (int rc = seq_amp<real>(c, p, B, q)) {
     return rc;
   }
   HIP_TRY(hipEventRecord(ln.ev1, ln.stream));
-  tail_mark(c, B, T, flags);
+  tail_issued(c, B, q);
   c->last_B = B;
   c->last_T = T;
-  c->zil_last = zil_for(*c, B);  // the layout d_z is left in by THIS run (a cached graph does not run seq_amp)
   return SA_OK;
 }
 
@@ -932,7 +895,7 @@ int sa_stage(sa_ctx* c, int B, const double* y, const double* Pl, const double* 
     if (rc) return rc;
   }
   if (beta0) {
-    c->at().fused_B = 0;  // d_beta no longer holds the estimate the fused decisions were taken from
+    tail_beta_rewritten(c->at());
     if ((rc = upload_sections(c, c->at().d_beta, beta0, B))) return rc;
   }
   return SA_OK;
@@ -1028,7 +991,7 @@ int sa_amp(sa_ctx* c, int B, const double* y, const double* Pl, int T, const dou
   if ((rc = sa_stage(c, B, y, Pl, beta0))) return rc;
   if (T == 0) {
     // the loop body never runs: beta is beta0 (or zeros)
-    c->at().fused_B = 0;
+    tail_beta_rewritten(c->at());
     if (!beta0) HIP_TRY(hipMemsetAsync(c->at().d_beta, 0, (size_t)B * c->L * c->M * rsz(c), c->at().stream));
     HIP_TRY(hipMemsetAsync(c->at().d_iters, 0, (size_t)B * sizeof(int), c->at().stream));
   } else {
@@ -1051,8 +1014,7 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   if (int rcs = sync_all(c)) return rcs;  // the profiled decode has the chip to itself (it stays on the current lane)
   if (int rcb = ensure_beta2(c, B)) return rcb;
   if (use_batched(*c, B)) lane_switch(c, 0);  // as sa_run
-  c->at().row_B = c->at().row_T = 0;  // as sa_run: a new decode of the lane (never a fused tail: fused_tail)
-  c->at().fused_B = 0;
+  tail_begin(c->at());
   if (int rcy = y_sync(c)) return rcy;
   if (use_batched(*c, B))
     if (int rci = ensure_invb(c)) return rci;
@@ -1064,9 +1026,10 @@ int profile_impl(sa_ctx* c, int B, int T, int flags, int rep, bool dispatch, dou
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
   HIP_TRY(hipEventRecord(e0, c->at().stream));
-  const int has_b0 = (flags & SA_FLAG_BETA0) ? 1 : 0;
-  int rc = c->prec == SA_PREC_F64 ? seq_amp<double>(c, B, T, flags & 0xff, has_b0)
-                                  : seq_amp<float>(c, B, T, flags & 0xff, has_b0);
+  const Plan p = plan_for(c, B);
+  const DecodeSeq q = decode_seq(*c, p, T, flags & 0xff, (flags & SA_FLAG_BETA0) != 0, true);  // never a fused tail
+  int rc = c->prec == SA_PREC_F64 ? seq_amp<double>(c, p, B, q) : seq_amp<float>(c, p, B, q);
+  tail_issued(c, B, q);
   c->prof = nullptr;
   (void)hipEventRecord(e1, c->at().stream);
   hipError_t e = hipStreamSynchronize(c->at().stream);
