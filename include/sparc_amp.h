@@ -459,6 +459,61 @@ int sa_se(int device, int B, int L, int M, int n, const double* Pl, const double
           double* sec_out, double* ms_out);
 int sa_se_draws(int device, int S, int M, const uint32_t* seeds, double* U_out);
 
+/* ---- spatially coupled SPARCs: base-matrix AMP ----
+ * A coupled design over a Hadamard-backend context `parent` of L sections of
+ * M columns and n rows: A[i, j] = sqrt(W[r(i), c(j)]) * At[i, j], At the
+ * parent's +-1/sqrt(n) operator, W an R x C base matrix (row-major, entries
+ * >= 0 and finite, a positive entry in every row and every column), row block
+ * r(i) = i / (n / R), column block c(l) = l / (L / C) of section l.  The
+ * decoder tracks one effective-noise level phi_r per row block and one
+ * tau_c^2 per column block; beta = 0, z = y, then for t < T
+ *   phi_r = sum_{i in r} z_i^2 / (n / R);  stop (index t) if t > 0 and every
+ *           phi_r equals the previous iteration's bit for bit: beta, z kept
+ *   1 / tau_c^2 = (1 / R) sum_r W[r, c] / phi_r
+ *   u_j = beta_j c_l / tau_c^2 + c_l sum_i A[i, j] z_i / phi_r(i),  c_l = sqrt(n Pl_l)
+ *   beta_j = c_l exp(u_j - max) / sum_section exp(...)
+ *   psi_c = P_c - sum_{j in c} beta_j^2 / n,  gamma_r = sum_c W[r, c] psi_c,  P_c = sum_{l in c} Pl_l
+ *   z_i = y_i - (A beta)_i + z_i gamma_r(i) / phi_r(i)
+ * which at R = C = 1, W = [[1]] is sa_amp's loop (sparc_ldpc.py:189-222).
+ *
+ * sa_sc_create: the coupled context borrows the parent's device tables and
+ * precision; the parent must outlive it.  It has its own stream and buffers.
+ *   SA_ERR_ARG: R or C < 1, W NULL, R does not divide n, C does not divide L,
+ *   a negative or non-finite entry, a row or column of W without a positive entry.
+ *   SA_ERR_UNSUPPORTED: R or C above SA_SC_MAX_BLOCKS; M not a power of two; a
+ *   parent that is not a Hadamard-backend context; n too large for z to fit
+ *   the section kernel's LDS image.
+ * sa_last_error names the argument; *out is not written on a refusal.
+ *
+ * sa_sc_Ab / sa_sc_Az: out[b] = A beta[b] (B x n) / A^T z[b] (B x L*M).
+ *
+ * sa_sc_amp decodes B codewords y (B x n) with section powers Pl [L]:
+ * beta_out B x (L*M); iters_out [B] (may be NULL) the stop index, T when the
+ * loop ran out; phi_out [B][T][R] (may be NULL) the phi_r of every iteration
+ * that ran, rows from a codeword's stop index on zero.  flags:
+ * SA_FLAG_NO_EARLY_STOP.  sa_sc_event_ms: the device time of the last
+ * sa_sc_amp's iterations (events around the loop's launches).
+ *
+ * sa_sc_mc: one call on the device for B Monte-Carlo reps: encodes
+ * y = A beta(idx) + noise (idx B x L, noise B x n binary64 or NULL; the
+ * kernels of sa_sc_Ab, the noise added in binary64), decodes, takes each
+ * section's argmax (first index on ties) into dec_out [B][L], the stop
+ * indices into iters_out [B] and each rep's bit errors (popcounts of
+ * decision ^ index summed over its sections, as sa_mc_run counts them) into
+ * errs_out [B]; any output may be NULL; ms_out: the device time of encoder,
+ * decode and decisions (events), or NULL. */
+enum { SA_SC_MAX_BLOCKS = 64 };
+typedef struct sa_sc sa_sc;
+int sa_sc_create(sa_ctx* parent, int R, int C, const double* W, sa_sc** out);
+void sa_sc_destroy(sa_sc* sc);
+int sa_sc_Ab(sa_sc* sc, int B, const double* beta, double* out);  /* A beta,  B x n    */
+int sa_sc_Az(sa_sc* sc, int B, const double* z, double* out);     /* A^T z,   B x L*M  */
+int sa_sc_amp(sa_sc* sc, int B, const double* y, const double* Pl, int T, double* beta_out,
+              int* iters_out, double* phi_out, int flags);
+double sa_sc_event_ms(sa_sc* sc);
+int sa_sc_mc(sa_sc* sc, int B, const int32_t* idx, const double* noise, const double* Pl, int T,
+             int flags, int32_t* dec_out, int32_t* iters_out, int32_t* errs_out, double* ms_out);
+
 /* Introspection. */
 /* The kernels a decode of B codewords runs: out8 = {section path (sa_sec_path),
  * Ab partials per codeword, row splits, codewords per batched workgroup,

@@ -26,5 +26,7 @@ from .threshold import (hard_initialisation, prep_y, calc_E, hist_E, calc_I_e, J
 from . import dist
 from . import se
 from .se import state_evolution, se_draws, pa_search, SEResult, PASearch
+from . import sc
+from .sc import base_matrix, sc_transforms, amp_sc, amp_sc_batch, mc_decode_sc, CoupledOperator
 
 __version__ = "0.1.0"

@@ -26,12 +26,22 @@
 //     k_sec4 / k_sec44 where the shape rules ask for them, unpacks them and
 //     compares every entry with inv and fwd2; one JSON object with the rule's
 //     answer and the byte counts, exit status 1 at the first difference.
+//   sa_host_check sc L M n prec R C W[0,0] W[0,1] ... W[R-1,C-1]
+//     the layout of a spatially coupled design (sa_sc.h: sc_layout) as one JSON
+//     object: the block sizes, the section groups [column block, first
+//     section, sections], the z^2 partials [row block, first row, rows], the
+//     LDS bytes and the limits; {"error", "message"} for a (R, C, W) that
+//     sa_sc_create refuses.  Runs the layout's invariants and compares the
+//     padded groups' Ab table with fwd_entry on a drawn ordering: exit status
+//     1 with the first violation on stderr.  W entries are read by strtod
+//     ("nan", "inf" included).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
 
+#include "sa_sc.h"
 #include "sa_seq.h"
 #include "sa_shape.h"
 #include "sa_tables.h"
@@ -43,7 +53,8 @@ static int usage() {
                        "       sa_host_check sweep L M backend prec plan n_cus B n0 n1\n"
                        "       sa_host_check seq L M n backend prec plan n_cus B T flags has_b0 profiled\n"
                        "       sa_host_check tables L M n prec plan\n"
-                       "       sa_host_check packed L M n prec plan\n");
+                       "       sa_host_check packed L M n prec plan\n"
+                       "       sa_host_check sc L M n prec R C W...\n");
   return 2;
 }
 
@@ -390,8 +401,69 @@ static int cmd_packed(int L, int M, int n, int prec, int plan) {
   return 0;
 }
 
+// The coupled design's layout (sa_sc.h), its invariants, and the padded groups' Ab table
+static int cmd_sc(int L, int M, int n, int prec, int R, int C, const std::vector<double>& W) {
+  ScLayout s;
+  std::string err;
+  if (int rc = sc_layout(s, L, M, n, prec, R, C, W.data(), err)) {
+    std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+    return 0;
+  }
+  const std::string bad = sc_check_layout(s);
+  CHECK(bad.empty(), "%s", bad.c_str());
+  std::vector<uint32_t> ord((size_t)L * n), all(s.w - 1);
+  for (int l = 0; l < L; ++l) {
+    std::mt19937 rng(0x0d0000u + (uint32_t)l);
+    std::iota(all.begin(), all.end(), 1u);
+    std::shuffle(all.begin(), all.end(), rng);
+    std::copy(all.begin(), all.begin() + n, ord.begin() + (size_t)l * n);
+  }
+  std::vector<uint16_t> fwd((size_t)s.G * n * kSpw, 0xffffu);
+  sc_fwd_table(s, ord.data(), fwd.data());
+  const int lgM = ilog2(M);
+  for (int g = 0; g < s.G; ++g)
+    for (int wv = 0; wv < kSpw; ++wv) {
+      const int l = sc_group_section(s, g, wv);
+      for (int r = 0; r < n; ++r) {
+        const uint16_t e = fwd[((size_t)g * n + r) * kSpw + wv];
+        const uint16_t want = l < 0 ? (uint16_t)0 : fwd_entry(ord[(size_t)l * n + r], lgM, M);
+        CHECK(e == want && (e & 0x7fffu) < (unsigned)M, "sc fwd[%d][%d][%d] = %#x, expected %#x", g, r, wv, e, want);
+      }
+    }
+  if (!s.own_fwd) {  // the groups are the parent's: group g holds sections 4 g .. 4 g + 3
+    for (int g = 0; g < s.G; ++g)
+      for (int wv = 0; wv < kSpw; ++wv)
+        CHECK(sc_group_section(s, g, wv) == g * kSpw + wv, "group %d is not the parent's", g);
+  }
+  std::printf("{\"R\": %d, \"C\": %d, \"L\": %d, \"M\": %d, \"n\": %d, \"n_r\": %d, \"L_c\": %d, \"gpc\": %d, \"G\": %d, "
+              "\"zpb\": %d, \"NZ\": %d, \"own_fwd\": %d, \"w\": %d, \"nhi\": %d, \"E\": %d, \"sec_lds\": %zu, "
+              "\"lds_limit\": %zu, \"max_blocks\": %d, \"groups\": [",
+              s.R, s.C, s.L, s.M, s.n, s.n_r, s.L_c, s.gpc, s.G, s.zpb, s.NZ, s.own_fwd ? 1 : 0, s.w, s.nhi, s.E, s.sec_lds,
+              kLdsBytes, kScMaxBlocks);
+  for (int g = 0; g < s.G; ++g) {
+    int cnt = 0;
+    for (int wv = 0; wv < kSpw; ++wv) cnt += sc_group_section(s, g, wv) >= 0;
+    std::printf("%s[%d, %d, %d]", g ? ", " : "", sc_group_block(s, g), sc_group_section(s, g, 0), cnt);
+  }
+  std::printf("], \"zparts\": [");
+  for (int q = 0; q < s.NZ; ++q)
+    std::printf("%s[%d, %d, %d]", q ? ", " : "", sc_zpart_block(s, q), sc_zpart_row0(s, q), sc_zpart_rows(s, q));
+  std::printf("]}\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage();
+  if (!std::strcmp(argv[1], "sc")) {
+    if (argc < 8) return usage();
+    int v[6];
+    for (int i = 0; i < 6; ++i) v[i] = std::atoi(argv[2 + i]);
+    std::vector<double> W;
+    for (int i = 8; i < argc; ++i) W.push_back(std::strtod(argv[i], nullptr));
+    // (a count that is not R x C: refused here, in front of sc_layout's reads)
+    if (v[4] >= 1 && v[5] >= 1 && (long long)v[4] * v[5] != (long long)W.size()) return usage();
+    return cmd_sc(v[0], v[1], v[2], v[3], v[4], v[5], W);
+  }
   std::vector<int> a;
   for (int i = 2; i < argc; ++i) a.push_back(std::atoi(argv[i]));
   if (!std::strcmp(argv[1], "shape") && a.size() == 8) return cmd_shape(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);

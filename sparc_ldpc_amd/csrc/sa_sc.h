@@ -1,0 +1,170 @@
+// sa_sc.h — the host rules of the spatially coupled decoder (sa_sc.hip) as
+// pure host code: what (R, C, W) a coupled design over an operator of L
+// sections of M columns and n rows may have, which row block a row and which
+// column block a section lies in, how the sections form the workgroups of
+// k_scsec and the rows the z^2 partials of k_scrow, the limits, and each
+// kernel's LDS bytes.  No HIP include: csrc/sa_host_check.cpp (`sc`) prints
+// the layout and runs its invariants on a machine without a GPU.
+//
+// The coupled design is A[i, j] = sqrt(W[r(i), c(j)]) * At[i, j], At the
+// +-1/sqrt(n) operator of the parent context, W an R x C base matrix, row
+// block r(i) = i / (n / R), column block c(l) = l / (L / C) (DESIGN.md
+// section 13).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "sa_shape.h"
+#include "sa_tables.h"
+
+namespace sa {
+
+// Row blocks R and column blocks C of a base matrix: at most one wavefront's
+// lanes, so that k_scrow holds the C values psi_c one per lane and k_scsec
+// writes the R values phi_r of an iteration with one store instruction.  The
+// LDS they cost k_scsec (three arrays of kScMaxBlocks reals, 1.5 KB in
+// binary64) is under 1 % of the image.
+constexpr int kScMaxBlocks = 64;  // SA_SC_MAX_BLOCKS
+static_assert(kScMaxBlocks == SA_SC_MAX_BLOCKS, "sparc_amp.h states the limit");
+constexpr int kScRowsPerBlk = 64; // rows of one z^2 partial (one k_scrow workgroup, one per lane)
+
+struct ScLayout {
+  int R = 0, C = 0;          // the base matrix is R x C
+  int L = 0, M = 0, n = 0, prec = 0;
+  int n_r = 0, L_c = 0;      // rows per row block, sections per column block
+  // section groups (k_scsec workgroups of kSpw sections, one wave each): gpc per
+  // column block, the last of a block padded with absent sections where
+  // L_c % kSpw != 0, so no group straddles a column block
+  int gpc = 0, G = 0;
+  // z^2 partials (k_scrow workgroups of kScRowsPerBlk rows): zpb per row block,
+  // the last of a block short where n_r % kScRowsPerBlk != 0
+  int zpb = 0, NZ = 0;
+  // the groups are the parent's groups of 4 consecutive sections (L_c % kSpw
+  // == 0: its Ab table fwd is borrowed), else the coupled context builds its own
+  bool own_fwd = false;
+  int w = 0, nhi = 0, E = 1;  // the parent operator's transform (Shape)
+  size_t sec_lds = 0;         // k_scsec's LDS bytes (k_scrow: none)
+};
+
+inline int sc_row_block(const ScLayout& s, int i) { return i / s.n_r; }
+inline int sc_col_block(const ScLayout& s, int l) { return l / s.L_c; }
+// column block of section group g, and its section of wave wv (-1: absent)
+inline int sc_group_block(const ScLayout& s, int g) { return g / s.gpc; }
+inline int sc_group_section(const ScLayout& s, int g, int wv) {
+  const int ls = (g % s.gpc) * kSpw + wv;
+  return ls < s.L_c ? sc_group_block(s, g) * s.L_c + ls : -1;
+}
+// row block of z^2 partial q, its first row and its number of rows
+inline int sc_zpart_block(const ScLayout& s, int q) { return q / s.zpb; }
+inline int sc_zpart_row0(const ScLayout& s, int q) { return (q / s.zpb) * s.n_r + (q % s.zpb) * kScRowsPerBlk; }
+inline int sc_zpart_rows(const ScLayout& s, int q) {
+  const int left = s.n_r - (q % s.zpb) * kScRowsPerBlk;
+  return left < kScRowsPerBlk ? left : kScRowsPerBlk;
+}
+
+// k_scsec's LDS image: k_sec's (z slots, 4 sections' T, 4 beta^2 partials),
+// then phi_r, W[r, c] / phi_r and the z scale of each row block, then the
+// four waves' stop flags
+inline size_t sc_sec_lds_need(int M, int n, size_t s) {
+  return sec_lds_need(M, n, s, true) + 3 * (size_t)kScMaxBlocks * s + 16;
+}
+
+// The layout of a coupled design, or why there is none: SA_ERR_ARG for a
+// (R, C, W) that is no base matrix of this (L, n), SA_ERR_UNSUPPORTED for a
+// valid one outside the kernels' range; err names the argument.
+inline int sc_layout(ScLayout& s, int L, int M, int n, int prec, int R, int C, const double* W, std::string& err) {
+  s = ScLayout();
+  if (L <= 0 || M <= 0 || n <= 0) { err = "L, M, n must be positive"; return SA_ERR_ARG; }
+  if (prec != SA_PREC_F32 && prec != SA_PREC_F64) { err = "unknown precision"; return SA_ERR_ARG; }
+  if (R < 1) { err = "R must be at least 1"; return SA_ERR_ARG; }
+  if (C < 1) { err = "C must be at least 1"; return SA_ERR_ARG; }
+  if (!W) { err = "W is NULL"; return SA_ERR_ARG; }
+  if (R > kScMaxBlocks) { err = "R above SA_SC_MAX_BLOCKS = " + std::to_string(kScMaxBlocks); return SA_ERR_UNSUPPORTED; }
+  if (C > kScMaxBlocks) { err = "C above SA_SC_MAX_BLOCKS = " + std::to_string(kScMaxBlocks); return SA_ERR_UNSUPPORTED; }
+  if ((M & (M - 1)) != 0) { err = "M must be a power of two for a coupled design"; return SA_ERR_UNSUPPORTED; }
+  if (M > 4096) { err = "M must be <= 4096"; return SA_ERR_UNSUPPORTED; }
+  if (n % R != 0) { err = "R = " + std::to_string(R) + " does not divide n = " + std::to_string(n); return SA_ERR_ARG; }
+  if (L % C != 0) { err = "C = " + std::to_string(C) + " does not divide L = " + std::to_string(L); return SA_ERR_ARG; }
+  for (int r = 0; r < R; ++r)
+    for (int c = 0; c < C; ++c) {
+      const double v = W[(size_t)r * C + c];
+      if (!std::isfinite(v)) { err = "W[" + std::to_string(r) + "," + std::to_string(c) + "] is not finite"; return SA_ERR_ARG; }
+      if (v < 0) { err = "W[" + std::to_string(r) + "," + std::to_string(c) + "] is negative"; return SA_ERR_ARG; }
+    }
+  for (int r = 0; r < R; ++r) {
+    bool any = false;
+    for (int c = 0; c < C; ++c) any = any || W[(size_t)r * C + c] > 0;
+    if (!any) { err = "W row " + std::to_string(r) + " has no positive entry"; return SA_ERR_ARG; }
+  }
+  for (int c = 0; c < C; ++c) {
+    bool any = false;
+    for (int r = 0; r < R; ++r) any = any || W[(size_t)r * C + c] > 0;
+    if (!any) { err = "W column " + std::to_string(c) + " has no positive entry"; return SA_ERR_ARG; }
+  }
+  const size_t sz = prec == SA_PREC_F64 ? 8 : 4;
+  s.sec_lds = sc_sec_lds_need(M, n, sz);
+  if (n >= 65535 || s.sec_lds > kLdsBytes) {
+    err = "n too large: z must fit the section kernel's LDS image (" + std::to_string(s.sec_lds) + " bytes needed)";
+    return SA_ERR_UNSUPPORTED;
+  }
+  s.R = R; s.C = C; s.L = L; s.M = M; s.n = n; s.prec = prec;
+  s.n_r = n / R;
+  s.L_c = L / C;
+  s.gpc = (s.L_c + kSpw - 1) / kSpw;
+  s.G = C * s.gpc;
+  s.zpb = (s.n_r + kScRowsPerBlk - 1) / kScRowsPerBlk;
+  s.NZ = R * s.zpb;
+  s.own_fwd = s.L_c % kSpw != 0;
+  const int mx = (M + 1) > (n + 1) ? (M + 1) : (n + 1);
+  s.w = 1 << ilog2(mx);
+  s.nhi = s.w / M;
+  s.E = 1;
+  while (s.E * 64 < M) s.E *= 2;
+  return SA_OK;
+}
+
+// The Ab table of the padded groups, [G][n][4]: fwd_entry of each present
+// section's ordering value, 0 for an absent section (whose T is zero).
+inline void sc_fwd_table(const ScLayout& s, const uint32_t* ordering, uint16_t* out) {
+  const int lgM = ilog2(s.M);
+  for (int g = 0; g < s.G; ++g)
+    for (int wv = 0; wv < kSpw; ++wv) {
+      const int l = sc_group_section(s, g, wv);
+      for (int r = 0; r < s.n; ++r)
+        out[((size_t)g * s.n + r) * kSpw + wv] = l < 0 ? (uint16_t)0 : fwd_entry(ordering[(size_t)l * s.n + r], lgM, s.M);
+    }
+}
+
+// What the kernels rely on, checked on a layout: every section in exactly one
+// group, no group across a column block; every row in exactly one z^2
+// partial, none across a row block; the LDS within the CU's.  Empty: holds.
+inline std::string sc_check_layout(const ScLayout& s) {
+  std::vector<int> seen(s.L, 0);
+  for (int g = 0; g < s.G; ++g)
+    for (int wv = 0; wv < kSpw; ++wv) {
+      const int l = sc_group_section(s, g, wv);
+      if (l < 0) continue;
+      if (l >= s.L) return "group " + std::to_string(g) + " names section " + std::to_string(l);
+      if (sc_col_block(s, l) != sc_group_block(s, g)) return "group " + std::to_string(g) + " straddles a column block";
+      ++seen[l];
+    }
+  for (int l = 0; l < s.L; ++l)
+    if (seen[l] != 1) return "section " + std::to_string(l) + " sits in " + std::to_string(seen[l]) + " groups";
+  std::vector<int> rows(s.n, 0);
+  for (int q = 0; q < s.NZ; ++q) {
+    const int r0 = sc_zpart_row0(s, q), cnt = sc_zpart_rows(s, q);
+    if (cnt < 1 || r0 < 0 || r0 + cnt > s.n) return "z^2 partial " + std::to_string(q) + " out of range";
+    if (sc_row_block(s, r0) != sc_zpart_block(s, q) || sc_row_block(s, r0 + cnt - 1) != sc_zpart_block(s, q))
+      return "z^2 partial " + std::to_string(q) + " straddles a row block";
+    for (int i = r0; i < r0 + cnt; ++i) ++rows[i];
+  }
+  for (int i = 0; i < s.n; ++i)
+    if (rows[i] != 1) return "row " + std::to_string(i) + " sits in " + std::to_string(rows[i]) + " z^2 partials";
+  if (s.NZ > s.n) return "more z^2 partials than z slots (k_scsec stages them there)";
+  if (s.sec_lds > kLdsBytes) return "k_scsec's LDS image past the CU's";
+  return "";
+}
+
+}  // namespace sa

@@ -1,0 +1,203 @@
+"""Spatially coupled SPARCs: base-matrix AMP on the device (``sa_sc_*`` in
+include/sparc_amp.h, kernels ``k_scsec`` / ``k_scrow``).
+
+The coupled design over the sub-sampled Hadamard operator Ã of
+``sparc_transforms(L, M, n, seed)`` is ``A[i, j] = sqrt(W[r(i), c(j)]) Ã[i, j]``
+for an R x C base matrix W: row i lies in row block ``i // (n // R)``, section l
+in column block ``l // (L // C)``.  AMP tracks one effective-noise level per
+row block (φ_r) and per column block (τ_c²); at ``W = [[1]]`` it is ``amp()``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from ._lib import as_f64, check, dptr
+from .operators import SparcOperator, _cached_operator, make_ordering, seed_array
+
+__all__ = ["base_matrix", "CoupledOperator", "ScAbOp", "ScAzOp", "sc_transforms", "amp_sc", "amp_sc_batch",
+           "mc_decode_sc"]
+
+
+def base_matrix(omega: int, Lambda: int) -> np.ndarray:
+    """The (ω, Λ) band-diagonal base matrix: R = Λ + ω - 1 rows, C = Λ columns,
+    W[r, c] = R / ω for c <= r <= c + ω - 1 and 0 elsewhere.  Every column has
+    mean 1, so each column of the coupled design keeps unit average norm."""
+    omega, Lambda = int(omega), int(Lambda)
+    if omega < 1 or Lambda < 1:
+        raise ValueError("omega and Lambda must be at least 1")
+    R = Lambda + omega - 1
+    W = np.zeros((R, Lambda))
+    for c in range(Lambda):
+        W[c:c + omega, c] = R / omega
+    return W
+
+
+class CoupledOperator:
+    """A coupled design on the device (one ``sa_sc``) over a Hadamard-backend
+    SparcOperator, whose tables it borrows and which it keeps alive."""
+
+    def __init__(self, parent: SparcOperator, W):
+        lib = _lib.load()
+        if not hasattr(lib, "sa_sc_create"):
+            raise _lib.SparcAmpError(_lib.SA_ERR_UNSUPPORTED, "this build of the library has no sa_sc_create")
+        W = as_f64(W)
+        if W.ndim != 2:
+            raise ValueError("W must be a 2-d base matrix (R x C)")
+        self.parent = parent
+        self.W = W
+        self.R, self.C = int(W.shape[0]), int(W.shape[1])
+        self.L, self.M, self.n = parent.L, parent.M, parent.n
+        self.precision, self.device = parent.precision, parent.device
+        self._lib = lib
+        self._sc = _lib.ct.c_void_p()
+        check(lib.sa_sc_create(parent.ctx, self.R, self.C, dptr(W), _lib.ct.byref(self._sc)))
+
+    def __del__(self):
+        sc = getattr(self, "_sc", None)
+        if sc is not None and sc.value:
+            try:
+                self._lib.sa_sc_destroy(sc)
+            except Exception:
+                pass
+            self._sc = None
+
+    def Ab_batch(self, beta) -> np.ndarray:
+        """A β for a (B, L*M) batch -> (B, n)."""
+        beta = as_f64(beta)
+        B = beta.shape[0]
+        assert beta.size == B * self.L * self.M
+        out = np.empty((B, self.n))
+        check(self._lib.sa_sc_Ab(self._sc, B, dptr(beta), dptr(out)))
+        return out
+
+    def Az_batch(self, z) -> np.ndarray:
+        """Aᵀ z for a (B, n) batch -> (B, L*M)."""
+        z = as_f64(z)
+        B = z.shape[0]
+        assert z.size == B * self.n
+        out = np.empty((B, self.L * self.M))
+        check(self._lib.sa_sc_Az(self._sc, B, dptr(z), dptr(out)))
+        return out
+
+    def amp_batch(self, y, Pl, T, early_stop=True):
+        """Decode B codewords: y (B, n) -> (β̂ (B, L*M), iters (B,), φ (B, T, R)).
+        iters[b] is the stop index (every φ_r bit-equal to the previous
+        iteration's), or T; φ rows from the stop index on are zero."""
+        y = as_f64(y)
+        B = y.shape[0] if y.ndim == 2 else 1
+        assert y.size == B * self.n, "y must hold B x n values"
+        Pl = as_f64(Pl).reshape(-1)
+        assert Pl.size == self.L, "Pl must hold L section powers"
+        T = int(T)
+        assert T >= 0
+        out = np.empty((B, self.L * self.M))
+        iters = np.empty(B, dtype=np.int32)
+        phi = np.zeros((B, T, self.R))
+        flags = 0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP
+        check(self._lib.sa_sc_amp(self._sc, B, dptr(y), dptr(Pl), T, dptr(out),
+                                  iters.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int)), dptr(phi), flags))
+        return out, iters, phi
+
+    def last_amp_ms(self) -> float:
+        """Device milliseconds of the last amp_batch's iterations (events)."""
+        return float(self._lib.sa_sc_event_ms(self._sc))
+
+    def mc(self, idx, noise, Pl, T, early_stop=True):
+        """Encode (y = A β(idx) + noise), decode, decide and count bit errors on
+        the device in one call: idx (B, L) int32, noise (B, n) or None ->
+        (decisions (B, L), stop indices (B,), bit errors (B,), device ms)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        B = idx.shape[0]
+        assert idx.shape == (B, self.L), "idx must be (B, L)"
+        nz = None
+        if noise is not None:
+            noise = as_f64(noise)
+            assert noise.size == B * self.n, "noise must be (B, n)"
+            nz = dptr(noise)
+        Pl = as_f64(Pl).reshape(-1)
+        assert Pl.size == self.L, "Pl must hold L section powers"
+        i32 = _lib.ct.POINTER(_lib.ct.c_int32)
+        dec = np.empty((B, self.L), dtype=np.int32)
+        its = np.empty(B, dtype=np.int32)
+        errs = np.empty(B, dtype=np.int32)
+        ms = np.zeros(1)
+        flags = 0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP
+        check(self._lib.sa_sc_mc(self._sc, B, idx.ctypes.data_as(i32), nz, dptr(Pl), int(T), flags,
+                                 dec.ctypes.data_as(i32), its.ctypes.data_as(i32), errs.ctypes.data_as(i32), dptr(ms)))
+        return dec, its, errs, float(ms[0])
+
+
+class ScAbOp:
+    """``Ab(β)`` -> A β, (n, 1) float64, for the coupled design."""
+
+    def __init__(self, op: CoupledOperator):
+        self.op = op
+
+    def __call__(self, b):
+        b = np.asarray(b)
+        assert b.size == self.op.L * self.op.M
+        return self.op.Ab_batch(b.reshape(1, -1)).reshape(-1, 1)
+
+
+class ScAzOp:
+    """``Az(z)`` -> Aᵀ z, (L*M, 1) float64, for the coupled design."""
+
+    def __init__(self, op: CoupledOperator):
+        self.op = op
+
+    def __call__(self, z):
+        z = np.asarray(z)
+        assert z.size == self.op.n
+        return self.op.Az_batch(z.reshape(1, -1)).reshape(-1, 1)
+
+
+def sc_transforms(L, M, n, W, seed=0, *, precision=None, device=None):
+    """The coupled design of base matrix W over sparc_transforms(L, M, n, seed)'s
+    operator: returns (Ab, Az, ordering), callables like AbOp / AzOp."""
+    ordering = make_ordering(L, M, n, seed)
+    parent = _cached_operator(L, M, n, ordering, "hadamard", precision, device)
+    op = CoupledOperator(parent, W)
+    return ScAbOp(op), ScAzOp(op), ordering
+
+
+def _coupled(Ab) -> CoupledOperator:
+    op = getattr(Ab, "op", None)
+    if not isinstance(op, CoupledOperator):
+        raise TypeError("Ab must come from sc_transforms (a coupled device operator); there is no host fallback")
+    return op
+
+
+def amp_sc_batch(y, Pl, T, Ab, *, early_stop=True):
+    """Coupled AMP of B codewords y (B, n): -> (β̂ (B, L*M), iters (B,), φ (B, T, R))."""
+    return _coupled(Ab).amp_batch(y, Pl, T, early_stop=early_stop)
+
+
+def amp_sc(y, Pl, L, M, T, Ab, Az, *, early_stop=True):
+    """Coupled AMP of one codeword, in amp()'s argument order: -> β̂, (L*M, 1)."""
+    op = _coupled(Ab)
+    assert (op.L, op.M) == (int(L), int(M)), "L, M must be the operator's"
+    if getattr(Az, "op", None) is not op:
+        raise TypeError("Ab and Az must come from one sc_transforms call")
+    y = as_f64(y).reshape(1, -1)
+    beta, _, _ = op.amp_batch(y, Pl, T, early_stop=early_stop)
+    return beta.reshape(-1, 1)
+
+
+def mc_decode_sc(Ab, Pl, sigma, T, seeds, batch=256, early_stop=True):
+    """Monte-Carlo reps on the coupled design, drawn as harness._draw_reps draws
+    them (RandomState(s).randint(0, M, L), then .randn(n) * σ), encoded, decoded
+    and decided on the device in batches of `batch`:
+    -> (bit errors (R,), stop indices (R,), decisions (R, L)), all int32."""
+    from .harness import draw_reps
+    op = _coupled(Ab)
+    seeds = seed_array(seeds)
+    nrep = len(seeds)
+    errs = np.empty(nrep, dtype=np.int32)
+    its = np.empty(nrep, dtype=np.int32)
+    dec = np.empty((nrep, op.L), dtype=np.int32)
+    for i0 in range(0, nrep, int(batch)):
+        sl = slice(i0, min(nrep, i0 + int(batch)))
+        idx, noise = draw_reps(seeds[sl], op.L, op.M, op.n, float(sigma))
+        dec[sl], its[sl], errs[sl], _ = op.mc(idx, noise, Pl, T, early_stop=early_stop)
+    return errs, its, dec
