@@ -514,6 +514,47 @@ double sa_sc_event_ms(sa_sc* sc);
 int sa_sc_mc(sa_sc* sc, int B, const int32_t* idx, const double* noise, const double* Pl, int T,
              int flags, int32_t* dec_out, int32_t* iters_out, int32_t* errs_out, double* ms_out);
 
+/* ---- coupled state evolution ----
+ * The scalar recursion that predicts a coupled decode, iteration by
+ * iteration, without a codeword: the per-row-block phi_r, the
+ * per-column-block tau_c^2 and section error rate.  Context-free like sa_se;
+ * binary64 on the device.  A batch of B configurations shares L and M; n, R,
+ * C [B], the base matrices W (row-major, back to back), Pl [B][L] and sigma
+ * [B] are per configuration.  With c_l = sqrt(n Pl_l), P_c = sum_{l in c} Pl_l
+ * (l in order) and the rows U of sa_se (exactly one of seeds and U):
+ *   psi_c^0 = P_c
+ *   phi_r^t = sigma^2 + sum_c W[r, c] psi_c^t                  (c in order)
+ *   1 / tau_c^2^t = (1 / R) sum_r W[r, c] / phi_r^t             (r in order)
+ *   a = c_l / tau_c(l)^t,  E_l as in sa_se,  a pair missed as in sa_se
+ *   x_c^t = sum_{l in c} (Pl_l / P_c) E_l,  psi_c^{t+1} = P_c (1 - x_c^t)
+ * the decoder's steps 1, 3, 5 and 6 applied to s = c e_true + tau_c U; at
+ * R = C = 1, W = [[1]] it is sa_se's recursion with tau^2 = phi.  Sections of
+ * one configuration and one column block whose powers are equal bit for bit
+ * are computed once.  For t >= 1 a column block whose tau_c^2 has the bits it
+ * had at t - 1 is not recomputed (E is a function of tau^2 and U alone, so
+ * the results are the same bits); flags = SA_SCSE_NO_SKIP recomputes it.  All
+ * T iterations are queued on one stream; the call waits once and copies back
+ * once.  A configuration's results do not depend on the rest of the batch.
+ *   phi_out [B][T+1][Rmax], tau2_out, x_out, miss_out [B][T][Cmax] (the missed
+ *   (section, sample) pairs of block c at t, out of (L / C) S), zero beyond a
+ *   configuration's own R and C; stop_out [B]: the predicted stop index, the
+ *   first t >= 1 at which every phi_r^t equals phi_r^{t-1} bit for bit (the
+ *   decoder's stopping rule), or T; sec_out [B][L] or NULL: E_l of the last
+ *   iteration; ms_out or NULL: device time of the draw and the iterations.
+ * SA_ERR_ARG (sa_last_error names the argument and the configuration; nothing
+ * is written): B, L, T, S < 1, M < 2, n, R or C < 1, R does not divide n, C
+ * does not divide L, a negative or non-finite entry of W, a row or column of W
+ * without a positive entry, a sigma that is not finite and > 0, a Pl that is
+ * negative or not finite, P_c = 0, Rmax or Cmax below the batch's largest,
+ * both or neither of seeds and U, unknown flags.  SA_ERR_UNSUPPORTED: R or C
+ * above SA_SC_MAX_BLOCKS, M > SA_SE_MAX_M (M need not be a power of two: SE
+ * never gathers), S > 2^24. */
+enum { SA_SCSE_NO_SKIP = 1 };
+int sa_sc_se(int device, int B, int L, int M, const int* n, const int* R, const int* C, const double* W,
+             const double* Pl, const double* sigma, int T, int S, const uint32_t* seeds, const double* U,
+             int Rmax, int Cmax, int flags, double* phi_out, double* tau2_out, double* x_out,
+             int64_t* miss_out, int* stop_out, double* sec_out, double* ms_out);
+
 /* Introspection. */
 /* The kernels a decode of B codewords runs: out8 = {section path (sa_sec_path),
  * Ab partials per codeword, row splits, codewords per batched workgroup,

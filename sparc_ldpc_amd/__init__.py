@@ -25,7 +25,8 @@ from .threshold import (hard_initialisation, prep_y, calc_E, hist_E, calc_I_e, J
                         soft_amp_ldpc_hardinit, ber_from_LLRs, soft_hardinit_plot, calc_E_batch, amp_exit_curve)
 from . import dist
 from . import se
-from .se import state_evolution, se_draws, pa_search, SEResult, PASearch
+from .se import (state_evolution, se_draws, pa_search, SEResult, PASearch, sc_state_evolution, sc_search, SCSEResult,
+                 SCSearch)
 from . import sc
 from .sc import base_matrix, sc_transforms, amp_sc, amp_sc_batch, mc_decode_sc, CoupledOperator
 

@@ -35,6 +35,7 @@ SA_FLAG_BETA0 = 0x100
 SA_PTR_DEVICE = 0x200
 SA_SC_MAX_BLOCKS = 64  # the most row / column blocks of a coupled design's base matrix (include/sparc_amp.h)
 SA_SE_MAX_M = 4096  # the largest section size sa_se holds (include/sparc_amp.h)
+SA_SCSE_NO_SKIP = 1  # sa_sc_se: recompute the column blocks whose tau^2 did not change
 SA_LLR_MODES = {"reference": 0, "two_sided": 1}  # sa_llr_ex: SA_LLR_REFERENCE, SA_LLR_TWO_SIDED
 
 # sa_create_ex plan options (include/sparc_amp.h): overrides of the built-in
@@ -75,6 +76,7 @@ EXPORTS = (
     "sa_draw_reps", "sa_mc_stage", "sa_mc_run", "sa_make_ordering", "sa_mc_draw", "sa_mc_fetch_draws",
     "sa_se", "sa_se_draws", "sa_encode_bits",
     "sa_sc_create", "sa_sc_destroy", "sa_sc_Ab", "sa_sc_Az", "sa_sc_amp", "sa_sc_event_ms", "sa_sc_mc",
+    "sa_sc_se",
 )
 
 _P = ct.c_void_p
@@ -144,6 +146,9 @@ _SIG = {
     "sa_sc_event_ms": (ct.c_double, [_P]),
     "sa_sc_mc": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D, _D, _I, _I, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32),
                       ct.POINTER(ct.c_int32), _D]),
+    "sa_sc_se": (_I, [_I, _I, _I, _I, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), _D, _D, _D, _I, _I,
+                      ct.POINTER(ct.c_uint32), _D, _I, _I, _I, _D, _D, _D, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int),
+                      _D, _D]),
 }
 
 _lib = None

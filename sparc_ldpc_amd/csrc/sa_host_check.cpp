@@ -35,6 +35,15 @@
 //     padded groups' Ab table with fwd_entry on a drawn ordering: exit status
 //     1 with the first violation on stderr.  W entries are read by strtod
 //     ("nan", "inf" included).
+//   sa_host_check scse B L M T S  then per configuration  n R C sigma W[0,0] ... W[R-1,C-1] Pl[0] ... Pl[L-1]
+//     the plan of a coupled state-evolution batch (sa_scse.h: scse_plan) as one
+//     JSON object: the per-configuration offsets (tau slots, row blocks, W,
+//     classes), the class range of every tau slot, every class [tau slot, c,
+//     weight, multiplicity], the class of every section, P_c, sigma^2, phi^0
+//     and tau^2^0, the chunking; {"error", "message"} for a batch that
+//     sa_sc_se refuses.  Runs the plan's invariants: exit status 1 with the
+//     first violation on stderr.  Reals are read by strtod and printed with 17
+//     significant digits.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +51,7 @@
 #include <numeric>
 
 #include "sa_sc.h"
+#include "sa_scse.h"
 #include "sa_seq.h"
 #include "sa_shape.h"
 #include "sa_tables.h"
@@ -54,7 +64,8 @@ static int usage() {
                        "       sa_host_check seq L M n backend prec plan n_cus B T flags has_b0 profiled\n"
                        "       sa_host_check tables L M n prec plan\n"
                        "       sa_host_check packed L M n prec plan\n"
-                       "       sa_host_check sc L M n prec R C W...\n");
+                       "       sa_host_check sc L M n prec R C W...\n"
+                       "       sa_host_check scse B L M T S {n R C sigma W... Pl...}...\n");
   return 2;
 }
 
@@ -452,8 +463,77 @@ static int cmd_sc(int L, int M, int n, int prec, int R, int C, const std::vector
   return 0;
 }
 
+// The plan of a coupled state-evolution batch (sa_scse.h) and its invariants
+template <typename T>
+static void print_list(const char* name, const std::vector<T>& v, const char* fmt, bool last = false) {
+  std::printf("\"%s\": [", name);
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i) std::printf(", ");
+    std::printf(fmt, v[i]);
+  }
+  std::printf(last ? "]" : "], ");
+}
+
+static int cmd_scse(int B, int L, int M, int T, int S, const std::vector<int>& n, const std::vector<int>& R,
+                    const std::vector<int>& C, const std::vector<double>& sigma, const std::vector<double>& W,
+                    const std::vector<double>& Pl) {
+  ScSePlan p;
+  std::string err;
+  if (int rc = scse_plan(p, B, L, M, n.data(), R.data(), C.data(), W.data(), Pl.data(), sigma.data(), T, S, err)) {
+    std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+    return 0;
+  }
+  const std::string bad = scse_check_plan(p, Pl.data());
+  CHECK(bad.empty(), "%s", bad.c_str());
+  std::printf("{\"B\": %d, \"L\": %d, \"M\": %d, \"K\": %d, \"NS\": %d, \"NR\": %d, \"Rmax\": %d, \"Cmax\": %d, "
+              "\"SC\": %d, \"NCH\": %d, \"grid\": %lld, \"classes_per_group\": %d, \"max_blocks\": %d, \"max_M\": %d, ",
+              p.B, p.L, p.M, p.K, p.NS, p.NR, p.Rmax, p.Cmax, p.SC, p.NCH, p.grid, kSeClasses, kScSeMaxBlocks, kSeMaxM);
+  print_list("slot_off", p.slot_off, "%d");
+  print_list("row_off", p.row_off, "%d");
+  print_list("w_off", p.w_off, "%lld");
+  print_list("cfg_off", p.cfg_off, "%d");
+  print_list("blk_off", p.blk_off, "%d");
+  print_list("sec_cls", p.sec_cls, "%d");
+  print_list("Pc", p.Pc, "%.17g");
+  print_list("sig2", p.sig2, "%.17g");
+  print_list("phi0", p.phi0, "%.17g");
+  print_list("tau20", p.tau20, "%.17g");
+  std::printf("\"classes\": [");
+  for (int k = 0; k < p.K; ++k)
+    std::printf("%s[%d, %.17g, %.17g, %d]", k ? ", " : "", p.cls_slot[k], p.cls_c[k], p.cls_w[k], p.cls_mult[k]);
+  std::printf("]}\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return usage();
+  if (!std::strcmp(argv[1], "scse")) {
+    if (argc < 7) return usage();
+    int v[5];
+    for (int i = 0; i < 5; ++i) v[i] = std::atoi(argv[2 + i]);
+    const int B = v[0], L = v[1];
+    std::vector<int> n, R, C;
+    std::vector<double> sigma, W, Pl;
+    int at = 7;
+    // (a list that ends early: refused here, in front of scse_plan's reads)
+    for (int b = 0; b < B; ++b) {
+      if (at + 4 > argc) return usage();
+      n.push_back(std::atoi(argv[at]));
+      R.push_back(std::atoi(argv[at + 1]));
+      C.push_back(std::atoi(argv[at + 2]));
+      sigma.push_back(std::strtod(argv[at + 3], nullptr));
+      at += 4;
+      const long long nw = (long long)std::max(R[b], 0) * std::max(C[b], 0), np = std::max(L, 0);
+      if (at + nw + np > argc) return usage();
+      for (long long i = 0; i < nw; ++i) W.push_back(std::strtod(argv[at++], nullptr));
+      for (long long i = 0; i < np; ++i) Pl.push_back(std::strtod(argv[at++], nullptr));
+    }
+    if (at != argc) return usage();
+    // (scse_plan reads nothing of a configuration it refuses at R or C < 1; the lists are never empty for its reads)
+    W.push_back(0.0);
+    Pl.push_back(0.0);
+    return cmd_scse(B, L, v[2], v[3], v[4], n, R, C, sigma, W, Pl);
+  }
   if (!std::strcmp(argv[1], "sc")) {
     if (argc < 8) return usage();
     int v[6];

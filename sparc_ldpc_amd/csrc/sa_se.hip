@@ -31,20 +31,23 @@
 // No floating-point atomics, no grid-wide barrier: every sum has one order, so
 // two calls on the same inputs return the same bits, and an allocation's
 // result does not depend on what else is in the batch.  Binary64 throughout.
+//
+// The second half of the file is the same for spatially coupled SPARCs
+// (sa_sc_se; host rules: sa_scse.h): one phi_r per row
+// block, one tau_c^2 per column block, classes per (configuration, column
+// block), k_scse_expect and k_scse_reduce in the places of the two kernels
+// above.
 #include "sa_common.h"
 #include "legacy_mt_dev.h"
+#include "sa_scse.h"
 
 #include <unordered_map>
 
 namespace sa {
 
-constexpr int kSeMaxM = SA_SE_MAX_M;  // the largest row of U a workgroup holds
-constexpr int kSeRow = 4096;          // binary64 values of U in a workgroup's LDS (32 KB)
-constexpr int kSeSamples = 16;        // samples per chunk, at most (SC = min(16, kSeRow / M))
-constexpr int kSeClasses = 8;         // classes per workgroup
+// (kSeMaxM, kSeRow, kSeSamples, kSeClasses: sa_scse.h, where the host rules size the chunks)
 constexpr int kSeThreads = 256;
 constexpr int kSeRedThreads = 1024;
-static_assert(kSeMaxM <= kSeRow, "one row must fit");
 
 struct SeArgs {
   const double* U;      // [S][M]
@@ -65,9 +68,27 @@ __device__ __forceinline__ long long se_wave_sum(long long v) {
   return v;
 }
 
-// (No contraction in the two kernels below: the operations are those of the
-// NumPy statement the tests hold them to, tests/se_ref.py, one rounding each;
-// what differs is the device library's exp and the order of the sums.)
+// One (class, sample) pair on one wave: the posterior of the true column and
+// whether the pair is missed, for the scalar av = c / tau, the sample's row u
+// and umax = max_{j >= 2} U_j of that row.  Uniform results.
+__device__ __forceinline__ void se_pair(double av, const double* u, double umax, int M, int lane, double& post, int& miss) {
+#pragma clang fp contract(off)
+  const double l0 = av * av + av * u[0];  // the true column's logit
+  const double mo = av * umax;            // the largest of the others
+  const double mx = fmax(l0, mo);
+  double sum = 0;
+#pragma unroll 4
+  for (int j = 1 + lane; j < M; j += 64) sum += exp(av * u[j] - mx);
+  sum = wave_sum(sum);
+  const double e0 = exp(l0 - mx);
+  post = e0 / (e0 + sum);
+  miss = l0 < mo ? 1 : 0;
+}
+
+// (No contraction in the kernels below: the operations are those of the
+// NumPy statements the tests hold them to, tests/se_ref.py and
+// tests/sc_se_ref.py, one rounding each; what differs is the device library's
+// exp and the order of the sums.)
 __global__ void __launch_bounds__(kSeThreads) k_se_expect(SeArgs a) {
 #pragma clang fp contract(off)
   __shared__ double rows[kSeRow];
@@ -95,18 +116,12 @@ __global__ void __launch_bounds__(kSeThreads) k_se_expect(SeArgs a) {
     const int kk = item / ns, s = item - kk * ns, k = k0 + kk;
     const double tau2 = a.tau2[(size_t)a.cls_b[k] * a.T1 + a.t];
     const double av = a.cls_c[k] / sqrt(tau2);
-    const double* u = rows + s * M;
-    const double l0 = av * av + av * u[0];  // the true column's logit
-    const double mo = av * umax[s];         // the largest of the others
-    const double mx = fmax(l0, mo);
-    double sum = 0;
-#pragma unroll 4
-    for (int j = 1 + lane; j < M; j += 64) sum += exp(av * u[j] - mx);
-    sum = wave_sum(sum);
+    double pv;
+    int mv;
+    se_pair(av, rows + s * M, umax[s], M, lane, pv, mv);
     if (lane == 0) {
-      const double e0 = exp(l0 - mx);
-      post[kk * kSeSamples + s] = e0 / (e0 + sum);
-      missf[kk * kSeSamples + s] = l0 < mo ? 1 : 0;
+      post[kk * kSeSamples + s] = pv;
+      missf[kk * kSeSamples + s] = mv;
     }
   }
   __syncthreads();
@@ -176,6 +191,173 @@ __global__ void __launch_bounds__(kSeRedThreads) k_se_reduce(SeRedArgs a) {
       a.tau2[(size_t)b * (a.T + 1) + a.t + 1] = a.sig2[b] + a.P[b] * (1.0 - s);
       a.miss[(size_t)b * a.T + a.t] = mm;
     }
+  }
+}
+
+// ---- coupled state evolution (sa_sc_se) ----------------------------------------
+// k_scse_expect is k_se_expect with two differences: a class reads tau^2 from
+// its tau slot (configuration, column block) of the iteration, and for t >= 1
+// a class whose slot holds the bits it held at t - 1 is frozen: E is a
+// deterministic function of (tau^2, U), so its [class][chunk] slots already
+// hold what this launch would write, and its exponentials are skipped.  A
+// workgroup whose classes are all frozen returns after the test.
+struct ScSeArgs {
+  const double* U;           // [S][M]
+  const double* cls_c;       // [K] c = sqrt(n Pl) of the class
+  const long long* cls_tau;  // [K] where its tau slot of t = 0 lies in tau2
+  const double* tau2;        // [B][T + 1][Cmax]
+  double* part_p;            // [K][NCH] posterior sums per sample chunk
+  int* part_m;               // [K][NCH] miss counts
+  int S, M, K, NCH, SC, Cmax, t, skip;
+};
+
+__global__ void __launch_bounds__(kSeThreads) k_scse_expect(ScSeArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double rows[kSeRow];
+  __shared__ double umax[kSeSamples];
+  __shared__ double post[kSeClasses * kSeSamples];
+  __shared__ int missf[kSeClasses * kSeSamples];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int ch = (int)(blockIdx.x % (unsigned)a.NCH), kc = (int)(blockIdx.x / (unsigned)a.NCH);
+  const int M = a.M;
+  const int s0 = ch * a.SC, ns = min(a.SC, a.S - s0);
+  const int k0 = kc * kSeClasses, nk = min(kSeClasses, a.K - k0);
+  // the live classes of this workgroup (uniform: every thread tests all nk <= 8)
+  const long long* tbits = (const long long*)a.tau2;
+  const long long trow = (long long)a.t * a.Cmax;
+  unsigned live = 0;
+  for (int kk = 0; kk < nk; ++kk) {
+    const long long at = a.cls_tau[k0 + kk] + trow;
+    const bool frozen = a.skip && a.t > 0 && tbits[at] == tbits[at - a.Cmax];
+    if (!frozen) live |= 1u << kk;
+  }
+  if (!live) return;
+  const double* src = a.U + (size_t)s0 * M;
+  for (int i = tid; i < ns * M; i += kSeThreads) rows[i] = src[i];
+  __syncthreads();
+  for (int s = wv; s < ns; s += kSeThreads / 64) {
+    double m = -INFINITY;
+    for (int j = 1 + lane; j < M; j += 64) m = fmax(m, rows[s * M + j]);
+    m = wave_max(m);
+    if (lane == 0) umax[s] = m;
+  }
+  __syncthreads();
+  for (int item = wv; item < nk * ns; item += kSeThreads / 64) {
+    const int kk = item / ns, s = item - kk * ns, k = k0 + kk;
+    if (!((live >> kk) & 1u)) continue;
+    const double tau2 = a.tau2[a.cls_tau[k] + trow];
+    const double av = a.cls_c[k] / sqrt(tau2);
+    double pv;
+    int mv;
+    se_pair(av, rows + s * M, umax[s], M, lane, pv, mv);
+    if (lane == 0) {
+      post[kk * kSeSamples + s] = pv;
+      missf[kk * kSeSamples + s] = mv;
+    }
+  }
+  __syncthreads();
+  if (tid < nk && ((live >> tid) & 1u)) {  // the chunk's samples in order
+    double p = 0;
+    int mc = 0;
+    for (int s = 0; s < ns; ++s) {
+      p += post[tid * kSeSamples + s];
+      mc += missf[tid * kSeSamples + s];
+    }
+    a.part_p[(size_t)(k0 + tid) * a.NCH + ch] = p;
+    a.part_m[(size_t)(k0 + tid) * a.NCH + ch] = mc;
+  }
+}
+
+// One workgroup per configuration.  A wave per class adds its slots as
+// k_se_reduce does; then, in the first wave, lane c forms x_c, psi_c and the
+// block's miss count over its classes in class order, lane r forms
+// phi_r^{t+1} in c order, and lane c forms tau_c^2^{t+1} in r order: the slot
+// the next launch reads (sa_scse.h: scse_phi_tau is the same on the host).
+// The predicted stop index is written once: the first t + 1 at which every
+// phi_r has the bits of the row before.
+struct ScSeRedArgs {
+  const double* part_p;
+  const int* part_m;
+  const int* cfg_off;      // [B + 1] class range of each configuration
+  const int* slot_off;     // [B + 1] its tau slots
+  const int* blk_off;      // [NS + 1] class range of each tau slot
+  const long long* w_off;  // [B + 1] its base matrix in W
+  const int* R;            // [B]
+  const int* C;            // [B]
+  const double* W;
+  const double* cls_w;     // [K] multiplicity * Pl / P_c
+  const int* cls_mult;     // [K]
+  const double* sig2;      // [B]
+  const double* Pc;        // [NS]
+  double* phi;             // [B][T + 1][Rmax]
+  double* tau2;            // [B][T + 1][Cmax]
+  double* x;               // [B][T][Cmax]
+  long long* miss;         // [B][T][Cmax]
+  long long* stop;         // [B], T until written
+  double* ek;              // [K] E of the class (the last launch's stay)
+  double* wx;              // [K] scratch: weight * E
+  long long* mk;           // [K] scratch: multiplicity * misses
+  int NCH, S, T, t, Rmax, Cmax;
+};
+
+__global__ void __launch_bounds__(kSeRedThreads) k_scse_reduce(ScSeRedArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double psi[kScSeMaxBlocks];
+  __shared__ double phis[kScSeMaxBlocks];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int k0 = a.cfg_off[b], k1 = a.cfg_off[b + 1];
+  for (int k = k0 + wv; k < k1; k += kSeRedThreads / 64) {
+    const double* pp = a.part_p + (size_t)k * a.NCH;
+    const int* pm = a.part_m + (size_t)k * a.NCH;
+    double s = 0;
+    int mc = 0;
+    for (int c = lane; c < a.NCH; c += 64) {
+      s += pp[c];
+      mc += pm[c];
+    }
+    s = wave_sum(s);
+    mc = se_wave_sum(mc);
+    if (lane == 0) {
+      const double E = s / (double)a.S;
+      a.ek[k] = E;
+      a.wx[k] = a.cls_w[k] * E;
+      a.mk[k] = (long long)a.cls_mult[k] * mc;
+    }
+  }
+  __syncthreads();
+  const int R = a.R[b], C = a.C[b], q0 = a.slot_off[b];  // R, C <= 64: one lane per block
+  const double* W = a.W + a.w_off[b];
+  if (wv == 0 && lane < C) {
+    double x = 0;
+    long long mm = 0;
+    for (int k = a.blk_off[q0 + lane]; k < a.blk_off[q0 + lane + 1]; ++k) {
+      x += a.wx[k];
+      mm += a.mk[k];
+    }
+    psi[lane] = a.Pc[q0 + lane] * (1.0 - x);
+    a.x[((size_t)b * a.T + a.t) * a.Cmax + lane] = x;
+    a.miss[((size_t)b * a.T + a.t) * a.Cmax + lane] = mm;
+  }
+  __syncthreads();
+  if (wv == 0) {
+    bool same = true;
+    if (lane < R) {
+      double acc = 0;
+      for (int c = 0; c < C; ++c) acc += W[(size_t)lane * C + c] * psi[c];
+      const double ph = a.sig2[b] + acc;
+      double* row = a.phi + ((size_t)b * (a.T + 1) + a.t + 1) * a.Rmax;
+      same = __double_as_longlong(ph) == __double_as_longlong(row[lane - a.Rmax]);
+      row[lane] = ph;
+      phis[lane] = ph;
+    }
+    const bool all = __all(same ? 1 : 0);
+    if (lane == 0 && all && a.stop[b] == a.T) a.stop[b] = a.t + 1;
+  }
+  __syncthreads();
+  if (wv == 0 && lane < C) {
+    double acc = 0;
+    for (int r = 0; r < R; ++r) acc += W[(size_t)r * C + lane] / phis[r];
+    a.tau2[((size_t)b * (a.T + 1) + a.t + 1) * a.Cmax + lane] = 1.0 / (acc / (double)R);
   }
 }
 
@@ -394,6 +576,116 @@ int sa_se(int device, int B, int L, int M, int n, const double* Pl, const double
   if (sec_out) {
     const double* ek = res.data() + n_tau + n_x;
     for (size_t i = 0; i < (size_t)B * L; ++i) sec_out[i] = ek[sec_cls[i]];
+  }
+  if (ms_out) {
+    float ms = -1.f;
+    HIP_TRY(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+    *ms_out = ms;
+  }
+  return SA_OK;
+}
+
+int sa_sc_se(int device, int B, int L, int M, const int* n, const int* R, const int* C, const double* W,
+             const double* Pl, const double* sigma, int T, int S, const uint32_t* seeds, const double* U, int Rmax,
+             int Cmax, int flags, double* phi_out, double* tau2_out, double* x_out, int64_t* miss_out, int* stop_out,
+             double* sec_out, double* ms_out) {
+  if (!phi_out || !tau2_out || !x_out || !miss_out || !stop_out)
+    return fail(SA_ERR_ARG, "sa_sc_se: phi_out, tau2_out, x_out, miss_out and stop_out must be given");
+  if ((seeds != nullptr) == (U != nullptr)) return fail(SA_ERR_ARG, "sa_sc_se: exactly one of seeds and U must be given");
+  if (flags & ~SA_SCSE_NO_SKIP) return fail(SA_ERR_ARG, "sa_sc_se: unknown flags");
+  ScSePlan p;
+  std::string err;
+  if (int rc = scse_plan(p, B, L, M, n, R, C, W, Pl, sigma, T, S, err)) return fail(rc, "sa_sc_se: " + err);
+  if (Rmax < p.Rmax) return fail(SA_ERR_ARG, "sa_sc_se: Rmax below the largest R of the batch");
+  if (Cmax < p.Cmax) return fail(SA_ERR_ARG, "sa_sc_se: Cmax below the largest C of the batch");
+  const int K = p.K, NCH = p.NCH;
+  std::vector<long long> cls_tau((size_t)K);
+  for (int b = 0; b < B; ++b)
+    for (int k = p.cfg_off[b]; k < p.cfg_off[b + 1]; ++k)
+      cls_tau[k] = (long long)b * (T + 1) * Cmax + (p.cls_slot[k] - p.slot_off[b]);
+
+  SeScope sc;
+  int rc;
+  if ((rc = sc.open("sa_sc_se", device))) return rc;
+  // one block of results: phi [B][T + 1][Rmax] | tau2 [B][T + 1][Cmax] | x [B][T][Cmax] | E [K] |
+  // misses [B][T][Cmax] | stop [B] | the draw's error flag; zero where a configuration has no block
+  const size_t n_phi = (size_t)B * (T + 1) * Rmax, n_tau = (size_t)B * (T + 1) * Cmax, n_x = (size_t)B * T * Cmax;
+  const size_t o_tau = n_phi, o_x = o_tau + n_tau, o_ek = o_x + n_x, o_miss = o_ek + K, o_stop = o_miss + n_x,
+               o_err = o_stop + B, n_res = o_err + 1;
+  std::vector<double> res(n_res, 0.0);
+  const long long stop0 = T;
+  for (int b = 0; b < B; ++b) {
+    std::memcpy(&res[(size_t)b * (T + 1) * Rmax], &p.phi0[p.row_off[b]], (size_t)p.R[b] * sizeof(double));
+    std::memcpy(&res[o_tau + (size_t)b * (T + 1) * Cmax], &p.tau20[p.slot_off[b]], (size_t)p.C[b] * sizeof(double));
+    std::memcpy(&res[o_stop + b], &stop0, sizeof(stop0));
+  }
+  double* d_res = nullptr;
+  if ((rc = sc.put(&d_res, res.data(), n_res))) return rc;
+  double *d_U = nullptr, *d_c = nullptr, *d_w = nullptr, *d_sig2 = nullptr, *d_Pc = nullptr, *d_W = nullptr, *d_pp = nullptr,
+         *d_wx = nullptr;
+  int *d_mult = nullptr, *d_cfg = nullptr, *d_slot = nullptr, *d_blk = nullptr, *d_R = nullptr, *d_C = nullptr, *d_pm = nullptr;
+  long long *d_mk = nullptr, *d_ctau = nullptr, *d_woff = nullptr;
+  if ((rc = sc.put(&d_c, p.cls_c.data(), (size_t)K))) return rc;
+  if ((rc = sc.put(&d_w, p.cls_w.data(), (size_t)K))) return rc;
+  if ((rc = sc.put(&d_mult, p.cls_mult.data(), (size_t)K))) return rc;
+  if ((rc = sc.put(&d_ctau, cls_tau.data(), (size_t)K))) return rc;
+  if ((rc = sc.put(&d_cfg, p.cfg_off.data(), (size_t)B + 1))) return rc;
+  if ((rc = sc.put(&d_slot, p.slot_off.data(), (size_t)B + 1))) return rc;
+  if ((rc = sc.put(&d_blk, p.blk_off.data(), (size_t)p.NS + 1))) return rc;
+  if ((rc = sc.put(&d_woff, p.w_off.data(), (size_t)B + 1))) return rc;
+  if ((rc = sc.put(&d_R, p.R.data(), (size_t)B))) return rc;
+  if ((rc = sc.put(&d_C, p.C.data(), (size_t)B))) return rc;
+  if ((rc = sc.put(&d_W, W, (size_t)p.w_off[B]))) return rc;
+  if ((rc = sc.put(&d_sig2, p.sig2.data(), (size_t)B))) return rc;
+  if ((rc = sc.put(&d_Pc, p.Pc.data(), (size_t)p.NS))) return rc;
+  if ((rc = sc.alloc(&d_pp, (size_t)K * NCH))) return rc;
+  if ((rc = sc.alloc(&d_pm, (size_t)K * NCH))) return rc;
+  if ((rc = sc.alloc(&d_wx, (size_t)K))) return rc;
+  if ((rc = sc.alloc(&d_mk, (size_t)K))) return rc;
+  if (U) {
+    if ((rc = sc.put(&d_U, U, (size_t)S * M))) return rc;
+  } else {
+    if ((rc = sc.alloc(&d_U, (size_t)S * M))) return rc;
+  }
+  long long* d_err = (long long*)(d_res + o_err);
+  HIP_TRY(hipEventRecord(sc.e0, sc.st));
+  if (seeds && (rc = se_draw(sc, seeds, S, M, d_U, d_err))) return rc;
+  ScSeArgs ea;
+  ea.U = d_U; ea.cls_c = d_c; ea.cls_tau = d_ctau; ea.tau2 = d_res + o_tau; ea.part_p = d_pp; ea.part_m = d_pm;
+  ea.S = S; ea.M = M; ea.K = K; ea.NCH = NCH; ea.SC = p.SC; ea.Cmax = Cmax; ea.t = 0;
+  ea.skip = (flags & SA_SCSE_NO_SKIP) ? 0 : 1;
+  ScSeRedArgs ra;
+  ra.part_p = d_pp; ra.part_m = d_pm; ra.cfg_off = d_cfg; ra.slot_off = d_slot; ra.blk_off = d_blk; ra.w_off = d_woff;
+  ra.R = d_R; ra.C = d_C; ra.W = d_W; ra.cls_w = d_w; ra.cls_mult = d_mult; ra.sig2 = d_sig2; ra.Pc = d_Pc;
+  ra.phi = d_res; ra.tau2 = d_res + o_tau; ra.x = d_res + o_x; ra.miss = (long long*)(d_res + o_miss);
+  ra.stop = (long long*)(d_res + o_stop); ra.ek = d_res + o_ek; ra.wx = d_wx; ra.mk = d_mk;
+  ra.NCH = NCH; ra.S = S; ra.T = T; ra.t = 0; ra.Rmax = Rmax; ra.Cmax = Cmax;
+  // every iteration queued on the one stream; the host waits once, below
+  for (int t = 0; t < T; ++t) {
+    ea.t = ra.t = t;
+    k_scse_expect<<<(unsigned)p.grid, kSeThreads, 0, sc.st>>>(ea);
+    k_scse_reduce<<<B, kSeRedThreads, 0, sc.st>>>(ra);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(sc.e1, sc.st));
+  HIP_TRY(hipMemcpyAsync(res.data(), d_res, n_res * sizeof(double), hipMemcpyDeviceToHost, sc.st));
+  HIP_TRY(hipStreamSynchronize(sc.st));
+  long long derr = 0;
+  std::memcpy(&derr, res.data() + o_err, sizeof(derr));
+  if (derr) return fail(SA_ERR_HIP, "sa_sc_se: a row's randn ran into the chunk cap");
+  std::memcpy(phi_out, res.data(), n_phi * sizeof(double));
+  for (int b = 0; b < B; ++b)  // the T rows the iterations read (row T is formed, never read)
+    std::memcpy(tau2_out + (size_t)b * T * Cmax, res.data() + o_tau + (size_t)b * (T + 1) * Cmax, (size_t)T * Cmax * sizeof(double));
+  std::memcpy(x_out, res.data() + o_x, n_x * sizeof(double));
+  std::memcpy(miss_out, res.data() + o_miss, n_x * sizeof(int64_t));
+  for (int b = 0; b < B; ++b) {
+    long long s = 0;
+    std::memcpy(&s, res.data() + o_stop + b, sizeof(s));
+    stop_out[b] = (int)s;
+  }
+  if (sec_out) {
+    const double* ek = res.data() + o_ek;
+    for (size_t i = 0; i < (size_t)B * L; ++i) sec_out[i] = ek[p.sec_cls[i]];
   }
   if (ms_out) {
     float ms = -1.f;

@@ -103,6 +103,14 @@ class CoupledOperator:
         """Device milliseconds of the last amp_batch's iterations (events)."""
         return float(self._lib.sa_sc_event_ms(self._sc))
 
+    def state_evolution(self, Pl, sigma, T, **kw):
+        """Coupled state evolution of this design (its own W, M and n): what
+        amp_batch's φ trace and error rate are predicted to be, without a
+        codeword.  -> se.SCSEResult; kw goes to se.sc_state_evolution."""
+        from .se import sc_state_evolution
+        kw.setdefault("device", self.device)
+        return sc_state_evolution(Pl, self.M, self.n, self.W, sigma, T, **kw)
+
     def mc(self, idx, noise, Pl, T, early_stop=True):
         """Encode (y = A β(idx) + noise), decode, decide and count bit errors on
         the device in one call: idx (B, L) int32, noise (B, n) or None ->

@@ -18,6 +18,11 @@ random numbers): a call is deterministic, and two allocations are compared on
 the same noise, so their difference has far less variance than either value.
 Fresh draws per iteration are not offered.  With ``draws="device"`` row s is
 ``RandomState(seed + s).randn(M)``, drawn on the device.
+
+Spatially coupled SPARCs (``sc.py``) have the same
+recursion with one effective-noise level per row block (phi_r) and per column
+block (tau_c^2) of the base matrix W: ``sc_state_evolution`` (sa_sc_se), on the
+same rows, and ``sc_search`` over (omega, Lambda) as ``pa_search`` is over (a, f).
 """
 from __future__ import annotations
 
@@ -28,7 +33,8 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["SEResult", "state_evolution", "se_draws", "PASearch", "pa_search"]
+__all__ = ["SEResult", "state_evolution", "se_draws", "PASearch", "pa_search",
+           "SCSEResult", "sc_state_evolution", "SCSearch", "sc_search"]
 
 
 @dataclass
@@ -150,3 +156,167 @@ def pa_search(L, M, n, P, sigma, a_values, f_values, T, C=None, **kw) -> PASearc
     i, j = np.unravel_index(int(np.argmax(xf)), shape)
     return PASearch(a_values=a_values, f_values=f_values, x=xf, ser=sf, iters=iters,
                     best=(float(a_values[i]), float(f_values[j])), result=r)
+
+
+@dataclass
+class SCSEResult:
+    """Coupled SE of one configuration: phi (T+1, R), tau2 (T, C), x (T, C), ser
+    (T, C) = the missed (section, sample) pairs of column block c / ((L / C) S),
+    ser_all (T,) = all missed pairs / (L S), miss (T, C) the raw counts, stop the
+    predicted stop index (the first t >= 1 at which every phi_r^t has the bits of
+    phi_r^{t-1}, the decoder's stopping rule; T: none), sections (L,) = E_l of
+    the last iteration, ms the device time of the draw and the iterations.
+
+    Of a batch: phi, tau2, x, ser and miss are lists of B such arrays, each of
+    its configuration's own R and C (nothing padded); ser_all (B, T), stop (B,),
+    sections (B, L); ``config(b)`` is configuration b's own SCSEResult."""
+    phi: object
+    tau2: object
+    x: object
+    ser: object
+    ser_all: np.ndarray
+    miss: object
+    stop: object
+    sections: np.ndarray
+    ms: float
+
+    def config(self, b) -> "SCSEResult":
+        if not isinstance(self.phi, list):
+            raise ValueError("not a batch")
+        return SCSEResult(phi=self.phi[b], tau2=self.tau2[b], x=self.x[b], ser=self.ser[b], ser_all=self.ser_all[b],
+                          miss=self.miss[b], stop=int(self.stop[b]), sections=self.sections[b], ms=self.ms)
+
+
+def _per_config(v, B, what, dtype):
+    a = np.asarray(v, dtype=dtype)
+    if a.ndim == 0:
+        a = np.full(B, a[()], dtype=dtype)
+    if a.shape != (B,):
+        raise ValueError(f"{what} must be a scalar or one value per configuration")
+    return np.ascontiguousarray(a)
+
+
+def sc_state_evolution(Pl, M, n, W, sigma, T, samples=1024, seed=0, draws="device", device=None, skip=True) -> SCSEResult:
+    """Coupled SE of one configuration (Pl 1-D, W an R x C base matrix) or of a
+    batch (Pl (B, L); W a list of B base matrices, or one for all; n and sigma
+    scalars or one value per configuration), all on the same Gaussian rows.
+
+    draws as in state_evolution.  skip=False recomputes the column blocks whose
+    tau_c^2 did not change from one iteration to the next (the same bits)."""
+    lib = _lib.load()
+    if not hasattr(lib, "sa_sc_se"):
+        raise _lib.SparcAmpError(_lib.SA_ERR_UNSUPPORTED, "this build of the library has no sa_sc_se")
+    Pl = _lib.as_f64(Pl)
+    one = Pl.ndim == 1
+    if Pl.ndim not in (1, 2):
+        raise ValueError("Pl must be 1-D or (B, L)")
+    Pl2 = np.ascontiguousarray(Pl.reshape(1, -1) if one else Pl)
+    B, L = Pl2.shape
+    if isinstance(W, np.ndarray) and W.ndim == 2 or one:
+        Ws = [_lib.as_f64(W)] * B
+    else:
+        Ws = [_lib.as_f64(w) for w in W]
+    if len(Ws) != B or any(w.ndim != 2 or w.size == 0 for w in Ws):
+        raise ValueError("W must be a 2-d base matrix (R x C), or one per configuration")
+    ns = _per_config(n, B, "n", np.int32)
+    sig = _per_config(sigma, B, "sigma", np.float64)
+    Rs = np.array([w.shape[0] for w in Ws], dtype=np.int32)
+    Cs = np.array([w.shape[1] for w in Ws], dtype=np.int32)
+    Wcat = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in Ws]))
+    if isinstance(draws, str):
+        if draws != "device":
+            raise ValueError('draws must be "device" or an (S, M) array')
+        S = int(samples)
+        seeds = _seeds(int(seed) + np.arange(max(S, 0), dtype=np.int64))
+        p_seeds, p_U = seeds.ctypes.data_as(ct.POINTER(ct.c_uint32)), None
+    else:
+        U = _lib.as_f64(draws)
+        if U.ndim != 2 or U.shape[1] != int(M):
+            raise ValueError("draws must be an (S, M) array")
+        S = U.shape[0]
+        p_seeds, p_U = None, _lib.dptr(U)
+    T = int(T)
+    Tn = max(T, 0)
+    Rmax, Cmax = int(Rs.max()), int(Cs.max())
+    phi = np.zeros((B, Tn + 1, Rmax))
+    tau2 = np.zeros((B, Tn, Cmax))
+    x = np.zeros((B, Tn, Cmax))
+    miss = np.zeros((B, Tn, Cmax), dtype=np.int64)
+    stop = np.zeros(B, dtype=np.int32)
+    sec = np.zeros((B, L))
+    ms = ct.c_double(0.0)
+    ip = ct.POINTER(ct.c_int)
+    _lib.check(lib.sa_sc_se(_device(device), B, L, int(M), ns.ctypes.data_as(ip), Rs.ctypes.data_as(ip),
+                            Cs.ctypes.data_as(ip), _lib.dptr(Wcat), _lib.dptr(Pl2), _lib.dptr(sig), T, S, p_seeds, p_U,
+                            Rmax, Cmax, 0 if skip else _lib.SA_SCSE_NO_SKIP, _lib.dptr(phi), _lib.dptr(tau2), _lib.dptr(x),
+                            miss.ctypes.data_as(ct.POINTER(ct.c_int64)), stop.ctypes.data_as(ip), _lib.dptr(sec),
+                            ct.cast(ct.pointer(ms), ct.POINTER(ct.c_double))))
+    phis = [phi[b, :, :Rs[b]].copy() for b in range(B)]
+    tau2s = [tau2[b, :, :Cs[b]].copy() for b in range(B)]
+    xs = [x[b, :, :Cs[b]].copy() for b in range(B)]
+    misses = [miss[b, :, :Cs[b]].copy() for b in range(B)]
+    sers = [misses[b] / float((L // Cs[b]) * S) for b in range(B)]
+    ser_all = miss.sum(axis=2) / float(L * S)
+    r = SCSEResult(phi=phis, tau2=tau2s, x=xs, ser=sers, ser_all=ser_all, miss=misses, stop=stop.astype(np.int64),
+                   sections=sec, ms=float(ms.value))
+    return r.config(0) if one else r
+
+
+@dataclass
+class SCSearch:
+    """sc_search's grids over (omega_values, Lambda_values): ``n`` the code
+    length each pair ran at, ``rate`` = L log2(M) / n, the final ``ser`` (all
+    sections), the predicted ``stop`` index, ``iters`` = the number of
+    iterations after which ser first had its final value, and ``best`` = the
+    (omega, Lambda) of the lowest final ser, then the smallest stop index, then
+    the first in row-major order; ``result`` is the batch's SCSEResult,
+    configuration i * len(Lambda_values) + j for (omega_values[i], Lambda_values[j])."""
+    omega_values: np.ndarray
+    Lambda_values: np.ndarray
+    n: np.ndarray
+    rate: np.ndarray
+    ser: np.ndarray
+    stop: np.ndarray
+    iters: np.ndarray
+    best: tuple
+    result: SCSEResult
+
+
+def sc_search(L, M, n, P, sigma, omega_values, Lambda_values, T, **kw) -> SCSearch:
+    """Coupled SE of every ``base_matrix(omega, Lambda)`` on the grid with the
+    flat allocation P / L, as one batch on the same Gaussian rows.  A pair runs
+    at the code length R ceil(n / R), R = Lambda + omega - 1: the smallest
+    multiple of R not below n, so that no pair runs above the asked rate.  A
+    pair whose Lambda does not divide L or whose R is above SA_SC_MAX_BLOCKS
+    raises ValueError.  kw goes to sc_state_evolution (samples, seed, draws,
+    device, skip)."""
+    from .sc import base_matrix
+    omega_values = np.atleast_1d(np.asarray(omega_values, dtype=np.int64))
+    Lambda_values = np.atleast_1d(np.asarray(Lambda_values, dtype=np.int64))
+    L, n = int(L), int(n)
+    Ws, ns = [], []
+    for om in omega_values:
+        for lam in Lambda_values:
+            om, lam = int(om), int(lam)
+            if om < 1 or lam < 1:
+                raise ValueError(f"(omega, Lambda) = ({om}, {lam}): both must be at least 1")
+            R = lam + om - 1
+            if L % lam != 0:
+                raise ValueError(f"(omega, Lambda) = ({om}, {lam}): Lambda does not divide L = {L}")
+            if R > _lib.SA_SC_MAX_BLOCKS:
+                raise ValueError(f"(omega, Lambda) = ({om}, {lam}): R = {R} row blocks, above SA_SC_MAX_BLOCKS = "
+                                 f"{_lib.SA_SC_MAX_BLOCKS}")
+            Ws.append(base_matrix(om, lam))
+            ns.append(R * -(-n // R))
+    Pl = np.full((len(Ws), L), float(P) / L)
+    r = sc_state_evolution(Pl, M, ns, Ws, sigma, T, **kw)
+    shape = (len(omega_values), len(Lambda_values))
+    sf = r.ser_all[:, -1].reshape(shape)
+    stop = np.asarray(r.stop).reshape(shape)
+    iters = ((r.ser_all == r.ser_all[:, -1:]).argmax(axis=1) + 1).reshape(shape)
+    order = sorted(range(len(Ws)), key=lambda q: (sf.reshape(-1)[q], stop.reshape(-1)[q], q))
+    i, j = np.unravel_index(order[0], shape)
+    n_grid = np.array(ns, dtype=np.int64).reshape(shape)
+    return SCSearch(omega_values=omega_values, Lambda_values=Lambda_values, n=n_grid,
+                    rate=L * np.log2(M) / n_grid, ser=sf, stop=stop, iters=iters,
+                    best=(int(omega_values[i]), int(Lambda_values[j])), result=r)
