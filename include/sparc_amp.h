@@ -501,7 +501,28 @@ int sa_se_draws(int device, int S, int M, const uint32_t* seeds, double* U_out);
  * indices into iters_out [B] and each rep's bit errors (popcounts of
  * decision ^ index summed over its sections, as sa_mc_run counts them) into
  * errs_out [B]; any output may be NULL; ms_out: the device time of encoder,
- * decode and decisions (events), or NULL. */
+ * decode and decisions (events), or NULL.
+ *
+ * sa_sc_amp_ex / sa_sc_mc_ex (since SA_VERSION 0.5):
+ * the same calls with an opt-in tolerance stop and frozen column blocks.
+ * stop_tol, freeze_tol >= 0 are taken in the context's precision; per codeword
+ * taul_c is the tau_c^2 at which block c's beta was last computed.
+ *   stop (index t) if t > 0 and |phi_r - phi_r^(t-1)| <= stop_tol * phi_r^(t-1)
+ *     for every r (stop_tol = 0: bit equality, the rule above;
+ *     SA_FLAG_NO_EARLY_STOP still disables it);
+ *   tau_c^2 = R / sum_r W[r, c] / phi_r; block c is live at t if t = 0, or
+ *     freeze_tol == 0 (off), or |tau_c^2 - taul_c| > freeze_tol * taul_c; for
+ *     live blocks taul_c = tau_c^2;
+ *   u and beta are computed for live blocks only: a frozen block's beta, psi_c
+ *     and A beta stay as its last live iteration left them; the psi, gamma and
+ *     z steps are unchanged.  A frozen block is live again by the same test
+ *     whenever its tau_c^2 has drifted: nothing is sticky.
+ * live_out [B][T][C] bytes (may be NULL): 1 where block c was live in
+ * iteration t, rows from a codeword's stop index on zero.  With both
+ * tolerances 0 the calls are sa_sc_amp / sa_sc_mc, bit for bit, and launch the
+ * same kernels (live_out is then 1 in front of the stop index).
+ *   SA_ERR_ARG: a negative, NaN or infinite stop_tol or freeze_tol (named in
+ *   sa_last_error); no output is written on a refusal. */
 enum { SA_SC_MAX_BLOCKS = 64 };
 typedef struct sa_sc sa_sc;
 int sa_sc_create(sa_ctx* parent, int R, int C, const double* W, sa_sc** out);
@@ -513,6 +534,12 @@ int sa_sc_amp(sa_sc* sc, int B, const double* y, const double* Pl, int T, double
 double sa_sc_event_ms(sa_sc* sc);
 int sa_sc_mc(sa_sc* sc, int B, const int32_t* idx, const double* noise, const double* Pl, int T,
              int flags, int32_t* dec_out, int32_t* iters_out, int32_t* errs_out, double* ms_out);
+int sa_sc_amp_ex(sa_sc* sc, int B, const double* y, const double* Pl, int T, double stop_tol,
+                 double freeze_tol, double* beta_out, int* iters_out, double* phi_out,
+                 unsigned char* live_out, int flags);
+int sa_sc_mc_ex(sa_sc* sc, int B, const int32_t* idx, const double* noise, const double* Pl, int T,
+                double stop_tol, double freeze_tol, int flags, int32_t* dec_out, int32_t* iters_out,
+                int32_t* errs_out, unsigned char* live_out, double* ms_out);
 
 /* ---- coupled state evolution ----
  * The scalar recursion that predicts a coupled decode, iteration by

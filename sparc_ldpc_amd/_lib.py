@@ -76,7 +76,7 @@ EXPORTS = (
     "sa_draw_reps", "sa_mc_stage", "sa_mc_run", "sa_make_ordering", "sa_mc_draw", "sa_mc_fetch_draws",
     "sa_se", "sa_se_draws", "sa_encode_bits",
     "sa_sc_create", "sa_sc_destroy", "sa_sc_Ab", "sa_sc_Az", "sa_sc_amp", "sa_sc_event_ms", "sa_sc_mc",
-    "sa_sc_se",
+    "sa_sc_amp_ex", "sa_sc_mc_ex", "sa_sc_se",
 )
 
 _P = ct.c_void_p
@@ -146,6 +146,10 @@ _SIG = {
     "sa_sc_event_ms": (ct.c_double, [_P]),
     "sa_sc_mc": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D, _D, _I, _I, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32),
                       ct.POINTER(ct.c_int32), _D]),
+    "sa_sc_amp_ex": (_I, [_P, _I, _D, _D, _I, ct.c_double, ct.c_double, _D, ct.POINTER(ct.c_int), _D,
+                          ct.POINTER(ct.c_ubyte), _I]),
+    "sa_sc_mc_ex": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D, _D, _I, ct.c_double, ct.c_double, _I, ct.POINTER(ct.c_int32),
+                         ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32), ct.POINTER(ct.c_ubyte), _D]),
     "sa_sc_se": (_I, [_I, _I, _I, _I, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), _D, _D, _D, _I, _I,
                       ct.POINTER(ct.c_uint32), _D, _I, _I, _I, _D, _D, _D, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int),
                       _D, _D]),

@@ -35,6 +35,16 @@
 //     padded groups' Ab table with fwd_entry on a drawn ordering: exit status
 //     1 with the first violation on stderr.  W entries are read by strtod
 //     ("nan", "inf" included).
+//   sa_host_check scwave L M n prec R C B T stop_tol freeze_tol want_live W[0,0] ... W[R-1,C-1]
+//     the plan of a coupled decode with a tolerance stop and frozen column
+//     blocks (sa_sc.h: sc_wave_plan) as one JSON object: whether k_scsec's wave
+//     form runs and which instance ("k_scsec<f32, 8>" / "k_scsec_wave<f32, 8>"),
+//     the tolerances as the kernel gets them (17 significant digits), whether
+//     the table loads wait for the liveness test, the grid, the LDS bytes and
+//     the bytes of the taul buffer and of the live trace; {"error", "message"}
+//     for a layout or a tolerance that is refused.  Runs the layout's and the
+//     wave form's invariants (sc_check_layout, sc_check_wave): exit status 1
+//     with the first violation on stderr.  Reals are read by strtod.
 //   sa_host_check scse B L M T S  then per configuration  n R C sigma W[0,0] ... W[R-1,C-1] Pl[0] ... Pl[L-1]
 //     the plan of a coupled state-evolution batch (sa_scse.h: scse_plan) as one
 //     JSON object: the per-configuration offsets (tau slots, row blocks, W,
@@ -65,6 +75,7 @@ static int usage() {
                        "       sa_host_check tables L M n prec plan\n"
                        "       sa_host_check packed L M n prec plan\n"
                        "       sa_host_check sc L M n prec R C W...\n"
+                       "       sa_host_check scwave L M n prec R C B T stop_tol freeze_tol want_live W...\n"
                        "       sa_host_check scse B L M T S {n R C sigma W... Pl...}...\n");
   return 2;
 }
@@ -463,6 +474,32 @@ static int cmd_sc(int L, int M, int n, int prec, int R, int C, const std::vector
   return 0;
 }
 
+// The plan of a coupled decode with tolerances (sa_sc.h: sc_wave_plan) and the wave form's invariants
+static int cmd_scwave(int L, int M, int n, int prec, int R, int C, int B, int T, double stop_tol, double freeze_tol,
+                      bool want_live, const std::vector<double>& W) {
+  ScLayout s;
+  ScWavePlan p;
+  std::string err;
+  int rc = sc_layout(s, L, M, n, prec, R, C, W.data(), err);
+  if (!rc) rc = sc_wave_plan(p, s, B, T, stop_tol, freeze_tol, want_live, err);
+  if (rc) {
+    std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+    return 0;
+  }
+  std::string bad = sc_check_layout(s);
+  CHECK(bad.empty(), "%s", bad.c_str());
+  bad = sc_check_wave(s, B, T);
+  CHECK(bad.empty(), "%s", bad.c_str());
+  CHECK(p.wave || (p.taul_bytes == 0 && p.live_bytes == 0 && !p.late_loads), "a decode without tolerances has extra workspace");
+  std::printf("{\"wave\": %d, \"instance\": \"%s<%s, %d>\", \"E\": %d, \"stop_tol\": %.17g, \"freeze_tol\": %.17g, "
+              "\"late_loads\": %d, \"grid\": [%d, %d], \"block\": 256, \"sec_lds\": %zu, \"lds_limit\": %zu, "
+              "\"taul_bytes\": %zu, \"live_bytes\": %zu, \"R\": %d, \"C\": %d, \"G\": %d, \"gpc\": %d}\n",
+              p.wave ? 1 : 0, p.wave ? "k_scsec_wave" : "k_scsec", prec == SA_PREC_F64 ? "f64" : "f32", s.E, s.E, p.stop_tol,
+              p.freeze_tol, p.late_loads ? 1 : 0, s.G, B, s.sec_lds, kLdsBytes, p.taul_bytes, p.live_bytes, s.R, s.C, s.G,
+              s.gpc);
+  return 0;
+}
+
 // The plan of a coupled state-evolution batch (sa_scse.h) and its invariants
 template <typename T>
 static void print_list(const char* name, const std::vector<T>& v, const char* fmt, bool last = false) {
@@ -533,6 +570,17 @@ int main(int argc, char** argv) {
     W.push_back(0.0);
     Pl.push_back(0.0);
     return cmd_scse(B, L, v[2], v[3], v[4], n, R, C, sigma, W, Pl);
+  }
+  if (!std::strcmp(argv[1], "scwave")) {
+    if (argc < 13) return usage();
+    int v[8];
+    for (int i = 0; i < 8; ++i) v[i] = std::atoi(argv[2 + i]);
+    const double st = std::strtod(argv[10], nullptr), ft = std::strtod(argv[11], nullptr);
+    const bool want_live = std::atoi(argv[12]) != 0;
+    std::vector<double> W;
+    for (int i = 13; i < argc; ++i) W.push_back(std::strtod(argv[i], nullptr));
+    if (v[4] < 1 || v[5] < 1 || (long long)v[4] * v[5] != (long long)W.size()) return usage();
+    return cmd_scwave(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], st, ft, want_live, W);
   }
   if (!std::strcmp(argv[1], "sc")) {
     if (argc < 8) return usage();

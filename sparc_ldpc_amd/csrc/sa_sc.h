@@ -167,4 +167,75 @@ inline std::string sc_check_layout(const ScLayout& s) {
   return "";
 }
 
+// ---- the tolerance stop and the frozen column blocks ----
+// taul, tau_c^2 of block c's last live iteration: [B][2][C] reals indexed by the
+// parity of t.  In the launch of iteration t every group reads parity t - 1 and
+// the first group of a block writes parity t, so no workgroup reads a word
+// another workgroup of the same launch writes (section 13's launch rule).
+inline size_t sc_taul_index(const ScLayout& s, int b, int t, int c) { return ((size_t)b * 2 + (t & 1)) * s.C + c; }
+inline size_t sc_taul_bytes(const ScLayout& s, int B) { return (size_t)B * 2 * s.C * (s.prec == SA_PREC_F64 ? 8 : 4); }
+// the live trace, [B][T][C] bytes
+inline size_t sc_live_index(const ScLayout& s, int T, int b, int t, int c) { return ((size_t)b * T + t) * s.C + c; }
+inline size_t sc_live_bytes(const ScLayout& s, int B, int T) { return (size_t)B * (T > 1 ? T : 1) * s.C; }
+
+// What a decode with (stop_tol, freeze_tol) launches.  The tolerances are taken
+// in the working precision (a binary32 context rounds them): wave == false, both
+// 0 there, is the decode without tolerances, k_scsec's default instances and no
+// extra workspace; else the wave form runs, with the table loads behind the
+// liveness test (late_loads) where a block may be frozen.
+struct ScWavePlan {
+  bool wave = false, late_loads = false;
+  double stop_tol = 0, freeze_tol = 0;  // as the kernel gets them
+  size_t taul_bytes = 0, live_bytes = 0;
+};
+
+inline int sc_wave_plan(ScWavePlan& p, const ScLayout& s, int B, int T, double stop_tol, double freeze_tol, bool want_live,
+                        std::string& err) {
+  p = ScWavePlan();
+  if (!std::isfinite(stop_tol) || stop_tol < 0) { err = "stop_tol must be finite and non-negative"; return SA_ERR_ARG; }
+  if (!std::isfinite(freeze_tol) || freeze_tol < 0) { err = "freeze_tol must be finite and non-negative"; return SA_ERR_ARG; }
+  if (B < 1 || T < 0) { err = "B must be positive and T non-negative"; return SA_ERR_ARG; }
+  const bool f32 = s.prec != SA_PREC_F64;
+  p.stop_tol = f32 ? (double)(float)stop_tol : stop_tol;
+  p.freeze_tol = f32 ? (double)(float)freeze_tol : freeze_tol;
+  if (!std::isfinite(p.stop_tol)) { err = "stop_tol is past the working precision's range"; return SA_ERR_ARG; }
+  if (!std::isfinite(p.freeze_tol)) { err = "freeze_tol is past the working precision's range"; return SA_ERR_ARG; }
+  p.wave = p.stop_tol > 0 || p.freeze_tol > 0;
+  p.late_loads = p.freeze_tol > 0;
+  if (p.wave) {
+    p.taul_bytes = sc_taul_bytes(s, B);
+    p.live_bytes = want_live ? sc_live_bytes(s, B, T) : 0;
+  }
+  return SA_OK;
+}
+
+// What the wave form relies on: in every launch the taul words read (parity
+// t - 1) and written (parity t) are disjoint and inside the buffer, a block has
+// exactly one writing group (g % gpc == 0), and the live trace's bytes are each
+// written by one group and inside theirs.  Empty: holds.
+inline std::string sc_check_wave(const ScLayout& s, int B, int T) {
+  const size_t words = sc_taul_bytes(s, B) / (s.prec == SA_PREC_F64 ? 8 : 4), lb = sc_live_bytes(s, B, T);
+  std::vector<int> writers(s.C, 0);
+  for (int g = 0; g < s.G; ++g)
+    if (g % s.gpc == 0) ++writers[sc_group_block(s, g)];
+  for (int c = 0; c < s.C; ++c)
+    if (writers[c] != 1) return "block " + std::to_string(c) + " has " + std::to_string(writers[c]) + " writing groups";
+  std::vector<unsigned char> seen(lb, 0);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < T; ++t) {
+      for (int c = 0; c < s.C; ++c) {
+        const size_t wr = sc_taul_index(s, b, t, c), li = sc_live_index(s, T, b, t, c);
+        if (wr >= words) return "taul write out of range";
+        if (li >= lb || seen[li]++) return "live trace byte out of range or written twice";
+        if (t == 0) continue;
+        for (int c2 = 0; c2 < s.C; ++c2)
+          if (sc_taul_index(s, b, t - 1, c2) == wr || sc_taul_index(s, b, t - 1, c2) >= words)
+            return "taul: a word read and written in the launch of iteration " + std::to_string(t);
+      }
+      // another codeword's words are never this one's
+      if (b + 1 < B && sc_taul_index(s, b + 1, 0, 0) <= sc_taul_index(s, b, 1, s.C - 1)) return "taul: codewords overlap";
+    }
+  return "";
+}
+
 }  // namespace sa

@@ -33,6 +33,10 @@ struct sa_sc {
   double* d_noise = nullptr;
   double* d_stage = nullptr;
   size_t stage_cap = 0;
+  // the wave form's state (sa_sc_amp_ex / sa_sc_mc_ex with a tolerance above 0): allocated at its first use
+  void* d_taul = nullptr;            // [wBcap][2][C]
+  unsigned char* d_live = nullptr;   // [wBcap][wTcap][C]
+  int wBcap = 0, wTcap = 0;
 };
 
 namespace sa {
@@ -58,6 +62,17 @@ struct ScSecArgs {
   const int* __restrict__ done;      // [B] set by k_scrow in the launch after the stop
   int L, M, n, w, nhi, G, gpc, Lc, R, C, nr, zpb, NZ, T, t, mode, early_stop;
   real sqrt_n;
+  static constexpr bool wave = false;
+};
+
+// The wave form's arguments: the tolerance stop and the
+// frozen column blocks.  SC_AMP only.
+template <typename real>
+struct ScWaveArgs : ScSecArgs<real> {
+  real stop_tol, freeze_tol;       // in the working precision; freeze_tol == 0: every block live
+  real* __restrict__ taul;         // [B][2][C] tau_c^2 of block c's last live iteration, by the parity of t
+  unsigned char* __restrict__ live;  // [B][T][C] the live bits, or null
+  static constexpr bool wave = true;
 };
 
 template <typename real>
@@ -90,8 +105,20 @@ struct ScRowArgs {
 //    u = (beta + At^T v) c_l / tau_c^2 as in the uncoupled kernels;
 //  - T_l = H_M beta_l staged, the group's unweighted Ab partial of every row.
 // SC_AB: the partials of the beta given.  SC_AZ: out = At^T (z sqrt(W[r, cb])) / sqrt(n).
-template <typename real, int E>
-__global__ void __launch_bounds__(256) k_scsec(ScSecArgs<real> a) {
+//
+// The wave form (Args = ScWaveArgs, SC_AMP; section 13b) stops on
+// |phi_r - last| <= stop_tol * last for every r and, with freeze_tol > 0 at
+// t > 0, leaves a block whose tau_c^2 is within freeze_tol of taul_c (that of
+// its last live iteration) alone: its workgroups return behind the phi / tau
+// prologue, in front of the z staging, and beta, abp and bbp of the block stay
+// as its last live iteration wrote them (k_scrow re-reads them).  taul is read
+// at parity t - 1 by every group and written at parity t by the block's first
+// group, frozen or live, so no workgroup reads a word another one of the same
+// launch writes.  Where a block may be frozen the table loads (bucket table,
+// beta, c_l, the first Ab rows) are issued behind the test, not at entry.  The
+// test is uniform over the workgroup: every thread forms the same tau_c^2 bits.
+template <typename real, int E, typename Args = ScSecArgs<real>>
+__global__ void __launch_bounds__(256) k_scsec(Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int KH = E >= 16 ? 2 : 16;
   constexpr int NQ = (E + 3) / 4;
@@ -120,7 +147,13 @@ __global__ void __launch_bounds__(256) k_scsec(ScSecArgs<real> a) {
   const ushort4* fw = a.fwd + (size_t)g * n;
   constexpr int KR = 8;  // rows per thread whose Ab-table loads are in flight together
   ushort4 f[KR];
-  if (a.mode != SC_AZ) {  // the first rows' entries with the kernel's first loads (as k_sec)
+  bool late = false;  // wave form: the block may be frozen, so the table loads wait for the test
+  real tlp = 0;       // taul_c as the previous iteration left it
+  if constexpr (Args::wave) {
+    late = a.mode == SC_AMP && a.t > 0 && a.freeze_tol > (real)0;
+    if (late) tlp = a.taul[((size_t)b * 2 + ((a.t - 1) & 1)) * a.C + cb];
+  }
+  if (a.mode != SC_AZ && !(Args::wave && late)) {  // the first rows' entries with the kernel's first loads (as k_sec)
 #pragma unroll
     for (int u = 0; u < KR; ++u) {
       const int r = u * 256 + tid;
@@ -135,9 +168,19 @@ __global__ void __launch_bounds__(256) k_scsec(ScSecArgs<real> a) {
     // k_scrow wrote done[b] in a launch of its own)
     if (a.mode == SC_AMP && a.done[b]) return;
     ushort4 tb[KH][NQ];
-    load_buckets<E, KH>(il, 0, a.nhi, M, lane, tb);
-    if (a.mode == SC_AMP) load_section<real, E>(bl, bprev, lane, M);
-    const real cl = ld_vmem(a.c + l);
+    real cl;
+    if constexpr (!Args::wave) {
+      load_buckets<E, KH>(il, 0, a.nhi, M, lane, tb);
+      if (a.mode == SC_AMP) load_section<real, E>(bl, bprev, lane, M);
+      cl = ld_vmem(a.c + l);
+    } else {
+      cl = 0;
+      if (!late) {
+        load_buckets<E, KH>(il, 0, a.nhi, M, lane, tb);
+        load_section<real, E>(bl, bprev, lane, M);
+        cl = ld_vmem(a.c + l);
+      }
+    }
     real tau2 = 1;
     if (a.mode == SC_AMP) {
       // every z^2 partial and the previous phi in one memory round trip, through
@@ -151,7 +194,11 @@ __global__ void __launch_bounds__(256) k_scsec(ScSecArgs<real> a) {
         real s = 0;
         for (int i = lane; i < a.zpb; i += 64) s += zs[r * a.zpb + i];
         const real ph = wave_sum(s) / (real)a.nr;
-        if (a.t > 0) neq = neq || !(ph == trm[r]);
+        if constexpr (Args::wave) {
+          if (a.t > 0) neq = neq || !(fabs(ph - trm[r]) <= a.stop_tol * trm[r]);  // stop_tol = 0: bit equality
+        } else {
+          if (a.t > 0) neq = neq || !(ph == trm[r]);
+        }
         if (lane == 0) phis[r] = ph;
       }
       if (lane == 0) neqw[wv] = neq ? 1 : 0;
@@ -167,6 +214,24 @@ __global__ void __launch_bounds__(256) k_scsec(ScSecArgs<real> a) {
       real acc = 0;
       for (int r = 0; r < a.R; ++r) acc += trm[r];
       tau2 = (real)a.R / acc;
+      if constexpr (Args::wave) {
+        const bool live = !late || fabs(tau2 - tlp) > a.freeze_tol * tlp;
+        if (g % a.gpc == 0 && tid == 0) {
+          a.taul[((size_t)b * 2 + (a.t & 1)) * a.C + cb] = live ? tau2 : tlp;
+          if (a.live) a.live[((size_t)b * a.T + a.t) * a.C + cb] = live ? 1 : 0;
+        }
+        if (!live) return;  // frozen: uniform over the workgroup, no barrier waits on it
+        if (late) {
+#pragma unroll
+          for (int u = 0; u < KR; ++u) {
+            const int r = u * 256 + tid;
+            f[u] = fw[r < n ? r : 0];
+          }
+          load_buckets<E, KH>(il, 0, a.nhi, M, lane, tb);
+          load_section<real, E>(bl, bprev, lane, M);
+          cl = ld_vmem(a.c + l);
+        }
+      }
       if (tid < a.R) scl[tid] = a.sqW[tid * a.C + cb] * tau2 / phis[tid];
     } else {
       if (tid < a.R) scl[tid] = a.sqW[tid * a.C + cb];
@@ -458,6 +523,30 @@ static int sc_workspace(sa_sc* s, int B, int T) {
   return SA_OK;
 }
 
+static void sc_free_wave(sa_sc* s) {
+  dev_free(s->d_taul); dev_free(s->d_live);
+  s->d_taul = nullptr;
+  s->d_live = nullptr;
+  s->wBcap = s->wTcap = 0;
+}
+
+// the wave form's buffers for B codewords and T iterations (sa_sc.h: sc_wave_plan's bytes; grown, never shrunk)
+static int sc_wave_workspace(sa_sc* s, int B, int T) {
+  if (B <= s->wBcap && T <= s->wTcap) return SA_OK;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const int nB = std::max(B, s->wBcap), nT = std::max(std::max(T, s->wTcap), 1);
+  sc_free_wave(s);
+  int rc = sc_alloc(&s->d_taul, sc_taul_bytes(s->lay, nB));
+  if (!rc) rc = sc_alloc((void**)&s->d_live, sc_live_bytes(s->lay, nB, nT));
+  if (rc) {
+    sc_free_wave(s);
+    return rc;
+  }
+  s->wBcap = nB;
+  s->wTcap = nT;
+  return SA_OK;
+}
+
 template <typename real>
 static ScSecArgs<real> sc_sec_args(sa_sc* s, int mode, int T, int t, int es) {
   const ScLayout& y = s->lay;
@@ -503,6 +592,21 @@ static int sc_launch_sec(sa_sc* s, int B, const ScSecArgs<real>& a) {
   return SA_OK;
 }
 
+// the wave form's instances: the same grid, block and LDS image
+template <typename real>
+static int sc_launch_wave(sa_sc* s, int B, const ScWaveArgs<real>& a) {
+  const dim3 grid(s->lay.G, B);
+  const size_t lds = s->lay.sec_lds;
+  switch (s->lay.E) {
+#define SA_SC_SEC(EE) case EE: k_scsec<real, EE, ScWaveArgs<real>><<<grid, 256, lds, s->stream>>>(a); break;
+    SA_SC_SEC(1) SA_SC_SEC(2) SA_SC_SEC(4) SA_SC_SEC(8) SA_SC_SEC(16) SA_SC_SEC(32) SA_SC_SEC(64)
+#undef SA_SC_SEC
+    default: return fail(SA_ERR_UNSUPPORTED, "k_scsec: M");
+  }
+  HIP_TRY(hipGetLastError());
+  return SA_OK;
+}
+
 template <typename real>
 static int sc_launch_row(sa_sc* s, int B, const ScRowArgs<real>& a) {
   k_scrow<real><<<dim3(s->lay.NZ, B), 64, 0, s->stream>>>(a);
@@ -513,14 +617,28 @@ static int sc_launch_row(sa_sc* s, int B, const ScRowArgs<real>& a) {
 // The decode of the y staged in d_y: z = y, then T times (k_scsec, k_scrow),
 // launched eagerly on the context's stream with no host synchronisation
 // between them (why no graph).
+// wv.wave (sc_wave_plan): k_scsec's wave form with the plan's tolerances, the
+// live trace into d_live where wv.live_bytes asks for one (zeroed in front, as
+// the phi trace); else exactly the launches of a decode without tolerances.
 template <typename real>
-static int sc_decode(sa_sc* s, int B, int T, int es) {
+static int sc_decode(sa_sc* s, int B, int T, int es, const ScWavePlan& wv) {
   const ScLayout& y = s->lay;
   HIP_TRY(hipMemsetAsync(s->d_beta, 0, (size_t)B * y.L * y.M * sizeof(real), s->stream));
   HIP_TRY(hipMemsetAsync(s->d_phi, 0, (size_t)B * std::max(T, 1) * y.R * sizeof(real), s->stream));
+  if (wv.wave && wv.live_bytes) HIP_TRY(hipMemsetAsync(s->d_live, 0, wv.live_bytes, s->stream));
   if (int rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_INIT, T, 0))) return rc;
   for (int t = 0; t < T; ++t) {
-    if (int rc = sc_launch_sec<real>(s, B, sc_sec_args<real>(s, SC_AMP, T, t, es))) return rc;
+    if (wv.wave) {
+      ScWaveArgs<real> a;
+      static_cast<ScSecArgs<real>&>(a) = sc_sec_args<real>(s, SC_AMP, T, t, es);
+      a.stop_tol = (real)wv.stop_tol;
+      a.freeze_tol = (real)wv.freeze_tol;
+      a.taul = (real*)s->d_taul;
+      a.live = wv.live_bytes ? s->d_live : nullptr;
+      if (int rc = sc_launch_wave<real>(s, B, a)) return rc;
+    } else {
+      if (int rc = sc_launch_sec<real>(s, B, sc_sec_args<real>(s, SC_AMP, T, t, es))) return rc;
+    }
     if (int rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_AMP, T, t))) return rc;
   }
   return SA_OK;
@@ -543,6 +661,10 @@ static hipError_t sc_lds_attrs_t() {
 #define SA_A(F) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)F, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
   SA_A((k_scsec<real, 1>)) SA_A((k_scsec<real, 2>)) SA_A((k_scsec<real, 4>)) SA_A((k_scsec<real, 8>))
   SA_A((k_scsec<real, 16>)) SA_A((k_scsec<real, 32>)) SA_A((k_scsec<real, 64>))
+  SA_A((k_scsec<real, 1, ScWaveArgs<real>>)) SA_A((k_scsec<real, 2, ScWaveArgs<real>>))
+  SA_A((k_scsec<real, 4, ScWaveArgs<real>>)) SA_A((k_scsec<real, 8, ScWaveArgs<real>>))
+  SA_A((k_scsec<real, 16, ScWaveArgs<real>>)) SA_A((k_scsec<real, 32, ScWaveArgs<real>>))
+  SA_A((k_scsec<real, 64, ScWaveArgs<real>>))
 #undef SA_A
   return e;
 }
@@ -642,6 +764,7 @@ void sa_sc_destroy(sa_sc* s) {
   (void)hipSetDevice(s->parent->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   sc_free_workspace(s);
+  sc_free_wave(s);
   dev_free(s->d_W); dev_free(s->d_sqW); dev_free(s->d_fwd); dev_free(s->d_c); dev_free(s->d_Pc);
   dev_free(s->d_stage);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -681,25 +804,38 @@ int sa_sc_Az(sa_sc* s, int B, const double* z, double* out) {
   return SA_OK;
 }
 
-int sa_sc_amp(sa_sc* s, int B, const double* yv, const double* Pl, int T, double* beta_out, int* iters_out,
-              double* phi_out, int flags) {
-  if (int rc = sc_check(s, B, "sa_sc_amp")) return rc;
-  if (!yv) return fail(SA_ERR_ARG, "sa_sc_amp: y is NULL");
-  if (!Pl) return fail(SA_ERR_ARG, "sa_sc_amp: Pl is NULL");
-  if (!beta_out) return fail(SA_ERR_ARG, "sa_sc_amp: beta_out is NULL");
-  if (T < 0) return fail(SA_ERR_ARG, "sa_sc_amp: T must be non-negative");
-  if (flags & ~SA_FLAG_NO_EARLY_STOP) return fail(SA_ERR_ARG, "sa_sc_amp: unknown flags");
-  HIP_TRY(hipSetDevice(s->parent->device));
+// The live trace of a decode without tolerances: every block of every iteration in front of the stop index
+static void sc_live_all(const ScLayout& y, int B, int T, const int* iters, unsigned char* live_out) {
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < T; ++t)
+      std::memset(live_out + sc_live_index(y, T, b, t, 0), t < iters[b] ? 1 : 0, (size_t)y.C);
+}
+
+static int sc_amp_impl(const char* what, sa_sc* s, int B, const double* yv, const double* Pl, int T, double stop_tol,
+                       double freeze_tol, double* beta_out, int* iters_out, double* phi_out, unsigned char* live_out,
+                       int flags) {
+  const std::string w = std::string(what) + ": ";
+  if (int rc = sc_check(s, B, what)) return rc;
+  if (!yv) return fail(SA_ERR_ARG, w + "y is NULL");
+  if (!Pl) return fail(SA_ERR_ARG, w + "Pl is NULL");
+  if (!beta_out) return fail(SA_ERR_ARG, w + "beta_out is NULL");
+  if (T < 0) return fail(SA_ERR_ARG, w + "T must be non-negative");
+  if (flags & ~SA_FLAG_NO_EARLY_STOP) return fail(SA_ERR_ARG, w + "unknown flags");
   const ScLayout& y = s->lay;
+  ScWavePlan wv;
+  std::string err;
+  if (int rc = sc_wave_plan(wv, y, B, T, stop_tol, freeze_tol, live_out != nullptr, err)) return fail(rc, w + err);
+  HIP_TRY(hipSetDevice(s->parent->device));
   for (int l = 0; l < y.L; ++l)
-    if (!(Pl[l] >= 0) || !std::isfinite(Pl[l])) return fail(SA_ERR_ARG, "sa_sc_amp: Pl must be non-negative and finite");
+    if (!(Pl[l] >= 0) || !std::isfinite(Pl[l])) return fail(SA_ERR_ARG, w + "Pl must be non-negative and finite");
   int rc = sc_workspace(s, B, T);
   if (rc) return rc;
+  if (wv.wave && (rc = sc_wave_workspace(s, B, T))) return rc;
   if ((rc = sc_set_power(s, Pl))) return rc;
   if ((rc = sc_upload(s, s->d_y, yv, (size_t)B * y.n))) return rc;
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
   HIP_TRY(hipEventRecord(s->ev0, s->stream));
-  rc = y.prec == SA_PREC_F64 ? sc_decode<double>(s, B, T, es) : sc_decode<float>(s, B, T, es);
+  rc = y.prec == SA_PREC_F64 ? sc_decode<double>(s, B, T, es, wv) : sc_decode<float>(s, B, T, es, wv);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(s->ev1, s->stream));
   s->timed = true;
@@ -709,13 +845,37 @@ int sa_sc_amp(sa_sc* s, int B, const double* yv, const double* Pl, int T, double
     if ((rc = sc_download(s, phi_out, s->d_phi, (size_t)B * T * y.R))) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
-  if (iters_out) {
-    HIP_TRY(hipMemcpyAsync(iters_out, s->d_iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  std::vector<int> own;
+  int* iters = iters_out;
+  if (!iters && live_out && !wv.wave) {
+    own.resize(B);
+    iters = own.data();
+  }
+  if (iters) {
+    HIP_TRY(hipMemcpyAsync(iters, s->d_iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     for (int b = 0; b < B; ++b)
-      if (iters_out[b] < 0) iters_out[b] = T;
+      if (iters[b] < 0) iters[b] = T;
+  }
+  if (live_out && T > 0) {
+    if (wv.wave) {
+      HIP_TRY(hipMemcpyAsync(live_out, s->d_live, (size_t)B * T * y.C, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipStreamSynchronize(s->stream));
+    } else {
+      sc_live_all(y, B, T, iters, live_out);
+    }
   }
   return SA_OK;
+}
+
+int sa_sc_amp(sa_sc* s, int B, const double* yv, const double* Pl, int T, double* beta_out, int* iters_out,
+              double* phi_out, int flags) {
+  return sc_amp_impl("sa_sc_amp", s, B, yv, Pl, T, 0.0, 0.0, beta_out, iters_out, phi_out, nullptr, flags);
+}
+
+int sa_sc_amp_ex(sa_sc* s, int B, const double* yv, const double* Pl, int T, double stop_tol, double freeze_tol,
+                 double* beta_out, int* iters_out, double* phi_out, unsigned char* live_out, int flags) {
+  return sc_amp_impl("sa_sc_amp_ex", s, B, yv, Pl, T, stop_tol, freeze_tol, beta_out, iters_out, phi_out, live_out, flags);
 }
 
 double sa_sc_event_ms(sa_sc* s) {
@@ -725,21 +885,27 @@ double sa_sc_event_ms(sa_sc* s) {
   return (double)ms;
 }
 
-int sa_sc_mc(sa_sc* s, int B, const int32_t* idx, const double* noise, const double* Pl, int T, int flags,
-             int32_t* dec_out, int32_t* iters_out, int32_t* errs_out, double* ms_out) {
-  if (int rc = sc_check(s, B, "sa_sc_mc")) return rc;
-  if (!idx) return fail(SA_ERR_ARG, "sa_sc_mc: idx is NULL");
-  if (!Pl) return fail(SA_ERR_ARG, "sa_sc_mc: Pl is NULL");
-  if (T < 0) return fail(SA_ERR_ARG, "sa_sc_mc: T must be non-negative");
-  if (flags & ~SA_FLAG_NO_EARLY_STOP) return fail(SA_ERR_ARG, "sa_sc_mc: unknown flags");
+static int sc_mc_impl(const char* what, sa_sc* s, int B, const int32_t* idx, const double* noise, const double* Pl, int T,
+                      double stop_tol, double freeze_tol, int flags, int32_t* dec_out, int32_t* iters_out,
+                      int32_t* errs_out, unsigned char* live_out, double* ms_out) {
+  const std::string w = std::string(what) + ": ";
+  if (int rc = sc_check(s, B, what)) return rc;
+  if (!idx) return fail(SA_ERR_ARG, w + "idx is NULL");
+  if (!Pl) return fail(SA_ERR_ARG, w + "Pl is NULL");
+  if (T < 0) return fail(SA_ERR_ARG, w + "T must be non-negative");
+  if (flags & ~SA_FLAG_NO_EARLY_STOP) return fail(SA_ERR_ARG, w + "unknown flags");
   const ScLayout& y = s->lay;
+  ScWavePlan wv;
+  std::string err;
+  if (int rc = sc_wave_plan(wv, y, B, T, stop_tol, freeze_tol, live_out != nullptr, err)) return fail(rc, w + err);
   for (size_t k = 0; k < (size_t)B * y.L; ++k)
-    if (idx[k] < 0 || idx[k] >= y.M) return fail(SA_ERR_ARG, "sa_sc_mc: idx outside [0, M)");
+    if (idx[k] < 0 || idx[k] >= y.M) return fail(SA_ERR_ARG, w + "idx outside [0, M)");
   for (int l = 0; l < y.L; ++l)
-    if (!(Pl[l] >= 0) || !std::isfinite(Pl[l])) return fail(SA_ERR_ARG, "sa_sc_mc: Pl must be non-negative and finite");
+    if (!(Pl[l] >= 0) || !std::isfinite(Pl[l])) return fail(SA_ERR_ARG, w + "Pl must be non-negative and finite");
   HIP_TRY(hipSetDevice(s->parent->device));
   int rc = sc_workspace(s, B, T);
   if (rc) return rc;
+  if (wv.wave && (rc = sc_wave_workspace(s, B, T))) return rc;
   if ((rc = sc_set_power(s, Pl))) return rc;
   const size_t z = sc_rsz(s), LM = (size_t)y.L * y.M;
   HIP_TRY(hipMemcpyAsync(s->d_idx, idx, (size_t)B * y.L * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
@@ -755,11 +921,11 @@ int sa_sc_mc(sa_sc* s, int B, const int32_t* idx, const double* noise, const dou
   if (y.prec == SA_PREC_F64) {
     k_sc_onehot<double><<<nb, 256, 0, s->stream>>>((double*)s->d_beta, s->d_idx, (const double*)s->d_c, y.L, y.M, B);
     rc = sc_ab<double>(s, B, noise ? s->d_noise : nullptr, s->d_y);
-    if (!rc) rc = sc_decode<double>(s, B, T, es);
+    if (!rc) rc = sc_decode<double>(s, B, T, es, wv);
   } else {
     k_sc_onehot<float><<<nb, 256, 0, s->stream>>>((float*)s->d_beta, s->d_idx, (const float*)s->d_c, y.L, y.M, B);
     rc = sc_ab<float>(s, B, noise ? s->d_noise : nullptr, s->d_y);
-    if (!rc) rc = sc_decode<float>(s, B, T, es);
+    if (!rc) rc = sc_decode<float>(s, B, T, es, wv);
   }
   if (rc) return rc;
 #define SA_SC_DEC(EE)                                                                                                  \
@@ -778,13 +944,35 @@ int sa_sc_mc(sa_sc* s, int B, const int32_t* idx, const double* noise, const dou
   if (dec_out) HIP_TRY(hipMemcpyAsync(dec_out, s->d_dec, (size_t)B * y.L * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
   if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out, s->d_iters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
   if (errs_out) HIP_TRY(hipMemcpyAsync(errs_out, s->d_errs, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  std::vector<int32_t> own;
+  if (live_out && T > 0) {
+    if (wv.wave) {
+      HIP_TRY(hipMemcpyAsync(live_out, s->d_live, (size_t)B * T * y.C, hipMemcpyDeviceToHost, s->stream));
+    } else if (!iters_out) {
+      own.resize(B);
+      HIP_TRY(hipMemcpyAsync(own.data(), s->d_iters, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    }
+  }
   HIP_TRY(hipStreamSynchronize(s->stream));
+  if (live_out && T > 0 && !wv.wave) sc_live_all(y, B, T, iters_out ? iters_out : own.data(), live_out);
   if (ms_out) {
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     *ms_out = (double)ms;
   }
   return SA_OK;
+}
+
+int sa_sc_mc(sa_sc* s, int B, const int32_t* idx, const double* noise, const double* Pl, int T, int flags,
+             int32_t* dec_out, int32_t* iters_out, int32_t* errs_out, double* ms_out) {
+  return sc_mc_impl("sa_sc_mc", s, B, idx, noise, Pl, T, 0.0, 0.0, flags, dec_out, iters_out, errs_out, nullptr, ms_out);
+}
+
+int sa_sc_mc_ex(sa_sc* s, int B, const int32_t* idx, const double* noise, const double* Pl, int T, double stop_tol,
+                double freeze_tol, int flags, int32_t* dec_out, int32_t* iters_out, int32_t* errs_out,
+                unsigned char* live_out, double* ms_out) {
+  return sc_mc_impl("sa_sc_mc_ex", s, B, idx, noise, Pl, T, stop_tol, freeze_tol, flags, dec_out, iters_out, errs_out,
+                    live_out, ms_out);
 }
 
 }  // extern "C"

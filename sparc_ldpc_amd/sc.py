@@ -6,6 +6,13 @@ The coupled design over the sub-sampled Hadamard operator Ã of
 for an R x C base matrix W: row i lies in row block ``i // (n // R)``, section l
 in column block ``l // (L // C)``.  AMP tracks one effective-noise level per
 row block (φ_r) and per column block (τ_c²); at ``W = [[1]]`` it is ``amp()``.
+
+Opt-in (``sa_sc_amp_ex`` / ``sa_sc_mc_ex``): ``stop_tol``
+stops a codeword once every φ_r is within ``stop_tol`` (relative) of the
+previous iteration's, ``freeze_tol`` leaves a column block alone while its τ_c²
+is within ``freeze_tol`` of the value its β was last computed at, and
+``return_live`` adds the (B, T, C) uint8 trace of the blocks that were computed.
+At the defaults (0, 0, False) every call is what it was.
 """
 from __future__ import annotations
 
@@ -80,10 +87,22 @@ class CoupledOperator:
         check(self._lib.sa_sc_Az(self._sc, B, dptr(z), dptr(out)))
         return out
 
-    def amp_batch(self, y, Pl, T, early_stop=True):
+    def _ex(self, name, stop_tol, freeze_tol, return_live):
+        """The `_ex` entry point where a tolerance or the live trace asks for it, else None."""
+        stop_tol, freeze_tol = float(stop_tol), float(freeze_tol)
+        if stop_tol == 0.0 and freeze_tol == 0.0 and not return_live:
+            return None
+        if not hasattr(self._lib, name):
+            raise _lib.SparcAmpError(_lib.SA_ERR_UNSUPPORTED, f"this build of the library has no {name}: stop_tol, "
+                                     "freeze_tol and return_live need it")
+        return getattr(self._lib, name)
+
+    def amp_batch(self, y, Pl, T, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
         """Decode B codewords: y (B, n) -> (β̂ (B, L*M), iters (B,), φ (B, T, R)).
         iters[b] is the stop index (every φ_r bit-equal to the previous
-        iteration's), or T; φ rows from the stop index on are zero."""
+        iteration's, or within stop_tol of it), or T; φ rows from the stop
+        index on are zero.  return_live appends live (B, T, C) uint8: 1 where
+        block c was computed in iteration t (0 from the stop index on)."""
         y = as_f64(y)
         B = y.shape[0] if y.ndim == 2 else 1
         assert y.size == B * self.n, "y must hold B x n values"
@@ -95,9 +114,15 @@ class CoupledOperator:
         iters = np.empty(B, dtype=np.int32)
         phi = np.zeros((B, T, self.R))
         flags = 0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP
-        check(self._lib.sa_sc_amp(self._sc, B, dptr(y), dptr(Pl), T, dptr(out),
-                                  iters.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int)), dptr(phi), flags))
-        return out, iters, phi
+        ip = iters.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int))
+        ex = self._ex("sa_sc_amp_ex", stop_tol, freeze_tol, return_live)
+        if ex is None:
+            check(self._lib.sa_sc_amp(self._sc, B, dptr(y), dptr(Pl), T, dptr(out), ip, dptr(phi), flags))
+            return out, iters, phi
+        live = np.zeros((B, T, self.C), dtype=np.uint8) if return_live else None
+        lp = live.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_ubyte)) if return_live else None
+        check(ex(self._sc, B, dptr(y), dptr(Pl), T, float(stop_tol), float(freeze_tol), dptr(out), ip, dptr(phi), lp, flags))
+        return (out, iters, phi, live) if return_live else (out, iters, phi)
 
     def last_amp_ms(self) -> float:
         """Device milliseconds of the last amp_batch's iterations (events)."""
@@ -111,10 +136,11 @@ class CoupledOperator:
         kw.setdefault("device", self.device)
         return sc_state_evolution(Pl, self.M, self.n, self.W, sigma, T, **kw)
 
-    def mc(self, idx, noise, Pl, T, early_stop=True):
+    def mc(self, idx, noise, Pl, T, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
         """Encode (y = A β(idx) + noise), decode, decide and count bit errors on
         the device in one call: idx (B, L) int32, noise (B, n) or None ->
-        (decisions (B, L), stop indices (B,), bit errors (B,), device ms)."""
+        (decisions (B, L), stop indices (B,), bit errors (B,), device ms), and
+        with return_live the live trace (B, T, C) uint8 behind them."""
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         B = idx.shape[0]
         assert idx.shape == (B, self.L), "idx must be (B, L)"
@@ -131,9 +157,16 @@ class CoupledOperator:
         errs = np.empty(B, dtype=np.int32)
         ms = np.zeros(1)
         flags = 0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP
-        check(self._lib.sa_sc_mc(self._sc, B, idx.ctypes.data_as(i32), nz, dptr(Pl), int(T), flags,
-                                 dec.ctypes.data_as(i32), its.ctypes.data_as(i32), errs.ctypes.data_as(i32), dptr(ms)))
-        return dec, its, errs, float(ms[0])
+        ex = self._ex("sa_sc_mc_ex", stop_tol, freeze_tol, return_live)
+        if ex is None:
+            check(self._lib.sa_sc_mc(self._sc, B, idx.ctypes.data_as(i32), nz, dptr(Pl), int(T), flags,
+                                     dec.ctypes.data_as(i32), its.ctypes.data_as(i32), errs.ctypes.data_as(i32), dptr(ms)))
+            return dec, its, errs, float(ms[0])
+        live = np.zeros((B, int(T), self.C), dtype=np.uint8) if return_live else None
+        lp = live.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_ubyte)) if return_live else None
+        check(ex(self._sc, B, idx.ctypes.data_as(i32), nz, dptr(Pl), int(T), float(stop_tol), float(freeze_tol), flags,
+                 dec.ctypes.data_as(i32), its.ctypes.data_as(i32), errs.ctypes.data_as(i32), lp, dptr(ms)))
+        return (dec, its, errs, float(ms[0]), live) if return_live else (dec, its, errs, float(ms[0]))
 
 
 class ScAbOp:
@@ -176,27 +209,32 @@ def _coupled(Ab) -> CoupledOperator:
     return op
 
 
-def amp_sc_batch(y, Pl, T, Ab, *, early_stop=True):
-    """Coupled AMP of B codewords y (B, n): -> (β̂ (B, L*M), iters (B,), φ (B, T, R))."""
-    return _coupled(Ab).amp_batch(y, Pl, T, early_stop=early_stop)
+def amp_sc_batch(y, Pl, T, Ab, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
+    """Coupled AMP of B codewords y (B, n): -> (β̂ (B, L*M), iters (B,), φ (B, T, R)),
+    with return_live also live (B, T, C) uint8 (CoupledOperator.amp_batch)."""
+    return _coupled(Ab).amp_batch(y, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol,
+                                  return_live=return_live)
 
 
-def amp_sc(y, Pl, L, M, T, Ab, Az, *, early_stop=True):
-    """Coupled AMP of one codeword, in amp()'s argument order: -> β̂, (L*M, 1)."""
+def amp_sc(y, Pl, L, M, T, Ab, Az, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
+    """Coupled AMP of one codeword, in amp()'s argument order: -> β̂, (L*M, 1);
+    with return_live -> (β̂, live (T, C) uint8)."""
     op = _coupled(Ab)
     assert (op.L, op.M) == (int(L), int(M)), "L, M must be the operator's"
     if getattr(Az, "op", None) is not op:
         raise TypeError("Ab and Az must come from one sc_transforms call")
     y = as_f64(y).reshape(1, -1)
-    beta, _, _ = op.amp_batch(y, Pl, T, early_stop=early_stop)
-    return beta.reshape(-1, 1)
+    res = op.amp_batch(y, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol, return_live=return_live)
+    beta = res[0].reshape(-1, 1)
+    return (beta, res[3][0]) if return_live else beta
 
 
-def mc_decode_sc(Ab, Pl, sigma, T, seeds, batch=256, early_stop=True):
+def mc_decode_sc(Ab, Pl, sigma, T, seeds, batch=256, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
     """Monte-Carlo reps on the coupled design, drawn as harness._draw_reps draws
     them (RandomState(s).randint(0, M, L), then .randn(n) * σ), encoded, decoded
     and decided on the device in batches of `batch`:
-    -> (bit errors (R,), stop indices (R,), decisions (R, L)), all int32."""
+    -> (bit errors (R,), stop indices (R,), decisions (R, L)), all int32, and
+    with return_live the live trace (R, T, C) uint8 behind them."""
     from .harness import draw_reps
     op = _coupled(Ab)
     seeds = seed_array(seeds)
@@ -204,8 +242,13 @@ def mc_decode_sc(Ab, Pl, sigma, T, seeds, batch=256, early_stop=True):
     errs = np.empty(nrep, dtype=np.int32)
     its = np.empty(nrep, dtype=np.int32)
     dec = np.empty((nrep, op.L), dtype=np.int32)
+    live = np.zeros((nrep, int(T), op.C), dtype=np.uint8) if return_live else None
     for i0 in range(0, nrep, int(batch)):
         sl = slice(i0, min(nrep, i0 + int(batch)))
         idx, noise = draw_reps(seeds[sl], op.L, op.M, op.n, float(sigma))
-        dec[sl], its[sl], errs[sl], _ = op.mc(idx, noise, Pl, T, early_stop=early_stop)
-    return errs, its, dec
+        res = op.mc(idx, noise, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol,
+                    return_live=return_live)
+        dec[sl], its[sl], errs[sl] = res[0], res[1], res[2]
+        if return_live:
+            live[sl] = res[4]
+    return (errs, its, dec, live) if return_live else (errs, its, dec)
