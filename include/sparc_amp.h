@@ -541,6 +541,67 @@ int sa_sc_mc_ex(sa_sc* sc, int B, const int32_t* idx, const double* noise, const
                 double stop_tol, double freeze_tol, int flags, int32_t* dec_out, int32_t* iters_out,
                 int32_t* errs_out, unsigned char* live_out, double* ms_out);
 
+/* ---- coupled AMP from a beta_0, the staged coupled context and the SPARC <->
+ * LDPC glue on it (since SA_VERSION 0.6) ----
+ * The beta_0 start is the uncoupled decoder's (sparc_ldpc.py:192-200) on the
+ * coupled design: beta = beta_0, z = y - A beta_0, no Onsager term at the
+ * start, then the loop above unchanged (iteration 0's u reads beta = beta_0).
+ * It composes with stop_tol / freeze_tol; at t = 0 every block is live.
+ *
+ * sa_sc_amp_start is sa_sc_amp_ex with a start beta0 [B][L*M]; with beta0 NULL
+ * it is that call, launch for launch.
+ *
+ * The staged calls keep y, beta and the traces on the device between calls, as
+ * sa_reserve ... sa_fetch do for a sa_ctx:
+ *   sa_sc_reserve       sizes the workspace for B codewords and T iterations
+ *                       (growing it drops whatever was staged);
+ *   sa_sc_stage_power   stages the section powers Pl [L];
+ *   sa_sc_stage         stages y [B][n] and, where given, beta0 [B][L*M];
+ *   sa_sc_encode        stages y = A beta(idx) + noise (idx [B][L] in [0, M),
+ *                       noise [B][n] binary64 or NULL; sa_sc_mc's encoder);
+ *   sa_sc_encode_bits   the same from device pointers: message bits [B][L log2 M]
+ *                       bytes, MSB first per section, and noise [B][n] binary64
+ *                       or NULL; idx_out [B][L] (host, may be NULL) receives the indices;
+ *   sa_sc_run           queues a decode of the staged y on the context's stream
+ *                       and returns; flags SA_FLAG_NO_EARLY_STOP, SA_FLAG_BETA0
+ *                       (start from the beta on the device: staged, written by
+ *                       the glue below, or left by the last run); the staged y
+ *                       survives any number of runs;
+ *   sa_sc_wait          waits for the stream;
+ *   sa_sc_fetch         beta_out [B][L*M], iters_out [B], phi_out [B][T][R] of
+ *                       the last run (each may be NULL);
+ *   sa_sc_decide        each section's argmax (first index on ties), idx_out [B][L].
+ * The glue works on the context's beta with the kernels, semantics and flags
+ * (SA_PTR_DEVICE included) of its sa_ctx namesakes: sa_sc_llr is sa_llr_ex,
+ * sa_sc_soft_beta0 is sa_soft_beta0, sa_sc_hard_indices is sa_hard_cancel
+ * without a dst, sa_sc_stage_onehot is sa_stage_onehot.  The protected
+ * sections are [l0, l0 + ns); any l0 >= 0 is legal, inside a column block too.
+ * The one-call entry points above overwrite the workspace: after one of them
+ * nothing is staged.
+ *   SA_ERR_ARG (sa_last_error names it; no output and nothing staged is
+ *   touched): B outside [1, 65535] or above the reserved batch, T above the
+ *   reserved T, a run with nothing staged ("nothing staged"), with B above the
+ *   staged batch or without staged powers, SA_FLAG_BETA0 or sa_sc_llr with no
+ *   beta on the device, l0 < 0, ns < 1, l0 + ns > L, an index outside [0, M),
+ *   a NULL argument that must not be, unknown flags or LLR mode, a bad
+ *   tolerance or clip.  SA_ERR_UNSUPPORTED: M < 2. */
+int sa_sc_amp_start(sa_sc* sc, int B, const double* y, const double* Pl, int T, const double* beta0,
+                    double stop_tol, double freeze_tol, double* beta_out, int* iters_out,
+                    double* phi_out, unsigned char* live_out, int flags);
+int sa_sc_reserve(sa_sc* sc, int B, int T);
+int sa_sc_stage_power(sa_sc* sc, const double* Pl);
+int sa_sc_stage(sa_sc* sc, int B, const double* y, const double* beta0);
+int sa_sc_encode(sa_sc* sc, int B, const int32_t* idx, const double* noise);
+int sa_sc_encode_bits(sa_sc* sc, int B, const uint8_t* d_bits, const double* d_noise, int32_t* idx_out);
+int sa_sc_run(sa_sc* sc, int B, int T, double stop_tol, double freeze_tol, int flags);
+int sa_sc_wait(sa_sc* sc);
+int sa_sc_fetch(sa_sc* sc, int B, double* beta_out, int* iters_out, double* phi_out);
+int sa_sc_decide(sa_sc* sc, int B, int32_t* idx_out);
+int sa_sc_llr(sa_sc* sc, int B, int l0, int ns, double* llr, int flags, int mode, double clip);
+int sa_sc_soft_beta0(sa_sc* sc, int B, int l0, int ns, const double* app, int flags);
+int sa_sc_hard_indices(sa_sc* sc, int B, int l0, int ns, const double* app, int flags, int32_t* idx_out);
+int sa_sc_stage_onehot(sa_sc* sc, int B, const int32_t* idx);
+
 /* ---- coupled state evolution ----
  * The scalar recursion that predicts a coupled decode, iteration by
  * iteration, without a codeword: the per-row-block phi_r, the

@@ -29,5 +29,7 @@ from .se import (state_evolution, se_draws, pa_search, SEResult, PASearch, sc_st
                  SCSearch)
 from . import sc
 from .sc import base_matrix, sc_transforms, amp_sc, amp_sc_batch, mc_decode_sc, CoupledOperator
+from . import sc_joint
+from .sc_joint import CoupledJointDecoder
 
 __version__ = "0.1.0"

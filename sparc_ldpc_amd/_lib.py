@@ -77,6 +77,9 @@ EXPORTS = (
     "sa_se", "sa_se_draws", "sa_encode_bits",
     "sa_sc_create", "sa_sc_destroy", "sa_sc_Ab", "sa_sc_Az", "sa_sc_amp", "sa_sc_event_ms", "sa_sc_mc",
     "sa_sc_amp_ex", "sa_sc_mc_ex", "sa_sc_se",
+    "sa_sc_amp_start", "sa_sc_reserve", "sa_sc_stage_power", "sa_sc_stage", "sa_sc_encode", "sa_sc_encode_bits",
+    "sa_sc_run", "sa_sc_wait", "sa_sc_fetch", "sa_sc_decide", "sa_sc_llr", "sa_sc_soft_beta0", "sa_sc_hard_indices",
+    "sa_sc_stage_onehot",
 )
 
 _P = ct.c_void_p
@@ -150,6 +153,21 @@ _SIG = {
                           ct.POINTER(ct.c_ubyte), _I]),
     "sa_sc_mc_ex": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D, _D, _I, ct.c_double, ct.c_double, _I, ct.POINTER(ct.c_int32),
                          ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32), ct.POINTER(ct.c_ubyte), _D]),
+    "sa_sc_amp_start": (_I, [_P, _I, _D, _D, _I, _D, ct.c_double, ct.c_double, _D, ct.POINTER(ct.c_int), _D,
+                             ct.POINTER(ct.c_ubyte), _I]),
+    "sa_sc_reserve": (_I, [_P, _I, _I]),
+    "sa_sc_stage_power": (_I, [_P, _D]),
+    "sa_sc_stage": (_I, [_P, _I, _D, _D]),
+    "sa_sc_encode": (_I, [_P, _I, ct.POINTER(ct.c_int32), _D]),
+    "sa_sc_encode_bits": (_I, [_P, _I, _P, _P, ct.POINTER(ct.c_int32)]),
+    "sa_sc_run": (_I, [_P, _I, _I, ct.c_double, ct.c_double, _I]),
+    "sa_sc_wait": (_I, [_P]),
+    "sa_sc_fetch": (_I, [_P, _I, _D, ct.POINTER(ct.c_int), _D]),
+    "sa_sc_decide": (_I, [_P, _I, ct.POINTER(ct.c_int32)]),
+    "sa_sc_llr": (_I, [_P, _I, _I, _I, _P, _I, _I, ct.c_double]),
+    "sa_sc_soft_beta0": (_I, [_P, _I, _I, _I, _P, _I]),
+    "sa_sc_hard_indices": (_I, [_P, _I, _I, _I, _P, _I, ct.POINTER(ct.c_int32)]),
+    "sa_sc_stage_onehot": (_I, [_P, _I, ct.POINTER(ct.c_int32)]),
     "sa_sc_se": (_I, [_I, _I, _I, _I, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), _D, _D, _D, _I, _I,
                       ct.POINTER(ct.c_uint32), _D, _I, _I, _I, _D, _D, _D, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int),
                       _D, _D]),

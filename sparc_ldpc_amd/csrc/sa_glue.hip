@@ -1,6 +1,7 @@
 // sa_glue.hip — SPARC <-> LDPC glue of the joint decoder on the device
 // (encoding, LLRs, bp2sp, hard / threshold decisions, cancellation).
 #include "sa_host.h"
+#include "sa_sc_ctx.h"
 
 // ---------------------------------------------------------------------------
 // SPARC <-> LDPC glue of the joint decoder (sparc_ldpc.py:257-314, 359-712)
@@ -320,6 +321,37 @@ int encode_staged(sa_ctx* c, int B, const double* d_noise, int32_t* idx_out) {
   return y_mark(c);
 }
 
+int launch_bits_idx(hipStream_t stream, const uint8_t* d_bits, int lgM, int L, int B, int32_t* d_idx) {
+  const size_t tot = (size_t)B * L;
+  k_bits_idx<<<(unsigned)((tot + 255) / 256), 256, 0, stream>>>(d_bits, lgM, L, B, d_idx);
+  HIP_TRY(hipGetLastError());
+  return SA_OK;
+}
+
+// ---- the same glue on a coupled context's d_beta ----
+// What every coupled glue call checks first: the section range (sa_sc.h:
+// sc_glue_check), then the batch and the staged state (sc_stage_rule).
+int sc_glue_begin(sa_sc* s, int call, int B, int l0, int ns, const char* who) {
+  if (!s) return fail(SA_ERR_ARG, std::string(who) + ": null context");
+  std::string err;
+  if (int rc = sc_glue_check(s->lay, l0, ns, err)) return fail(rc, std::string(who) + ": " + err);
+  if (int rc = sc_stage_rule(s->st, call, B, s->Bcap, err)) return fail(rc, std::string(who) + ": " + err);
+  HIP_TRY(hipSetDevice(s->parent->device));
+  return SA_OK;
+}
+
+// dev_in for a coupled context: the device pointer itself, or the host values copied into the staging buffer
+int sc_dev_in(sa_sc* s, const double* p, size_t count, int flags, const double** out) {
+  if (flags & SA_PTR_DEVICE) {
+    *out = p;
+    return SA_OK;
+  }
+  if (int rc = sc_stage(s, count)) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_stage, p, count * 8, hipMemcpyHostToDevice, s->stream));
+  *out = s->d_stage;
+  return SA_OK;
+}
+
 }  // namespace sa
 
 using namespace sa;
@@ -520,5 +552,93 @@ int sa_cancel_scaled(sa_ctx* c, int B, const int32_t* idx, double scale, sa_ctx*
 }
 
 int sa_cancel(sa_ctx* c, int B, const int32_t* idx, sa_ctx* dst) { return sa_cancel_scaled(c, B, idx, 1.0, dst); }
+
+int sa_sc_llr(sa_sc* s, int B, int l0, int ns, double* llr, int flags, int mode, double clip) {
+  if (s && !llr) return fail(SA_ERR_ARG, "sa_sc_llr: llr is NULL");
+  if (mode != SA_LLR_REFERENCE && mode != SA_LLR_TWO_SIDED) return fail(SA_ERR_ARG, "sa_sc_llr: unknown mode");
+  if (!(clip >= 0.0)) return fail(SA_ERR_ARG, "sa_sc_llr: clip must be positive, or 0 / +inf for none");
+  int rc = sc_glue_begin(s, SC_CALL_LLR, B, l0, ns, "sa_sc_llr");
+  if (rc) return rc;
+  const double lim = std::isinf(clip) ? 0.0 : clip;  // 0: no clip
+  const ScLayout& y = s->lay;
+  const int lgM = ilog2(y.M);
+  const size_t cnt = (size_t)B * ns * lgM;
+  double* d_out = llr;
+  if (!(flags & SA_PTR_DEVICE)) {
+    if ((rc = sc_stage(s, cnt))) return rc;
+    d_out = s->d_stage;
+  }
+  const size_t lds = (size_t)y.M * sizeof(double);
+  if (mode == SA_LLR_TWO_SIDED) {
+    if (y.prec == SA_PREC_F64)
+      k_llr2<double><<<B * ns, 64, lds, s->stream>>>((const double*)s->d_beta, s->d_cd, y.L, y.M, lgM, l0, ns, lim, d_out);
+    else
+      k_llr2<float><<<B * ns, 64, lds, s->stream>>>((const float*)s->d_beta, s->d_cd, y.L, y.M, lgM, l0, ns, lim, d_out);
+  } else {
+    if (y.prec == SA_PREC_F64)
+      k_llr<double><<<B * ns, 64, lds, s->stream>>>((const double*)s->d_beta, s->d_cd, y.L, y.M, lgM, l0, ns, d_out);
+    else
+      k_llr<float><<<B * ns, 64, lds, s->stream>>>((const float*)s->d_beta, s->d_cd, y.L, y.M, lgM, l0, ns, d_out);
+    if (lim > 0.0) k_llr_clip<<<grid_of(cnt), 256, 0, s->stream>>>(d_out, cnt, lim);
+  }
+  HIP_TRY(hipGetLastError());
+  if (!(flags & SA_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(llr, d_out, cnt * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
+}
+
+int sa_sc_soft_beta0(sa_sc* s, int B, int l0, int ns, const double* app, int flags) {
+  if (s && !app) return fail(SA_ERR_ARG, "sa_sc_soft_beta0: app is NULL");
+  int rc = sc_glue_begin(s, SC_CALL_SOFT_BETA0, B, l0, ns, "sa_sc_soft_beta0");
+  if (rc) return rc;
+  const ScLayout& y = s->lay;
+  const int lgM = ilog2(y.M);
+  const double* d_app = nullptr;
+  if ((rc = sc_dev_in(s, app, (size_t)B * ns * lgM, flags, &d_app))) return rc;
+  const size_t tot = (size_t)B * y.L * y.M, lds = (size_t)y.M * sizeof(double);
+  if (y.prec == SA_PREC_F64) {
+    if (ns < y.L) k_rescale<double><<<grid_of(tot), 256, 0, s->stream>>>((double*)s->d_beta, s->d_cd, y.L, y.M, l0, ns, B);
+    k_soft_sec<double><<<B * ns, 64, lds, s->stream>>>(d_app, s->d_cd, y.L, y.M, lgM, l0, ns, (double*)s->d_beta);
+  } else {
+    if (ns < y.L) k_rescale<float><<<grid_of(tot), 256, 0, s->stream>>>((float*)s->d_beta, s->d_cd, y.L, y.M, l0, ns, B);
+    k_soft_sec<float><<<B * ns, 64, lds, s->stream>>>(d_app, s->d_cd, y.L, y.M, lgM, l0, ns, (float*)s->d_beta);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
+}
+
+int sa_sc_hard_indices(sa_sc* s, int B, int l0, int ns, const double* app, int flags, int32_t* idx_out) {
+  if (s && (!app || !idx_out)) return fail(SA_ERR_ARG, "sa_sc_hard_indices: null argument");
+  int rc = sc_glue_begin(s, SC_CALL_HARD, B, l0, ns, "sa_sc_hard_indices");
+  if (rc) return rc;
+  const int lgM = ilog2(s->lay.M);
+  const double* d_app = nullptr;
+  if ((rc = sc_dev_in(s, app, (size_t)B * ns * lgM, flags, &d_app))) return rc;
+  k_app_idx<<<(B * ns + 255) / 256, 256, 0, s->stream>>>(d_app, lgM, ns, B, s->d_idx);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(idx_out, s->d_idx, (size_t)B * ns * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
+}
+
+int sa_sc_stage_onehot(sa_sc* s, int B, const int32_t* idx) {
+  if (s && !idx) return fail(SA_ERR_ARG, "sa_sc_stage_onehot: idx is NULL");
+  if (s && B >= 1 && B <= s->Bcap)
+    for (size_t i = 0; i < (size_t)B * s->lay.L; ++i)
+      if (idx[i] < 0 || idx[i] >= s->lay.M) return fail(SA_ERR_ARG, "sa_sc_stage_onehot: index outside [0, M)");
+  int rc = sc_glue_begin(s, SC_CALL_ONEHOT, B, 0, s ? s->lay.L : 1, "sa_sc_stage_onehot");
+  if (rc) return rc;
+  const ScLayout& y = s->lay;
+  HIP_TRY(hipMemcpyAsync(s->d_idx, idx, (size_t)B * y.L * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  const size_t tot = (size_t)B * y.L * y.M;
+  if (y.prec == SA_PREC_F64)
+    k_onehot<double><<<grid_of(tot), 256, 0, s->stream>>>(s->d_idx, s->d_cd, y.L, y.M, B, 1.0, (double*)s->d_beta);
+  else
+    k_onehot<float><<<grid_of(tot), 256, 0, s->stream>>>(s->d_idx, s->d_cd, y.L, y.M, B, 1.0, (float*)s->d_beta);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
+}
 
 }  // extern "C"

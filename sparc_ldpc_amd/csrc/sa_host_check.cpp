@@ -36,6 +36,7 @@
 //     1 with the first violation on stderr.  W entries are read by strtod
 //     ("nan", "inf" included).
 //   sa_host_check scwave L M n prec R C B T stop_tol freeze_tol want_live W[0,0] ... W[R-1,C-1]
+//   sa_host_check scjoint L M n prec R C B T l0 ns beta0 stop_tol freeze_tol W[0,0] ... W[R-1,C-1] [call ...]
 //     the plan of a coupled decode with a tolerance stop and frozen column
 //     blocks (sa_sc.h: sc_wave_plan) as one JSON object: whether k_scsec's wave
 //     form runs and which instance ("k_scsec<f32, 8>" / "k_scsec_wave<f32, 8>"),
@@ -76,6 +77,7 @@ static int usage() {
                        "       sa_host_check packed L M n prec plan\n"
                        "       sa_host_check sc L M n prec R C W...\n"
                        "       sa_host_check scwave L M n prec R C B T stop_tol freeze_tol want_live W...\n"
+                       "       sa_host_check scjoint L M n prec R C B T l0 ns beta0 stop_tol freeze_tol W... [call ...]\n"
                        "       sa_host_check scse B L M T S {n R C sigma W... Pl...}...\n");
   return 2;
 }
@@ -500,6 +502,73 @@ static int cmd_scwave(int L, int M, int n, int prec, int R, int C, int B, int T,
   return 0;
 }
 
+// The staged coupled context and the glue on it (sa_sc.h): the section-range check, the
+// launch list of a decode with or without a beta_0, the extra workspace, and the state rule walked over `calls`
+// (reserve sizes the workspace to B; every other call is made with B codewords, `runbig` with B + 1)
+static int cmd_scjoint(int L, int M, int n, int prec, int R, int C, int B, int T, int l0, int ns, bool beta0,
+                       double stop_tol, double freeze_tol, const std::vector<double>& W,
+                       const std::vector<std::string>& calls) {
+  ScLayout s;
+  ScWavePlan p;
+  std::string err;
+  int rc = sc_layout(s, L, M, n, prec, R, C, W.data(), err);
+  if (!rc) rc = sc_glue_check(s, l0, ns, err);
+  if (!rc) rc = sc_wave_plan(p, s, B, T, stop_tol, freeze_tol, false, err);
+  if (rc) {
+    std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+    return 0;
+  }
+  const std::string bad = sc_check_layout(s);
+  CHECK(bad.empty(), "%s", bad.c_str());
+  const std::vector<ScLaunch> with = sc_decode_launches(T, beta0, p), plain = sc_decode_launches(T, false, p);
+  // a beta_0 changes the head of the list alone: the loop's launches are the decode's without one
+  CHECK(with.size() == plain.size() + (beta0 ? 1 : 0), "launch list lengths %zu, %zu", with.size(), plain.size());
+  for (int k = 1; k <= 2 * T; ++k) {
+    const ScLaunch &a = with[with.size() - k], &b = plain[plain.size() - k];
+    CHECK(a.step == b.step && a.t == b.t, "loop launch %d from the end differs", k);
+  }
+  // k_scstart's grid is k_scrow's: every row of every z^2 partial inside [0, n)
+  for (int q = 0; q < s.NZ; ++q)
+    CHECK(sc_zpart_row0(s, q) >= 0 && sc_zpart_row0(s, q) + sc_zpart_rows(s, q) <= s.n, "z^2 partial %d out of range", q);
+  std::printf("{\"l0\": %d, \"ns\": %d, \"lgM\": %d, \"rescale\": %d, \"l0_block\": %d, \"l0_on_block_edge\": %d, "
+              "\"cd_bytes\": %zu, \"glue_stage_bytes\": %zu, \"start_grid\": [%d, %d], \"start_block\": 64, "
+              "\"n_r\": %d, \"L_c\": %d, \"zpb\": %d, \"own_fwd\": %d, \"launches\": [",
+              l0, ns, ilog2(M), ns < L ? 1 : 0, sc_col_block(s, l0), l0 % s.L_c == 0 ? 1 : 0, sc_cd_bytes(s),
+              sc_glue_stage_bytes(s, B, ns), s.NZ, B, s.n_r, s.L_c, s.zpb, s.own_fwd ? 1 : 0);
+  for (size_t k = 0; k < with.size(); ++k) std::printf("%s\"%s\"", k ? ", " : "", sc_step_name(with[k].step));
+  std::printf("], \"walk\": [");
+  static const struct { const char* name; int call; } kCalls[] = {
+      {"resize", SC_CALL_RESIZE}, {"onecall", SC_CALL_ONE_CALL}, {"power", SC_CALL_STAGE_POWER}, {"stage", SC_CALL_STAGE},
+      {"stage0", SC_CALL_STAGE_BETA0}, {"encode", SC_CALL_ENCODE}, {"run", SC_CALL_RUN}, {"run0", SC_CALL_RUN_BETA0},
+      {"fetch", SC_CALL_FETCH}, {"llr", SC_CALL_LLR}, {"hard", SC_CALL_HARD}, {"soft", SC_CALL_SOFT_BETA0},
+      {"onehot", SC_CALL_ONEHOT}, {"runbig", SC_CALL_RUN}};
+  ScStageState st;
+  int Bcap = 0;
+  for (size_t k = 0; k < calls.size(); ++k) {
+    int call = -1;
+    for (const auto& c : kCalls)
+      if (calls[k] == c.name) call = c.call;
+    std::string msg;
+    int r = SA_OK;
+    if (calls[k] == "reserve") {  // sc_workspace: grown, never shrunk; a reallocation drops the stage
+      if (B > Bcap) {
+        Bcap = B;
+        sc_stage_rule(st, SC_CALL_RESIZE, 0, 0, msg);
+      }
+    } else {
+      CHECK(call >= 0, "unknown call %s", calls[k].c_str());
+      const ScStageState before = st;
+      r = sc_stage_rule(st, call, calls[k] == "runbig" ? B + 1 : B, Bcap, msg);
+      CHECK(r == SA_OK || (st.power == before.power && st.y == before.y && st.beta == before.beta && st.B == before.B),
+            "a refused %s changed the state", calls[k].c_str());
+    }
+    std::printf("%s[\"%s\", %d, \"%s\", %d, %d, %d, %d]", k ? ", " : "", calls[k].c_str(), r, msg.c_str(), st.power ? 1 : 0,
+                st.y ? 1 : 0, st.beta ? 1 : 0, st.B);
+  }
+  std::printf("]}\n");
+  return 0;
+}
+
 // The plan of a coupled state-evolution batch (sa_scse.h) and its invariants
 template <typename T>
 static void print_list(const char* name, const std::vector<T>& v, const char* fmt, bool last = false) {
@@ -570,6 +639,18 @@ int main(int argc, char** argv) {
     W.push_back(0.0);
     Pl.push_back(0.0);
     return cmd_scse(B, L, v[2], v[3], v[4], n, R, C, sigma, W, Pl);
+  }
+  if (!std::strcmp(argv[1], "scjoint")) {
+    if (argc < 15) return usage();
+    int v[11];
+    for (int i = 0; i < 11; ++i) v[i] = std::atoi(argv[2 + i]);
+    const double st = std::strtod(argv[13], nullptr), ft = std::strtod(argv[14], nullptr);
+    if (v[4] < 1 || v[5] < 1 || 15 + (long long)v[4] * v[5] > argc) return usage();
+    const int nw = v[4] * v[5];
+    std::vector<double> W;
+    for (int i = 15; i < 15 + nw; ++i) W.push_back(std::strtod(argv[i], nullptr));
+    std::vector<std::string> calls(argv + 15 + nw, argv + argc);
+    return cmd_scjoint(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10] != 0, st, ft, W, calls);
   }
   if (!std::strcmp(argv[1], "scwave")) {
     if (argc < 13) return usage();

@@ -238,4 +238,140 @@ inline std::string sc_check_wave(const ScLayout& s, int B, int T) {
   return "";
 }
 
+// ---- the beta_0 start, the staged context and the glue on it ----
+// What a decode launches, in order.  Without a beta_0 it is the list the
+// decoder has always had; with one, beta stays as staged and A beta_0 (sc_ab:
+// k_scsec in SC_AB mode, k_scrow in SCR_ABOUT) and k_scstart (z = y - A beta_0,
+// its z^2 partials, iters = -1, done = 0) stand in for the SCR_INIT row launch.
+// sc_decode (sa_sc.hip) walks this list and launches nothing else.
+enum ScStep {
+  SCS_MEMSET_BETA, SCS_MEMSET_PHI, SCS_MEMSET_LIVE, SCS_ROW_INIT, SCS_SEC_AB, SCS_ROW_ABOUT, SCS_START, SCS_SEC_AMP,
+  SCS_SEC_WAVE, SCS_ROW_AMP
+};
+struct ScLaunch {
+  int step, t;
+};
+
+inline const char* sc_step_name(int step) {
+  switch (step) {
+    case SCS_MEMSET_BETA: return "memset beta";
+    case SCS_MEMSET_PHI: return "memset phi";
+    case SCS_MEMSET_LIVE: return "memset live";
+    case SCS_ROW_INIT: return "k_scrow SCR_INIT";
+    case SCS_SEC_AB: return "k_scsec SC_AB";
+    case SCS_ROW_ABOUT: return "k_scrow SCR_ABOUT";
+    case SCS_START: return "k_scstart";
+    case SCS_SEC_AMP: return "k_scsec SC_AMP";
+    case SCS_SEC_WAVE: return "k_scsec_wave SC_AMP";
+    case SCS_ROW_AMP: return "k_scrow SCR_AMP";
+  }
+  return "?";
+}
+
+inline std::vector<ScLaunch> sc_decode_launches(int T, bool beta0, const ScWavePlan& wv) {
+  std::vector<ScLaunch> v;
+  if (!beta0) v.push_back({SCS_MEMSET_BETA, 0});
+  v.push_back({SCS_MEMSET_PHI, 0});
+  if (wv.wave && wv.live_bytes) v.push_back({SCS_MEMSET_LIVE, 0});
+  if (beta0) {
+    v.push_back({SCS_SEC_AB, 0});
+    v.push_back({SCS_ROW_ABOUT, 0});
+    v.push_back({SCS_START, 0});
+  } else {
+    v.push_back({SCS_ROW_INIT, 0});
+  }
+  for (int t = 0; t < T; ++t) {
+    v.push_back({wv.wave ? SCS_SEC_WAVE : SCS_SEC_AMP, t});
+    v.push_back({SCS_ROW_AMP, t});
+  }
+  return v;
+}
+
+// The staged life cycle: what is on the device between calls.  power: c_l and
+// P_c of a sa_sc_stage_power (or of a one-call decode, which stages its own); y: a staged input
+// of B codewords in d_y; beta: a beta in d_beta a decode may start from (staged,
+// written by the glue, or left by the last run).
+struct ScStageState {
+  bool power = false, y = false, beta = false;
+  int B = 0;
+};
+
+enum ScCall {
+  SC_CALL_RESIZE,       // the workspace was reallocated: nothing staged survives
+  SC_CALL_ONE_CALL,     // sa_sc_amp*, sa_sc_mc*, sa_sc_Ab / Az: they overwrite the workspace
+  SC_CALL_STAGE_POWER,
+  SC_CALL_STAGE,        // y alone
+  SC_CALL_STAGE_BETA0,  // y and beta_0
+  SC_CALL_ENCODE,       // sa_sc_encode, sa_sc_encode_bits
+  SC_CALL_RUN,
+  SC_CALL_RUN_BETA0,    // SA_FLAG_BETA0
+  SC_CALL_FETCH,        // sa_sc_fetch, sa_sc_decide
+  SC_CALL_LLR,          // reads beta
+  SC_CALL_HARD,         // sa_sc_hard_indices: reads the app alone
+  SC_CALL_SOFT_BETA0,   // rewrites beta
+  SC_CALL_ONEHOT
+};
+
+// The argument and state checks of a staged call of B codewords on a context
+// whose workspace holds Bcap, and the state it leaves.  SA_ERR_ARG with err
+// naming the reason, state untouched; SA_OK and the new state otherwise.
+inline int sc_stage_rule(ScStageState& st, int call, int B, int Bcap, std::string& err) {
+  if (call == SC_CALL_RESIZE || call == SC_CALL_ONE_CALL) {
+    st.y = st.beta = false;
+    st.B = 0;
+    return SA_OK;
+  }
+  if (call == SC_CALL_STAGE_POWER) {
+    st.power = true;
+    return SA_OK;
+  }
+  if (B < 1 || B > 65535) { err = "B must be in [1, 65535]"; return SA_ERR_ARG; }
+  if (B > Bcap) { err = "batch larger than the reserved workspace (sa_sc_reserve)"; return SA_ERR_ARG; }
+  const bool needs_power = call != SC_CALL_STAGE && call != SC_CALL_STAGE_BETA0 && call != SC_CALL_FETCH;
+  if (needs_power && !st.power) { err = "power allocation not staged"; return SA_ERR_ARG; }
+  switch (call) {
+    case SC_CALL_STAGE:
+    case SC_CALL_STAGE_BETA0:
+    case SC_CALL_ENCODE:
+      st.y = true;
+      st.B = B;
+      st.beta = call == SC_CALL_STAGE_BETA0;
+      return SA_OK;
+    case SC_CALL_RUN:
+    case SC_CALL_RUN_BETA0:
+      if (!st.y) { err = "nothing staged"; return SA_ERR_ARG; }
+      if (B > st.B) { err = "B above the staged batch"; return SA_ERR_ARG; }
+      if (call == SC_CALL_RUN_BETA0 && !st.beta) { err = "SA_FLAG_BETA0: no beta staged"; return SA_ERR_ARG; }
+      st.beta = true;  // the estimate the run leaves
+      return SA_OK;
+    case SC_CALL_LLR:
+      if (!st.beta) { err = "no beta staged"; return SA_ERR_ARG; }
+      return SA_OK;
+    case SC_CALL_SOFT_BETA0:
+    case SC_CALL_ONEHOT:
+      st.beta = true;
+      return SA_OK;
+    default:
+      return SA_OK;
+  }
+}
+
+// The section range of a glue call: the LDPC code's sections [l0, l0 + ns).
+// Any l0 is legal, 0 (every section protected) and one inside a column block included.
+inline int sc_glue_check(const ScLayout& s, int l0, int ns, std::string& err) {
+  if (l0 < 0) { err = "l0 must be non-negative"; return SA_ERR_ARG; }
+  if (ns < 1) { err = "ns must be at least 1"; return SA_ERR_ARG; }
+  if ((long long)l0 + ns > s.L) { err = "section range outside [0, L)"; return SA_ERR_ARG; }
+  if (s.M < 2) { err = "M < 2 carries no bits"; return SA_ERR_UNSUPPORTED; }
+  return SA_OK;
+}
+
+// What the staged context and the glue hold beyond the decoder's workspace: c_l
+// in binary64 for the glue kernels, and the binary64 staging buffer of a glue
+// call that is handed host LLRs / a-posteriori values (none with SA_PTR_DEVICE).
+inline size_t sc_cd_bytes(const ScLayout& s) { return (size_t)s.L * sizeof(double); }
+inline size_t sc_glue_stage_bytes(const ScLayout& s, int B, int ns) {
+  return (size_t)B * ns * ilog2(s.M) * sizeof(double);
+}
+
 }  // namespace sa

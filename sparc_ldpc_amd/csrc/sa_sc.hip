@@ -12,32 +12,7 @@
 // gather (A^T) and to the groups' partials in the row kernel (A).  A coupled
 // context borrows the parent's bucket table (and its Ab table where the column
 // blocks are whole groups of four sections) and has its own stream and buffers.
-#include "sa_host.h"
-#include "sa_sc.h"
-
-struct sa_sc {
-  sa_ctx* parent = nullptr;
-  sa::ScLayout lay;
-  std::vector<double> W;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;  // ev0 / ev1 bracket the last sa_sc_amp's loop
-  void *d_W = nullptr, *d_sqW = nullptr;  // [R][C] in the context precision: W and sqrt(W)
-  uint16_t* d_fwd = nullptr;              // the padded groups' Ab table (ScLayout::own_fwd), else null
-  void *d_c = nullptr, *d_Pc = nullptr;   // [L] sqrt(n Pl), [C] column-block powers
-  int Bcap = 0, Tcap = 0;
-  void *d_y = nullptr, *d_z = nullptr, *d_beta = nullptr, *d_out = nullptr;
-  void *d_abp = nullptr, *d_bbp = nullptr, *d_zzp = nullptr, *d_phi = nullptr;
-  int *d_iters = nullptr, *d_done = nullptr;
-  int32_t *d_idx = nullptr, *d_dec = nullptr, *d_errs = nullptr;
-  double* d_noise = nullptr;
-  double* d_stage = nullptr;
-  size_t stage_cap = 0;
-  // the wave form's state (sa_sc_amp_ex / sa_sc_mc_ex with a tolerance above 0): allocated at its first use
-  void* d_taul = nullptr;            // [wBcap][2][C]
-  unsigned char* d_live = nullptr;   // [wBcap][wTcap][C]
-  int wBcap = 0, wTcap = 0;
-};
+#include "sa_sc_ctx.h"
 
 namespace sa {
 
@@ -397,6 +372,42 @@ __global__ void __launch_bounds__(64) k_scrow(ScRowArgs<real> a) {
   if (lane == 0) a.zzp[(size_t)b * a.NZ + q] = s;
 }
 
+// The beta_0 start: z = y - A beta_0 with A beta_0 as
+// sc_ab left it in ab [B][n], the z^2 partials, iters = -1 and done = 0.  The
+// grid and indexing of k_scrow (one wavefront per z^2 partial and codeword) and
+// its wave_sum, so the partials are formed in SCR_INIT's order; a kernel of its
+// own, so that k_scrow compiles to what it compiled to.
+template <typename real>
+__global__ void __launch_bounds__(64) k_scstart(const real* __restrict__ y, const real* __restrict__ ab,
+                                                real* __restrict__ z, real* __restrict__ zzp, int* __restrict__ iters,
+                                                int* __restrict__ done, int n, int nr, int zpb, int NZ) {
+  const int q = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int r = q / zpb, li = (q % zpb) * kScRowsPerBlk + lane;
+  const bool valid = li < nr;
+  const size_t o = (size_t)b * n + r * nr + (valid ? li : 0);
+  real zn = 0;
+  if (valid) {
+    zn = y[o] - ab[o];
+    z[o] = zn;
+  }
+  if (q == 0 && lane == 0) {
+    iters[b] = -1;
+    done[b] = 0;
+  }
+  const real s = wave_sum(zn * zn);
+  if (lane == 0) zzp[(size_t)b * NZ + q] = s;
+}
+
+// Section decisions of the staged context (sa_sc_decide): argmax, first index on ties
+template <typename real, int E>
+__global__ void __launch_bounds__(256) k_sc_argmax(const real* beta, int32_t* dec, int L, int M) {
+  const int lane = threadIdx.x & 63;
+  const int l = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (l >= L) return;
+  const int bi = section_argmax<real, E>(beta + ((size_t)b * L + l) * M, lane, M, 0);
+  if (lane == 0) dec[(size_t)b * L + l] = bi;
+}
+
 // one-hot beta(idx) with c_l at column idx[b][l] (beta zeroed in front)
 template <typename real>
 __global__ void k_sc_onehot(real* beta, const int32_t* idx, const real* c, int L, int M, int B) {
@@ -444,7 +455,7 @@ static int sc_alloc(void** p, size_t bytes) {
 
 static int sc_blocks(size_t count) { return (int)std::min<size_t>(std::max<size_t>((count + 255) / 256, 1), 4096); }
 
-static int sc_stage(sa_sc* s, size_t count) {
+int sc_stage(sa_sc* s, size_t count) {
   if (count <= s->stage_cap) return SA_OK;
   HIP_TRY(hipStreamSynchronize(s->stream));
   dev_free(s->d_stage);
@@ -490,6 +501,9 @@ static void sc_free_workspace(sa_sc* s) {
   s->d_idx = s->d_dec = s->d_errs = nullptr;
   s->d_noise = nullptr;
   s->Bcap = s->Tcap = 0;
+  std::string none;
+  sc_stage_rule(s->st, SC_CALL_RESIZE, 0, 0, none);  // nothing staged survives
+  s->Trun = -1;
 }
 
 // buffers for B codewords and T iterations (grown, never shrunk)
@@ -616,30 +630,69 @@ static int sc_launch_row(sa_sc* s, int B, const ScRowArgs<real>& a) {
 
 // The decode of the y staged in d_y: z = y, then T times (k_scsec, k_scrow),
 // launched eagerly on the context's stream with no host synchronisation
-// between them (why no graph).
+// between them (why no graph).  The launches are
+// sc_decode_launches' (sa_sc.h), in its order: with beta0 the staged d_beta is
+// the start and z = y - A beta_0 (section 13c).
 // wv.wave (sc_wave_plan): k_scsec's wave form with the plan's tolerances, the
 // live trace into d_live where wv.live_bytes asks for one (zeroed in front, as
 // the phi trace); else exactly the launches of a decode without tolerances.
 template <typename real>
-static int sc_decode(sa_sc* s, int B, int T, int es, const ScWavePlan& wv) {
+static int sc_ab(sa_sc* s, int B, const double* d_noise, void* d_out);
+
+template <typename real>
+static int sc_launch_start(sa_sc* s, int B) {
   const ScLayout& y = s->lay;
-  HIP_TRY(hipMemsetAsync(s->d_beta, 0, (size_t)B * y.L * y.M * sizeof(real), s->stream));
-  HIP_TRY(hipMemsetAsync(s->d_phi, 0, (size_t)B * std::max(T, 1) * y.R * sizeof(real), s->stream));
-  if (wv.wave && wv.live_bytes) HIP_TRY(hipMemsetAsync(s->d_live, 0, wv.live_bytes, s->stream));
-  if (int rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_INIT, T, 0))) return rc;
-  for (int t = 0; t < T; ++t) {
-    if (wv.wave) {
-      ScWaveArgs<real> a;
-      static_cast<ScSecArgs<real>&>(a) = sc_sec_args<real>(s, SC_AMP, T, t, es);
-      a.stop_tol = (real)wv.stop_tol;
-      a.freeze_tol = (real)wv.freeze_tol;
-      a.taul = (real*)s->d_taul;
-      a.live = wv.live_bytes ? s->d_live : nullptr;
-      if (int rc = sc_launch_wave<real>(s, B, a)) return rc;
-    } else {
-      if (int rc = sc_launch_sec<real>(s, B, sc_sec_args<real>(s, SC_AMP, T, t, es))) return rc;
+  k_scstart<real><<<dim3(y.NZ, B), 64, 0, s->stream>>>((const real*)s->d_y, (const real*)s->d_out, (real*)s->d_z,
+                                                       (real*)s->d_zzp, s->d_iters, s->d_done, y.n, y.n_r, y.zpb, y.NZ);
+  HIP_TRY(hipGetLastError());
+  return SA_OK;
+}
+
+template <typename real>
+static int sc_decode(sa_sc* s, int B, int T, int es, const ScWavePlan& wv, bool beta0 = false) {
+  const ScLayout& y = s->lay;
+  for (const ScLaunch& l : sc_decode_launches(T, beta0, wv)) {
+    int rc = SA_OK;
+    switch (l.step) {
+      case SCS_MEMSET_BETA:
+        HIP_TRY(hipMemsetAsync(s->d_beta, 0, (size_t)B * y.L * y.M * sizeof(real), s->stream));
+        break;
+      case SCS_MEMSET_PHI:
+        HIP_TRY(hipMemsetAsync(s->d_phi, 0, (size_t)B * std::max(T, 1) * y.R * sizeof(real), s->stream));
+        break;
+      case SCS_MEMSET_LIVE:
+        HIP_TRY(hipMemsetAsync(s->d_live, 0, wv.live_bytes, s->stream));
+        break;
+      case SCS_ROW_INIT:
+        rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_INIT, T, 0));
+        break;
+      case SCS_SEC_AB:  // with SCS_ROW_ABOUT: A beta_0 into d_out
+        rc = sc_launch_sec<real>(s, B, sc_sec_args<real>(s, SC_AB, 1, 0, 0));
+        break;
+      case SCS_ROW_ABOUT:
+        rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_ABOUT, 1, 0));
+        break;
+      case SCS_START:
+        rc = sc_launch_start<real>(s, B);
+        break;
+      case SCS_SEC_AMP:
+        rc = sc_launch_sec<real>(s, B, sc_sec_args<real>(s, SC_AMP, T, l.t, es));
+        break;
+      case SCS_SEC_WAVE: {
+        ScWaveArgs<real> a;
+        static_cast<ScSecArgs<real>&>(a) = sc_sec_args<real>(s, SC_AMP, T, l.t, es);
+        a.stop_tol = (real)wv.stop_tol;
+        a.freeze_tol = (real)wv.freeze_tol;
+        a.taul = (real*)s->d_taul;
+        a.live = wv.live_bytes ? s->d_live : nullptr;
+        rc = sc_launch_wave<real>(s, B, a);
+        break;
+      }
+      case SCS_ROW_AMP:
+        rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_AMP, T, l.t));
+        break;
     }
-    if (int rc = sc_launch_row<real>(s, B, sc_row_args<real>(s, SCR_AMP, T, t))) return rc;
+    if (rc) return rc;
   }
   return SA_OK;
 }
@@ -670,6 +723,7 @@ static hipError_t sc_lds_attrs_t() {
 }
 
 // c_l = sqrt(n Pl_l) and P_c = sum of Pl over column block c, in binary64 on the host, then the context precision
+// (and c_l once more as binary64, d_cd)
 static int sc_set_power(sa_sc* s, const double* Pl) {
   const ScLayout& y = s->lay;
   std::vector<double> v((size_t)y.L + y.C, 0.0);
@@ -680,8 +734,17 @@ static int sc_set_power(sa_sc* s, const double* Pl) {
   }
   if (int rc = sc_upload(s, s->d_c, v.data(), y.L)) return rc;
   if (int rc = sc_upload(s, s->d_Pc, v.data() + y.L, y.C)) return rc;
+  // the glue kernels of sa_glue.hip read c_l as binary64
+  HIP_TRY(hipMemcpyAsync(s->d_cd, v.data(), (size_t)y.L * sizeof(double), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));  // v is a host temporary
-  return SA_OK;
+  std::string none;
+  return sc_stage_rule(s->st, SC_CALL_STAGE_POWER, 0, 0, none);
+}
+
+// a one-call entry point overwrites the workspace: nothing staged survives it
+static void sc_one_call(sa_sc* s) {
+  std::string none;
+  sc_stage_rule(s->st, SC_CALL_ONE_CALL, 0, 0, none);
 }
 
 static int sc_check(const sa_sc* s, int B, const char* what) {
@@ -733,6 +796,7 @@ int sa_sc_create(sa_ctx* parent, int R, int C, const double* W, sa_sc** out) {
   if (!rc) rc = sc_alloc(&s->d_sqW, RC * z);
   if (!rc) rc = sc_alloc(&s->d_c, (size_t)lay.L * z);
   if (!rc) rc = sc_alloc(&s->d_Pc, (size_t)C * z);
+  if (!rc) rc = sc_alloc((void**)&s->d_cd, sc_cd_bytes(lay));
   std::vector<double> sq(RC);
   for (size_t k = 0; k < RC; ++k) sq[k] = std::sqrt(W[k]);
   if (!rc) rc = sc_upload(s, s->d_W, W, RC);
@@ -765,7 +829,7 @@ void sa_sc_destroy(sa_sc* s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   sc_free_workspace(s);
   sc_free_wave(s);
-  dev_free(s->d_W); dev_free(s->d_sqW); dev_free(s->d_fwd); dev_free(s->d_c); dev_free(s->d_Pc);
+  dev_free(s->d_W); dev_free(s->d_sqW); dev_free(s->d_fwd); dev_free(s->d_c); dev_free(s->d_Pc); dev_free(s->d_cd);
   dev_free(s->d_stage);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -779,6 +843,7 @@ int sa_sc_Ab(sa_sc* s, int B, const double* beta, double* out) {
   HIP_TRY(hipSetDevice(s->parent->device));
   int rc = sc_workspace(s, B, 1);
   if (rc) return rc;
+  sc_one_call(s);
   const ScLayout& y = s->lay;
   if ((rc = sc_upload(s, s->d_beta, beta, (size_t)B * y.L * y.M))) return rc;
   rc = y.prec == SA_PREC_F64 ? sc_ab<double>(s, B, nullptr, s->d_out) : sc_ab<float>(s, B, nullptr, s->d_out);
@@ -794,6 +859,7 @@ int sa_sc_Az(sa_sc* s, int B, const double* z, double* out) {
   HIP_TRY(hipSetDevice(s->parent->device));
   int rc = sc_workspace(s, B, 1);
   if (rc) return rc;
+  sc_one_call(s);
   const ScLayout& y = s->lay;
   if ((rc = sc_upload(s, s->d_z, z, (size_t)B * y.n))) return rc;
   rc = y.prec == SA_PREC_F64 ? sc_launch_sec<double>(s, B, sc_sec_args<double>(s, SC_AZ, 1, 0, 0))
@@ -813,7 +879,7 @@ static void sc_live_all(const ScLayout& y, int B, int T, const int* iters, unsig
 
 static int sc_amp_impl(const char* what, sa_sc* s, int B, const double* yv, const double* Pl, int T, double stop_tol,
                        double freeze_tol, double* beta_out, int* iters_out, double* phi_out, unsigned char* live_out,
-                       int flags) {
+                       int flags, const double* beta0 = nullptr) {
   const std::string w = std::string(what) + ": ";
   if (int rc = sc_check(s, B, what)) return rc;
   if (!yv) return fail(SA_ERR_ARG, w + "y is NULL");
@@ -830,12 +896,15 @@ static int sc_amp_impl(const char* what, sa_sc* s, int B, const double* yv, cons
     if (!(Pl[l] >= 0) || !std::isfinite(Pl[l])) return fail(SA_ERR_ARG, w + "Pl must be non-negative and finite");
   int rc = sc_workspace(s, B, T);
   if (rc) return rc;
+  sc_one_call(s);
   if (wv.wave && (rc = sc_wave_workspace(s, B, T))) return rc;
   if ((rc = sc_set_power(s, Pl))) return rc;
   if ((rc = sc_upload(s, s->d_y, yv, (size_t)B * y.n))) return rc;
+  if (beta0 && (rc = sc_upload(s, s->d_beta, beta0, (size_t)B * y.L * y.M))) return rc;
   const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
   HIP_TRY(hipEventRecord(s->ev0, s->stream));
-  rc = y.prec == SA_PREC_F64 ? sc_decode<double>(s, B, T, es, wv) : sc_decode<float>(s, B, T, es, wv);
+  rc = y.prec == SA_PREC_F64 ? sc_decode<double>(s, B, T, es, wv, beta0 != nullptr)
+                             : sc_decode<float>(s, B, T, es, wv, beta0 != nullptr);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(s->ev1, s->stream));
   s->timed = true;
@@ -878,6 +947,13 @@ int sa_sc_amp_ex(sa_sc* s, int B, const double* yv, const double* Pl, int T, dou
   return sc_amp_impl("sa_sc_amp_ex", s, B, yv, Pl, T, stop_tol, freeze_tol, beta_out, iters_out, phi_out, live_out, flags);
 }
 
+int sa_sc_amp_start(sa_sc* s, int B, const double* yv, const double* Pl, int T, const double* beta0, double stop_tol,
+                    double freeze_tol, double* beta_out, int* iters_out, double* phi_out, unsigned char* live_out,
+                    int flags) {
+  return sc_amp_impl("sa_sc_amp_start", s, B, yv, Pl, T, stop_tol, freeze_tol, beta_out, iters_out, phi_out, live_out,
+                     flags, beta0);
+}
+
 double sa_sc_event_ms(sa_sc* s) {
   if (!s || !s->timed) return -1.0;
   float ms = 0;
@@ -905,6 +981,7 @@ static int sc_mc_impl(const char* what, sa_sc* s, int B, const int32_t* idx, con
   HIP_TRY(hipSetDevice(s->parent->device));
   int rc = sc_workspace(s, B, T);
   if (rc) return rc;
+  sc_one_call(s);
   if (wv.wave && (rc = sc_wave_workspace(s, B, T))) return rc;
   if ((rc = sc_set_power(s, Pl))) return rc;
   const size_t z = sc_rsz(s), LM = (size_t)y.L * y.M;
@@ -973,6 +1050,164 @@ int sa_sc_mc_ex(sa_sc* s, int B, const int32_t* idx, const double* noise, const 
                 unsigned char* live_out, double* ms_out) {
   return sc_mc_impl("sa_sc_mc_ex", s, B, idx, noise, Pl, T, stop_tol, freeze_tol, flags, dec_out, iters_out, errs_out,
                     live_out, ms_out);
+}
+
+// ---- the staged, device-resident life cycle ----
+// sc_stage_rule on the context: the checks alone (commit = false, in front of the work) or with the state it leaves
+static int sc_rule(sa_sc* s, int call, int B, const char* what, bool commit = true) {
+  if (!s) return fail(SA_ERR_ARG, std::string(what) + ": null context");
+  std::string err;
+  ScStageState probe = s->st;
+  if (int rc = sc_stage_rule(commit ? s->st : probe, call, B, s->Bcap, err)) return fail(rc, std::string(what) + ": " + err);
+  return SA_OK;
+}
+
+int sa_sc_reserve(sa_sc* s, int B, int T) {
+  if (int rc = sc_check(s, B, "sa_sc_reserve")) return rc;
+  if (T < 0) return fail(SA_ERR_ARG, "sa_sc_reserve: T must be non-negative");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  return sc_workspace(s, B, T);
+}
+
+int sa_sc_stage_power(sa_sc* s, const double* Pl) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_stage_power: null context");
+  if (!Pl) return fail(SA_ERR_ARG, "sa_sc_stage_power: Pl is NULL");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  return sc_set_power(s, Pl);
+}
+
+int sa_sc_stage(sa_sc* s, int B, const double* yv, const double* beta0) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_stage: null context");
+  if (!yv) return fail(SA_ERR_ARG, "sa_sc_stage: y is NULL");
+  if (int rc = sc_rule(s, beta0 ? SC_CALL_STAGE_BETA0 : SC_CALL_STAGE, B, "sa_sc_stage", false)) return rc;
+  HIP_TRY(hipSetDevice(s->parent->device));
+  const ScLayout& y = s->lay;
+  int rc = sc_upload(s, s->d_y, yv, (size_t)B * y.n);
+  if (rc) return rc;
+  if (beta0 && (rc = sc_upload(s, s->d_beta, beta0, (size_t)B * y.L * y.M))) return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return sc_rule(s, beta0 ? SC_CALL_STAGE_BETA0 : SC_CALL_STAGE, B, "sa_sc_stage");
+}
+
+// y = A beta(d_idx) + d_noise (NULL: none) of B codewords into d_y, by the kernels of sa_sc_Ab (as sa_sc_mc encodes)
+static int sc_encode_staged(sa_sc* s, int B, const double* d_noise, int32_t* idx_out) {
+  const ScLayout& y = s->lay;
+  const int nb = (B * y.L + 255) / 256;
+  HIP_TRY(hipMemsetAsync(s->d_beta, 0, (size_t)B * y.L * y.M * sc_rsz(s), s->stream));
+  int rc;
+  if (y.prec == SA_PREC_F64) {
+    k_sc_onehot<double><<<nb, 256, 0, s->stream>>>((double*)s->d_beta, s->d_idx, (const double*)s->d_c, y.L, y.M, B);
+    rc = sc_ab<double>(s, B, d_noise, s->d_y);
+  } else {
+    k_sc_onehot<float><<<nb, 256, 0, s->stream>>>((float*)s->d_beta, s->d_idx, (const float*)s->d_c, y.L, y.M, B);
+    rc = sc_ab<float>(s, B, d_noise, s->d_y);
+  }
+  if (rc) return rc;
+  if (idx_out)
+    HIP_TRY(hipMemcpyAsync(idx_out, s->d_idx, (size_t)B * y.L * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return sc_rule(s, SC_CALL_ENCODE, B, "sa_sc_encode");
+}
+
+int sa_sc_encode(sa_sc* s, int B, const int32_t* idx, const double* noise) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_encode: null context");
+  if (!idx) return fail(SA_ERR_ARG, "sa_sc_encode: idx is NULL");
+  if (int rc = sc_rule(s, SC_CALL_ENCODE, B, "sa_sc_encode", false)) return rc;
+  const ScLayout& y = s->lay;
+  for (size_t k = 0; k < (size_t)B * y.L; ++k)
+    if (idx[k] < 0 || idx[k] >= y.M) return fail(SA_ERR_ARG, "sa_sc_encode: idx outside [0, M)");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  s->st.y = s->st.beta = false;  // d_y and d_beta are being rewritten
+  HIP_TRY(hipMemcpyAsync(s->d_idx, idx, (size_t)B * y.L * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  if (noise) HIP_TRY(hipMemcpyAsync(s->d_noise, noise, (size_t)B * y.n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  return sc_encode_staged(s, B, noise ? s->d_noise : nullptr, nullptr);
+}
+
+int sa_sc_encode_bits(sa_sc* s, int B, const uint8_t* d_bits, const double* d_noise, int32_t* idx_out) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_encode_bits: null context");
+  if (!d_bits) return fail(SA_ERR_ARG, "sa_sc_encode_bits: bits is NULL");
+  if (int rc = sc_rule(s, SC_CALL_ENCODE, B, "sa_sc_encode_bits", false)) return rc;
+  const ScLayout& y = s->lay;
+  if (y.M < 2) return fail(SA_ERR_UNSUPPORTED, "sa_sc_encode_bits: M < 2 carries no bits");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  s->st.y = s->st.beta = false;
+  if (int rc = launch_bits_idx(s->stream, d_bits, ilog2(y.M), y.L, B, s->d_idx)) return rc;
+  return sc_encode_staged(s, B, d_noise, idx_out);
+}
+
+int sa_sc_run(sa_sc* s, int B, int T, double stop_tol, double freeze_tol, int flags) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_run: null context");
+  if (flags & ~(SA_FLAG_NO_EARLY_STOP | SA_FLAG_BETA0)) return fail(SA_ERR_ARG, "sa_sc_run: unknown flags");
+  if (T < 0 || T > std::max(s->Tcap, 0)) return fail(SA_ERR_ARG, "sa_sc_run: T outside the reserved workspace (sa_sc_reserve)");
+  const bool b0 = (flags & SA_FLAG_BETA0) != 0;
+  if (int rc = sc_rule(s, b0 ? SC_CALL_RUN_BETA0 : SC_CALL_RUN, B, "sa_sc_run", false)) return rc;
+  const ScLayout& y = s->lay;
+  ScWavePlan wv;
+  std::string err;
+  int rc = sc_wave_plan(wv, y, B, T, stop_tol, freeze_tol, false, err);
+  if (rc) return fail(rc, "sa_sc_run: " + err);
+  sc_rule(s, b0 ? SC_CALL_RUN_BETA0 : SC_CALL_RUN, B, "sa_sc_run");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  if (wv.wave && (rc = sc_wave_workspace(s, B, T))) return rc;
+  const int es = (flags & SA_FLAG_NO_EARLY_STOP) ? 0 : 1;
+  HIP_TRY(hipEventRecord(s->ev0, s->stream));
+  rc = y.prec == SA_PREC_F64 ? sc_decode<double>(s, B, T, es, wv, b0) : sc_decode<float>(s, B, T, es, wv, b0);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(s->ev1, s->stream));
+  s->timed = true;
+  s->Trun = T;
+  return SA_OK;
+}
+
+int sa_sc_wait(sa_sc* s) {
+  if (!s) return fail(SA_ERR_ARG, "sa_sc_wait: null context");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
+}
+
+int sa_sc_fetch(sa_sc* s, int B, double* beta_out, int* iters_out, double* phi_out) {
+  if (int rc = sc_rule(s, SC_CALL_FETCH, B, "sa_sc_fetch")) return rc;
+  if ((iters_out || phi_out) && s->Trun < 0) return fail(SA_ERR_ARG, "sa_sc_fetch: no run to read the stop indices of");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  const ScLayout& y = s->lay;
+  int rc;
+  if (beta_out) {
+    if ((rc = sc_download(s, beta_out, s->d_beta, (size_t)B * y.L * y.M))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  if (phi_out && s->Trun > 0) {
+    if ((rc = sc_download(s, phi_out, s->d_phi, (size_t)B * s->Trun * y.R))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  if (iters_out) {
+    HIP_TRY(hipMemcpyAsync(iters_out, s->d_iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (int b = 0; b < B; ++b)
+      if (iters_out[b] < 0) iters_out[b] = s->Trun;
+  }
+  return SA_OK;
+}
+
+int sa_sc_decide(sa_sc* s, int B, int32_t* idx_out) {
+  if (int rc = sc_rule(s, SC_CALL_FETCH, B, "sa_sc_decide")) return rc;
+  if (!idx_out) return fail(SA_ERR_ARG, "sa_sc_decide: idx_out is NULL");
+  HIP_TRY(hipSetDevice(s->parent->device));
+  const ScLayout& y = s->lay;
+  const dim3 dgrid((y.L + 3) / 4, B);
+#define SA_SC_ARG(EE)                                                                                              \
+  case EE:                                                                                                         \
+    if (y.prec == SA_PREC_F64)                                                                                     \
+      k_sc_argmax<double, EE><<<dgrid, 256, 0, s->stream>>>((const double*)s->d_beta, s->d_dec, y.L, y.M);         \
+    else                                                                                                           \
+      k_sc_argmax<float, EE><<<dgrid, 256, 0, s->stream>>>((const float*)s->d_beta, s->d_dec, y.L, y.M);           \
+    break;
+  switch (y.E) { SA_SC_ARG(1) SA_SC_ARG(2) SA_SC_ARG(4) SA_SC_ARG(8) SA_SC_ARG(16) SA_SC_ARG(32) SA_SC_ARG(64) }
+#undef SA_SC_ARG
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(idx_out, s->d_dec, (size_t)B * y.L * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SA_OK;
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@
 
 // 0.3: sa_profile / sa_profile_rep write 2 * sa_profile_kinds() + 1 doubles (13 since 0.2)
 // 0.4: sa_profile_dispatch (dispatch-bound event pairs), sa_decide_async / sa_decide_collect
-#define SA_VERSION "sparc_amp 0.5 gfx950"
+#define SA_VERSION "sparc_amp 0.6 gfx950"
 
 #include "sa_host.h"
 

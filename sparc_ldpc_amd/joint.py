@@ -160,6 +160,8 @@ class JointDecoder:
     """AMP operator + LDPC code + the shortened operator of the unprotected
     sections, for B-codeword batches of the joint schemes."""
 
+    pipelined = True  # mc_joint may decode a batch as two concurrent halves (JointPipeline)
+
     def __init__(self, L, M, n, code, T, backend=None, precision=None, device=None, seed=0, twin_of=None,
                  ordering=None, **options):
         """twin_of: another JointDecoder whose operator tables this one shares
@@ -587,7 +589,9 @@ def mc_joint(jd: JointDecoder, Pl, sigma, seeds, mode, soft_iter=2, batch=256, t
     The messages are the host's bit for bit; the noise is the host's up to the
     device library's log, so a rep's counts may differ from its host-drawn
     ones.  Seeds outside [0, 2**32) raise ValueError, and so does
-    unit_cancel=True, which reads the host noise."""
+    unit_cancel=True, which reads the host noise.
+    A decoder on a coupled design (sc_joint.CoupledJointDecoder) is never
+    pipelined: the default resolves to off and pipeline=True raises ValueError."""
     _check_draws(draws, unit_cancel)
     seeds = list(seeds)
     if draws == "device":
@@ -595,6 +599,10 @@ def mc_joint(jd: JointDecoder, Pl, sigma, seeds, mode, soft_iter=2, batch=256, t
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
         seeds = [int(s) for s in seed_array(seeds)]
+    if not jd.pipelined:
+        if pipeline:
+            raise ValueError("pipeline=True: a coupled joint decoder is not pipelined")
+        pipeline = False
     parts = []
     for s0 in range(0, len(seeds), batch):
         chunk = seeds[s0:s0 + batch]

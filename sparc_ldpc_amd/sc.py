@@ -13,6 +13,13 @@ previous iteration's, ``freeze_tol`` leaves a column block alone while its Ï„_cÂ
 is within ``freeze_tol`` of the value its Î² was last computed at, and
 ``return_live`` adds the (B, T, C) uint8 trace of the blocks that were computed.
 At the defaults (0, 0, False) every call is what it was.
+
+A decode may start from a Î²â‚€ (``beta0`` / ``beta``: Î² = Î²â‚€, z = y âˆ’ A Î²â‚€, then
+the same loop; ``sa_sc_amp_start``), and a CoupledOperator has SparcOperator's
+device-resident life cycle (reserve, stage_power, stage / encode / encode_bits,
+run, wait, decide, fetch_beta) and its SPARC <-> LDPC glue (llr, soft_beta0,
+hard_cancel, stage_onehot) on the coupled context's Î², which is what
+sc_joint.CoupledJointDecoder runs on.
 """
 from __future__ import annotations
 
@@ -20,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import as_f64, check, dptr
-from .operators import SparcOperator, _cached_operator, make_ordering, seed_array
+from .operators import SparcOperator, _cached_operator, llr_mode, make_ordering, seed_array
 
 __all__ = ["base_matrix", "CoupledOperator", "ScAbOp", "ScAzOp", "sc_transforms", "amp_sc", "amp_sc_batch",
            "mc_decode_sc"]
@@ -97,8 +104,15 @@ class CoupledOperator:
                                      "freeze_tol and return_live need it")
         return getattr(self._lib, name)
 
-    def amp_batch(self, y, Pl, T, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
+    def _need(self, name):
+        """A late entry point of the library, or SA_ERR_UNSUPPORTED naming it."""
+        if not hasattr(self._lib, name):
+            raise _lib.SparcAmpError(_lib.SA_ERR_UNSUPPORTED, f"this build of the library has no {name}")
+        return getattr(self._lib, name)
+
+    def amp_batch(self, y, Pl, T, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False, beta0=None):
         """Decode B codewords: y (B, n) -> (Î²Ì‚ (B, L*M), iters (B,), Ï† (B, T, R)).
+        beta0 (B, L*M) or None: the start, Î² = Î²â‚€ and z = y âˆ’ A Î²â‚€ (None: Î² = 0).
         iters[b] is the stop index (every Ï†_r bit-equal to the previous
         iteration's, or within stop_tol of it), or T; Ï† rows from the stop
         index on are zero.  return_live appends live (B, T, C) uint8: 1 where
@@ -115,6 +129,14 @@ class CoupledOperator:
         phi = np.zeros((B, T, self.R))
         flags = 0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP
         ip = iters.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int))
+        if beta0 is not None:
+            beta0 = as_f64(beta0)
+            assert beta0.size == B * self.L * self.M, "Î²â‚€ must hold L*M values per codeword"
+            live = np.zeros((B, T, self.C), dtype=np.uint8) if return_live else None
+            lp = live.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_ubyte)) if return_live else None
+            check(self._need("sa_sc_amp_start")(self._sc, B, dptr(y), dptr(Pl), T, dptr(beta0), float(stop_tol),
+                                                float(freeze_tol), dptr(out), ip, dptr(phi), lp, flags))
+            return (out, iters, phi, live) if return_live else (out, iters, phi)
         ex = self._ex("sa_sc_amp_ex", stop_tol, freeze_tol, return_live)
         if ex is None:
             check(self._lib.sa_sc_amp(self._sc, B, dptr(y), dptr(Pl), T, dptr(out), ip, dptr(phi), flags))
@@ -169,6 +191,123 @@ class CoupledOperator:
         return (dec, its, errs, float(ms[0]), live) if return_live else (dec, its, errs, float(ms[0]))
 
 
+    # ---- the staged, device-resident path (SparcOperator's names and signatures) ----
+    _I32 = _lib.ct.POINTER(_lib.ct.c_int32)
+
+    def reserve(self, B, T):
+        check(self._need("sa_sc_reserve")(self._sc, int(B), int(T)))
+
+    def stage_power(self, B, Pl):
+        """Stage the section powers (c_l = sqrt(n Pl_l)); B is SparcOperator's argument and is not needed here."""
+        Pl = as_f64(Pl).reshape(-1)
+        assert Pl.size == self.L, "Pl must hold L section powers"
+        check(self._need("sa_sc_stage_power")(self._sc, dptr(Pl)))
+
+    def stage(self, y, Pl=None, beta0=None):
+        """Stage y (B, n), with Pl the section powers and with beta0 (B, L*M) a start for run(beta0=True)."""
+        y = as_f64(y)
+        B = y.shape[0] if y.ndim == 2 else 1
+        assert y.size == B * self.n, "y must hold B x n values"
+        if Pl is not None:
+            self.stage_power(B, Pl)
+        if beta0 is not None:
+            beta0 = as_f64(beta0)
+            assert beta0.size == B * self.L * self.M, "Î²â‚€ must hold L*M values per codeword"
+        check(self._need("sa_sc_stage")(self._sc, B, dptr(y), None if beta0 is None else dptr(beta0)))
+        return B
+
+    def encode(self, idx, noise=None):
+        """Stage y = A Î²(idx) + noise; idx (B, L) section indices."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        B = idx.shape[0]
+        assert idx.shape == (B, self.L)
+        nz = None
+        if noise is not None:
+            noise = as_f64(noise)
+            assert noise.size == B * self.n
+            nz = dptr(noise)
+        check(self._need("sa_sc_encode")(self._sc, B, idx.ctypes.data_as(self._I32), nz))
+        return B
+
+    def encode_bits(self, B, d_bits, d_noise=None, fetch_idx=True):
+        """encode from message bits on the device (SparcOperator.encode_bits): int device pointers to (B, L log2 M)
+        uint8 bits and to (B, n) float64 noise or None.  Returns the section indices (B, L) int32 (None without
+        fetch_idx)."""
+        idx = np.empty((int(B), self.L), dtype=np.int32) if fetch_idx else None
+        check(self._need("sa_sc_encode_bits")(self._sc, int(B), _lib.ct.c_void_p(d_bits), _lib.ct.c_void_p(d_noise),
+                                              None if idx is None else idx.ctypes.data_as(self._I32)))
+        return idx
+
+    def run(self, B, T, early_stop=True, beta0=False, stop_tol=0.0, freeze_tol=0.0):
+        """Queue a decode of the staged y; beta0: start from the Î² on the device (staged, soft_beta0's,
+        stage_onehot's or the last run's)."""
+        flags = (0 if early_stop else _lib.SA_FLAG_NO_EARLY_STOP) | (_lib.SA_FLAG_BETA0 if beta0 else 0)
+        check(self._need("sa_sc_run")(self._sc, int(B), int(T), float(stop_tol), float(freeze_tol), flags))
+        self._T_run = int(T)
+
+    def wait(self):
+        check(self._need("sa_sc_wait")(self._sc))
+
+    def decide(self, B):
+        """Section argmax of the Î² on the device, (B, L) int32."""
+        idx = np.empty((int(B), self.L), dtype=np.int32)
+        check(self._need("sa_sc_decide")(self._sc, int(B), idx.ctypes.data_as(self._I32)))
+        return idx
+
+    def iters(self, B):
+        """Stop index of each codeword of the last run (T when the loop ran out)."""
+        it = np.empty(int(B), dtype=np.int32)
+        check(self._need("sa_sc_fetch")(self._sc, int(B), None, it.ctypes.data_as(_lib.ct.POINTER(_lib.ct.c_int)), None))
+        return it
+
+    def fetch_beta(self, B):
+        """The Î² on the device, (B, L*M)."""
+        out = np.empty((int(B), self.L * self.M))
+        check(self._need("sa_sc_fetch")(self._sc, int(B), dptr(out), None, None))
+        return out
+
+    def fetch_phi(self, B, T):
+        """The Ï† trace of the last run (of T iterations), (B, T, R)."""
+        assert int(T) == getattr(self, "_T_run", None), "T must be the last run's"
+        phi = np.zeros((int(B), int(T), self.R))
+        check(self._need("sa_sc_fetch")(self._sc, int(B), None, None, dptr(phi)))
+        return phi
+
+    def llr(self, B, l0, ns, out=None, mode="reference", clip=None):
+        """LDPC-bit LLRs of sections [l0, l0+ns) of the Î² on the device (SparcOperator.llr)."""
+        m = llr_mode(mode)
+        lgm = int(np.log2(self.M))
+        if out is None:
+            out = np.empty((B, ns * lgm))
+        p, fl = SparcOperator._ptr(out)
+        check(self._need("sa_sc_llr")(self._sc, int(B), int(l0), int(ns), p, fl, m,
+                                      float("inf") if clip is None else float(clip)))
+        return out
+
+    def soft_beta0(self, B, l0, ns, app):
+        """Î²â‚€ = Î² with sections [l0, l0+ns) from the LDPC app (SparcOperator.soft_beta0)."""
+        if not isinstance(app, int):
+            app = as_f64(app)
+        p, fl = SparcOperator._ptr(app)
+        check(self._need("sa_sc_soft_beta0")(self._sc, int(B), int(l0), int(ns), p, fl))
+
+    def hard_cancel(self, B, l0, ns, app):
+        """Hard LDPC decisions of sections [l0, l0+ns) -> (B, ns) indices (SparcOperator.hard_cancel with no dst:
+        a coupled design has no shortened operator to cancel into)."""
+        if not isinstance(app, int):
+            app = as_f64(app)
+        p, fl = SparcOperator._ptr(app)
+        idx = np.empty((int(B), int(ns)), dtype=np.int32)
+        check(self._need("sa_sc_hard_indices")(self._sc, int(B), int(l0), int(ns), p, fl, idx.ctypes.data_as(self._I32)))
+        return idx
+
+    def stage_onehot(self, idx):
+        """Stage the one-hot Î²â‚€ of section indices idx (B, L) for run(..., beta0=True)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        assert idx.ndim == 2 and idx.shape[1] == self.L
+        check(self._need("sa_sc_stage_onehot")(self._sc, idx.shape[0], idx.ctypes.data_as(self._I32)))
+
+
 class ScAbOp:
     """``Ab(Î²)`` -> A Î², (n, 1) float64, for the coupled design."""
 
@@ -209,24 +348,39 @@ def _coupled(Ab) -> CoupledOperator:
     return op
 
 
-def amp_sc_batch(y, Pl, T, Ab, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
+def amp_sc_batch(y, Pl, T, Ab, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False, beta0=None):
     """Coupled AMP of B codewords y (B, n): -> (Î²Ì‚ (B, L*M), iters (B,), Ï† (B, T, R)),
-    with return_live also live (B, T, C) uint8 (CoupledOperator.amp_batch)."""
+    with return_live also live (B, T, C) uint8 (CoupledOperator.amp_batch); beta0 (B, L*M): the start."""
     return _coupled(Ab).amp_batch(y, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol,
-                                  return_live=return_live)
+                                  return_live=return_live, beta0=beta0)
 
 
-def amp_sc(y, Pl, L, M, T, Ab, Az, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
+def _start(beta, LM):
+    """amp()'s Î² argument: None or the reference's np.array([None]) sentinel (the zero start), else (L*M,) or (L*M, 1)."""
+    if beta is None:
+        return None
+    b = np.asarray(beta)
+    if b.dtype == object and b.size == 1 and b.reshape(-1)[0] is None:
+        return None
+    b = as_f64(b)
+    if b.size != LM or b.ndim > 2 or (b.ndim == 2 and b.shape[1] != 1):
+        raise ValueError("beta must be (L*M,) or (L*M, 1)")
+    return b.reshape(1, -1)
+
+
+def amp_sc(y, Pl, L, M, T, Ab, Az, beta=None, *, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
     """Coupled AMP of one codeword, in amp()'s argument order: -> Î²Ì‚, (L*M, 1);
-    with return_live -> (Î²Ì‚, live (T, C) uint8)."""
+    with return_live -> (Î²Ì‚, live (T, C) uint8).  beta: the start Î²â‚€ (Î² = Î²â‚€, z = y âˆ’ A Î²â‚€), (L*M,) or (L*M, 1);
+    None or np.array([None]) is the zero start."""
     op = _coupled(Ab)
     assert (op.L, op.M) == (int(L), int(M)), "L, M must be the operator's"
     if getattr(Az, "op", None) is not op:
         raise TypeError("Ab and Az must come from one sc_transforms call")
     y = as_f64(y).reshape(1, -1)
-    res = op.amp_batch(y, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol, return_live=return_live)
-    beta = res[0].reshape(-1, 1)
-    return (beta, res[3][0]) if return_live else beta
+    res = op.amp_batch(y, Pl, T, early_stop=early_stop, stop_tol=stop_tol, freeze_tol=freeze_tol, return_live=return_live,
+                       beta0=_start(beta, op.L * op.M))
+    out = res[0].reshape(-1, 1)
+    return (out, res[3][0]) if return_live else out
 
 
 def mc_decode_sc(Ab, Pl, sigma, T, seeds, batch=256, early_stop=True, stop_tol=0.0, freeze_tol=0.0, return_live=False):
